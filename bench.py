@@ -16,9 +16,14 @@ rank assembles the rows of B of its read block, one all-gather of the panels (RC
 the output columns i % N == r; the timed step has no collective.  Rank 0 also times the whole set on its own GPU, so the line
 carries the same-workload single-GPU time next to the N-GPU one.
 
+A plain run sets up the headline set, warms up, times --steps passes, writes the last pass's pair records if --dump-outputs DIR is
+given, and prints the line.  Every other record named above and below (the copy ceiling, the warm k-mer count, layout_ab, xdrop,
+dropin_call, ingest, e2e, cpu_baseline, config_10k, config_hifi; for N > 1 the X-drop stage and the single-GPU run of the same
+workload) is measured only with --full; the --no-* options trim a --full run.
+
 Prints ONE JSON line (rank 0).  roofline: HBM, algorithmic bytes 14*nnzA + 6*F + 16*P per step over the row-kernel time measured
-with HIP events on the library's stream.  cpu_baseline: the reference's own HashSpGEMM (oracle/_ref/libbella_ref.so) on this
-box's host cores; falls back to the C port."""
+with HIP events on the library's stream.  cpu_baseline: the reference's own HashSpGEMM (oracle/_ref/libbella_ref.so) on the host
+cores this process may use; falls back to the C port."""
 import argparse
 import json
 import os
@@ -34,6 +39,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
 BIG_READS = 100000       # configs[3]
 SAMPLE_READS = 30000     # CPU baseline sample of the 100k set
+DUMP_BYTES = 48 << 20    # --dump-outputs: total size of the .npy files (a fixed sample of the records beyond it)
 
 
 def log(*a):
@@ -76,7 +82,11 @@ def run_cpu_baseline(codes, offsets, tk, tr, tp, nkmers, what):
     """the reference's HashSpGEMM on the given reads/tuples in a child process; returns the cpu_baseline object"""
     import tempfile
     try:
-        cores = os.cpu_count() or 1
+        # the cores this process may use (a shared box grants a share of its CPUs; OMP_NUM_THREADS says how many), not os.cpu_count():
+        # an OpenMP team larger than that waits on itself
+        cores = len(os.sched_getaffinity(0)) or 1
+        if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+            cores = max(1, min(cores, int(os.environ["OMP_NUM_THREADS"])))
         with tempfile.TemporaryDirectory() as tmp:
             npz = os.path.join(tmp, "w.npz")
             np.savez(npz, codes=codes, offsets=offsets, tk=tk, tr=tr, tp=tp, nkmers=np.int64(nkmers))
@@ -110,6 +120,33 @@ def timed_passes(eng, pars, steps, warmup, sync):
     acc["elapsed"] = time.perf_counter() - ts
     acc["npairs"], acc["flops"], acc["steps"] = npairs, flops, steps
     return acc
+
+
+def _sample(n, k, seed):
+    """ascending indices: all of range(n) if n <= k, else a fixed sample of about k of them (same n and seed -> same sample)"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=k, dtype=np.int64))
+
+
+def dump_outputs(eng, out_dir, acc):
+    """--dump-outputs: what the timed pass hands a caller (bella_hip_get_pairs: the pair records and the column pointers of the last
+    pass) as .npy files, float64 for ids / offsets / totals and float32 for the u16 fields (exact in both), within DUMP_BYTES; beyond
+    it a fixed seeded sample of the records, pair_index.npy saying which"""
+    os.makedirs(out_dir, exist_ok=True)
+    pairs, _, colptr = eng.get_pairs(ext=False)
+    assert len(pairs) == acc["npairs"]
+    save = lambda name, a: np.save(os.path.join(out_dir, name + ".npy"), a)
+    save("totals", np.array([acc["npairs"], acc["flops"]], dtype=np.float64))           # pairs, products of the last pass
+    cols = _sample(len(colptr), DUMP_BYTES // 4 // 8, 1)
+    save("colptr", colptr[cols].astype(np.float64))
+    if len(cols) < len(colptr):
+        save("colptr_index", cols.astype(np.float64))
+    per_pair = 8 + sum(8 if pairs.dtype[f].itemsize > 2 else 4 for f in pairs.dtype.names)
+    idx = _sample(len(pairs), (DUMP_BYTES - 16 * len(cols)) // per_pair, 0)
+    save("pair_index", idx.astype(np.float64))
+    for f in pairs.dtype.names:                                              # rid, cid, count, seedH, seedV, flags
+        save("pair_" + f, pairs[f][idx].astype(np.float64 if pairs.dtype[f].itemsize > 2 else np.float32))
 
 
 def roofline_of(acc, nnz_share, copy_gbps, traffic_key, expand_ms=0.0, layout="default"):
@@ -369,9 +406,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reads", type=int, default=0, help="override the read count of the headline workload (development)")
     ap.add_argument("--read-len", type=int, default=10000)
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline as well (the records the module docstring "
+                    "lists); the --no-* options below trim such a run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="N=1: after the timed steps, write the last step's pair records "
+                    "(a fixed sample beyond %d MB) and column pointers to DIR/<name>.npy" % (DUMP_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-10k", "--no-100k", dest="no_10k", action="store_true", help="N=1: skip the config_10k sub-record (configs[1] / configs[2])")
-    ap.add_argument("--no-xdrop", action="store_true", help="N=1: skip the X-drop records (configs[2]; configs[3]'s alignment stage)")
+    ap.add_argument("--no-xdrop", action="store_true", help="skip the X-drop records (configs[2]; configs[3]'s alignment stage)")
     ap.add_argument("--no-hifi", action="store_true", help="N=1: skip the config_hifi sub-record (configs[4]'s regime, 10k HiFi reads)")
     ap.add_argument("--no-dropin", action="store_true", help="N=1: skip the dropin_call records (the shim's call sequence, cold, wall clock)")
     ap.add_argument("--no-e2e", action="store_true", help="N=1: skip the e2e records (bella_amd/bin/bella-hip on the read set's FASTQ, wall clock)")
@@ -384,6 +425,12 @@ def main():
     a = ap.parse_args()
     if a.cpu_baseline_child:
         return cpu_baseline_child(a.cpu_baseline_child, a.threads)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    if not a.full:                                      # a plain run: the headline only
+        a.no_cpu_baseline = a.no_10k = a.no_xdrop = a.no_hifi = a.no_dropin = a.no_e2e = a.no_layout_ab = True
 
     import torch
     import torch.distributed as dist
@@ -473,7 +520,7 @@ def main():
             have_dist_count = False
             nk, nt, ndistinct = eng.count_kmers(17, 2, 8)
             kc_ms = eng.timings().kcount_ms
-            if world == 1:
+            if world == 1 and a.full:
                 # kcount_ms is the FIRST call on this fresh context (what a run pays); a second call (buffers in place) is recorded as warm
                 eng.count_kmers(17, 2, 8)
                 kc_runs = [kc_ms, eng.timings().kcount_ms]
@@ -522,7 +569,7 @@ def main():
 
     # measured device-copy ceiling: 1 GiB device-to-device, read + write bytes per second
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and a.full:
         try:
             src = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
             dst = torch.empty_like(src)
@@ -543,12 +590,14 @@ def main():
     if world == 1:
         import threading
 
-        def one_set(nreads, key, steps, warmup, want_cpu, full_cpu_in_background):
+        def one_set(nreads, key, steps, warmup, want_cpu, full_cpu_in_background, dump_dir=None):
             """everything the line reports about one PacBio-shaped read set on one GPU: the timed SpGEMM step, roofline, the cold
             front end, the layout A/B, X-drop on all candidate pairs, the drop-in call, ingest, the CPU baseline"""
             eng, info = prepare(nreads, False)
             eng.set_debug(2 | a.debug_flags)                 # diagnostics array (pair_ext) off in the timed path
             acc = timed_passes(eng, pars, steps, warmup, sync)
+            if dump_dir:                                     # before anything else runs a pass on this context
+                dump_outputs(eng, dump_dir, acc)
             colptr, _, _ = eng.get_B()
             nnz = int(colptr[-1])
             elapsed = acc["elapsed"]
@@ -598,7 +647,7 @@ def main():
         # HEADLINE: configs[3]'s read set (100k reads) on ONE GPU, SpGEMM-only -- the set BASELINE.json quotes the 40 % HBM-roofline
         # target on; configs[1] (10k reads) and configs[2] (its X-drop stage) travel as config_10k
         big = one_set(nreads, "100k" if nreads == BIG_READS else "10k" if nreads == 10000 else "none", a.steps, a.warmup,
-                      not a.no_cpu_baseline, True)
+                      not a.no_cpu_baseline, True, a.dump_outputs)
         out = {
             "metric": "candidate overlap pairs/sec", "value": big["value"], "unit": "pairs/s", "n_gpus": 1,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": big["ms_per_step"], "higher_is_better": True, "scaling": "strong",
@@ -704,7 +753,7 @@ def main():
     single = None
     colptr, _, _ = eng.get_B()
     nnz = int(colptr[-1])
-    if rank == 0:
+    if rank == 0 and a.full:
         # the same workload on ONE GPU, set-up included (a fresh context on rank 0's device): the denominator of the speed-ups
         e1 = Engine(local)
         if info.get("reserve_ms") is not None:               # like the ranks: the slab is reserved outside the timed set-up

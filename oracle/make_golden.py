@@ -305,6 +305,27 @@ def eval_kats(sets=("toy120", "toylen80", "toyhifi50"), min_overlaps=(300, 500, 
     return out
 
 
+def ref_kats():
+    """tests/golden/ref_kat.json: the reference's own answers (oracle/_ref/libbella_ref.so, in-process) on the inputs of the tests
+    that pin the oracle to the reference's code -- B of every golden set (digests), HashSpGEMM on a fresh 60-read set (the output
+    files), alignSeqAn on 150 random seed extensions"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _oracle as O
+    os.environ["OMP_NUM_THREADS"] = "1"
+    out = {"build_B": {}}
+    for name in ("sanity3", "toy120", "toylen80", "toyhifi50", "toyrep90", "toysync60", "toymin70", "toyjunk220"):
+        rs = synth.read_fastq(os.path.join(GOLD, name, "reads.fastq.gz"))
+        z = np.load(os.path.join(GOLD, name, "tuples.npz"))
+        out["build_B"][name] = [O.digest(x) for x in O.ref_build_B(rs.nreads, int(z["nkmers"]), z["kmer"], z["read"], z["pos"])]
+    rs, t = O.fresh_spgemm_input()
+    with tempfile.TemporaryDirectory() as tmp:
+        out["hashspgemm_fresh60"] = {key: O.ref_hashspgemm(rs.seqs(), rs.names, t.nkmers, t.kmer, t.read, t.pos, os.path.join(tmp, key + ".out"),
+                                                           skip=skip)[0].decode() for key, skip in (("skip", True), ("align", False))}
+    out["seqan_trials"] = [list(O.ref_seqan_align(*tr)) for tr in O.seqan_trials()]
+    json.dump(out, open(os.path.join(GOLD, "ref_kat.json"), "w"), indent=0)
+    return out
+
+
 def junk_rich_set():
     """mostly unrelated reads (coverage 2) and k = 11: almost every candidate pair is a chance k-mer hit, a third of the
     alignments start with no positive cell (the reference's uninitialised maxpos)"""
@@ -318,6 +339,9 @@ def main():
         return
     if "--logan-only" in sys.argv:
         logan_kats()
+        return
+    if "--refkat-only" in sys.argv:
+        ref_kats()
         return
     if "--junk-only" in sys.argv:
         make_set("toyjunk220", junk_rich_set(), ["-k", "11"], aslr_check=True)
@@ -337,6 +361,7 @@ def main():
     xavier_kats()
     logan_kats()
     eval_kats()
+    ref_kats()
     # read intervals of the reference's E. coli sample (dataset/ecsample-truth.txt, columns 3-4): the FASTQ itself is not in
     # the reference snapshot; the intervals shape the "ecsample-like" synthetic set of BASELINE configs[0]
     iv = np.loadtxt(os.path.join(REF, "dataset", "ecsample-truth.txt"), usecols=(2, 3), dtype=np.int64)

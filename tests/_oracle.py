@@ -288,6 +288,53 @@ def align_lines(names, seqs, pairs, x=7, k=17, err=0.15, delta=0.1, paf=False):
     return "".join(out).encode(), alns, passed
 
 
+# ---- inputs of the tests that check the oracle against the reference's own code: the answers the reference gave on them are stored in
+# tests/golden/ref_kat.json (oracle/make_golden.py --refkat-only), so those tests run where oracle/_ref was not built ----------------
+def fresh_spgemm_input():
+    """60 synthetic reads (1.5 kb, 15 % error) and their tuples under k = 17, l = 2, u = 8 (our own k-mer ids)"""
+    from bella_testkit import synth
+    rs = synth.make_reads(60, read_len=1500, err=0.15, seed=123)
+    return rs, synth.count_and_tuples(rs, 17, 2, 8)
+
+
+def seqan_trials():
+    """(row, col, i, j, x, k) of 150 random seed extensions: true overlaps at several error rates, unrelated pairs, both strands, seeds
+    at the sequence ends, X from 3 to 50"""
+    from bella_testkit import synth
+    rng = np.random.default_rng(123)
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    out = []
+    for trial in range(150):
+        L = int(rng.integers(60, 2500))
+        a = bytes(synth.BASES[rng.integers(0, 4, size=L, dtype=np.uint8)])
+        e = float(rng.choice([0.0, 0.05, 0.15, 0.3]))
+        keep = rng.random(L) >= e * 0.5
+        b = bytearray(np.frombuffer(a, np.uint8)[keep].tobytes())
+        for t in np.nonzero(rng.random(len(b)) < e * 0.5)[0]:
+            b[t] = b"ACGT"[int(rng.integers(0, 4))]
+        b = bytes(b) if trial % 5 else bytes(synth.BASES[rng.integers(0, 4, size=L, dtype=np.uint8)])
+        k, x = 17, int(rng.choice([3, 7, 15, 50]))
+        if len(b) < k + 2:
+            continue
+        i, j = int(rng.integers(0, len(a) - k)), int(rng.integers(0, len(b) - k))
+        if trial % 7 == 0:
+            i = 0
+        if trial % 11 == 0:
+            j = len(b) - k
+        b = b[:j] + a[i:i + k] + b[j + k:]
+        if trial % 2:
+            a, i = a[::-1].translate(comp), len(a) - i - k
+        out.append((a, b, i, j, x, k))
+    return out
+
+
+def digest(a) -> str:
+    """dtype, length and SHA-256 of an array's bytes"""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    return "%s:%d:%s" % (a.dtype.str, a.size, hashlib.sha256(a.tobytes()).hexdigest())
+
+
 # ---- the reference itself, in-process (only where oracle/_ref was built) ---------------------------
 _ref = None
 

@@ -168,3 +168,44 @@ def test_bench_xdrop_instruction_constants_match_the_isa_listing():
     assert get("XDROP_VALU_HALF_RATE") == int(m.group(2)) and get("XDROP_VALU_FULL_RATE") == int(m.group(3))
     assert int(m.group(1)) == int(m.group(2)) + int(m.group(3))
     assert get("XDROP_VALU_CHECKPOINT") == round(int(o.group(1)) / 16.0)
+
+
+def test_bench_dump_outputs_exact_bounded_and_repeatable(tmp_path):
+    """bench.py --dump-outputs on what bella_hip_get_pairs hands back: every value exact in its float type, the files within
+    DUMP_BYTES (a seeded sample of the records beyond it, pair_index saying which), the same files for the same records"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+
+    class Eng:
+        def __init__(self, npairs, ncols):
+            self.pairs = np.zeros(npairs, _lib.PAIR_DT)
+            for f in _lib.PAIR_DT.names:
+                hi = 1 << (8 * _lib.PAIR_DT[f].itemsize)
+                self.pairs[f] = rng.integers(hi - 1000, hi, npairs) if f in ("rid", "count") else rng.integers(0, hi, npairs)
+            self.colptr = np.sort(rng.integers(0, npairs + 1, ncols + 1)).astype(np.uint64)
+
+        def get_pairs(self, ext=True):
+            assert not ext
+            return self.pairs.copy(), None, self.colptr.copy()
+
+    for npairs, ncols in ((5000, 300), (3000000, 100000)):
+        e = Eng(npairs, ncols)
+        outs = []
+        for run in ("a", "b"):
+            d = tmp_path / ("%d_%s" % (npairs, run))
+            bench.dump_outputs(e, str(d), {"npairs": npairs, "flops": 12345})
+            outs.append({f.stem: np.load(f) for f in d.iterdir()})
+            assert sum(f.stat().st_size for f in d.iterdir()) <= bench.DUMP_BYTES + 4096
+        got = outs[0]
+        assert set(got) == set(outs[1]) and all(np.array_equal(got[k], outs[1][k]) for k in got)
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert got["totals"].tolist() == [npairs, 12345]
+        assert np.array_equal(got["colptr"], e.colptr) and "colptr_index" not in got
+        idx = got["pair_index"].astype(np.int64)
+        assert np.all(np.diff(idx) > 0) and idx[-1] < npairs
+        assert (len(idx) == npairs) == (npairs == 5000)
+        for f in _lib.PAIR_DT.names:
+            assert np.array_equal(got["pair_" + f].astype(np.int64), e.pairs[f][idx].astype(np.int64)), f

@@ -85,7 +85,6 @@ def test_choose_bin_matches_std_sort():
         assert O.lib().oracle_choose_bin(s, len(s)) == int(np.argmax(s))
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 def test_choose_bin_vs_libstdcxx_large():
     """> 16 bins: std::sort is introsort; compare our restatement with the real libstdc++ via a tiny
     C++ helper compiled on the fly (uses the reference's comparator semantics, common.h:112-117)."""
@@ -112,30 +111,37 @@ def test_choose_bin_vs_libstdcxx_large():
             assert O.lib().oracle_choose_bin(s, n) == exp, (trial, n)
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
+def _ref_kat():
+    """the reference's own answers on the inputs below (oracle/make_golden.py --refkat-only, from oracle/_ref/libbella_ref.so)"""
+    return json.load(open(os.path.join(GOLD, "ref_kat.json")))
+
+
 def test_build_B_matches_reference_code(golden):
+    """the oracle's B of every golden set == the reference's (stored digests; the reference itself too where oracle/_ref was built)"""
     g = golden
     a = O.build_B(g.rs.nreads, g.tk, g.tr, g.tp)
-    b = O.ref_build_B(g.rs.nreads, g.nkmers, g.tk, g.tr, g.tp)
-    for x, y in zip(a, b):
-        assert np.array_equal(x, y)
+    assert [O.digest(x) for x in a] == _ref_kat()["build_B"][g.name]
+    if O.have_ref():
+        b = O.ref_build_B(g.rs.nreads, g.nkmers, g.tk, g.tr, g.tp)
+        for x, y in zip(a, b):
+            assert np.array_equal(x, y)
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 def test_hashspgemm_matches_reference_code_on_fresh_input(tmp_path):
-    """Fresh synthetic input (not a committed fixture), our own k-mer ids: the reference's HashSpGEMM run
-    in-process through the shim vs the oracle, byte for byte, skip-alignment and aligned."""
-    from bella_testkit import synth
-    rs = synth.make_reads(60, read_len=1500, err=0.15, seed=123)
-    t = synth.count_and_tuples(rs, 17, 2, 8)
+    """Fresh synthetic input (generated, not a committed read set), our own k-mer ids: the reference's HashSpGEMM (its output files,
+    stored; run in-process through the shim where oracle/_ref was built) vs the oracle, byte for byte, skip-alignment and aligned."""
+    rs, t = O.fresh_spgemm_input()
     seqs = rs.seqs()
-    os.environ["OMP_NUM_THREADS"] = "1"
-    data, so, se = O.ref_hashspgemm(seqs, rs.names, t.nkmers, t.kmer, t.read, t.pos, str(tmp_path / "r.out"), skip=True)
+    kat = _ref_kat()["hashspgemm_fresh60"]
+    data, data2 = kat["skip"].encode(), kat["align"].encode()
+    if O.have_ref():
+        os.environ["OMP_NUM_THREADS"] = "1"
+        assert O.ref_hashspgemm(seqs, rs.names, t.nkmers, t.kmer, t.read, t.pos, str(tmp_path / "r.out"), skip=True)[0] == data
+        assert O.ref_hashspgemm(seqs, rs.names, t.nkmers, t.kmer, t.read, t.pos, str(tmp_path / "a.out"), skip=False)[0] == data2
     Bc, Br, Bv = O.build_B(rs.nreads, t.kmer, t.read, t.pos)
     _, _, pairs = O.spgemm(seqs, t.nkmers, Bc, Br, Bv, 17)
     assert len(pairs) > 50
     assert O.skip_lines(rs.names, rs.lengths, pairs) == data
-    data2, _, _ = O.ref_hashspgemm(seqs, rs.names, t.nkmers, t.kmer, t.read, t.pos, str(tmp_path / "a.out"), skip=False)
     got, alns, _ = O.align_lines(rs.names, seqs, pairs, 7, 17, 0.15)
     if got != data2:
         flagged = {(rs.names[p["cid"]], rs.names[p["rid"]]) for p, a in zip(pairs, alns) if a["flagged"]}
@@ -202,39 +208,17 @@ def test_logan_restatement_matches_seqan_known_answers():
         assert got == k["expect"] and ("c" if o["strand"] else "n") == k["strand"], k["name"]
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 def test_logan_restatement_matches_seqan_in_process():
     """fresh random pairs (true overlaps at several error rates, unrelated pairs, both strands, seeds at the sequence ends, X from
-    3 to 50) through the reference's own alignSeqAn"""
-    from bella_testkit import synth
-    rng = np.random.default_rng(123)
-    comp = bytes.maketrans(b"ACGT", b"TGCA")
-    n = 0
-    for trial in range(150):
-        L = int(rng.integers(60, 2500))
-        a = bytes(synth.BASES[rng.integers(0, 4, size=L, dtype=np.uint8)])
-        e = float(rng.choice([0.0, 0.05, 0.15, 0.3]))
-        keep = rng.random(L) >= e * 0.5
-        b = bytearray(np.frombuffer(a, np.uint8)[keep].tobytes())
-        for t in np.nonzero(rng.random(len(b)) < e * 0.5)[0]:
-            b[t] = b"ACGT"[int(rng.integers(0, 4))]
-        b = bytes(b) if trial % 5 else bytes(synth.BASES[rng.integers(0, 4, size=L, dtype=np.uint8)])
-        k, x = 17, int(rng.choice([3, 7, 15, 50]))
-        if len(b) < k + 2:
-            continue
-        i, j = int(rng.integers(0, len(a) - k)), int(rng.integers(0, len(b) - k))
-        if trial % 7 == 0:
-            i = 0
-        if trial % 11 == 0:
-            j = len(b) - k
-        b = b[:j] + a[i:i + k] + b[j + k:]
-        if trial % 2:
-            a, i = a[::-1].translate(comp), len(a) - i - k
-        ref, st = O.ref_seqan_align(a, b, i, j, x, k)
-        o = O.logan_align(a, b, i, j, x, k)
-        assert [int(o["score"]), int(o["begH"]), int(o["endH"]), int(o["begV"]), int(o["endV"])] == ref and ("c" if o["strand"] else "n") == st, trial
-        n += 1
-    assert n > 100
+    3 to 50) against the reference's own alignSeqAn (its answers stored; called in-process too where oracle/_ref was built)"""
+    trials = O.seqan_trials()
+    kat = _ref_kat()["seqan_trials"]
+    assert len(trials) == len(kat) > 100
+    for n, (tr, (ref, st)) in enumerate(zip(trials, kat)):
+        if O.have_ref():
+            assert O.ref_seqan_align(*tr) == (ref, st), n
+        o = O.logan_align(*tr)
+        assert [int(o["score"]), int(o["begH"]), int(o["endH"]), int(o["begV"]), int(o["endV"])] == ref and ("c" if o["strand"] else "n") == st, n
 
 
 def test_parallel_restatement_takes_the_reads_as_one_buffer():

@@ -6,7 +6,7 @@ rocprofv3 -L 2>/dev/null | grep -i -E "ICACHE|IFETCH|INST_LEVEL|SQ_WAIT_INST|SQ_
 cat $O/counters.txt | cut -c1-160
 for SET in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY" "SQ_IFETCH_LEVEL SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INST_CYCLES_SALU"; do
   D=$O/p_$(echo $SET | cut -c1-12 | tr ' ' _); rm -rf $D
-  timeout 300 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d $D -o t -- python $R/bench.py --reads 100000 --steps 3 --warmup 1 --no-cpu-baseline --no-xdrop --no-dropin --no-hifi --no-layout-ab > /dev/null 2>$D.err
+  timeout 300 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d $D -o t -- python $R/bench.py --full --reads 100000 --steps 3 --warmup 1 --no-cpu-baseline --no-xdrop --no-dropin --no-hifi --no-layout-ab > /dev/null 2>$D.err
   python - <<PY
 import csv, collections, glob
 agg = collections.defaultdict(lambda: collections.defaultdict(float))

@@ -16,6 +16,9 @@ EXT_DT = np.dtype([("nbins", "<u2"), ("support", "<u2"), ("binov", "<u2"), ("pad
 ALN_DT = np.dtype([("score", "<i4"), ("begH", "<i4"), ("endH", "<i4"), ("begV", "<i4"), ("endV", "<i4"), ("ov", "<u2"),
                    ("strand", "u1"), ("passed", "u1"), ("steps", "<u4"), ("flagged", "<u4")])
 SEED_DT = np.dtype([("rid", "<u4"), ("cid", "<u4"), ("seedH", "<u2"), ("seedV", "<u2")])
+TRACE_DT = np.dtype([("op_off", "<u8"), ("nops", "<u4"), ("band", "<u4"), ("score", "<i4"), ("tbegH", "<i4"), ("tendH", "<i4"), ("tbegV", "<i4"),
+                     ("tendV", "<i4"), ("n_eq", "<u4"), ("n_x", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("widened", "<u4")])
+assert TRACE_DT.itemsize == 56
 assert PAIR_DT.itemsize == 16 and EXT_DT.itemsize == 8 and ALN_DT.itemsize == 32 and SEED_DT.itemsize == 12
 
 
@@ -47,6 +50,12 @@ class Memory(C.Structure):
     _fields_ = [("reads_bytes", C.c_uint64), ("matrix_bytes", C.c_uint64), ("layout_A_bytes", C.c_uint64), ("layout_B_bytes", C.c_uint64),
                 ("rowlist_bytes", C.c_uint64), ("pass_bytes", C.c_uint64), ("other_bytes", C.c_uint64), ("owned_nnz", C.c_uint64),
                 ("layout_shared", C.c_uint64), ("live_nnz", C.c_uint64)]
+
+
+class TraceStats(C.Structure):
+    _fields_ = [("dp_ms", C.c_double), ("walk_ms", C.c_double), ("total_ms", C.c_double), ("pairs", C.c_uint64), ("extensions", C.c_uint64),
+                ("widened_extensions", C.c_uint64), ("repeated_pairs", C.c_uint64), ("dp_cells", C.c_uint64), ("dir_bytes", C.c_uint64), ("dir_bytes_peak", C.c_uint64),
+                ("ops", C.c_uint64), ("batches", C.c_uint32), ("band0", C.c_uint32)]
 
 
 # every symbol include/bella_hip.h declares: (name, restype, argtypes)
@@ -103,6 +112,13 @@ SIGNATURES = [
     ("bella_hip_xdrop_batch_exact", C.c_int, [vp, vp, C.c_uint64, C.POINTER(Params), vp]),
     ("bella_hip_write_output", C.c_int, [C.c_char_p, C.POINTER(Params), C.c_int, C.c_uint32, vp, vp, vp, vp, C.c_uint64, C.c_int,
                                          C.POINTER(WriteStats)]),
+    ("bella_hip_trace_pairs", C.c_int, [vp, C.POINTER(Params), C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("bella_hip_get_traces", C.c_int, [vp, vp, vp]),
+    ("bella_hip_trace_batch", C.c_int, [vp, vp, vp, C.c_uint64, C.POINTER(Params), C.c_uint32, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bella_hip_get_batch_ops", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_get_trace_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_write_output_traced", C.c_int, [C.c_char_p, C.POINTER(Params), C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int,
+                                                C.POINTER(WriteStats)]),
     ("bella_hip_get_timings", C.c_int, [vp, C.POINTER(Timings)]),
     ("bella_hip_get_memory", C.c_int, [vp, C.POINTER(Memory)]),
     ("bella_hip_get_memory_sized", C.c_int, [vp, vp, C.c_uint64]),

@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import ALN_DT, EXT_DT, PAIR_DT, SEED_DT, Memory, Params, Timings, WriteStats
+from ._lib import ALN_DT, EXT_DT, PAIR_DT, SEED_DT, TRACE_DT, Memory, Params, Timings, TraceStats, WriteStats
 
 
 class BellaHipError(RuntimeError):
@@ -312,6 +312,35 @@ class Engine:
         self._chk(fn(self.h, _p(seeds), len(seeds), C.byref(cp), _p(out)))
         return out
 
+    # ---- traced alignments (base-level: run-length ops, len << 4 | op, op 0 '=' 1 'X' 2 'I' 3 'D') ----
+    def trace_pairs(self, pars: BellaPars, band0: int = 0, passed_only: bool = True):
+        """Traces the pairs of the last align_pairs.  Returns (traces[npairs] of TRACE_DT, untraced: nops == 0; ops uint32)."""
+        nt, no = C.c_uint64(0), C.c_uint64(0)
+        cp = pars.c()
+        self._chk(self.lib.bella_hip_trace_pairs(self.h, C.byref(cp), band0, 1 if passed_only else 0, C.byref(nt), C.byref(no)))
+        tr = np.zeros(self.npairs, TRACE_DT)
+        ops = np.zeros(no.value, np.uint32)
+        self._chk(self.lib.bella_hip_get_traces(self.h, _p(tr), _p(ops)))
+        return tr, ops
+
+    def trace_batch(self, seeds: np.ndarray, alns: np.ndarray, pars: BellaPars, band0: int = 0):
+        """The same on explicit seeds and their alignments (what xdrop_batch returned for them, or any rectangles)."""
+        seeds = np.ascontiguousarray(seeds, SEED_DT)
+        alns = np.ascontiguousarray(alns, ALN_DT)
+        assert len(seeds) == len(alns)
+        tr = np.zeros(len(seeds), TRACE_DT)
+        cp = pars.c()
+        no = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_trace_batch(self.h, _p(seeds), _p(alns), len(seeds), C.byref(cp), band0, _p(tr), None, 0, C.byref(no)))
+        ops = np.zeros(no.value, np.uint32)           # the runs wait in the context: one trace, then the copy
+        self._chk(self.lib.bella_hip_get_batch_ops(self.h, _p(ops), no.value))
+        return tr, ops
+
+    def trace_stats(self) -> TraceStats:
+        t = TraceStats()
+        self._chk(self.lib.bella_hip_get_trace_stats(self.h, C.byref(t), C.sizeof(t)))
+        return t
+
     def memory(self) -> Memory:
         m = Memory()
         self._chk(self.lib.bella_hip_get_memory(self.h, C.byref(m)))
@@ -383,6 +412,38 @@ def write_output(filename: str, pars: BellaPars, names, lengths, pairs, alns=Non
                                     alns.ctypes.data if alns is not None and len(alns) else None, len(pairs), nthreads, C.byref(st))
     if rc:
         raise BellaHipError(rc, "bella_hip_write_output failed")
+    return st
+
+
+def cigar_strings(traces, ops, reverse=None):
+    """CIGAR text (= X I D) of every trace; "" for an untraced pair.  reverse (bool per trace, e.g. alns["strand"] == 1): runs in
+    reverse order, as the PAF writer prints a '-' strand line."""
+    out = []
+    for n, t in enumerate(traces):
+        o = ops[int(t["op_off"]):int(t["op_off"]) + int(t["nops"])]
+        if reverse is not None and reverse[n]:
+            o = o[::-1]
+        out.append("".join("%d%s" % (int(w) >> 4, "=XID"[int(w) & 3]) for w in o))
+    return out
+
+
+def write_output_traced(filename: str, pars: BellaPars, names, lengths, pairs, alns, traces, ops, nthreads: int = 0) -> WriteStats:
+    """bella_hip_write_output_traced: true PAF (columns 10/11 = residue matches / block length, AS ov NM cg tags); APPENDS."""
+    lib = _lib.load()
+    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    arr = (C.c_char_p * len(enc))(*enc)
+    lens = np.ascontiguousarray(lengths, np.uint32)
+    pairs = np.ascontiguousarray(pairs, PAIR_DT)
+    alns = np.ascontiguousarray(alns, ALN_DT)
+    traces = np.ascontiguousarray(traces, TRACE_DT)
+    ops = np.ascontiguousarray(ops, np.uint32)
+    assert len(pairs) == len(alns) == len(traces)
+    st = WriteStats()
+    cp = pars.c()
+    rc = lib.bella_hip_write_output_traced(filename.encode(), C.byref(cp), len(enc), C.cast(arr, C.c_void_p), lens.ctypes.data, _p(pairs), _p(alns),
+                                           _p(traces), _p(ops), len(ops), len(pairs), nthreads, C.byref(st))
+    if rc:
+        raise BellaHipError(rc, "bella_hip_write_output_traced failed")
     return st
 
 

@@ -26,6 +26,7 @@
 #include "logan.hpp"
 #include "order.hpp"
 #include "spgemm.hpp"
+#include "trace.hpp"
 #include "util.hpp"
 #include "wide.hpp"
 #include "writer.hpp"
@@ -186,6 +187,14 @@ struct bella_ctx {
     // alignment
     uint64_t nalns = 0;
     Buf alns, seeds, xest, xest2, xids, xorder, xres, xstate, xlive, lg_res, lg_redo, lg_scratch;
+    // traced alignments of the last bella_hip_trace_pairs (records index-aligned with the pairs; the ops stay on the host)
+    bool have_traces = false;
+    std::vector<bella_trace> traces;
+    std::vector<uint32_t> trace_ops;
+    std::vector<uint32_t> batch_ops;     // runs of the last bella_hip_trace_batch
+    bool have_batch_ops = false;
+    bella_trace_stats trace_stats{};
+    Buf tr_exts, tr_lists, tr_res, tr_pres, tr_opoff, tr_dirs, tr_scr, tr_ops;
     bella_timings tm{};
     hipEvent_t ev[12]{};
     uint32_t* pinned = nullptr;          // 128 host words the per-pass read backs land in
@@ -3460,6 +3469,7 @@ static int align_pairs_impl(bella_ctx* c, const bella_params* p, uint64_t* npass
     if (rc) { (void)hipDeviceSynchronize(); return rc; }      // (an error may leave class slices in flight on the side streams)
     c->nalns = c->npairs;
     c->have_alns = true;
+    c->have_traces = false;
     if (npassed) {
         // small reduction on the host side of the ABI would need a copy; count on device instead
         ENSURE(c, c->cubtmp, 64);
@@ -3539,6 +3549,298 @@ int bella_hip_get_timings(bella_ctx* c, bella_timings* t) {
     if (!c || !t) return BELLA_ERR_BAD_ARG;
     *t = c->tm;
     return 0;
+}
+
+}  // extern "C"
+
+// ---- traced alignments (trace.hpp) ---------------------------------------------------------------------------
+namespace {
+struct TraceJob { uint32_t rid, cid, seedH, seedV; bella_aln a; };
+
+// Traces jobs[0 .. n): out[n] records, ops appended to `ops` (op_off counts from the vector's start).  Pairs run in batches sized by
+// the free device memory (the direction bytes dominate); a pair whose path touched its band's edge on a side goes back into the queue
+// with that side's band doubled, until no side touches or the band holds the side's whole rectangle.
+int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& jobs, uint32_t band0, bella_trace* out, std::vector<uint32_t>& ops,
+              bella_trace_stats& st) {
+    using clk = std::chrono::steady_clock;
+    const auto t_begin = clk::now();
+    st = bella_trace_stats{};
+    if (band0 == 0) band0 = BELLA_TRACE_DEFAULT_BAND;
+    uint32_t b0 = kTrMinBand;
+    while (b0 < band0 && b0 < kTrMaxBand) b0 <<= 1;
+    st.band0 = b0;
+    const uint32_t k = p->kmer_size;
+    const size_t n = jobs.size();
+    if (!n) return 0;
+    std::vector<uint64_t> off((size_t)c->nreads + 1);
+    HIPCHK(c, hipMemcpy(off.data(), c->roff.p, 8 * ((size_t)c->nreads + 1), hipMemcpyDeviceToHost));
+    struct Side { int64_t gH, gV; uint32_t n, m, band, cover; int32_t dH, dV; };
+    struct Work { Side s[2]; uint32_t comp, widened; int32_t seedHo; };
+    std::vector<Work> W(n);
+    for (size_t q = 0; q < n; ++q) {
+        const TraceJob& j = jobs[q];
+        if (j.rid >= c->nreads || j.cid >= c->nreads) return fail(c, BELLA_ERR_BAD_ARG, "trace %zu: read id out of range", q);
+        const int64_t lh = (int64_t)(off[j.rid + 1] - off[j.rid]), lv = (int64_t)(off[j.cid + 1] - off[j.cid]);
+        if ((int64_t)j.seedH + k > lh || (int64_t)j.seedV + k > lv) return fail(c, BELLA_ERR_BAD_ARG, "trace %zu: k-mer past the end of a read", q);
+        if (j.a.strand > 1) return fail(c, BELLA_ERR_BAD_ARG, "trace %zu: strand must be 0 or 1", q);
+        const int64_t sH = j.a.strand ? lh - (int64_t)j.seedH - k : (int64_t)j.seedH, sV = j.seedV;     // the seed on the oriented H (align.hpp:181-182)
+        auto clampi = [](int64_t x, int64_t hi) { return (uint32_t)(x < 0 ? 0 : (x > hi ? hi : x)); };
+        Work& w = W[q];
+        w.comp = j.a.strand ? 3u : 0u;
+        w.widened = 0;
+        w.seedHo = (int32_t)sH;
+        const int64_t gH = (int64_t)off[j.rid], gV = (int64_t)off[j.cid];
+        Side& L = w.s[0];
+        Side& R = w.s[1];
+        L.m = clampi(sH - j.a.begH, sH); L.n = clampi(sV - j.a.begV, sV);
+        // (xavier.h:356-360: when the right extension does not run the reference overwrites the BEGIN points with the reads' lengths; a
+        // begin point behind the seed says nothing about the left side, whose rectangle then reaches to the reads' starts)
+        if (j.a.begH > sH || j.a.begV > sV) { L.m = (uint32_t)sH; L.n = (uint32_t)sV; }
+        R.m = clampi((int64_t)j.a.endH - (sH + k), lh - sH - k); R.n = clampi((int64_t)j.a.endV - (sV + k), lv - sV - k);
+        // element t of the left sequences: oriented H at sH - 1 - t, V at sV - 1 - t; of the right ones: sH + k + t, sV + k + t
+        if (!j.a.strand) { L.gH = gH + sH - 1; L.dH = -1; R.gH = gH + sH + k; R.dH = 1; }
+        else { L.gH = gH + lh - sH; L.dH = 1; R.gH = gH + lh - 1 - sH - k; R.dH = -1; }                  // oriented H[x] = complement of H[len - 1 - x]
+        L.gV = gV + sV - 1; L.dV = -1; R.gV = gV + sV + k; R.dV = 1;
+        for (Side& s : w.s) { s.cover = trace_cover_band(s.n, s.m); s.band = b0 < s.cover ? b0 : s.cover; }
+    }
+    // memory of a batch: directions + (wide) scratch; a quarter of what is free, at most 16 GB, at least what the largest pair needs
+    size_t mfree = 0, mtotal = 0;
+    HIPCHK(c, hipMemGetInfo(&mfree, &mtotal));
+    mfree += c->pool.bytes + c->pool.arena.largest_hole() + c->tr_dirs.cap;
+    uint64_t budget = std::min<uint64_t>((uint64_t)mfree / 4, 16ull << 30);
+    if (budget < (64ull << 20)) budget = 64ull << 20;
+    auto side_dir_bytes = [](const Side& s) { return ((uint64_t)trace_rows(s.n, s.m, s.band) * (s.band / 4) + 15) & ~15ull; };
+    auto side_scr_ints = [](const Side& s) { return s.band > kTrRegBand ? 2ull * s.band : 0ull; };
+    constexpr uint32_t kMaxBatchPairs = 1u << 20;
+    std::vector<uint32_t> queue(n), next;
+    for (size_t q = 0; q < n; ++q) queue[q] = (uint32_t)q;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1)); HIPCHK(c, hipEventCreate(&e2));
+    struct EvGuard { hipEvent_t a, b, d; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(d); } } evg{e0, e1, e2};
+    std::vector<TraceExt> exts;
+    std::vector<uint32_t> lists[4];
+    std::vector<TracePairRes> pres;
+    std::vector<TraceExtRes> eres;
+    std::vector<uint64_t> opoff;
+    const uint32_t* const packed = ptr<uint32_t>(c->packed);
+    while (!queue.empty()) {
+        next.clear();
+        size_t at = 0;
+        while (at < queue.size()) {
+            // ---- cut a batch
+            uint64_t dbytes = 0, sints = 0;
+            exts.clear();
+            for (auto& l : lists) l.clear();
+            size_t end = at;
+            while (end < queue.size() && end - at < kMaxBatchPairs) {
+                const Work& w = W[queue[end]];
+                const uint64_t need = side_dir_bytes(w.s[0]) + side_dir_bytes(w.s[1]) + 4 * (side_scr_ints(w.s[0]) + side_scr_ints(w.s[1]));
+                if (end > at && dbytes + 4 * sints + need > budget) break;
+                for (int sd = 0; sd < 2; ++sd) {
+                    const Side& s = w.s[sd];
+                    TraceExt e{};
+                    e.gH = s.gH; e.gV = s.gV; e.dir_off = dbytes; e.scr_off = sints; e.n = s.n; e.m = s.m; e.band = s.band; e.dH = s.dH; e.dV = s.dV;
+                    e.comp = w.comp;
+                    const uint32_t cls = s.band == 256 ? 0u : s.band == 512 ? 1u : s.band == 1024 ? 2u : 3u;
+                    lists[cls].push_back((uint32_t)exts.size());
+                    exts.push_back(e);
+                    dbytes += side_dir_bytes(s);
+                    sints += side_scr_ints(s);
+                    st.dp_cells += (uint64_t)trace_rows(s.n, s.m, s.band) * s.band;
+                    st.dir_bytes += side_dir_bytes(s);
+                }
+                ++end;
+            }
+            const uint32_t nb = (uint32_t)(end - at);
+            st.batches++;
+            st.extensions += 2ull * nb;
+            if (dbytes > st.dir_bytes_peak) st.dir_bytes_peak = dbytes;
+            // ---- upload, DP
+            ENSURE(c, c->tr_exts, sizeof(TraceExt) * exts.size());
+            ENSURE(c, c->tr_lists, 4 * exts.size());
+            ENSURE(c, c->tr_res, sizeof(TraceExtRes) * exts.size());
+            ENSURE(c, c->tr_pres, sizeof(TracePairRes) * nb);
+            ENSURE(c, c->tr_opoff, 8 * (size_t)nb);
+            ENSURE(c, c->tr_dirs, (size_t)dbytes + 64);
+            if (sints) ENSURE(c, c->tr_scr, 4 * (size_t)sints + 64);
+            HIPCHK(c, hipMemcpyAsync(c->tr_exts.p, exts.data(), sizeof(TraceExt) * exts.size(), hipMemcpyHostToDevice, c->stream));
+            uint32_t lo[5] = {0, 0, 0, 0, 0};
+            {
+                std::vector<uint32_t> all;
+                all.reserve(exts.size());
+                for (int q = 0; q < 4; ++q) { lo[q] = (uint32_t)all.size(); all.insert(all.end(), lists[q].begin(), lists[q].end()); }
+                lo[4] = (uint32_t)all.size();
+                HIPCHK(c, hipMemcpyAsync(c->tr_lists.p, all.data(), 4 * all.size(), hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));             // (the host vectors are reused by the next batch)
+            }
+            const TraceExt* const dex = ptr<TraceExt>(c->tr_exts);
+            const uint32_t* const dl = ptr<uint32_t>(c->tr_lists);
+            uint8_t* const ddirs = ptr<uint8_t>(c->tr_dirs);
+            TraceExtRes* const dres = ptr<TraceExtRes>(c->tr_res);
+            HIPCHK(c, hipEventRecord(e0, c->stream));
+            const uint32_t wpb = kTraceBlock / 64;
+            if (lo[1] > lo[0]) { k_trace_dp<4><<<nblk(lo[1] - lo[0], wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[0], lo[1] - lo[0], packed, ddirs, dres); KCHK(c); }
+            if (lo[2] > lo[1]) { k_trace_dp<8><<<nblk(lo[2] - lo[1], wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[1], lo[2] - lo[1], packed, ddirs, dres); KCHK(c); }
+            if (lo[3] > lo[2]) { k_trace_dp<16><<<nblk(lo[3] - lo[2], wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[2], lo[3] - lo[2], packed, ddirs, dres); KCHK(c); }
+            if (lo[4] > lo[3]) { k_trace_dp_wide<<<lo[4] - lo[3], 64, 0, c->stream>>>(dex, dl + lo[3], lo[4] - lo[3], packed, ddirs, ptr<int>(c->tr_scr), dres); KCHK(c); }
+            HIPCHK(c, hipEventRecord(e1, c->stream));
+            k_trace_count<<<nblk(nb, 64), 64, 0, c->stream>>>(dex, dres, nb, packed, ddirs, (int)k, ptr<TracePairRes>(c->tr_pres));
+            KCHK(c);
+            HIPCHK(c, hipEventRecord(e2, c->stream));
+            pres.resize(nb);
+            eres.resize(exts.size());
+            HIPCHK(c, hipMemcpyAsync(pres.data(), c->tr_pres.p, sizeof(TracePairRes) * nb, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(eres.data(), c->tr_res.p, sizeof(TraceExtRes) * exts.size(), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            st.dp_ms += ev_ms(e0, e1);
+            st.walk_ms += ev_ms(e1, e2);
+            // ---- who is done, who goes again
+            opoff.assign(nb, ~0ull);
+            uint64_t bops = 0;
+            for (uint32_t q = 0; q < nb; ++q) {
+                const uint32_t id = queue[at + q];
+                Work& w = W[id];
+                // (a pair goes again as a whole: the writing walk needs the directions of both sides in one batch, so the side that did not
+                // touch is computed again with its band unchanged -- same result; at ~0.1 % of the pairs this costs nothing measurable)
+                bool again = false;
+                for (int sd = 0; sd < 2; ++sd)
+                    if ((pres[q].touch >> sd & 1u) && w.s[sd].band < w.s[sd].cover) { w.s[sd].band *= 2; w.widened++; st.widened_extensions++; again = true; }
+                if (again) { next.push_back(id); st.repeated_pairs++; continue; }
+                const TraceJob& j = jobs[id];
+                const TraceExtRes &rl = eres[2 * q], &rr = eres[2 * q + 1];
+                bella_trace& t = out[id];
+                t.op_off = ops.size() + bops;
+                t.nops = pres[q].nops;
+                t.band = std::max(w.s[0].band, w.s[1].band);
+                t.score = rl.score + pres[q].seed_score + rr.score;
+                t.tbegH = w.seedHo - (int32_t)rl.bj; t.tbegV = (int32_t)j.seedV - (int32_t)rl.bi;
+                t.tendH = w.seedHo + (int32_t)k + (int32_t)rr.bj; t.tendV = (int32_t)j.seedV + (int32_t)k + (int32_t)rr.bi;
+                t.n_eq = pres[q].n_eq; t.n_x = pres[q].n_x; t.n_ins = pres[q].n_ins; t.n_del = pres[q].n_del;
+                t.widened = w.widened;
+                opoff[q] = bops;
+                bops += pres[q].nops;
+                st.pairs++;
+            }
+            if (bops) {
+                ENSURE(c, c->tr_ops, 4 * (size_t)bops);
+                HIPCHK(c, hipMemcpyAsync(c->tr_opoff.p, opoff.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, hipEventRecord(e0, c->stream));
+                k_trace_write<<<nblk(nb, 64), 64, 0, c->stream>>>(dex, dres, nb, packed, ddirs, (int)k, ptr<uint64_t>(c->tr_opoff), ptr<TracePairRes>(c->tr_pres),
+                                                                  ptr<uint32_t>(c->tr_ops));
+                KCHK(c);
+                HIPCHK(c, hipEventRecord(e1, c->stream));
+                const size_t base = ops.size();
+                ops.resize(base + bops);
+                HIPCHK(c, c->stager.d2h(ops.data() + base, c->tr_ops.p, 4 * (size_t)bops, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                st.walk_ms += ev_ms(e0, e1);
+                st.ops += bops;
+            }
+            at = end;
+        }
+        queue.swap(next);
+    }
+    st.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    return 0;
+}
+
+void trace_release(bella_ctx* c) {      // the batch buffers go back (directions: gigabytes) once a call is over
+    for (Buf* b : {&c->tr_exts, &c->tr_lists, &c->tr_res, &c->tr_pres, &c->tr_opoff, &c->tr_dirs, &c->tr_scr, &c->tr_ops}) release(*b);
+}
+}  // namespace
+
+extern "C" {
+
+int bella_hip_trace_pairs(bella_ctx* c, const bella_params* p, uint32_t band0, int passed_only, uint64_t* ntraced, uint64_t* nops) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_alns) return fail(c, BELLA_ERR_STATE, "align_pairs first");
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->have_traces = false;
+    const size_t n = (size_t)c->nalns;
+    std::vector<bella_pair> pairs(n);
+    std::vector<bella_aln> alns(n);
+    if (n) {
+        HIPCHK(c, c->stager.d2h(pairs.data(), c->pairs.p, sizeof(bella_pair) * n, c->stream));
+        HIPCHK(c, c->stager.d2h(alns.data(), c->alns.p, sizeof(bella_aln) * n, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    std::vector<TraceJob> jobs;
+    std::vector<size_t> which;
+    for (size_t i = 0; i < n; ++i)
+        if (!passed_only || alns[i].passed) { jobs.push_back(TraceJob{pairs[i].rid, pairs[i].cid, pairs[i].seedH, pairs[i].seedV, alns[i]}); which.push_back(i); }
+    std::vector<bella_trace> tr(jobs.size());
+    c->trace_ops.clear();
+    rc = run_trace(c, p, jobs, band0, tr.data(), c->trace_ops, c->trace_stats);
+    trace_release(c);
+    if (rc) { (void)hipDeviceSynchronize(); return rc; }
+    c->traces.assign(n, bella_trace{});
+    for (size_t i = 0; i < which.size(); ++i) c->traces[which[i]] = tr[i];
+    c->have_traces = true;
+    if (ntraced) *ntraced = jobs.size();
+    if (nops) *nops = c->trace_ops.size();
+    return 0;
+}
+
+int bella_hip_get_traces(bella_ctx* c, bella_trace* out, uint32_t* ops) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_traces || !c->have_alns) return fail(c, BELLA_ERR_STATE, "trace_pairs first");
+    if (out && !c->traces.empty()) std::memcpy(out, c->traces.data(), sizeof(bella_trace) * c->traces.size());
+    if (ops && !c->trace_ops.empty()) std::memcpy(ops, c->trace_ops.data(), 4 * c->trace_ops.size());
+    return 0;
+}
+
+int bella_hip_trace_batch(bella_ctx* c, const bella_seed* seeds, const bella_aln* alns, uint64_t n, const bella_params* p, uint32_t band0, bella_trace* out,
+                          uint32_t* ops, uint64_t ops_cap, uint64_t* nops) {
+    if (!c || !p || (n && (!seeds || !alns || !out))) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
+    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (p->kmer_size < 1 || p->kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<TraceJob> jobs((size_t)n);
+    for (uint64_t i = 0; i < n; ++i) jobs[(size_t)i] = TraceJob{seeds[i].rid, seeds[i].cid, seeds[i].seedH, seeds[i].seedV, alns[i]};
+    std::vector<uint32_t>& v = c->batch_ops;       // the runs stay with the context: a caller that could not know their number fetches them
+    v.clear();
+    c->have_batch_ops = false;
+    bella_trace_stats st;
+    const int rc = run_trace(c, p, jobs, band0, out, v, st);
+    trace_release(c);
+    if (rc) { (void)hipDeviceSynchronize(); return rc; }
+    c->trace_stats = st;
+    c->have_batch_ops = true;
+    if (nops) *nops = v.size();
+    if (!ops) return 0;
+    if (v.size() > ops_cap) return fail(c, BELLA_ERR_NOMEM, "trace_batch: %zu ops, room for %llu (bella_hip_get_batch_ops hands them out)", v.size(), (unsigned long long)ops_cap);
+    if (!v.empty()) std::memcpy(ops, v.data(), 4 * v.size());
+    return 0;
+}
+
+int bella_hip_get_batch_ops(bella_ctx* c, uint32_t* ops, uint64_t ops_cap) {
+    if (!c || (!ops && ops_cap)) return BELLA_ERR_BAD_ARG;
+    if (!c->have_batch_ops) return fail(c, BELLA_ERR_STATE, "trace_batch first");
+    if (c->batch_ops.size() > ops_cap) return fail(c, BELLA_ERR_BAD_ARG, "get_batch_ops: %zu ops, room for %llu", c->batch_ops.size(), (unsigned long long)ops_cap);
+    if (!c->batch_ops.empty()) std::memcpy(ops, c->batch_ops.data(), 4 * c->batch_ops.size());
+    return 0;
+}
+
+int bella_hip_get_trace_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    std::memcpy(out, &c->trace_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_trace_stats)));
+    return 0;
+}
+
+int bella_hip_write_output_traced(const char* path, const bella_params* p, uint32_t nreads, const char* const* names, const uint32_t* lens, const bella_pair* pairs,
+                                  const bella_aln* alns, const bella_trace* traces, const uint32_t* ops, uint64_t nops_total, uint64_t npairs, int nthreads,
+                                  bella_write_stats* stats) {
+    std::string err;
+    if ((npairs && (!traces || !alns)) || (nops_total && !ops) || (p && p->skip_alignment)) {     // (no pairs: nothing is required, as in bella_hip_write_output)
+        fprintf(stderr, "bella_hip_write_output_traced: traces and alignments are required\n");
+        return BELLA_ERR_BAD_ARG;
+    }
+    static const bella_trace none{};
+    const int rc = write_output_impl(path, p, 1, nreads, names, lens, pairs, alns, npairs, nthreads, stats, err, traces ? traces : &none, ops, nops_total);
+    if (rc) fprintf(stderr, "bella_hip_write_output_traced: %s\n", err.c_str());
+    return rc;
 }
 
 }  // extern "C"

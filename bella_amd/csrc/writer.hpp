@@ -66,7 +66,7 @@ inline int writer_seed_overlap(const bella_pair& p, int len1, int len2, unsigned
 // one record -> its line (or nothing: an alignment that did not pass); returns whether a line was produced
 template <typename Sink>
 inline bool format_record(Sink& b, const bella_params& p, int paf, const char* const* names, const uint32_t* name_len, const uint32_t* lens,
-                          const bella_pair& q, const bella_aln* a) {
+                          const bella_pair& q, const bella_aln* a, const bella_trace* tr = nullptr, const uint32_t* ops = nullptr) {
     const uint32_t r1 = q.rid, r2 = q.cid;
     const unsigned short l1 = (unsigned short)lens[r1], l2 = (unsigned short)lens[r2];       // overlap.hpp:539-540 (unsigned short)
     if (p.skip_alignment) {                                                      // overlap.hpp:577-588
@@ -76,6 +76,22 @@ inline bool format_record(Sink& b, const bella_params& p, int paf, const char* c
         return true;
     }
     if (!a->passed) return false;                                                // PostAlignDecision, overlap.hpp:413-497
+    if (tr) {                                                                    // true PAF (bella_hip_write_output_traced): no reference counterpart
+        if (!tr->nops) return false;
+        int begH = tr->tbegH, endH = tr->tendH;
+        if (a->strand) { const unsigned int tmp = (unsigned int)begH; begH = l1 - endH; endH = (int)(l1 - tmp); }
+        const uint64_t nm = (uint64_t)tr->n_x + tr->n_ins + tr->n_del;
+        b.str(names[r2], name_len[r2]); b.ch('\t'); b.u(l2); b.ch('\t'); b.i(tr->tbegV); b.ch('\t'); b.i(tr->tendV); b.ch('\t'); b.ch(a->strand ? '-' : '+'); b.ch('\t');
+        b.str(names[r1], name_len[r1]); b.ch('\t'); b.u(l1); b.ch('\t'); b.i(begH); b.ch('\t'); b.i(endH); b.ch('\t'); b.u(tr->n_eq); b.ch('\t'); b.u(tr->n_eq + nm); b.ch('\t');
+        b.u(255); b.str("\tAS:i:", 6); b.i(a->score); b.str("\tov:i:", 6); b.u(a->ov); b.str("\tNM:i:", 6); b.u(nm); b.str("\tcg:Z:", 6);
+        const uint32_t* const o = ops + tr->op_off;
+        for (uint32_t x = 0; x < tr->nops; ++x) {
+            const uint32_t w = a->strand ? o[tr->nops - 1 - x] : o[x];
+            b.u(w >> 4); b.ch("=XID"[w & 3]);
+        }
+        b.ch('\n');
+        return true;
+    }
     if (!paf) {
         b.str(names[r2], name_len[r2]); b.ch('\t'); b.str(names[r1], name_len[r1]); b.ch('\t');
         b.u(q.count); b.ch('\t'); b.i(a->score); b.ch('\t'); b.u(a->ov); b.ch('\t'); b.ch(a->strand ? 'c' : 'n'); b.ch('\t');
@@ -93,6 +109,7 @@ inline bool format_record(Sink& b, const bella_params& p, int paf, const char* c
 struct WriteShare {
     bella_write_stats st{};
     bool bad_id = false;
+    bool bad_trace = false;                                                      // a trace record whose runs lie outside the ops array
     bool io_fail = false;
     bool size_mismatch = false;
     std::vector<char> buf;                                                       // the piece being formatted
@@ -100,11 +117,13 @@ struct WriteShare {
 
 // pass 1 of a share: validate, measure, and the statistics of overlap.hpp:531-590
 inline void measure_share(WriteShare& w, const bella_params& p, int paf, uint32_t nreads, const char* const* names, const uint32_t* name_len,
-                          const uint32_t* lens, const bella_pair* pairs, const bella_aln* alns, uint64_t lo, uint64_t hi) {
+                          const uint32_t* lens, const bella_pair* pairs, const bella_aln* alns, uint64_t lo, uint64_t hi, const bella_trace* traces = nullptr,
+                          const uint32_t* ops = nullptr, uint64_t nops_total = 0) {
     CountSink c;
     for (uint64_t n = lo; n < hi; ++n) {
         const bella_pair& q = pairs[n];
         if (q.rid >= nreads || q.cid >= nreads) { w.bad_id = true; return; }
+        if (traces && traces[n].nops && (traces[n].op_off > nops_total || traces[n].nops > nops_total - traces[n].op_off)) { w.bad_trace = true; return; }
         if (!p.skip_alignment) {
             const bella_aln& a = alns[n];
             ++w.st.aligned_pairs;
@@ -113,7 +132,7 @@ inline void measure_share(WriteShare& w, const bella_params& p, int paf, uint32_
             if (!a.passed) w.st.bases_failed += (uint64_t)(int64_t)(a.endV - a.begV);
             else w.st.bases_passed += (uint64_t)(int64_t)(a.endV - a.begV);
         }
-        if (format_record(c, p, paf, names, name_len, lens, q, alns ? alns + n : nullptr)) ++w.st.lines;
+        if (format_record(c, p, paf, names, name_len, lens, q, alns ? alns + n : nullptr, traces ? traces + n : nullptr, ops)) ++w.st.lines;
     }
     w.st.bytes = c.n;
 }
@@ -126,7 +145,8 @@ inline void measure_share(WriteShare& w, const bella_params& p, int paf, uint32_
 // 690-1180 ms at 64-256; formatting into a shared mapping of the file instead collapses on page-fault contention: 1.0 s at 8
 // threads, 7.0 s at 256).  So nthreads = 0 means min(hardware threads, 16).
 inline int write_output_impl(const char* path, const bella_params* p, int paf, uint32_t nreads, const char* const* names, const uint32_t* lens,
-                             const bella_pair* pairs, const bella_aln* alns, uint64_t npairs, int nthreads, bella_write_stats* out, std::string& err) {
+                             const bella_pair* pairs, const bella_aln* alns, uint64_t npairs, int nthreads, bella_write_stats* out, std::string& err,
+                             const bella_trace* traces = nullptr, const uint32_t* ops = nullptr, uint64_t nops_total = 0) {
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     if (!path || !p || (nreads && (!names || !lens)) || (npairs && !pairs) || (npairs && !p->skip_alignment && !alns)) { err = "null argument"; return BELLA_ERR_BAD_ARG; }
@@ -144,9 +164,11 @@ inline int write_output_impl(const char* path, const bella_params* p, int paf, u
         for (auto& x : th) x.join();
     };
     auto lo_of = [&](int t) { return npairs * (uint64_t)t / (uint64_t)T; };
-    on_threads([&](int t) { measure_share(W[(size_t)t], *p, paf, nreads, names, name_len.data(), lens, pairs, alns, lo_of(t), lo_of(t + 1)); });
+    on_threads([&](int t) { measure_share(W[(size_t)t], *p, paf, nreads, names, name_len.data(), lens, pairs, alns, lo_of(t), lo_of(t + 1), traces, ops, nops_total); });
     for (auto& w : W)
         if (w.bad_id) { err = "pair record with a read id out of range"; return BELLA_ERR_BAD_ARG; }
+    for (auto& w : W)
+        if (w.bad_trace) { err = "trace record whose runs lie outside the ops array"; return BELLA_ERR_BAD_ARG; }
     const auto t1 = clk::now();
     // sizes -> offsets -> every thread puts its lines at its place (overlap.hpp:603-642), after what the file already holds
     // (the file is opened in append mode there, :613: a later stage goes behind an earlier one)
@@ -163,6 +185,11 @@ inline int write_output_impl(const char* path, const bella_params* p, int paf, u
         const size_t kPiece = (size_t)1 << 20;
         size_t slack = 256;
         for (uint32_t r = 0; r < nreads; ++r) slack = std::max<size_t>(slack, 2 * (size_t)name_len[r] + 256);           // (one line at most)
+        if (traces) {                                                            // (a traced line carries its runs: at most 9 digits + the op letter each)
+            uint32_t most = 0;
+            for (uint64_t n = 0; n < npairs; ++n) most = std::max(most, traces[n].nops);
+            slack += 10 * (size_t)most;
+        }
         {
             // every thread: format about a megabyte into a buffer that stays in its cache, write it at its running offset, again
             on_threads([&](int t) {
@@ -182,7 +209,7 @@ inline int write_output_impl(const char* path, const bella_params* p, int paf, u
                     return true;
                 };
                 for (uint64_t n = lo_of(t), hi = lo_of(t + 1); n < hi; ++n) {
-                    format_record(s, *p, paf, names, name_len.data(), lens, pairs[n], alns ? alns + n : nullptr);
+                    format_record(s, *p, paf, names, name_len.data(), lens, pairs[n], alns ? alns + n : nullptr, traces ? traces + n : nullptr, ops);
                     if ((size_t)(s.p - w.buf.data()) >= kPiece && !flush()) return;
                 }
                 if (!flush()) return;

@@ -53,6 +53,8 @@ struct Worker {
     std::vector<uint64_t> colptr;            // colptrC of the last pass (nreads + 1)
     RawBuf<bella_pair> pairs;
     RawBuf<bella_aln> alns;
+    RawBuf<bella_trace> traces;              // --cigar: the stage's traced alignments and their runs
+    RawBuf<uint32_t> ops;
     uint64_t nnzc = 0;
 };
 // what the last call of this process did (tests, logs): every column must be computed by the numeric phase exactly once
@@ -103,6 +105,8 @@ struct StageOpts {
     const char* filename = nullptr;  // the output file: lines are APPENDED
     const char* tag = "bella_hip_driver.hpp";   // the log lines' file name
     int exact = 0;                   // alignments by the exact (growing band) X-drop of the reference's CUDA build
+    int cigar = 0;                   // true PAF: every stage traces its passed pairs before it writes them (needs paf, no skip_alignment)
+    uint32_t trace_band = 0;         // first band of the traces; 0 = the library's default
 };
 
 // Stage plan (overlap.hpp:365-404,682-710), passes, alignment, output.  W[g].ctx holds the operands, laid out for the output columns
@@ -138,6 +142,13 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
                 else check(w.ctx, bella_hip_align_pairs(w.ctx, &p, &npass), "bella_hip_align_pairs");
                 w.alns.resize(w.nnzc);
                 if (w.nnzc) check(w.ctx, bella_hip_get_alignments(w.ctx, w.alns.data()), "bella_hip_get_alignments");
+                if (o.cigar) {
+                    uint64_t ntr = 0, nops = 0;
+                    check(w.ctx, bella_hip_trace_pairs(w.ctx, &p, o.trace_band, 1, &ntr, &nops), "bella_hip_trace_pairs");
+                    w.traces.resize(w.nnzc);
+                    w.ops.resize(nops);                                       // (host memory: 4 bytes per run; -m stages bound it as they bound the records)
+                    check(w.ctx, bella_hip_get_traces(w.ctx, w.traces.data(), w.ops.data()), "bella_hip_get_traces");
+                }
             }
         });
     };
@@ -205,16 +216,30 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         uint64_t np = W[0].nnzc;
         std::vector<bella_pair> mp;
         std::vector<bella_aln> ma;
+        std::vector<bella_trace> mt;
+        std::vector<uint32_t> mo;
+        const bella_trace* tt = W[0].traces.data();
+        const uint32_t* oo = W[0].ops.data();
+        uint64_t no = W[0].ops.size();
         if (N > 1) {
             for (uint32_t i = lo; i < hi; ++i) {
                 const Worker& w = W[(size_t)(i % (uint32_t)N)];
                 mp.insert(mp.end(), w.pairs.begin() + (std::ptrdiff_t)w.colptr[i], w.pairs.begin() + (std::ptrdiff_t)w.colptr[i + 1]);
                 if (!p.skip_alignment) ma.insert(ma.end(), w.alns.begin() + (std::ptrdiff_t)w.colptr[i], w.alns.begin() + (std::ptrdiff_t)w.colptr[i + 1]);
+                if (o.cigar)
+                    for (uint64_t q = w.colptr[i]; q < w.colptr[i + 1]; ++q) {       // the runs move into one array, the records' offsets with them
+                        bella_trace t = w.traces.data()[q];
+                        const uint32_t* src = w.ops.data() + t.op_off;
+                        t.op_off = mo.size();
+                        mo.insert(mo.end(), src, src + t.nops);
+                        mt.push_back(t);
+                    }
             }
-            pp = mp.data(); aa = ma.data(); np = mp.size();
+            pp = mp.data(); aa = ma.data(); np = mp.size(); tt = mt.data(); oo = mo.data(); no = mo.size();
         }
         bella_write_stats ws;
-        const int wrc = bella_hip_write_output(o.filename, &p, o.paf ? 1 : 0, nreads, names, lens, pp, p.skip_alignment ? nullptr : aa, np, 0, &ws);
+        const int wrc = o.cigar ? bella_hip_write_output_traced(o.filename, &p, nreads, names, lens, pp, aa, tt, oo, no, np, 0, &ws)
+                                : bella_hip_write_output(o.filename, &p, o.paf ? 1 : 0, nreads, names, lens, pp, p.skip_alignment ? nullptr : aa, np, 0, &ws);
         if (wrc) check(nullptr, wrc, "bella_hip_write_output");
         cs.write_seconds += ws.seconds;
         cs.lines += ws.lines;

@@ -15,6 +15,8 @@
 // count).  --tuples FILE takes the reference's `readbykmers.mtx` dump (include/common/bellaio.h:2-47: "nreads nkmers ntuples", then
 // "read+1 kmer+1 pos" per line) instead of counting: same ids as that reference run, same output file byte for byte.
 //
+// --paf --cigar: true PAF: every stage traces its passed pairs on the device before it writes them.
+//
 // Not built (rejected loudly): --hopc, --estimate, --split-count > 1.
 #include <sys/stat.h>
 #include <chrono>
@@ -36,7 +38,8 @@ struct Options {
     std::string fastq_list, output, tuples;
     int kmer = 17, xdrop = 7, memory = 8000, bin_size = 500, gpus = 1, split_count = 1, window = 0, upper = 8, lower = 2;
     double error = 0.15, deviation = 0.1;
-    bool estimate = false, skip_alignment = false, paf = false, hopc = false, syncmer = false, help = false, exact = false;
+    bool estimate = false, skip_alignment = false, paf = false, hopc = false, syncmer = false, help = false, exact = false, cigar = false;
+    int trace_band = 0;
 };
 
 const char* kHelp =
@@ -63,6 +66,8 @@ const char* kHelp =
     "  -l, --lower-freq arg       K-mer Frequency Lower Bound (default: 2)\n"
     "      --tuples arg           readbykmers.mtx of a reference run: its k-mer ids instead of counting\n"
     "      --exact-xdrop          the exact (growing band) X-drop of the reference's GPU build instead of Xavier\n"
+    "      --cigar                with --paf: true PAF -- base-level alignment of every line (residue matches, block length, NM, cg:Z:)\n"
+    "      --trace-band arg       first band of the base-level alignments, in diagonals (default: 256; doubled where a path touches it)\n"
     "  -h, --help                 Usage\n";
 
 [[noreturn]] void die(const std::string& msg) {
@@ -79,7 +84,7 @@ Options parse(int argc, char** argv) {
         {"error", 'e', 2, &o.error}, {"estimate", 0, 0, &o.estimate}, {"skip-alignment", 0, 0, &o.skip_alignment}, {"memory", 'm', 1, &o.memory},
         {"score-deviation", 0, 2, &o.deviation}, {"bin-size", 'b', 1, &o.bin_size}, {"paf", 0, 0, &o.paf}, {"gpus", 'g', 1, &o.gpus},
         {"split-count", 0, 1, &o.split_count}, {"hopc", 0, 0, &o.hopc}, {"window", 'w', 1, &o.window}, {"syncmer", 's', 0, &o.syncmer},
-        {"upper-freq", 'u', 1, &o.upper}, {"lower-freq", 'l', 1, &o.lower}, {"tuples", 0, 3, &o.tuples}, {"exact-xdrop", 0, 0, &o.exact},
+        {"upper-freq", 'u', 1, &o.upper}, {"lower-freq", 'l', 1, &o.lower}, {"tuples", 0, 3, &o.tuples}, {"exact-xdrop", 0, 0, &o.exact}, {"cigar", 0, 0, &o.cigar}, {"trace-band", 0, 1, &o.trace_band},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
         char* end = nullptr;
@@ -163,6 +168,10 @@ int main(int argc, char** argv) {
     if (o.hopc) die("--hopc is not built (the HOPC representation, include/kmercount.hpp: outside this engine's parity contract)");
     if (o.estimate) die("--estimate is not built (error-rate estimation from the quality strings): pass -e");
     if (o.split_count != 1) die("--split-count > 1 is not built: the device counter takes the whole k-mer space in one call (or in passes of its own)");
+    if (o.cigar && !o.paf) die("--cigar needs --paf (the base-level alignment is written as PAF columns 10-11 and the cg:Z: tag)");
+    if (o.cigar && o.skip_alignment) die("--cigar cannot be combined with --skip-alignment (there is no alignment to trace)");
+    if (o.trace_band < 0 || o.trace_band > (1 << 18)) die("--trace-band must be in [0, 262144]");
+    if (o.trace_band && !o.cigar) die("--trace-band needs --cigar");
     if (o.kmer < 1 || o.kmer > 32) die("-k must be in [1,32] (one 64-bit word per k-mer, Kmer.hpp:27-28)");
     const std::string outfile = o.output + ".out";                  // main.cpp:113-130
     std::remove(outfile.c_str());
@@ -295,6 +304,8 @@ int main(int argc, char** argv) {
     so.filename = outfile.c_str();
     so.tag = tag;
     so.exact = o.exact ? 1 : 0;
+    so.cigar = o.cigar ? 1 : 0;
+    so.trace_band = (uint32_t)o.trace_band;
     const double t_stages = now_s();
     run_stages(W, so, names.data(), lens.data());
     {

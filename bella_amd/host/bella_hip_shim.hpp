@@ -74,6 +74,18 @@ void HashSpGEMM(const CSC<uint32_t, unsigned short>& A, const CSC<uint32_t, unsi
     o.per_nnz = (double)(sizeof(spmatPtr_) + sizeof(uint32_t));
     o.filename = filename;
     o.tag = "bella_hip_shim.hpp";
+    // BELLApars has no field for it: BELLA_HIP_CIGAR=1 in the environment turns --paf into true PAF (every stage traces its passed pairs
+    // before it writes them: DESIGN.md section 9); BELLA_HIP_TRACE_BAND = first band
+    if (const char* e = std::getenv("BELLA_HIP_CIGAR")) {
+        const bool want = *e && *e != '0';
+        o.cigar = (want && bpars.outputPaf && !bpars.skipAlignment) ? 1 : 0;
+        if (want && !o.cigar) std::cerr << "bella_hip: BELLA_HIP_CIGAR is set but ignored: it needs --paf and no --skip-alignment" << std::endl;
+    }
+    if (const char* e = std::getenv("BELLA_HIP_TRACE_BAND")) {
+        const unsigned long v = std::strtoul(e, nullptr, 10);
+        if (v > (1ul << 18)) std::cerr << "bella_hip: BELLA_HIP_TRACE_BAND must be in [0, 262144]: ignored" << std::endl;
+        else o.trace_band = (uint32_t)v;
+    }
 
     std::vector<Worker> W((size_t)N);
     uint8_t comm_id[BELLA_HIP_COMM_ID_BYTES];

@@ -292,6 +292,73 @@ int bella_hip_write_output(const char* path, const bella_params* p, int paf, uin
 int bella_hip_align_pairs_exact(bella_ctx* ctx, const bella_params* p, uint64_t* npassed);
 int bella_hip_xdrop_batch_exact(bella_ctx* ctx, const bella_seed* seeds, uint64_t n, const bella_params* p, bella_aln* out);
 
+/* ---- traced alignments: base-level alignment of a pair, as run-length ops (no counterpart in the reference) ----
+ * Scoring is the X-drop's (match +1, mismatch -1, gap -1, linear).  For a pair with alignment a, V = read cid, H = read rid reverse-
+ * complemented when a.strand == 1, the seed at (seedH', seedV) where xavierAlign places it, the traced alignment is: an extension from
+ * the seed's start leftwards inside [a.begH, seedH') x [a.begV, seedV), the seed's k columns, an extension from the seed's end inside
+ * [seedH' + k, a.endH) x [seedV + k, a.endV).  An extension is anchored at the seed and FREE at its far end: it ends at the cell with
+ * the best score (ties: smallest i + j, then smallest i; i counts bases of V, j of H, from the seed).  So a trace has its own end
+ * points, inside the X-drop's.  The DP runs in a band of `band0` diagonals (a power of two >= 256; 0 = BELLA_TRACE_DEFAULT_BAND)
+ * centred on the seed's diagonal; a side whose path touches the band's first or last diagonal is redone with the band doubled until it
+ * does not, or the band holds the side's whole rectangle (then the score is the exact optimum of the definition).
+ * ops: one uint32 per run, len << 4 | op, op 0 '=' match, 1 'X' mismatch, 2 'I' (a base of V only), 3 'D' (a base of H only);
+ * adjacent runs differ; in V order (left part, seed, right part). */
+#define BELLA_TRACE_DEFAULT_BAND 256
+typedef struct {
+    uint64_t op_off;          /* first run of this pair in the ops array                                    */
+    uint32_t nops;            /* runs; 0 = the pair was not traced                                          */
+    uint32_t band;            /* band finally used (the larger of the two sides)                            */
+    int32_t score;            /* left + seed + right under the scoring above                                */
+    int32_t tbegH, tendH;     /* same coordinate convention as bella_aln                                    */
+    int32_t tbegV, tendV;
+    uint32_t n_eq, n_x, n_ins, n_del;   /* bases, not runs                                                 */
+    uint32_t widened;         /* band doublings this pair took (both sides)                                 */
+} bella_trace;
+/* What the last bella_hip_trace_pairs / _batch did.  A sized struct (it will grow): bella_hip_get_trace_stats writes at most
+ * struct_size bytes. */
+typedef struct {
+    double dp_ms;                 /* DP kernels (device time, all batches and widening rounds)               */
+    double walk_ms;               /* backtrace kernels: counting walk + writing walk                         */
+    double total_ms;              /* the whole call on the host clock, copies of the ops to the host included */
+    uint64_t pairs;               /* pairs traced                                                            */
+    uint64_t extensions;          /* extension DPs run: 2 per pair and 2 more every time a pair is repeated    */
+    uint64_t widened_extensions;  /* sides whose band was doubled (a side can count more than once)           */
+    uint64_t repeated_pairs;      /* times a pair went again because a side touched its band: the pair is repeated as a whole,
+                                     also the side that did not touch (same band, same result)                */
+    uint64_t dp_cells;            /* band cells computed                                                     */
+    uint64_t dir_bytes;           /* direction bytes written (dp_cells / 4), summed over the batches          */
+    uint64_t dir_bytes_peak;      /* the largest batch's direction buffer                                    */
+    uint64_t ops;                 /* runs written                                                            */
+    uint32_t batches;
+    uint32_t band0;               /* the band the first round used                                           */
+} bella_trace_stats;
+/* Traces the pairs of the last bella_hip_align_pairs / _exact (passed_only != 0: those with bella_aln::passed).  *ntraced pairs,
+ * *nops runs in all.  BELLA_ERR_STATE without alignments.  Pairs run in batches sized from the free device memory (direction bytes:
+ * rows x band / 4 per extension); the ops are staged on the HOST batch by batch and stay there until the next call: 4 bytes per run,
+ * about 2,400 runs = 9.5 KB per pair of 10 kb reads at 15 % error, and bella_hip_get_traces copies them once more into the caller's
+ * array.  A caller with more passed pairs than its host memory holds runs traces stage by stage (bella_hip_set_column_range). */
+int bella_hip_trace_pairs(bella_ctx* ctx, const bella_params* p, uint32_t band0, int passed_only, uint64_t* ntraced, uint64_t* nops);
+/* out[npairs] index-aligned with bella_hip_get_pairs (untraced pairs: nops = 0); ops[*nops of trace_pairs].  Either may be NULL. */
+int bella_hip_get_traces(bella_ctx* ctx, bella_trace* out, uint32_t* ops);
+/* The same on explicit seeds and alignments (the twin of bella_hip_xdrop_batch: alns[i] is what it returned for seeds[i], or any
+ * rectangle the caller wants traced; end points are clamped to the reads).  Seed columns that do not match become 'X'.
+ * out[n]; *nops = runs in all.  The runs stay with the context until the next call: with ops == NULL the call only reports *nops and
+ * bella_hip_get_batch_ops copies them out (nobody can know their number beforehand; the trace is not run twice); with ops != NULL
+ * they are copied into ops[ops_cap], BELLA_ERR_NOMEM when they do not fit (they can still be fetched). */
+int bella_hip_trace_batch(bella_ctx* ctx, const bella_seed* seeds, const bella_aln* alns, uint64_t n, const bella_params* p, uint32_t band0,
+                          bella_trace* out, uint32_t* ops, uint64_t ops_cap, uint64_t* nops);
+int bella_hip_get_batch_ops(bella_ctx* ctx, uint32_t* ops, uint64_t ops_cap);
+int bella_hip_get_trace_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+/* bella_hip_write_output for true PAF: one line per passed pair THAT HAS A TRACE (nops > 0), columns 1-9 as the PAF of
+ * bella_hip_write_output but with the trace's end points, column 10 = n_eq, 11 = n_eq + n_x + n_ins + n_del, 12 = 255, then
+ * AS:i:<X-drop score> ov:i:<ov> NM:i:<n_x + n_ins + n_del> cg:Z:<runs as = X I D>.  Strand '-': H coordinates on the original
+ * strand and the runs in reverse order (the CIGAR reads along the target's forward strand).  traces[npairs], ops[nops_total] = the
+ * array their op_off point into: a record whose runs lie outside it is BELLA_ERR_BAD_ARG.  npairs == 0 needs no arrays (an empty
+ * stage appends nothing, as with bella_hip_write_output). */
+int bella_hip_write_output_traced(const char* path, const bella_params* p, uint32_t nreads, const char* const* names, const uint32_t* lens,
+                                  const bella_pair* pairs, const bella_aln* alns, const bella_trace* traces, const uint32_t* ops, uint64_t nops_total,
+                                  uint64_t npairs, int nthreads, bella_write_stats* stats);
+
 /* ---- multi-GPU: one context per GPU, RCCL over xGMI ------------------------------------------------
  * The reference's multi-GPU path hands alignment batches to the devices inside one call (loganGPU/functions.cuh:441-443,
  * 498-637; include/align.hpp:226-229) and has no collective.  Here reads are 1D row-block partitioned: context r assembles the

@@ -19,6 +19,10 @@ SEED_DT = np.dtype([("rid", "<u4"), ("cid", "<u4"), ("seedH", "<u2"), ("seedV", 
 TRACE_DT = np.dtype([("op_off", "<u8"), ("nops", "<u4"), ("band", "<u4"), ("score", "<i4"), ("tbegH", "<i4"), ("tendH", "<i4"), ("tbegV", "<i4"),
                      ("tendV", "<i4"), ("n_eq", "<u4"), ("n_x", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("widened", "<u4")])
 assert TRACE_DT.itemsize == 56
+CONS_DT = np.dtype([("len_before", "<u4"), ("len_after", "<u4"), ("substituted", "<u4"), ("deleted", "<u4"), ("inserted", "<u4"), ("covered", "<u4"),
+                    ("depth_sum", "<u8")])
+assert CONS_DT.itemsize == 32
+PILEUP_COUNTERS = 9      # per base: votes for A C G T, del, one inserted A C G T in the junction before the base
 assert PAIR_DT.itemsize == 16 and EXT_DT.itemsize == 8 and ALN_DT.itemsize == 32 and SEED_DT.itemsize == 12
 
 
@@ -55,7 +59,12 @@ class Memory(C.Structure):
 class TraceStats(C.Structure):
     _fields_ = [("dp_ms", C.c_double), ("walk_ms", C.c_double), ("total_ms", C.c_double), ("pairs", C.c_uint64), ("extensions", C.c_uint64),
                 ("widened_extensions", C.c_uint64), ("repeated_pairs", C.c_uint64), ("dp_cells", C.c_uint64), ("dir_bytes", C.c_uint64), ("dir_bytes_peak", C.c_uint64),
-                ("ops", C.c_uint64), ("batches", C.c_uint32), ("band0", C.c_uint32)]
+                ("ops", C.c_uint64), ("batches", C.c_uint32), ("band0", C.c_uint32), ("vote_ms", C.c_double), ("votes", C.c_uint64),
+                ("ops_host_bytes", C.c_uint64)]
+
+
+class ConsensusParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_depth", C.c_uint32)]
 
 
 # every symbol include/bella_hip.h declares: (name, restype, argtypes)
@@ -119,6 +128,14 @@ SIGNATURES = [
     ("bella_hip_get_trace_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_write_output_traced", C.c_int, [C.c_char_p, C.POINTER(Params), C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int,
                                                 C.POINTER(WriteStats)]),
+    ("bella_hip_pileup_reset", C.c_int, [vp]),
+    ("bella_hip_trace_pairs_pileup", C.c_int, [vp, C.POINTER(Params), C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("bella_hip_get_pileup", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+    ("bella_hip_add_pileup", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+    ("bella_hip_get_pileup_bytes", C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    ("bella_hip_consensus", C.c_int, [vp, C.POINTER(ConsensusParams), C.POINTER(C.c_uint64)]),
+    ("bella_hip_get_consensus", C.c_int, [vp, vp, vp, vp]),
+    ("bella_hip_write_fasta", C.c_int, [C.c_char_p, C.c_uint32, vp, vp, vp, C.c_int]),
     ("bella_hip_get_timings", C.c_int, [vp, C.POINTER(Timings)]),
     ("bella_hip_get_memory", C.c_int, [vp, C.POINTER(Memory)]),
     ("bella_hip_get_memory_sized", C.c_int, [vp, vp, C.c_uint64]),

@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import ALN_DT, EXT_DT, PAIR_DT, SEED_DT, TRACE_DT, Memory, Params, Timings, TraceStats, WriteStats
+from ._lib import ALN_DT, CONS_DT, EXT_DT, PAIR_DT, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
 class BellaHipError(RuntimeError):
@@ -313,15 +313,62 @@ class Engine:
         return out
 
     # ---- traced alignments (base-level: run-length ops, len << 4 | op, op 0 '=' 1 'X' 2 'I' 3 'D') ----
-    def trace_pairs(self, pars: BellaPars, band0: int = 0, passed_only: bool = True):
-        """Traces the pairs of the last align_pairs.  Returns (traces[npairs] of TRACE_DT, untraced: nops == 0; ops uint32)."""
+    def trace_pairs(self, pars: BellaPars, band0: int = 0, passed_only: bool = True, pileup: bool = False, keep_ops: bool = True):
+        """Traces the pairs of the last align_pairs.  Returns (traces[npairs] of TRACE_DT, untraced: nops == 0; ops uint32).
+        pileup=True (needs pileup_reset, passed pairs only): every traced pair also votes into the pileup table on the device; with
+        keep_ops=False the runs never reach the host and `ops` comes back empty (the records are the same)."""
         nt, no = C.c_uint64(0), C.c_uint64(0)
         cp = pars.c()
-        self._chk(self.lib.bella_hip_trace_pairs(self.h, C.byref(cp), band0, 1 if passed_only else 0, C.byref(nt), C.byref(no)))
+        if pileup:
+            if not passed_only:
+                raise ValueError("pileup=True traces the passed pairs only")
+            self._chk(self.lib.bella_hip_trace_pairs_pileup(self.h, C.byref(cp), band0, 1 if keep_ops else 0, C.byref(nt), C.byref(no)))
+        else:
+            self._chk(self.lib.bella_hip_trace_pairs(self.h, C.byref(cp), band0, 1 if passed_only else 0, C.byref(nt), C.byref(no)))
         tr = np.zeros(self.npairs, TRACE_DT)
-        ops = np.zeros(no.value, np.uint32)
+        ops = np.zeros(no.value if (keep_ops or not pileup) else 0, np.uint32)
         self._chk(self.lib.bella_hip_get_traces(self.h, _p(tr), _p(ops)))
         return tr, ops
+
+    # ---- read correction: pileup of the traced alignments, consensus ----
+    def pileup_reset(self):
+        """allocates (first use) and zeroes the pileup table of the loaded reads: 9 uint32 per base"""
+        self._chk(self.lib.bella_hip_pileup_reset(self.h))
+
+    def _range_bases(self, first, n):
+        if first < 0 or n < 0 or first + n > self.nreads:
+            raise ValueError("reads [%d, %d) out of range" % (first, first + n))
+        return int(np.asarray(self.lengths[first:first + n], np.int64).sum())
+
+    def get_pileup(self, first: int = 0, n: int = None) -> np.ndarray:
+        """(bases of the reads [first, first + n), 9) uint32: votes for A C G T, del, inserted A C G T before the base"""
+        n = self.nreads - first if n is None else n
+        out = np.zeros((self._range_bases(first, n), PILEUP_COUNTERS), np.uint32)
+        self._chk(self.lib.bella_hip_get_pileup(self.h, first, n, _p(out)))
+        return out
+
+    def add_pileup(self, first: int, n: int, counters: np.ndarray):
+        """adds a (bases, 9) uint32 array (another context's get_pileup of the same reads) into the table"""
+        a = np.ascontiguousarray(counters, np.uint32)
+        if a.shape != (self._range_bases(first, n), PILEUP_COUNTERS):
+            raise ValueError("counters must have shape (bases of the reads, 9)")
+        self._chk(self.lib.bella_hip_add_pileup(self.h, first, n, _p(a)))
+
+    def pileup_bytes(self) -> int:
+        b = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_get_pileup_bytes(self.h, C.byref(b)))
+        return b.value
+
+    def consensus(self, min_depth: int = 3):
+        """majority-vote consensus of every read from the table: (offsets uint64[nreads + 1], bases uint8 ASCII, stats of CONS_DT)"""
+        cp = ConsensusParams(C.sizeof(ConsensusParams), min_depth)
+        tot = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_consensus(self.h, C.byref(cp), C.byref(tot)))
+        offs = np.zeros(self.nreads + 1, np.uint64)
+        bases = np.zeros(tot.value, np.uint8)
+        stats = np.zeros(self.nreads, CONS_DT)
+        self._chk(self.lib.bella_hip_get_consensus(self.h, offs.ctypes.data, _p(bases), _p(stats)))
+        return offs, bases, stats
 
     def trace_batch(self, seeds: np.ndarray, alns: np.ndarray, pars: BellaPars, band0: int = 0):
         """The same on explicit seeds and their alignments (what xdrop_batch returned for them, or any rectangles)."""
@@ -445,6 +492,19 @@ def write_output_traced(filename: str, pars: BellaPars, names, lengths, pairs, a
     if rc:
         raise BellaHipError(rc, "bella_hip_write_output_traced failed")
     return st
+
+
+def write_fasta(filename: str, names, offsets, bases, append: bool = False) -> None:
+    """bella_hip_write_fasta: '>name' + one sequence line per read (what Engine.consensus returned), reads in input order."""
+    lib = _lib.load()
+    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    b = np.ascontiguousarray(bases, np.uint8)
+    assert len(offs) == len(enc) + 1
+    rc = lib.bella_hip_write_fasta(os.fsencode(filename), len(enc), C.cast(arr, C.c_void_p), offs.ctypes.data, _p(b), 1 if append else 0)
+    if rc:
+        raise BellaHipError(rc, "bella_hip_write_fasta failed")
 
 
 def hash_spgemm(engine: Engine, pars: BellaPars, filename: str, stdout=sys.stdout, stages: int = 1):

@@ -25,6 +25,7 @@
 #include "kcount.hpp"
 #include "logan.hpp"
 #include "order.hpp"
+#include "pileup.hpp"
 #include "spgemm.hpp"
 #include "trace.hpp"
 #include "util.hpp"
@@ -195,6 +196,11 @@ struct bella_ctx {
     bool have_batch_ops = false;
     bella_trace_stats trace_stats{};
     Buf tr_exts, tr_lists, tr_res, tr_pres, tr_opoff, tr_dirs, tr_scr, tr_ops;
+    bool trace_ops_kept = true;          // false: the last call piled its runs up on the device and did not stage them (keep_ops == 0)
+    // read correction (pileup.hpp): the table of the loaded reads, and the last consensus
+    bool have_pile = false, have_cons = false;
+    uint64_t cons_total = 0;
+    Buf pile, pile_pairs, pile_cnt, pile_tmp, cons_emit, cons_scan, cons_out, cons_offs, cons_stats;
     bella_timings tm{};
     hipEvent_t ev[12]{};
     uint32_t* pinned = nullptr;          // 128 host words the per-pass read backs land in
@@ -747,7 +753,9 @@ void bella_hip_destroy(bella_ctx* c) {
                   &c->rowlists, &c->tiercaps, &c->tmp_pairs, &c->tmp_ext, &c->pairs, &c->ext, &c->sortscr, &c->ws,
                   &c->status, &c->cubtmp, &c->alns, &c->seeds, &c->plist_hv, &c->overflow, &c->ctl, &c->retry, &c->orderlist, &c->order_ws, &c->w_f, &c->w_off, &c->w_key, &c->w_key2, &c->w_idx, &c->w_idx2, &c->w_hv, &c->w_ovfl,
                   &c->w_plist, &c->w_scr, &c->w_rlen, &c->w_rstart, &c->w_rrank, &c->w_redo, &c->w_segfirst, &c->w_toff, &c->w_table, &c->w_nruns, &c->w_desc, &c->w_gtab, &c->w_gcount, &c->w_gbase, &c->w_rfirst, &c->w_aent2, &c->w_aov, &c->kc_nk, &c->kc_koff, &c->kc_hist, &c->kc_keys, &c->kc_alt, &c->kc_runlen,
-                  &c->kc_flag, &c->kc_slot, &c->kc_nruns, &c->kc_dcode, &c->kc_dcount, &c->kc_hkey, &c->kc_hval, &c->kc_found, &c->kc_tstart, &c->kc_cursor, &c->kc_sel, &c->kc_ringo, &c->kc_ringp, &c->kc_opos, &c->kc_oid, &c->kc_opos2, &c->kc_oid2, &c->xest, &c->xest2, &c->xids, &c->xorder, &c->xres, &c->xstate, &c->xlive, &c->lg_res, &c->lg_redo, &c->lg_scratch};
+                  &c->kc_flag, &c->kc_slot, &c->kc_nruns, &c->kc_dcode, &c->kc_dcount, &c->kc_hkey, &c->kc_hval, &c->kc_found, &c->kc_tstart, &c->kc_cursor, &c->kc_sel, &c->kc_ringo, &c->kc_ringp, &c->kc_opos, &c->kc_oid, &c->kc_opos2, &c->kc_oid2, &c->xest, &c->xest2, &c->xids, &c->xorder, &c->xres, &c->xstate, &c->xlive, &c->lg_res, &c->lg_redo, &c->lg_scratch,
+                  &c->tr_exts, &c->tr_lists, &c->tr_res, &c->tr_pres, &c->tr_opoff, &c->tr_dirs, &c->tr_scr, &c->tr_ops,
+                  &c->pile, &c->pile_pairs, &c->pile_cnt, &c->pile_tmp, &c->cons_emit, &c->cons_scan, &c->cons_out, &c->cons_offs, &c->cons_stats};
     for (Buf* b : all) release(*b);
     trim_pool(c->pool);
     if (c->pool.arena.base) { (void)hipFree(c->pool.arena.base); c->pool.arena = Arena(); }
@@ -927,6 +935,8 @@ static int set_reads_impl(bella_ctx* c, const uint64_t* offsets, uint32_t nreads
     c->have_reads = true;
     c->have_matrix = c->have_pairs = c->have_alns = false;
     c->have_tuples = false;
+    for (Buf* b : {&c->pile, &c->cons_out, &c->cons_offs, &c->cons_stats}) release(*b);      // (the pileup belongs to the reads it was sized for)
+    c->have_pile = c->have_cons = false;
     return 0;
 }
 
@@ -3560,8 +3570,10 @@ struct TraceJob { uint32_t rid, cid, seedH, seedV; bella_aln a; };
 // Traces jobs[0 .. n): out[n] records, ops appended to `ops` (op_off counts from the vector's start).  Pairs run in batches sized by
 // the free device memory (the direction bytes dominate); a pair whose path touched its band's edge on a side goes back into the queue
 // with that side's band doubled, until no side touches or the band holds the side's whole rectangle.
+// vote: every finished pair's runs also vote into the context's pileup table (pileup.hpp), from the batch's op array on the device;
+// keep_ops == false: the runs are not copied to the host (`ops` stays as it is; the records' op_off count as if they had been).
 int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& jobs, uint32_t band0, bella_trace* out, std::vector<uint32_t>& ops,
-              bella_trace_stats& st) {
+              bella_trace_stats& st, bool vote = false, bool keep_ops = true) {
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     st = bella_trace_stats{};
@@ -3614,14 +3626,20 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
     constexpr uint32_t kMaxBatchPairs = 1u << 20;
     std::vector<uint32_t> queue(n), next;
     for (size_t q = 0; q < n; ++q) queue[q] = (uint32_t)q;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1)); HIPCHK(c, hipEventCreate(&e2));
-    struct EvGuard { hipEvent_t a, b, d; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(d); } } evg{e0, e1, e2};
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
+    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1)); HIPCHK(c, hipEventCreate(&e2)); HIPCHK(c, hipEventCreate(&e3));
+    struct EvGuard { hipEvent_t a, b, d, e; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(d); (void)hipEventDestroy(e); } } evg{e0, e1, e2, e3};
     std::vector<TraceExt> exts;
     std::vector<uint32_t> lists[4];
     std::vector<TracePairRes> pres;
     std::vector<TraceExtRes> eres;
     std::vector<uint64_t> opoff;
+    std::vector<PilePair> votep;
+    uint64_t ops_seen = ops.size();                                   // runs written so far (= ops.size() while the runs are kept)
+    if (vote) {
+        ENSURE(c, c->pile_cnt, 8);
+        HIPCHK(c, hipMemsetAsync(c->pile_cnt.p, 0, 8, c->stream));
+    }
     const uint32_t* const packed = ptr<uint32_t>(c->packed);
     while (!queue.empty()) {
         next.clear();
@@ -3696,6 +3714,7 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
             st.walk_ms += ev_ms(e1, e2);
             // ---- who is done, who goes again
             opoff.assign(nb, ~0ull);
+            votep.clear();
             uint64_t bops = 0;
             for (uint32_t q = 0; q < nb; ++q) {
                 const uint32_t id = queue[at + q];
@@ -3709,7 +3728,7 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                 const TraceJob& j = jobs[id];
                 const TraceExtRes &rl = eres[2 * q], &rr = eres[2 * q + 1];
                 bella_trace& t = out[id];
-                t.op_off = ops.size() + bops;
+                t.op_off = ops_seen + bops;
                 t.nops = pres[q].nops;
                 t.band = std::max(w.s[0].band, w.s[1].band);
                 t.score = rl.score + pres[q].seed_score + rr.score;
@@ -3717,6 +3736,9 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                 t.tendH = w.seedHo + (int32_t)k + (int32_t)rr.bj; t.tendV = (int32_t)j.seedV + (int32_t)k + (int32_t)rr.bi;
                 t.n_eq = pres[q].n_eq; t.n_x = pres[q].n_x; t.n_ins = pres[q].n_ins; t.n_del = pres[q].n_del;
                 t.widened = w.widened;
+                if (vote && t.nops)
+                    votep.push_back(PilePair{off[j.cid], off[j.rid], bops, t.nops, (uint32_t)(off[j.cid + 1] - off[j.cid]), (uint32_t)(off[j.rid + 1] - off[j.rid]),
+                                             j.a.strand ? 1u : 0u, t.tbegV, t.tbegH});
                 opoff[q] = bops;
                 bops += pres[q].nops;
                 st.pairs++;
@@ -3729,16 +3751,36 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                                                                   ptr<uint32_t>(c->tr_ops));
                 KCHK(c);
                 HIPCHK(c, hipEventRecord(e1, c->stream));
-                const size_t base = ops.size();
-                ops.resize(base + bops);
-                HIPCHK(c, c->stager.d2h(ops.data() + base, c->tr_ops.p, 4 * (size_t)bops, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
+                if (vote && !votep.empty()) {                           // the batch's runs vote while they are in device memory
+                    ENSURE(c, c->pile_pairs, sizeof(PilePair) * votep.size());
+                    HIPCHK(c, hipMemcpyAsync(c->pile_pairs.p, votep.data(), sizeof(PilePair) * votep.size(), hipMemcpyHostToDevice, c->stream));
+                    HIPCHK(c, hipEventRecord(e2, c->stream));
+                    k_pile_vote<<<nblk(votep.size(), kPileBlock / 64), kPileBlock, 0, c->stream>>>(ptr<PilePair>(c->pile_pairs), (uint32_t)votep.size(), ptr<uint32_t>(c->tr_ops),
+                                                                                                   packed, ptr<uint32_t>(c->pile), ptr<unsigned long long>(c->pile_cnt));
+                    KCHK(c);
+                    HIPCHK(c, hipEventRecord(e3, c->stream));
+                }
+                if (keep_ops) {
+                    const size_t base = ops.size();
+                    ops.resize(base + bops);
+                    HIPCHK(c, c->stager.d2h(ops.data() + base, c->tr_ops.p, 4 * (size_t)bops, c->stream));
+                    st.ops_host_bytes += 4 * bops;
+                }
+                HIPCHK(c, hipStreamSynchronize(c->stream));              // (votep and opoff are reused by the next batch)
                 st.walk_ms += ev_ms(e0, e1);
+                if (vote && !votep.empty()) st.vote_ms += ev_ms(e2, e3);
+                ops_seen += bops;
                 st.ops += bops;
             }
             at = end;
         }
         queue.swap(next);
+    }
+    if (vote) {
+        unsigned long long nv = 0;
+        HIPCHK(c, hipMemcpyAsync(&nv, c->pile_cnt.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.votes = nv;
     }
     st.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
     return 0;
@@ -3749,11 +3791,10 @@ void trace_release(bella_ctx* c) {      // the batch buffers go back (directions
 }
 }  // namespace
 
-extern "C" {
-
-int bella_hip_trace_pairs(bella_ctx* c, const bella_params* p, uint32_t band0, int passed_only, uint64_t* ntraced, uint64_t* nops) {
+static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0, int passed_only, bool vote, bool keep_ops, uint64_t* ntraced, uint64_t* nops) {
     if (!c) return BELLA_ERR_BAD_ARG;
     if (!c->have_alns) return fail(c, BELLA_ERR_STATE, "align_pairs first");
+    if (vote && !c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
     int rc = check_params(c, p);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -3772,20 +3813,35 @@ int bella_hip_trace_pairs(bella_ctx* c, const bella_params* p, uint32_t band0, i
         if (!passed_only || alns[i].passed) { jobs.push_back(TraceJob{pairs[i].rid, pairs[i].cid, pairs[i].seedH, pairs[i].seedV, alns[i]}); which.push_back(i); }
     std::vector<bella_trace> tr(jobs.size());
     c->trace_ops.clear();
-    rc = run_trace(c, p, jobs, band0, tr.data(), c->trace_ops, c->trace_stats);
+    if (!keep_ops) std::vector<uint32_t>().swap(c->trace_ops);
+    if (vote) c->have_cons = false;
+    rc = run_trace(c, p, jobs, band0, tr.data(), c->trace_ops, c->trace_stats, vote, keep_ops);
     trace_release(c);
+    if (vote) release(c->pile_pairs);
     if (rc) { (void)hipDeviceSynchronize(); return rc; }
     c->traces.assign(n, bella_trace{});
     for (size_t i = 0; i < which.size(); ++i) c->traces[which[i]] = tr[i];
     c->have_traces = true;
+    c->trace_ops_kept = keep_ops;
     if (ntraced) *ntraced = jobs.size();
-    if (nops) *nops = c->trace_ops.size();
+    if (nops) *nops = c->trace_stats.ops;
     return 0;
+}
+
+extern "C" {
+
+int bella_hip_trace_pairs(bella_ctx* c, const bella_params* p, uint32_t band0, int passed_only, uint64_t* ntraced, uint64_t* nops) {
+    return trace_pairs_impl(c, p, band0, passed_only, false, true, ntraced, nops);
+}
+
+int bella_hip_trace_pairs_pileup(bella_ctx* c, const bella_params* p, uint32_t band0, int keep_ops, uint64_t* ntraced, uint64_t* nops) {
+    return trace_pairs_impl(c, p, band0, 1, true, keep_ops != 0, ntraced, nops);
 }
 
 int bella_hip_get_traces(bella_ctx* c, bella_trace* out, uint32_t* ops) {
     if (!c) return BELLA_ERR_BAD_ARG;
     if (!c->have_traces || !c->have_alns) return fail(c, BELLA_ERR_STATE, "trace_pairs first");
+    if (ops && !c->trace_ops_kept) return fail(c, BELLA_ERR_STATE, "the last bella_hip_trace_pairs_pileup ran with keep_ops = 0: the runs were not kept (pass ops = NULL)");
     if (out && !c->traces.empty()) std::memcpy(out, c->traces.data(), sizeof(bella_trace) * c->traces.size());
     if (ops && !c->trace_ops.empty()) std::memcpy(ops, c->trace_ops.data(), 4 * c->trace_ops.size());
     return 0;
@@ -3826,6 +3882,158 @@ int bella_hip_get_batch_ops(bella_ctx* c, uint32_t* ops, uint64_t ops_cap) {
 int bella_hip_get_trace_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     if (!c || !out) return BELLA_ERR_BAD_ARG;
     std::memcpy(out, &c->trace_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_trace_stats)));
+    return 0;
+}
+
+// ---- read correction (pileup.hpp) ----------------------------------------------------------------------------
+struct EmitCount {
+    __host__ __device__ uint64_t operator()(const uint8_t& v) const { return (uint64_t)(v & 3u); }
+};
+
+int bella_hip_pileup_reset(bella_ctx* c) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->total_bases * kPileCounters * 4;
+    c->have_pile = c->have_cons = false;
+    if (ensure_bytes(c, c->pile, bytes))
+        return fail(c, BELLA_ERR_NOMEM, "the pileup table needs %zu bytes of device memory (36 per base of %llu bases) and they do not fit", bytes,
+                    (unsigned long long)c->total_bases);
+    HIPCHK(c, hipMemsetAsync(c->pile.p, 0, bytes ? bytes : 16, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->have_pile = true;
+    return 0;
+}
+
+int bella_hip_get_pileup_bytes(bella_ctx* c, uint64_t* bytes) {
+    if (!c || !bytes) return BELLA_ERR_BAD_ARG;
+    *bytes = c->have_pile ? (uint64_t)c->total_bases * kPileCounters * 4 : 0;
+    return 0;
+}
+
+// counters [*first, *first + *count) of the table = the reads [first_read, first_read + nreads)
+static int pileup_range(bella_ctx* c, uint32_t first_read, uint32_t nreads, uint64_t* first, uint64_t* count) {
+    if (!c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
+    if ((uint64_t)first_read + nreads > c->nreads) return fail(c, BELLA_ERR_BAD_ARG, "reads [%u, %u + %u) out of range", first_read, first_read, nreads);
+    uint64_t a = 0, b = 0;
+    for (uint32_t r = 0; r < first_read + nreads; ++r) { if (r < first_read) a += c->host_lens[r]; b += c->host_lens[r]; }
+    *first = a * kPileCounters;
+    *count = (b - a) * kPileCounters;
+    return 0;
+}
+
+int bella_hip_get_pileup(bella_ctx* c, uint32_t first_read, uint32_t nreads, uint32_t* out) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    uint64_t first = 0, count = 0;
+    const int rc = pileup_range(c, first_read, nreads, &first, &count);
+    if (rc) return rc;
+    if (!count) return 0;
+    if (!out) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->stager.d2h(out, ptr<uint32_t>(c->pile) + first, 4 * (size_t)count, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bella_hip_add_pileup(bella_ctx* c, uint32_t first_read, uint32_t nreads, const uint32_t* in) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    uint64_t first = 0, count = 0;
+    const int rc = pileup_range(c, first_read, nreads, &first, &count);
+    if (rc) return rc;
+    if (!count) return 0;
+    if (!in) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->have_cons = false;
+    constexpr uint64_t kChunk = 16ull << 20;                          // counters per step: 64 MB of device scratch whatever the range
+    ENSURE(c, c->pile_tmp, 4 * (size_t)std::min(kChunk, count));
+    for (uint64_t o = 0; o < count; o += kChunk) {
+        const uint64_t n = std::min(kChunk, count - o);
+        HIPCHK(c, c->stager.h2d(c->pile_tmp.p, in + o, 4 * (size_t)n, c->stream));
+        k_pile_add<<<nblk(n), 256, 0, c->stream>>>(ptr<uint32_t>(c->pile) + first + o, ptr<uint32_t>(c->pile_tmp), n);
+        KCHK(c);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    release(c->pile_tmp);
+    return 0;
+}
+
+int bella_hip_consensus(bella_ctx* c, const bella_consensus_params* params, uint64_t* total_bases) {
+    if (!c || !params) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
+    if (params->struct_size < sizeof(bella_consensus_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_consensus_params: struct_size %u is too small", params->struct_size);
+    if (params->min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
+    if (!c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->have_cons = false;
+    const uint64_t total = c->total_bases;
+    const uint32_t nr = c->nreads;
+    if (total >= 0x7FFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "consensus: the read set must have fewer than 2^31 bases");
+    ENSURE(c, c->cons_emit, (size_t)total + 1);
+    ENSURE(c, c->cons_scan, 8 * ((size_t)total + 1));
+    ENSURE(c, c->cons_offs, 8 * ((size_t)nr + 1));
+    ENSURE(c, c->cons_stats, sizeof(bella_consensus_read) * std::max<size_t>(nr, 1));
+    HIPCHK(c, hipMemsetAsync(c->cons_stats.p, 0, sizeof(bella_consensus_read) * std::max<size_t>(nr, 1), c->stream));
+    HIPCHK(c, hipMemsetAsync(ptr<uint8_t>(c->cons_emit) + total, 0, 1, c->stream));
+    if (total) {
+        k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(c->pile), ptr<uint32_t>(c->packed), ptr<uint64_t>(c->roff), nr, total, params->min_depth,
+                                                          ptr<uint8_t>(c->cons_emit), ptr<bella_consensus_read>(c->cons_stats));
+        KCHK(c);
+    }
+    {
+        hipcub::TransformInputIterator<uint64_t, EmitCount, const uint8_t*> it(ptr<uint8_t>(c->cons_emit), EmitCount());
+        size_t tb = 0;
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, ptr<uint64_t>(c->cons_scan), (int)(total + 1), c->stream));
+        ENSURE(c, c->cubtmp, tb);
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, ptr<uint64_t>(c->cons_scan), (int)(total + 1), c->stream));
+    }
+    uint64_t nout = 0;
+    HIPCHK(c, hipMemcpyAsync(&nout, ptr<uint64_t>(c->cons_scan) + total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ENSURE(c, c->cons_out, (size_t)nout);
+    if (total) {
+        k_cons_write<<<nblk(total), 256, 0, c->stream>>>(ptr<uint8_t>(c->cons_emit), ptr<uint64_t>(c->cons_scan), total, ptr<uint8_t>(c->cons_out));
+        KCHK(c);
+    }
+    k_cons_reads<<<nblk((uint64_t)nr + 1), 256, 0, c->stream>>>(ptr<uint64_t>(c->roff), ptr<uint64_t>(c->cons_scan), nr, ptr<uint64_t>(c->cons_offs),
+                                                                 ptr<bella_consensus_read>(c->cons_stats));
+    KCHK(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    release(c->cons_emit);
+    release(c->cons_scan);
+    c->cons_total = nout;
+    c->have_cons = true;
+    if (total_bases) *total_bases = nout;
+    return 0;
+}
+
+int bella_hip_get_consensus(bella_ctx* c, uint64_t* offsets, uint8_t* bases, bella_consensus_read* stats) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_cons) return fail(c, BELLA_ERR_STATE, "bella_hip_consensus first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (offsets) HIPCHK(c, c->stager.d2h(offsets, c->cons_offs.p, 8 * ((size_t)c->nreads + 1), c->stream));
+    if (bases && c->cons_total) HIPCHK(c, c->stager.d2h(bases, c->cons_out.p, (size_t)c->cons_total, c->stream));
+    if (stats && c->nreads) HIPCHK(c, c->stager.d2h(stats, c->cons_stats.p, sizeof(bella_consensus_read) * (size_t)c->nreads, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* names, const uint64_t* offsets, const uint8_t* bases, int append) {
+    if (!path || (nreads && (!names || !offsets)) || (nreads && offsets[nreads] && !bases)) {
+        fprintf(stderr, "bella_hip_write_fasta: null argument\n");
+        return BELLA_ERR_BAD_ARG;
+    }
+    FILE* f = std::fopen(path, append ? "ab" : "wb");
+    if (!f) { fprintf(stderr, "bella_hip_write_fasta: cannot open %s\n", path); return BELLA_ERR_BAD_ARG; }
+    std::vector<char> buf((size_t)4 << 20);
+    std::setvbuf(f, buf.data(), _IOFBF, buf.size());
+    bool ok = true;
+    for (uint32_t r = 0; r < nreads && ok; ++r) {
+        if (!names[r] || offsets[r + 1] < offsets[r]) { ok = false; break; }
+        const size_t n = (size_t)(offsets[r + 1] - offsets[r]);
+        ok = std::fputc('>', f) != EOF && std::fputs(names[r], f) != EOF && std::fputc('\n', f) != EOF && (n == 0 || std::fwrite(bases + offsets[r], 1, n, f) == n) &&
+             std::fputc('\n', f) != EOF;
+    }
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) { fprintf(stderr, "bella_hip_write_fasta: writing %s failed\n", path); return BELLA_ERR_BAD_ARG; }
     return 0;
 }
 

@@ -1,0 +1,226 @@
+// pileup.hpp -- read correction: a per-read pileup accumulated from the traced alignments, and the consensus call, on gfx950.
+//
+// Nothing in the reference does this (it ends at the overlap / alignment file); the definition is this project's own and is written
+// down in DESIGN.md section 10.  In short: every base position of every read owns nine uint32 counters (36 bytes): base[4] = votes for
+// A, C, G, T at the position, del = votes that the base is not there, ins[4] = votes for ONE base inserted in the junction just before
+// the position.  A traced pair (V = read cid, H' = read rid oriented by the strand) votes on both of its reads: an aligned column votes
+// the other read's base, a gap base votes `del` on the read that has the base, a gap run votes one `ins` on the read that lacks it.
+// Everything is an integer sum, so the table does not depend on the order the votes arrive in.
+//
+// Mapping of the vote kernel.  One wavefront per pair, looping over the pair's runs 64 at a time: lane l loads run 64 c + l, three
+// inclusive wave scans (bases of V, bases of H', columns) give every run its start (i, j) and its first column -- the segmented scan of
+// the pair; the columns of the 64 runs are then dealt to the lanes 64 at a time (a 6-step search over the lanes' column prefix finds a
+// column's run), so consecutive lanes hold consecutive columns of a run = consecutive 36-byte records of the table, whatever the run
+// lengths are (at 15 % error a run is 4 columns long on average: one lane per run or one loop per run would leave the wave idle).
+// The other choice, a flat list of runs balanced by bases over all pairs, needs a device-wide segmented scan and a second pass; the
+// pairs of a batch are thousands and each has thousands of columns, so one wavefront per pair already fills the device.
+// No LDS: the run table of a chunk lives in the lanes' registers and is read with cross-lane permutes.
+//
+// The consensus is three passes over the table: k_cons_decide (per position: 0, 1 or 2 bases, per-read statistics reduced per wave),
+// an exclusive scan of the emit counts (hipCUB), k_cons_write (ASCII bases at their offsets) + k_cons_reads (per-read offsets).
+#pragma once
+#include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
+#include "../../include/bella_hip.h"
+#include "core.hpp"
+#include "trace.hpp"
+
+namespace bella {
+
+constexpr int kPileCounters = 9;       // base[4], del, ins[4]
+enum { kPileDel = 4, kPileIns = 5 };
+
+// one traced pair of a batch, as the vote kernel reads it
+struct PilePair {
+    uint64_t rowV, rowH;   // first base of read cid / rid among all bases: row of the table and position in the packed reads
+    uint64_t op_off;       // first run in the batch's op array
+    uint32_t nops;
+    uint32_t lenV, lenH;
+    uint32_t strand;       // 1: H' = reverse complement of H
+    int32_t i0, j0;        // tbegV, tbegH: where the ops start on V and on H'
+};
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ uint32_t pile_base(const uint32_t* packed, uint64_t g) { return (packed[g >> 4] >> ((uint32_t)(g & 15) * 2)) & 3u; }
+
+__device__ __forceinline__ uint32_t pile_scan_incl(uint32_t x, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    return x;
+}
+
+constexpr int kPileBlock = 256;        // four independent wavefronts
+
+__global__ __launch_bounds__(kPileBlock) void k_pile_vote(const PilePair* pp, uint32_t npairs, const uint32_t* ops, const uint32_t* packed, uint32_t* table,
+                                                          unsigned long long* votes) {
+    const uint32_t q = (uint32_t)(((uint64_t)blockIdx.x * kPileBlock + threadIdx.x) >> 6);
+    if (q >= npairs) return;                                          // (whole wavefronts leave)
+    const int lane = (int)(threadIdx.x & 63);
+    const PilePair P = pp[q];
+    const uint32_t* const po = ops + P.op_off;
+    const uint32_t comp = P.strand ? 3u : 0u;
+    uint32_t ci = (uint32_t)P.i0, cj = (uint32_t)P.j0;               // where the chunk's first run starts
+    uint32_t nv = 0;
+    for (uint32_t c0 = 0; c0 < P.nops; c0 += 64) {
+        const uint32_t w = c0 + lane < P.nops ? po[c0 + lane] : 0u;
+        const uint32_t op = w & 15u, len = w >> 4;
+        const uint32_t di = op != kOpDel ? len : 0u, dj = op != kOpIns ? len : 0u;
+        const uint32_t ei = pile_scan_incl(di, lane), ej = pile_scan_incl(dj, lane), ec = pile_scan_incl(len, lane);
+        const uint32_t si = ci + ei - di, sj = cj + ej - dj;          // this lane's run starts at (si, sj)
+        const uint32_t total = __shfl(ec, 63, 64);
+        for (uint32_t t0 = 0; t0 < total; t0 += 64) {
+            const bool live = t0 + lane < total;
+            const uint32_t t = live ? t0 + lane : total - 1;
+            int r = 0;                                                // the first run whose columns end behind t
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) {
+                const uint32_t e = __shfl(ec, r + s - 1, 64);
+                if (e <= t) r += s;
+            }
+            const uint32_t rw = __shfl(w, r, 64), rend = __shfl(ec, r, 64), ri = __shfl(si, r, 64), rj = __shfl(sj, r, 64);
+            if (!live) continue;
+            const uint32_t rop = rw & 15u, rlen = rw >> 4;
+            const uint32_t o = t - (rend - rlen);
+            const uint32_t i = ri + (rop != kOpDel ? o : 0u), j = rj + (rop != kOpIns ? o : 0u);
+            // position j of H' is position lenH - 1 - j of H on strand 1, its base the complement
+            const uint64_t gH = P.rowH + (P.strand ? (uint64_t)P.lenH - 1 - j : (uint64_t)j);
+            if (rop <= kOpX) {
+                if (i < P.lenV && j < P.lenH) {
+                    const uint32_t vb = pile_base(packed, P.rowV + i), hb = pile_base(packed, gH) ^ comp;
+                    atomicAdd(table + (P.rowV + i) * kPileCounters + hb, 1u);
+                    atomicAdd(table + gH * kPileCounters + (vb ^ comp), 1u);
+                    nv += 2;
+                }
+            } else if (rop == kOpIns) {                               // a base of V only
+                if (i < P.lenV) { atomicAdd(table + (P.rowV + i) * kPileCounters + kPileDel, 1u); ++nv; }
+                if (o == 0) {
+                    // H lacks the run: one vote into the junction before rj of H' = junction lenH - rj of H on strand 1, with the base
+                    // that comes first in H's own direction (strand 1: the complement of the run's last base)
+                    const uint32_t jn = P.strand ? P.lenH - rj : rj;
+                    const uint32_t iv = P.strand ? ri + rlen - 1 : ri;
+                    if (rj <= P.lenH && jn < P.lenH && iv < P.lenV) {
+                        atomicAdd(table + (P.rowH + jn) * kPileCounters + kPileIns + (pile_base(packed, P.rowV + iv) ^ comp), 1u);
+                        ++nv;
+                    }
+                }
+            } else if (rop == kOpDel) {                               // a base of H' only
+                if (j < P.lenH) { atomicAdd(table + gH * kPileCounters + kPileDel, 1u); ++nv; }
+                if (o == 0 && ri < P.lenV && rj < P.lenH) {           // V lacks the run: its first base, into the junction before ri
+                    atomicAdd(table + (P.rowV + ri) * kPileCounters + kPileIns + (pile_base(packed, gH) ^ comp), 1u);
+                    ++nv;
+                }
+            }
+        }
+        ci += __shfl(ei, 63, 64);
+        cj += __shfl(ej, 63, 64);
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) nv += __shfl_xor(nv, d, 64);
+    if (lane == 0 && nv) atomicAdd(votes, (unsigned long long)nv);
+}
+
+// table[first + x] += add[x]  (bella_hip_add_pileup: another context's counters)
+__global__ void k_pile_add(uint32_t* table, const uint32_t* add, uint64_t n) {
+    const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < n) table[x] += add[x];
+}
+
+// ---- consensus ------------------------------------------------------------------------------------------------------------------
+// Per position g (a row of the table): emit[g] = count | first base << 2 | second base << 4.  A junction's inserted base comes before
+// the position's own.  Per-read statistics: a wavefront whose 64 positions lie in one read reduces across its lanes first.
+__global__ __launch_bounds__(256) void k_cons_decide(const uint32_t* table, const uint32_t* packed, const uint64_t* roff, uint32_t nreads, uint64_t total,
+                                                     uint32_t min_depth, uint8_t* emit, bella_consensus_read* stats) {
+    const uint64_t g0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = g0 < total;
+    const uint64_t g = live ? g0 : total - 1;
+    const int lane = (int)(threadIdx.x & 63);
+    uint32_t lo = 0, hi = nreads;                                     // the read of g: the last r with roff[r] <= g
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (roff[mid] <= g) lo = mid; else hi = mid;
+    }
+    const uint32_t r = lo;
+    const uint32_t p = (uint32_t)(g - roff[r]);
+    const uint32_t* const row = table + g * kPileCounters;
+    uint32_t cb[4] = {row[0], row[1], row[2], row[3]};
+    const uint32_t del = row[kPileDel];
+    const uint64_t depth = (uint64_t)cb[0] + cb[1] + cb[2] + cb[3] + del;
+    const uint32_t own = pile_base(packed, g);
+    uint32_t n = 0, code = 0, n_ins = 0, n_del = 0, n_sub = 0, cov = 0;
+    if (p >= 1) {                                                     // the junction before p
+        const uint32_t* const pr = row - kPileCounters;
+        const uint64_t dprev = (uint64_t)pr[0] + pr[1] + pr[2] + pr[3] + pr[kPileDel];
+        const uint64_t cmin = dprev < depth ? dprev : depth;
+        const uint32_t in[4] = {row[kPileIns], row[kPileIns + 1], row[kPileIns + 2], row[kPileIns + 3]};
+        const uint64_t I = (uint64_t)in[0] + in[1] + in[2] + in[3];
+        if (cmin >= min_depth && 2 * I > cmin + 1) {
+            uint32_t best = 0;
+            for (uint32_t x = 1; x < 4; ++x) if (in[x] > in[best]) best = x;
+            code |= best << (2 + 2 * n);
+            ++n; n_ins = 1;
+        }
+    }
+    if (depth < min_depth) {
+        code |= own << (2 + 2 * n); ++n;
+    } else {
+        cov = 1;
+        if (2 * (uint64_t)del > depth + 1) n_del = 1;
+        else {
+            uint64_t wv[4];
+            for (uint32_t x = 0; x < 4; ++x) wv[x] = (uint64_t)cb[x] + (x == own ? 1u : 0u);
+            uint32_t best = 0;
+            for (uint32_t x = 1; x < 4; ++x) if (wv[x] > wv[best]) best = x;
+            if (wv[own] == wv[best]) best = own;
+            code |= best << (2 + 2 * n); ++n;
+            n_sub = best != own ? 1u : 0u;
+        }
+    }
+    if (live) emit[g] = (uint8_t)(code | n);
+    // statistics
+    uint32_t s_sub = live ? n_sub : 0u, s_del = live ? n_del : 0u, s_ins = live ? n_ins : 0u, s_cov = live ? cov : 0u;
+    unsigned long long s_depth = live ? depth : 0ull;
+    const uint32_t r0 = __shfl(r, 0, 64);
+    if (__all(!live || r == r0)) {
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            s_sub += __shfl_xor(s_sub, d, 64); s_del += __shfl_xor(s_del, d, 64); s_ins += __shfl_xor(s_ins, d, 64); s_cov += __shfl_xor(s_cov, d, 64);
+            s_depth += __shfl_xor(s_depth, d, 64);
+        }
+        if (lane != 0) return;
+    }
+    bella_consensus_read* const st = stats + r;
+    if (s_sub) atomicAdd(&st->substituted, s_sub);
+    if (s_del) atomicAdd(&st->deleted, s_del);
+    if (s_ins) atomicAdd(&st->inserted, s_ins);
+    if (s_cov) atomicAdd(&st->covered, s_cov);
+    if (s_depth) atomicAdd((unsigned long long*)&st->depth_sum, s_depth);
+}
+
+// scan[g] = bases emitted before position g (scan[total] = all of them)
+__global__ void k_cons_write(const uint8_t* emit, const uint64_t* scan, uint64_t total, uint8_t* out) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    const uint32_t e = emit[g], n = e & 3u;
+    const uint64_t o = scan[g];
+    if (n >= 1) out[o] = (uint8_t)"ACGT"[(e >> 2) & 3u];
+    if (n >= 2) out[o + 1] = (uint8_t)"ACGT"[(e >> 4) & 3u];
+}
+
+__global__ void k_cons_reads(const uint64_t* roff, const uint64_t* scan, uint32_t nreads, uint64_t* offs, bella_consensus_read* stats) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > nreads) return;
+    const uint64_t o = scan[roff[r]];
+    offs[r] = o;
+    if (r < nreads) {
+        stats[r].len_before = (uint32_t)(roff[r + 1] - roff[r]);
+        stats[r].len_after = (uint32_t)(scan[roff[r + 1]] - o);
+    }
+}
+#endif
+
+}  // namespace bella

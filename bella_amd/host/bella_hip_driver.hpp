@@ -107,7 +107,49 @@ struct StageOpts {
     int exact = 0;                   // alignments by the exact (growing band) X-drop of the reference's CUDA build
     int cigar = 0;                   // true PAF: every stage traces its passed pairs before it writes them (needs paf, no skip_alignment)
     uint32_t trace_band = 0;         // first band of the traces; 0 = the library's default
+    const char* correct = nullptr;   // read correction: every stage piles its traced pairs up on the device, the consensus
+                                     // of every read is written to this FASTA file after the last stage (needs alignment)
+    uint32_t min_depth = 3;          // ... positions with fewer votes keep the read's own base
 };
+
+// Read correction after the last stage: the tables of the contexts 1 .. N-1 (each piled up its own columns) are added into context 0 in
+// chunks of whole reads of at most ~4 M bases (144 MB on the host, whatever the read set), then the consensus and the FASTA file.
+inline void write_corrected(std::vector<Worker>& W, const StageOpts& o, const char* const* names, const uint32_t* lens) {
+    const uint32_t nreads = o.nreads;
+    bella_ctx* const c0 = W[0].ctx;
+    if (o.N > 1) {
+        constexpr uint64_t kChunkBases = 4ull << 20;
+        std::vector<uint32_t> buf;
+        for (uint32_t lo = 0; lo < nreads;) {
+            uint32_t hi = lo;
+            uint64_t nb = 0;
+            while (hi < nreads && (hi == lo || nb + lens[hi] <= kChunkBases)) nb += lens[hi++];
+            buf.resize((size_t)nb * BELLA_PILEUP_COUNTERS);
+            for (int g = 1; g < o.N; ++g) {
+                check(W[(size_t)g].ctx, bella_hip_get_pileup(W[(size_t)g].ctx, lo, hi - lo, buf.data()), "bella_hip_get_pileup");
+                check(c0, bella_hip_add_pileup(c0, lo, hi - lo, buf.data()), "bella_hip_add_pileup");
+            }
+            lo = hi;
+        }
+    }
+    bella_consensus_params cp;
+    cp.struct_size = (uint32_t)sizeof(cp);
+    cp.min_depth = o.min_depth;
+    uint64_t total = 0;
+    check(c0, bella_hip_consensus(c0, &cp, &total), "bella_hip_consensus");
+    std::vector<uint64_t> offs((size_t)nreads + 1, 0);
+    RawBuf<uint8_t> bases;
+    bases.resize((size_t)total);
+    std::vector<bella_consensus_read> st(nreads);
+    check(c0, bella_hip_get_consensus(c0, offs.data(), bases.data(), st.data()), "bella_hip_get_consensus");
+    const int wrc = bella_hip_write_fasta(o.correct, nreads, names, offs.data(), bases.data(), 0);
+    if (wrc) check(nullptr, wrc, "bella_hip_write_fasta");
+    uint64_t sub = 0, del = 0, ins = 0, cov = 0, all = 0;
+    for (const auto& s : st) { sub += s.substituted; del += s.deleted; ins += s.inserted; cov += s.covered; all += s.len_before; }
+    const std::string CorrectedReads = std::to_string(nreads) + " reads, " + std::to_string(all) + " -> " + std::to_string(total) + " bases, " + std::to_string(cov) +
+                                       " positions covered, " + std::to_string(sub) + " substituted, " + std::to_string(del) + " deleted, " + std::to_string(ins) + " inserted";
+    BELLA_HIP_LOGT(o.tag, CorrectedReads);
+}
 
 // Stage plan (overlap.hpp:365-404,682-710), passes, alignment, output.  W[g].ctx holds the operands, laid out for the output columns
 // i % N == g.  The products (estimateFLOP, a sum over a count stream) bound nnz(C) from above: if even they fit one stage the numeric phase
@@ -142,9 +184,11 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
                 else check(w.ctx, bella_hip_align_pairs(w.ctx, &p, &npass), "bella_hip_align_pairs");
                 w.alns.resize(w.nnzc);
                 if (w.nnzc) check(w.ctx, bella_hip_get_alignments(w.ctx, w.alns.data()), "bella_hip_get_alignments");
+                uint64_t ntr = 0, nops = 0;
+                // (--correct: the stage's runs vote on the device; they come to the host only when the true PAF wants them too)
+                if (o.correct) check(w.ctx, bella_hip_trace_pairs_pileup(w.ctx, &p, o.trace_band, o.cigar ? 1 : 0, &ntr, &nops), "bella_hip_trace_pairs_pileup");
+                else if (o.cigar) check(w.ctx, bella_hip_trace_pairs(w.ctx, &p, o.trace_band, 1, &ntr, &nops), "bella_hip_trace_pairs");
                 if (o.cigar) {
-                    uint64_t ntr = 0, nops = 0;
-                    check(w.ctx, bella_hip_trace_pairs(w.ctx, &p, o.trace_band, 1, &ntr, &nops), "bella_hip_trace_pairs");
                     w.traces.resize(w.nnzc);
                     w.ops.resize(nops);                                       // (host memory: 4 bytes per run; -m stages bound it as they bound the records)
                     check(w.ctx, bella_hip_get_traces(w.ctx, w.traces.data(), w.ops.data()), "bella_hip_get_traces");
@@ -159,6 +203,7 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
             colptrC[i + 1] = colptrC[i] + (w.colptr[i + 1] - w.colptr[i]);
         }
     };
+    if (o.correct) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_pileup_reset(W[(size_t)g].ctx), "bella_hip_pileup_reset"); });
     CallStats& cs = last_call_stats();
     cs = CallStats();
     const double free_memory = o.total_memory_mb * 1024 * 1024;               // estimateMemory, overlap.hpp:365-404 (no LINUX/OSX define)
@@ -266,6 +311,7 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         const std::string OutputtingTime = std::to_string(ws.seconds) + " seconds";
         BELLA_HIP_LOGT(tag, OutputtingTime);
     }
+    if (o.correct) write_corrected(W, o, names, lens);
     cs.nreads = nreads; cs.stages = stages; cs.contexts = N; cs.nnzc = nnzc;
     for (auto& w : W) {
         bella_timings tm;

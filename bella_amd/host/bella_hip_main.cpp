@@ -16,6 +16,8 @@
 // "read+1 kmer+1 pos" per line) instead of counting: same ids as that reference run, same output file byte for byte.
 //
 // --paf --cigar: true PAF: every stage traces its passed pairs on the device before it writes them.
+// --correct FILE: read correction: every stage's traced pairs vote into a per-read pileup on the device, the
+// consensus of every read goes to FILE as FASTA after the last stage; the main output file is what it is without the option.
 //
 // Not built (rejected loudly): --hopc, --estimate, --split-count > 1.
 #include <sys/stat.h>
@@ -35,11 +37,12 @@
 namespace {
 
 struct Options {
-    std::string fastq_list, output, tuples;
+    std::string fastq_list, output, tuples, correct;
     int kmer = 17, xdrop = 7, memory = 8000, bin_size = 500, gpus = 1, split_count = 1, window = 0, upper = 8, lower = 2;
     double error = 0.15, deviation = 0.1;
     bool estimate = false, skip_alignment = false, paf = false, hopc = false, syncmer = false, help = false, exact = false, cigar = false;
-    int trace_band = 0;
+    int trace_band = 0, min_depth = 3;
+    bool min_depth_given = false;
 };
 
 const char* kHelp =
@@ -68,6 +71,8 @@ const char* kHelp =
     "      --exact-xdrop          the exact (growing band) X-drop of the reference's GPU build instead of Xavier\n"
     "      --cigar                with --paf: true PAF -- base-level alignment of every line (residue matches, block length, NM, cg:Z:)\n"
     "      --trace-band arg       first band of the base-level alignments, in diagonals (default: 256; doubled where a path touches it)\n"
+    "      --correct arg          corrected reads (FASTA): per-read pileup of the base-level alignments on the device, majority consensus\n"
+    "      --min-depth arg        with --correct: votes a position needs before it is changed (default: 3)\n"
     "  -h, --help                 Usage\n";
 
 [[noreturn]] void die(const std::string& msg) {
@@ -85,6 +90,7 @@ Options parse(int argc, char** argv) {
         {"score-deviation", 0, 2, &o.deviation}, {"bin-size", 'b', 1, &o.bin_size}, {"paf", 0, 0, &o.paf}, {"gpus", 'g', 1, &o.gpus},
         {"split-count", 0, 1, &o.split_count}, {"hopc", 0, 0, &o.hopc}, {"window", 'w', 1, &o.window}, {"syncmer", 's', 0, &o.syncmer},
         {"upper-freq", 'u', 1, &o.upper}, {"lower-freq", 'l', 1, &o.lower}, {"tuples", 0, 3, &o.tuples}, {"exact-xdrop", 0, 0, &o.exact}, {"cigar", 0, 0, &o.cigar}, {"trace-band", 0, 1, &o.trace_band},
+        {"correct", 0, 3, &o.correct}, {"min-depth", 0, 1, &o.min_depth},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
         char* end = nullptr;
@@ -118,6 +124,7 @@ Options parse(int argc, char** argv) {
             val = argv[++i];
         }
         assign(*sp, val, a);
+        if (sp->dst == &o.min_depth) o.min_depth_given = true;
     }
     return o;
 }
@@ -171,7 +178,10 @@ int main(int argc, char** argv) {
     if (o.cigar && !o.paf) die("--cigar needs --paf (the base-level alignment is written as PAF columns 10-11 and the cg:Z: tag)");
     if (o.cigar && o.skip_alignment) die("--cigar cannot be combined with --skip-alignment (there is no alignment to trace)");
     if (o.trace_band < 0 || o.trace_band > (1 << 18)) die("--trace-band must be in [0, 262144]");
-    if (o.trace_band && !o.cigar) die("--trace-band needs --cigar");
+    if (o.trace_band && !o.cigar && o.correct.empty()) die("--trace-band needs --cigar or --correct");
+    if (!o.correct.empty() && o.skip_alignment) die("--correct cannot be combined with --skip-alignment (the pileup is made of base-level alignments)");
+    if (o.min_depth_given && o.min_depth < 1) die("--min-depth must be at least 1");
+    if (o.min_depth_given && o.correct.empty()) die("--min-depth needs --correct");
     if (o.kmer < 1 || o.kmer > 32) die("-k must be in [1,32] (one 64-bit word per k-mer, Kmer.hpp:27-28)");
     const std::string outfile = o.output + ".out";                  // main.cpp:113-130
     std::remove(outfile.c_str());
@@ -306,6 +316,8 @@ int main(int argc, char** argv) {
     so.exact = o.exact ? 1 : 0;
     so.cigar = o.cigar ? 1 : 0;
     so.trace_band = (uint32_t)o.trace_band;
+    so.correct = o.correct.empty() ? nullptr : o.correct.c_str();
+    so.min_depth = (uint32_t)o.min_depth;
     const double t_stages = now_s();
     run_stages(W, so, names.data(), lens.data());
     {

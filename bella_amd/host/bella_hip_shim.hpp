@@ -86,6 +86,16 @@ void HashSpGEMM(const CSC<uint32_t, unsigned short>& A, const CSC<uint32_t, unsi
         if (v > (1ul << 18)) std::cerr << "bella_hip: BELLA_HIP_TRACE_BAND must be in [0, 262144]: ignored" << std::endl;
         else o.trace_band = (uint32_t)v;
     }
+    // BELLA_HIP_CORRECT=<path>: corrected reads as FASTA; BELLA_HIP_MIN_DEPTH = votes a position needs (default 3)
+    if (const char* e = std::getenv("BELLA_HIP_CORRECT")) {
+        if (*e && !bpars.skipAlignment) o.correct = e;
+        else if (*e) std::cerr << "bella_hip: BELLA_HIP_CORRECT is set but ignored: it needs an alignment (no --skip-alignment)" << std::endl;
+    }
+    if (const char* e = std::getenv("BELLA_HIP_MIN_DEPTH")) {
+        const unsigned long v = std::strtoul(e, nullptr, 10);
+        if (v < 1 || v > 0xFFFFFFFFul) std::cerr << "bella_hip: BELLA_HIP_MIN_DEPTH must be at least 1: ignored" << std::endl;
+        else o.min_depth = (uint32_t)v;
+    }
 
     std::vector<Worker> W((size_t)N);
     uint8_t comm_id[BELLA_HIP_COMM_ID_BYTES];

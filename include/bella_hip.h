@@ -331,6 +331,9 @@ typedef struct {
     uint64_t ops;                 /* runs written                                                            */
     uint32_t batches;
     uint32_t band0;               /* the band the first round used                                           */
+    double vote_ms;               /* bella_hip_trace_pairs_pileup: the vote kernel (device time, all batches) */
+    uint64_t votes;               /* ... counter increments it issued                                        */
+    uint64_t ops_host_bytes;      /* bytes of runs the call staged on the host (0 with keep_ops == 0)         */
 } bella_trace_stats;
 /* Traces the pairs of the last bella_hip_align_pairs / _exact (passed_only != 0: those with bella_aln::passed).  *ntraced pairs,
  * *nops runs in all.  BELLA_ERR_STATE without alignments.  Pairs run in batches sized from the free device memory (direction bytes:
@@ -358,6 +361,52 @@ int bella_hip_get_trace_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 int bella_hip_write_output_traced(const char* path, const bella_params* p, uint32_t nreads, const char* const* names, const uint32_t* lens,
                                   const bella_pair* pairs, const bella_aln* alns, const bella_trace* traces, const uint32_t* ops, uint64_t nops_total,
                                   uint64_t npairs, int nthreads, bella_write_stats* stats);
+
+/* ---- read correction: pileup of the traced alignments and consensus (no counterpart in the reference) --------
+ * The table: for every base position of every read nine uint32 counters, BELLA_PILEUP_COUNTERS * 4 = 36 bytes per base, in read order:
+ * [0..3] votes for A, C, G, T at the position, [4] votes that the base is not there, [5..8] votes for ONE base (A, C, G, T) inserted in
+ * the junction just before the position.  A traced pair votes on both of its reads (V = read cid, H = read rid; on strand 1 every vote on H
+ * lands at the mirrored position with the complemented base); a run of inserted bases casts one vote, with the base that comes first in
+ * the voted read's own direction; the junction behind a read's last base has no counters.  Counters are plain sums (a counter above
+ * 2^32 - 1 is out of scope), so the table does not depend on the order of the pairs, batches, stages or contexts. */
+#define BELLA_PILEUP_COUNTERS 9
+/* Allocates (first use) and zeroes the table for the loaded reads: 36 bytes x total bases of device memory, BELLA_ERR_NOMEM when it does not
+ * fit.  Loading other reads drops the table. */
+int bella_hip_pileup_reset(bella_ctx* ctx);
+/* What bella_hip_trace_pairs(passed_only = 1) does, and every traced pair's votes added to the table, batch by batch, from the batch's runs
+ * while they are in device memory.  keep_ops == 0: the runs are not staged on the host (host memory of the call does not grow with the
+ * pairs); bella_hip_get_traces then hands out the records only (ops must be NULL) -- op_off / nops are what they would be with the runs
+ * kept.  keep_ops != 0: the context is left exactly as bella_hip_trace_pairs leaves it.  The table accumulates over calls until the next
+ * bella_hip_pileup_reset; a pair repeated with a wider band votes once, with its final trace.  BELLA_ERR_STATE without a table. */
+int bella_hip_trace_pairs_pileup(bella_ctx* ctx, const bella_params* p, uint32_t band0, int keep_ops, uint64_t* ntraced, uint64_t* nops);
+/* Copies the counters of the reads [first_read, first_read + nreads) out (out: 9 uint32 per base of those reads), or adds a caller's
+ * counters into the table (how several contexts merge: each piles up its own columns, one of them adds the others' tables). */
+int bella_hip_get_pileup(bella_ctx* ctx, uint32_t first_read, uint32_t nreads, uint32_t* out);
+int bella_hip_add_pileup(bella_ctx* ctx, uint32_t first_read, uint32_t nreads, const uint32_t* in);
+/* device bytes of the table (0 without one) */
+int bella_hip_get_pileup_bytes(bella_ctx* ctx, uint64_t* bytes);
+/* Consensus of every read from the table.  With depth(p) = sum of base[p] + del[p], own base b[p], for p = 0 .. len - 1:
+ * (1) junction before p (p >= 1): c = min(depth(p - 1), depth(p)), I = sum of ins[p]; if c >= min_depth and 2 I > c + 1 emit the base with
+ * the most ins votes (ties: A < C < G < T); (2) position p: depth(p) < min_depth emits b[p]; else 2 del[p] > depth(p) + 1 emits nothing;
+ * else emits the base of largest base[p][x] + (x == b[p]) (ties: b[p] if it is one of them, else A < C < G < T).  A read nobody voted on
+ * comes out unchanged.  The result stays with the context for bella_hip_get_consensus. */
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_consensus_params) of the caller's header (the struct may grow) */
+    uint32_t min_depth;           /* >= 1; the documented default is 3                                          */
+} bella_consensus_params;
+typedef struct {
+    uint32_t len_before, len_after;
+    uint32_t substituted;         /* positions whose emitted base differs from the read's                       */
+    uint32_t deleted;             /* positions that emitted nothing                                             */
+    uint32_t inserted;            /* junctions that emitted a base                                              */
+    uint32_t covered;             /* positions with depth >= min_depth                                          */
+    uint64_t depth_sum;           /* sum of depth over the read's positions                                     */
+} bella_consensus_read;
+int bella_hip_consensus(bella_ctx* ctx, const bella_consensus_params* params, uint64_t* total_bases);
+/* offsets[nreads + 1] into bases[total_bases] (upper-case ASCII), stats[nreads].  Any pointer may be NULL. */
+int bella_hip_get_consensus(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases, bella_consensus_read* stats);
+/* ">name\n" + one sequence line per read, in input order.  append == 0 truncates the file.  Plain host code, no context. */
+int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* names, const uint64_t* offsets, const uint8_t* bases, int append);
 
 /* ---- multi-GPU: one context per GPU, RCCL over xGMI ------------------------------------------------
  * The reference's multi-GPU path hands alignment batches to the devices inside one call (loganGPU/functions.cuh:441-443,

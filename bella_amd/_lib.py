@@ -22,6 +22,11 @@ assert TRACE_DT.itemsize == 56
 CONS_DT = np.dtype([("len_before", "<u4"), ("len_after", "<u4"), ("substituted", "<u4"), ("deleted", "<u4"), ("inserted", "<u4"), ("covered", "<u4"),
                     ("depth_sum", "<u8")])
 assert CONS_DT.itemsize == 32
+OVL_DT = np.dtype([("cid", "<u4"), ("rid", "<u4"), ("begV", "<i4"), ("endV", "<i4"), ("begH", "<i4"), ("endH", "<i4"), ("score", "<i4"),
+                   ("strand", "u1"), ("pad", "u1", (3,))])
+EDGE_DT = np.dtype([("src", "<u4"), ("dst", "<u4"), ("len", "<u4"), ("ovl", "<u4"), ("rec", "<u4"), ("flags", "<u4")])
+assert OVL_DT.itemsize == 32 and EDGE_DT.itemsize == 24
+TRACE_PASSED_ONLY, TRACE_DROP_OPS, TRACE_PILEUP = 1, 2, 4
 PILEUP_COUNTERS = 9      # per base: votes for A C G T, del, one inserted A C G T in the junction before the base
 assert PAIR_DT.itemsize == 16 and EXT_DT.itemsize == 8 and ALN_DT.itemsize == 32 and SEED_DT.itemsize == 12
 
@@ -65,6 +70,18 @@ class TraceStats(C.Structure):
 
 class ConsensusParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_depth", C.c_uint32)]
+
+
+class GraphParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_overlap", C.c_uint32), ("max_overhang", C.c_uint32), ("overhang_permille", C.c_uint32),
+                ("fuzz", C.c_uint32)]
+
+
+class GraphStats(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("n_short", C.c_uint64), ("n_internal", C.c_uint64), ("contained_reads", C.c_uint64),
+                ("edges_all", C.c_uint64), ("edges_kept", C.c_uint64), ("edges_reduced", C.c_uint64), ("edges_final", C.c_uint64),
+                ("max_degree", C.c_uint32), ("overcap_vertices", C.c_uint32), ("classify_ms", C.c_double), ("sort_ms", C.c_double),
+                ("reduce_ms", C.c_double), ("host_ms", C.c_double)]
 
 
 # every symbol include/bella_hip.h declares: (name, restype, argtypes)
@@ -136,6 +153,16 @@ SIGNATURES = [
     ("bella_hip_consensus", C.c_int, [vp, C.POINTER(ConsensusParams), C.POINTER(C.c_uint64)]),
     ("bella_hip_get_consensus", C.c_int, [vp, vp, vp, vp]),
     ("bella_hip_write_fasta", C.c_int, [C.c_char_p, C.c_uint32, vp, vp, vp, C.c_int]),
+    ("bella_hip_graph_reset", C.c_int, [vp]),
+    ("bella_hip_graph_add_overlaps", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_graph_add_traced", C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    ("bella_hip_graph_get_overlaps", C.c_int, [vp, vp, C.POINTER(C.c_uint64)]),
+    ("bella_hip_graph_build", C.c_int, [vp, C.POINTER(GraphParams)]),
+    ("bella_hip_graph_get", C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), vp, vp, vp]),
+    ("bella_hip_graph_get_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_trace_pairs_flags", C.c_int, [vp, C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("bella_hip_get_read_bases", C.c_int, [vp, vp, vp]),
+    ("bella_hip_write_gfa", C.c_int, [C.c_char_p, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
     ("bella_hip_get_timings", C.c_int, [vp, C.POINTER(Timings)]),
     ("bella_hip_get_memory", C.c_int, [vp, C.POINTER(Memory)]),
     ("bella_hip_get_memory_sized", C.c_int, [vp, vp, C.c_uint64]),

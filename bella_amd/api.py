@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import ALN_DT, CONS_DT, EXT_DT, PAIR_DT, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
+from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, OVL_DT, PAIR_DT, GraphParams, GraphStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
 class BellaHipError(RuntimeError):
@@ -370,6 +370,75 @@ class Engine:
         self._chk(self.lib.bella_hip_get_consensus(self.h, offs.ctypes.data, _p(bases), _p(stats)))
         return offs, bases, stats
 
+    # ---- string graph: overlap classes, containment, transitive reduction ----
+    GRAPH_DEFAULTS = dict(min_overlap=1000, max_overhang=1000, overhang_permille=800, fuzz=1000)
+
+    def trace_pairs_records(self, pars: BellaPars, band0: int = 0, passed_only: bool = True):
+        """bella_hip_trace_pairs_flags with the runs dropped: traces[npairs] of TRACE_DT only -- no run is written or staged (what the
+        graph needs: graph_add_traced reads the end points)."""
+        nt, no = C.c_uint64(0), C.c_uint64(0)
+        cp = pars.c()
+        flags = _lib.TRACE_DROP_OPS | (_lib.TRACE_PASSED_ONLY if passed_only else 0)
+        self._chk(self.lib.bella_hip_trace_pairs_flags(self.h, C.byref(cp), band0, flags, C.byref(nt), C.byref(no)))
+        tr = np.zeros(self.npairs, TRACE_DT)
+        self._chk(self.lib.bella_hip_get_traces(self.h, _p(tr), None))
+        return tr
+
+    def graph_reset(self):
+        self._chk(self.lib.bella_hip_graph_reset(self.h))
+
+    def graph_add_overlaps(self, recs: np.ndarray):
+        """appends explicit overlap records (OVL_DT); they accumulate until graph_reset or other reads"""
+        recs = np.ascontiguousarray(recs, OVL_DT)
+        self._chk(self.lib.bella_hip_graph_add_overlaps(self.h, _p(recs), len(recs)))
+
+    def graph_add_traced(self) -> int:
+        """appends one record per passed, traced pair of the last align_pairs + trace_pairs; returns how many"""
+        n = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_graph_add_traced(self.h, C.byref(n)))
+        return n.value
+
+    def graph_overlaps(self) -> np.ndarray:
+        n = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_graph_get_overlaps(self.h, None, C.byref(n)))
+        out = np.zeros(n.value, OVL_DT)
+        self._chk(self.lib.bella_hip_graph_get_overlaps(self.h, _p(out), C.byref(n)))
+        return out
+
+    def graph_build(self, **params):
+        """classifies the accumulated records, drops contained reads, reduces transitively (on the device); min_overlap, max_overhang,
+        overhang_permille, fuzz default to 1000, 1000, 800, 1000"""
+        p = dict(self.GRAPH_DEFAULTS)
+        for k, v in params.items():
+            if k not in p:
+                raise TypeError("unknown graph parameter %r" % k)
+            p[k] = int(v)
+        gp = GraphParams(C.sizeof(GraphParams), p["min_overlap"], p["max_overhang"], p["overhang_permille"], p["fuzz"])
+        self._chk(self.lib.bella_hip_graph_build(self.h, C.byref(gp)))
+
+    def graph(self):
+        """(offsets uint64[2 nreads + 1], edges of EDGE_DT in list order, contained uint8[nreads]) of the last graph_build"""
+        nv, ne = C.c_uint32(0), C.c_uint64(0)
+        self._chk(self.lib.bella_hip_graph_get(self.h, C.byref(nv), C.byref(ne), None, None, None))
+        offs = np.zeros(nv.value + 1, np.uint64)
+        edges = np.zeros(ne.value, EDGE_DT)
+        cont = np.zeros(nv.value // 2, np.uint8)
+        self._chk(self.lib.bella_hip_graph_get(self.h, None, None, offs.ctypes.data, _p(edges), _p(cont)))
+        return offs, edges, cont
+
+    def graph_stats(self) -> dict:
+        st = GraphStats()
+        self._chk(self.lib.bella_hip_graph_get_stats(self.h, C.byref(st), C.sizeof(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def read_bases(self):
+        """(offsets uint64[nreads + 1], bases uint8 ASCII) of the loaded reads"""
+        offs = np.zeros(self.nreads + 1, np.uint64)
+        self._chk(self.lib.bella_hip_get_read_bases(self.h, offs.ctypes.data, None))
+        bases = np.zeros(int(offs[-1]), np.uint8)
+        self._chk(self.lib.bella_hip_get_read_bases(self.h, None, _p(bases)))
+        return offs, bases
+
     def trace_batch(self, seeds: np.ndarray, alns: np.ndarray, pars: BellaPars, band0: int = 0):
         """The same on explicit seeds and their alignments (what xdrop_batch returned for them, or any rectangles)."""
         seeds = np.ascontiguousarray(seeds, SEED_DT)
@@ -505,6 +574,27 @@ def write_fasta(filename: str, names, offsets, bases, append: bool = False) -> N
     rc = lib.bella_hip_write_fasta(os.fsencode(filename), len(enc), C.cast(arr, C.c_void_p), offs.ctypes.data, _p(b), 1 if append else 0)
     if rc:
         raise BellaHipError(rc, "bella_hip_write_fasta failed")
+
+
+def write_gfa(filename: str, names, lengths, offsets, edges, contained, seqs=None) -> None:
+    """bella_hip_write_gfa: GFA 1 of a graph (what Engine.graph returned): S lines of the non-contained reads in input order -- with the
+    reads' own bases (seqs: one bytes per read) or '*' -- and one L line per edge in list order."""
+    lib = _lib.load()
+    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    lens = np.ascontiguousarray(lengths, np.uint32)
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    edges = np.ascontiguousarray(edges, EDGE_DT)
+    cont = np.ascontiguousarray(contained, np.uint8)
+    assert len(offs) == 2 * len(enc) + 1 and len(cont) == len(enc) == len(lens) and int(offs[-1]) == len(edges)
+    boffs = bases = None
+    if seqs is not None:
+        boffs = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+        bases = np.frombuffer(b"".join(bytes(s) for s in seqs), np.uint8)
+    rc = lib.bella_hip_write_gfa(os.fsencode(filename), len(enc), C.cast(arr, C.c_void_p), _p(lens), boffs.ctypes.data if boffs is not None else None,
+                                 (bases.ctypes.data if len(bases) else boffs.ctypes.data) if bases is not None else None, offs.ctypes.data, _p(edges), _p(cont))
+    if rc:
+        raise BellaHipError(rc, "bella_hip_write_gfa failed")
 
 
 def hash_spgemm(engine: Engine, pars: BellaPars, filename: str, stdout=sys.stdout, stages: int = 1):

@@ -22,6 +22,7 @@
 #include "comm.hpp"
 #include "core.hpp"
 #include "fastq.hpp"
+#include "graph.hpp"
 #include "kcount.hpp"
 #include "logan.hpp"
 #include "order.hpp"
@@ -201,6 +202,14 @@ struct bella_ctx {
     bool have_pile = false, have_cons = false;
     uint64_t cons_total = 0;
     Buf pile, pile_pairs, pile_cnt, pile_tmp, cons_emit, cons_scan, cons_out, cons_offs, cons_stats;
+    // string graph (graph.hpp): the accumulated overlap records, and the last build's result (both on the host: the
+    // graph is small next to what it was made from)
+    std::vector<bella_overlap> g_recs;
+    bool have_graph = false;
+    std::vector<uint64_t> g_off;
+    std::vector<bella_graph_edge> g_edges;
+    std::vector<uint8_t> g_cont;
+    bella_graph_stats g_stats{};
     bella_timings tm{};
     hipEvent_t ev[12]{};
     uint32_t* pinned = nullptr;          // 128 host words the per-pass read backs land in
@@ -937,6 +946,8 @@ static int set_reads_impl(bella_ctx* c, const uint64_t* offsets, uint32_t nreads
     c->have_tuples = false;
     for (Buf* b : {&c->pile, &c->cons_out, &c->cons_offs, &c->cons_stats}) release(*b);      // (the pileup belongs to the reads it was sized for)
     c->have_pile = c->have_cons = false;
+    c->g_recs.clear();                                                // (so do the overlap records and the graph)
+    c->have_graph = false;
     return 0;
 }
 
@@ -3743,7 +3754,10 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                 bops += pres[q].nops;
                 st.pairs++;
             }
-            if (bops) {
+            if (bops && !keep_ops && !vote) {                          // nobody reads the runs: the records are complete without the writing walk
+                ops_seen += bops;
+                st.ops += bops;
+            } else if (bops) {
                 ENSURE(c, c->tr_ops, 4 * (size_t)bops);
                 HIPCHK(c, hipMemcpyAsync(c->tr_opoff.p, opoff.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, c->stream));
                 HIPCHK(c, hipEventRecord(e0, c->stream));
@@ -3838,10 +3852,18 @@ int bella_hip_trace_pairs_pileup(bella_ctx* c, const bella_params* p, uint32_t b
     return trace_pairs_impl(c, p, band0, 1, true, keep_ops != 0, ntraced, nops);
 }
 
+int bella_hip_trace_pairs_flags(bella_ctx* c, const bella_params* p, uint32_t band0, uint32_t flags, uint64_t* ntraced, uint64_t* nops) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (flags & ~(BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS | BELLA_TRACE_PILEUP)) return fail(c, BELLA_ERR_BAD_ARG, "trace_pairs_flags: unknown flag");
+    const bool vote = (flags & BELLA_TRACE_PILEUP) != 0;
+    if (vote && !(flags & BELLA_TRACE_PASSED_ONLY)) return fail(c, BELLA_ERR_BAD_ARG, "trace_pairs_flags: the pileup takes the passed pairs only");
+    return trace_pairs_impl(c, p, band0, (flags & BELLA_TRACE_PASSED_ONLY) ? 1 : 0, vote, !(flags & BELLA_TRACE_DROP_OPS), ntraced, nops);
+}
+
 int bella_hip_get_traces(bella_ctx* c, bella_trace* out, uint32_t* ops) {
     if (!c) return BELLA_ERR_BAD_ARG;
     if (!c->have_traces || !c->have_alns) return fail(c, BELLA_ERR_STATE, "trace_pairs first");
-    if (ops && !c->trace_ops_kept) return fail(c, BELLA_ERR_STATE, "the last bella_hip_trace_pairs_pileup ran with keep_ops = 0: the runs were not kept (pass ops = NULL)");
+    if (ops && !c->trace_ops_kept) return fail(c, BELLA_ERR_STATE, "the last trace ran with keep_ops = 0 / BELLA_TRACE_DROP_OPS: the runs were not kept (pass ops = NULL)");
     if (out && !c->traces.empty()) std::memcpy(out, c->traces.data(), sizeof(bella_trace) * c->traces.size());
     if (ops && !c->trace_ops.empty()) std::memcpy(ops, c->trace_ops.data(), 4 * c->trace_ops.size());
     return 0;
@@ -4034,6 +4056,289 @@ int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* 
     }
     if (std::fclose(f) != 0) ok = false;
     if (!ok) { fprintf(stderr, "bella_hip_write_fasta: writing %s failed\n", path); return BELLA_ERR_BAD_ARG; }
+    return 0;
+}
+
+// ---- string graph (graph.hpp) ----------------------------------------------------------------------------------
+struct KeepU32 {
+    __host__ __device__ uint32_t operator()(const uint8_t& v) const { return (uint32_t)v; }
+};
+
+int bella_hip_graph_reset(bella_ctx* c) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    std::vector<bella_overlap>().swap(c->g_recs);
+    c->have_graph = false;
+    return 0;
+}
+
+int bella_hip_graph_add_overlaps(bella_ctx* c, const bella_overlap* recs, uint64_t n) {
+    if (!c || (n && !recs)) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
+    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (c->g_recs.size() + n >= (1ull << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 overlap records");
+    for (uint64_t i = 0; i < n; ++i) {
+        const bella_overlap& r = recs[i];
+        if (r.cid == r.rid || r.cid >= c->nreads || r.rid >= c->nreads || r.strand > 1)
+            return fail(c, BELLA_ERR_BAD_ARG, "overlap record %llu: reads %u and %u (of %u), strand %u", (unsigned long long)i, r.cid, r.rid, c->nreads, (unsigned)r.strand);
+        const int64_t l1 = c->host_lens[r.cid], l2 = c->host_lens[r.rid];
+        if (r.begV < 0 || r.begV >= r.endV || r.endV > l1 || r.begH < 0 || r.begH >= r.endH || r.endH > l2)
+            return fail(c, BELLA_ERR_BAD_ARG, "overlap record %llu: [%d, %d) of %lld bases and [%d, %d) of %lld", (unsigned long long)i, r.begV, r.endV, (long long)l1, r.begH,
+                        r.endH, (long long)l2);
+    }
+    c->g_recs.insert(c->g_recs.end(), recs, recs + n);
+    c->have_graph = false;
+    return 0;
+}
+
+int bella_hip_graph_add_traced(bella_ctx* c, uint64_t* added) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_traces || !c->have_alns) return fail(c, BELLA_ERR_STATE, "trace_pairs first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->nalns;
+    if (c->traces.size() != n) return fail(c, BELLA_ERR_STATE, "the traces are not those of the last alignment");
+    std::vector<bella_pair> pairs(n);
+    std::vector<bella_aln> alns(n);
+    if (n) {
+        HIPCHK(c, c->stager.d2h(pairs.data(), c->pairs.p, sizeof(bella_pair) * n, c->stream));
+        HIPCHK(c, c->stager.d2h(alns.data(), c->alns.p, sizeof(bella_aln) * n, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    std::vector<bella_overlap> recs;
+    for (size_t i = 0; i < n; ++i) {
+        const bella_trace& t = c->traces[i];
+        if (!alns[i].passed || !t.nops) continue;
+        bella_overlap r{};
+        r.cid = pairs[i].cid; r.rid = pairs[i].rid;
+        r.begV = t.tbegV; r.endV = t.tendV; r.begH = t.tbegH; r.endH = t.tendH;
+        r.score = alns[i].score;
+        r.strand = alns[i].strand ? 1 : 0;
+        recs.push_back(r);
+    }
+    const int rc = bella_hip_graph_add_overlaps(c, recs.data(), recs.size());
+    if (rc) return rc;
+    if (added) *added = recs.size();
+    return 0;
+}
+
+int bella_hip_graph_get_overlaps(bella_ctx* c, bella_overlap* out, uint64_t* n) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (n) *n = c->g_recs.size();
+    if (out && !c->g_recs.empty()) std::memcpy(out, c->g_recs.data(), sizeof(bella_overlap) * c->g_recs.size());
+    return 0;
+}
+
+int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
+    using clk = std::chrono::steady_clock;
+    if (!c) return BELLA_ERR_BAD_ARG;
+    bella_graph_params gp{(uint32_t)sizeof(bella_graph_params), 1000, 1000, 800, 1000};
+    if (params) {
+        if (params->struct_size < sizeof(bella_graph_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_graph_params: struct_size %u is too small", params->struct_size);
+        gp = *params;
+    }
+    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const auto t_begin = clk::now();
+    c->have_graph = false;
+    const uint32_t nr = c->nreads, nv = 2 * nr;
+    const uint32_t n = (uint32_t)c->g_recs.size(), nc = 2 * n;
+    if (nr >= (1u << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 reads");
+    bella_graph_stats st{};
+    st.records = n;
+    Buf recs, cand, cont, cnt, ok, deg, off, key1, key1b, idx, idxb, key2, key2b, edges, pos, bykey, bykeyb, gmark, red, keep, scan, fin, foff;
+    struct Guard { std::vector<Buf*> v; ~Guard() { for (Buf* b : v) release(*b); } } guard{{&recs, &cand, &cont, &cnt, &ok, &deg, &off, &key1, &key1b, &idx, &idxb, &key2, &key2b,
+                                                                                           &edges, &pos, &bykey, &bykeyb, &gmark, &red, &keep, &scan, &fin, &foff}};
+    ENSURE(c, recs, sizeof(bella_overlap) * (size_t)n);
+    ENSURE(c, cand, sizeof(bella_graph_edge) * (size_t)nc);
+    ENSURE(c, cont, 4 * (size_t)nr);
+    ENSURE(c, cnt, 4 * kGcCount);
+    ENSURE(c, ok, nc);
+    ENSURE(c, deg, 4 * ((size_t)nv + 1));
+    ENSURE(c, off, 4 * ((size_t)nv + 1));
+    ENSURE(c, key1, 4 * (size_t)nc); ENSURE(c, key1b, 4 * (size_t)nc);
+    ENSURE(c, idx, 4 * (size_t)nc); ENSURE(c, idxb, 4 * (size_t)nc);
+    ENSURE(c, key2, 8 * (size_t)nc); ENSURE(c, key2b, 8 * (size_t)nc);
+    ENSURE(c, pos, 4 * (size_t)nc);
+    uint32_t* const d_cnt = ptr<uint32_t>(cnt);
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
+    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1)); HIPCHK(c, hipEventCreate(&e2)); HIPCHK(c, hipEventCreate(&e3));
+    struct EvGuard { hipEvent_t a, b, d, e; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(d); (void)hipEventDestroy(e); } } evg{e0, e1, e2, e3};
+    if (n) HIPCHK(c, c->stager.h2d(recs.p, c->g_recs.data(), sizeof(bella_overlap) * (size_t)n, c->stream));
+    HIPCHK(c, hipMemsetAsync(cont.p, 0, std::max<size_t>(4 * (size_t)nr, 16), c->stream));
+    HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kGcCount, c->stream));
+    HIPCHK(c, hipMemsetAsync(deg.p, 0, 4 * ((size_t)nv + 1), c->stream));
+    // ---- classes
+    HIPCHK(c, hipEventRecord(e0, c->stream));
+    if (n) {
+        k_graph_classify<<<nblk(n), 256, 0, c->stream>>>(ptr<bella_overlap>(recs), n, ptr<uint64_t>(c->roff), gp.min_overlap, gp.max_overhang, gp.overhang_permille,
+                                                         ptr<bella_graph_edge>(cand), ptr<uint32_t>(cont), d_cnt);
+        KCHK(c);
+    }
+    HIPCHK(c, hipEventRecord(e1, c->stream));
+    // ---- lists: filter, degrees, scan, two stable sorts, gather
+    if (nc) {
+        k_graph_filter<<<nblk(nc), 256, 0, c->stream>>>(ptr<bella_graph_edge>(cand), nc, ptr<uint32_t>(cont), ptr<uint8_t>(ok), ptr<uint32_t>(deg), ptr<uint32_t>(key1),
+                                                        ptr<uint32_t>(idx), d_cnt);
+        KCHK(c);
+    }
+    {
+        size_t tb = 0;
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ptr<uint32_t>(deg), ptr<uint32_t>(off), (int)(nv + 1), c->stream));
+        ENSURE(c, c->cubtmp, tb);
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, ptr<uint32_t>(deg), ptr<uint32_t>(off), (int)(nv + 1), c->stream));
+    }
+    if (nc) {
+        size_t tb = 0;
+        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, ptr<uint32_t>(key1), ptr<uint32_t>(key1b), ptr<uint32_t>(idx), ptr<uint32_t>(idxb), (int)nc, 0, 32, c->stream));
+        ENSURE(c, c->cubtmp, tb);
+        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, tb, ptr<uint32_t>(key1), ptr<uint32_t>(key1b), ptr<uint32_t>(idx), ptr<uint32_t>(idxb), (int)nc, 0, 32, c->stream));
+        k_graph_key2<<<nblk(nc), 256, 0, c->stream>>>(ptr<bella_graph_edge>(cand), ptr<uint8_t>(ok), ptr<uint32_t>(idxb), nc, ptr<uint64_t>(key2));
+        KCHK(c);
+        tb = 0;
+        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, ptr<uint64_t>(key2), ptr<uint64_t>(key2b), ptr<uint32_t>(idxb), ptr<uint32_t>(idx), (int)nc, 0, 64, c->stream));
+        ENSURE(c, c->cubtmp, tb);
+        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, tb, ptr<uint64_t>(key2), ptr<uint64_t>(key2b), ptr<uint32_t>(idxb), ptr<uint32_t>(idx), (int)nc, 0, 64, c->stream));
+    }
+    uint32_t hc[kGcCount] = {};
+    HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kGcCount, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t m = hc[kGcEdgesKept];
+    ENSURE(c, edges, sizeof(bella_graph_edge) * (size_t)m);
+    ENSURE(c, bykey, 8 * (size_t)m); ENSURE(c, bykeyb, 8 * (size_t)m);
+    if (m) {
+        k_graph_gather<<<nblk(m), 256, 0, c->stream>>>(ptr<bella_graph_edge>(cand), ptr<uint32_t>(idx), m, ptr<bella_graph_edge>(edges), ptr<uint32_t>(pos), ptr<uint64_t>(bykey));
+        KCHK(c);
+    }
+    k_graph_vertex_stats<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), nv, ptr<uint32_t>(cont), nr, kGraphLdsCap, d_cnt);
+    KCHK(c);
+    HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kGcCount, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const bool force_global = (c->debug & (1u << 19)) != 0;
+    const bool need_global = m && (force_global || hc[kGcOvercap] != 0);
+    const uint64_t* d_bykey = nullptr;
+    if (need_global) {                                                    // the over-cap path's neighbour sets: every vertex's dst values, ascending
+        size_t tb = 0;
+        HIPCHK(c, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, ptr<uint64_t>(bykey), ptr<uint64_t>(bykeyb), (int)m, 0, 64, c->stream));
+        ENSURE(c, c->cubtmp, tb);
+        HIPCHK(c, hipcub::DeviceRadixSort::SortKeys(c->cubtmp.p, tb, ptr<uint64_t>(bykey), ptr<uint64_t>(bykeyb), (int)m, 0, 64, c->stream));
+        d_bykey = ptr<uint64_t>(bykeyb);
+        ENSURE(c, gmark, m);
+    }
+    HIPCHK(c, hipEventRecord(e2, c->stream));
+    // ---- reduction, twin pass, compaction
+    ENSURE(c, red, (size_t)m + 1);
+    ENSURE(c, keep, (size_t)m + 1);
+    ENSURE(c, scan, 4 * ((size_t)m + 1));
+    ENSURE(c, foff, 8 * ((size_t)nv + 1));
+    HIPCHK(c, hipMemsetAsync(red.p, 0, (size_t)m + 1, c->stream));
+    if (m) {
+        k_graph_reduce<<<nblk(nv, kGraphBlock / 64), kGraphBlock, 0, c->stream>>>(ptr<uint32_t>(off), ptr<bella_graph_edge>(edges), nv, gp.fuzz, force_global ? 1u : 0u, d_bykey,
+                                                                                 need_global ? ptr<uint8_t>(gmark) : nullptr, ptr<uint8_t>(red), d_cnt);
+        KCHK(c);
+    }
+    k_graph_symmetric<<<nblk((uint64_t)m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(edges), m, ptr<uint32_t>(pos), ptr<uint8_t>(red), ptr<uint8_t>(keep));
+    KCHK(c);
+    {
+        hipcub::TransformInputIterator<uint32_t, KeepU32, const uint8_t*> it(ptr<uint8_t>(keep), KeepU32());
+        size_t tb = 0;
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, ptr<uint32_t>(scan), (int)(m + 1), c->stream));
+        ENSURE(c, c->cubtmp, tb);
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, ptr<uint32_t>(scan), (int)(m + 1), c->stream));
+    }
+    uint32_t nfinal = 0;
+    HIPCHK(c, hipMemcpyAsync(&nfinal, ptr<uint32_t>(scan) + m, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kGcCount, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (hc[kGcDuplicate]) return fail(c, BELLA_ERR_BAD_ARG, "graph: two overlap records for one read pair (an edge's source and target must be unique)");
+    ENSURE(c, fin, sizeof(bella_graph_edge) * (size_t)nfinal);
+    if (m) {
+        k_graph_compact<<<nblk(m), 256, 0, c->stream>>>(ptr<bella_graph_edge>(edges), ptr<uint8_t>(keep), ptr<uint32_t>(scan), m, ptr<bella_graph_edge>(fin));
+        KCHK(c);
+    }
+    k_graph_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint64_t>(foff));
+    KCHK(c);
+    HIPCHK(c, hipEventRecord(e3, c->stream));
+    c->g_off.assign((size_t)nv + 1, 0);
+    c->g_edges.assign(nfinal, bella_graph_edge{});
+    std::vector<uint32_t> cont32(nr);
+    HIPCHK(c, hipMemcpyAsync(c->g_off.data(), foff.p, 8 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
+    if (nfinal) HIPCHK(c, c->stager.d2h(c->g_edges.data(), fin.p, sizeof(bella_graph_edge) * (size_t)nfinal, c->stream));
+    if (nr) HIPCHK(c, hipMemcpyAsync(cont32.data(), cont.p, 4 * (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->g_cont.resize(nr);
+    for (uint32_t r = 0; r < nr; ++r) c->g_cont[r] = cont32[r] ? 1 : 0;
+    st.n_short = hc[kGcShort]; st.n_internal = hc[kGcInternal]; st.contained_reads = hc[kGcContained];
+    st.edges_all = hc[kGcEdgesAll]; st.edges_kept = m; st.edges_reduced = hc[kGcReduced]; st.edges_final = nfinal;
+    st.max_degree = hc[kGcMaxDegree]; st.overcap_vertices = hc[kGcOvercap];
+    st.classify_ms = ev_ms(e0, e1); st.sort_ms = ev_ms(e1, e2); st.reduce_ms = ev_ms(e2, e3);
+    st.host_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    c->g_stats = st;
+    c->have_graph = true;
+    return 0;
+}
+
+int bella_hip_graph_get(bella_ctx* c, uint32_t* nvertices, uint64_t* nedges, uint64_t* offsets, bella_graph_edge* edges, uint8_t* contained) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    if (nvertices) *nvertices = (uint32_t)(c->g_off.size() - 1);
+    if (nedges) *nedges = c->g_edges.size();
+    if (offsets) std::memcpy(offsets, c->g_off.data(), 8 * c->g_off.size());
+    if (edges && !c->g_edges.empty()) std::memcpy(edges, c->g_edges.data(), sizeof(bella_graph_edge) * c->g_edges.size());
+    if (contained && !c->g_cont.empty()) std::memcpy(contained, c->g_cont.data(), c->g_cont.size());
+    return 0;
+}
+
+int bella_hip_graph_get_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    std::memcpy(out, &c->g_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_graph_stats)));
+    return 0;
+}
+
+int bella_hip_get_read_bases(bella_ctx* c, uint64_t* offsets, uint8_t* bases) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (offsets) {
+        offsets[0] = 0;
+        for (uint32_t r = 0; r < c->nreads; ++r) offsets[r + 1] = offsets[r] + c->host_lens[r];
+    }
+    if (bases && c->total_bases) {
+        const size_t nw = (size_t)((c->total_bases + 15) / 16);
+        std::vector<uint32_t> w(nw);
+        HIPCHK(c, c->stager.d2h(w.data(), c->packed.p, 4 * nw, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (uint64_t g = 0; g < c->total_bases; ++g) bases[g] = (uint8_t)"ACGT"[(w[(size_t)(g >> 4)] >> ((uint32_t)(g & 15) * 2)) & 3u];
+    }
+    return 0;
+}
+
+int bella_hip_write_gfa(const char* path, uint32_t nreads, const char* const* names, const uint32_t* lens, const uint64_t* base_offsets, const uint8_t* bases,
+                        const uint64_t* offsets, const bella_graph_edge* edges, const uint8_t* contained) {
+    if (!path || !offsets || (nreads && (!names || !lens || !contained)) || (bases && !base_offsets) || (offsets[2 * (size_t)nreads] && !edges)) {
+        fprintf(stderr, "bella_hip_write_gfa: null argument\n");
+        return BELLA_ERR_BAD_ARG;
+    }
+    const uint64_t ne = offsets[2 * (size_t)nreads];
+    for (uint64_t i = 0; i < ne; ++i)
+        if (edges[i].src >= 2 * (uint64_t)nreads || edges[i].dst >= 2 * (uint64_t)nreads) { fprintf(stderr, "bella_hip_write_gfa: edge %llu: vertex out of range\n", (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
+    FILE* f = std::fopen(path, "wb");
+    if (!f) { fprintf(stderr, "bella_hip_write_gfa: cannot open %s\n", path); return BELLA_ERR_BAD_ARG; }
+    std::vector<char> buf((size_t)4 << 20);
+    std::setvbuf(f, buf.data(), _IOFBF, buf.size());
+    bool ok = std::fputs("H\tVN:Z:1.0\n", f) != EOF;
+    for (uint32_t r = 0; r < nreads && ok; ++r) {
+        if (contained[r]) continue;
+        if (!names[r]) { ok = false; break; }
+        ok = std::fprintf(f, "S\t%s\t", names[r]) > 0;
+        if (ok && bases) { const size_t nb = (size_t)(base_offsets[r + 1] - base_offsets[r]); ok = nb == 0 || std::fwrite(bases + base_offsets[r], 1, nb, f) == nb; }
+        else if (ok) ok = std::fputc('*', f) != EOF;
+        ok = ok && std::fprintf(f, "\tLN:i:%u\n", lens[r]) > 0;
+    }
+    for (uint64_t i = 0; i < ne && ok; ++i) {
+        const bella_graph_edge& e = edges[i];
+        ok = std::fprintf(f, "L\t%s\t%c\t%s\t%c\t%uM\tel:i:%u\trc:i:%u\n", names[e.src >> 1], (e.src & 1) ? '-' : '+', names[e.dst >> 1], (e.dst & 1) ? '-' : '+', e.ovl, e.len, e.rec) > 0;
+    }
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) { fprintf(stderr, "bella_hip_write_gfa: writing %s failed\n", path); return BELLA_ERR_BAD_ARG; }
     return 0;
 }
 

@@ -110,7 +110,60 @@ struct StageOpts {
     const char* correct = nullptr;   // read correction: every stage piles its traced pairs up on the device, the consensus
                                      // of every read is written to this FASTA file after the last stage (needs alignment)
     uint32_t min_depth = 3;          // ... positions with fewer votes keep the read's own base
+    const char* gfa = nullptr;       // string graph: every stage adds its traced passed pairs as overlap records, the graph is
+                                     // built on the device after the last stage and written to this GFA 1 file (needs alignment)
+    uint32_t gfa_min_overlap = 1000, gfa_max_overhang = 1000, gfa_fuzz = 1000;
+    int gfa_no_seq = 0;              // S lines carry '*' instead of the reads' bases
 };
+
+// The string graph after the last stage: the records of the contexts 1 .. N-1 (each added its own columns' pairs) are gathered into
+// context 0 in the single-context order -- column ascending; a column's pairs all come from one context, in its order -- then the build
+// on the device and the GFA file.
+inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* const* names, const uint32_t* lens) {
+    bella_ctx* const c0 = W[0].ctx;
+    if (o.N > 1) {
+        std::vector<bella_overlap> all;
+        for (int g = 0; g < o.N; ++g) {
+            bella_ctx* const cg = W[(size_t)g].ctx;
+            uint64_t n = 0;
+            check(cg, bella_hip_graph_get_overlaps(cg, nullptr, &n), "bella_hip_graph_get_overlaps");
+            const size_t at = all.size();
+            all.resize(at + (size_t)n);
+            if (n) check(cg, bella_hip_graph_get_overlaps(cg, all.data() + at, &n), "bella_hip_graph_get_overlaps");
+        }
+        std::stable_sort(all.begin(), all.end(), [](const bella_overlap& a, const bella_overlap& b) { return a.cid < b.cid; });
+        check(c0, bella_hip_graph_reset(c0), "bella_hip_graph_reset");
+        check(c0, bella_hip_graph_add_overlaps(c0, all.data(), all.size()), "bella_hip_graph_add_overlaps");
+    }
+    bella_graph_params gp;
+    gp.struct_size = (uint32_t)sizeof(gp);
+    gp.min_overlap = o.gfa_min_overlap; gp.max_overhang = o.gfa_max_overhang; gp.overhang_permille = 800; gp.fuzz = o.gfa_fuzz;
+    check(c0, bella_hip_graph_build(c0, &gp), "bella_hip_graph_build");
+    uint32_t nv = 0;
+    uint64_t ne = 0;
+    check(c0, bella_hip_graph_get(c0, &nv, &ne, nullptr, nullptr, nullptr), "bella_hip_graph_get");
+    std::vector<uint64_t> offs((size_t)nv + 1, 0);
+    std::vector<bella_graph_edge> edges((size_t)ne);
+    std::vector<uint8_t> contained(o.nreads, 0);
+    check(c0, bella_hip_graph_get(c0, nullptr, nullptr, offs.data(), edges.data(), contained.data()), "bella_hip_graph_get");
+    std::vector<uint64_t> boffs;
+    RawBuf<uint8_t> bases;
+    if (!o.gfa_no_seq) {
+        boffs.assign((size_t)o.nreads + 1, 0);
+        check(c0, bella_hip_get_read_bases(c0, boffs.data(), nullptr), "bella_hip_get_read_bases");
+        bases.resize((size_t)boffs[o.nreads] + 1);
+        check(c0, bella_hip_get_read_bases(c0, nullptr, bases.data()), "bella_hip_get_read_bases");
+    }
+    const int wrc = bella_hip_write_gfa(o.gfa, o.nreads, names, lens, o.gfa_no_seq ? nullptr : boffs.data(), o.gfa_no_seq ? nullptr : bases.data(), offs.data(), edges.data(),
+                                        contained.data());
+    if (wrc) check(nullptr, wrc, "bella_hip_write_gfa");
+    bella_graph_stats st;
+    check(c0, bella_hip_graph_get_stats(c0, &st, sizeof(st)), "bella_hip_graph_get_stats");
+    const std::string StringGraph = std::to_string(st.records) + " records (" + std::to_string(st.n_short) + " short, " + std::to_string(st.n_internal) + " internal), " +
+                                    std::to_string(st.contained_reads) + " contained reads, " + std::to_string(st.edges_kept) + " edges, " + std::to_string(st.edges_reduced) +
+                                    " reduced, " + std::to_string(st.edges_final) + " final";
+    BELLA_HIP_LOGT(o.tag, StringGraph);
+}
 
 // Read correction after the last stage: the tables of the contexts 1 .. N-1 (each piled up its own columns) are added into context 0 in
 // chunks of whole reads of at most ~4 M bases (144 MB on the host, whatever the read set), then the consensus and the FASTA file.
@@ -188,6 +241,9 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
                 // (--correct: the stage's runs vote on the device; they come to the host only when the true PAF wants them too)
                 if (o.correct) check(w.ctx, bella_hip_trace_pairs_pileup(w.ctx, &p, o.trace_band, o.cigar ? 1 : 0, &ntr, &nops), "bella_hip_trace_pairs_pileup");
                 else if (o.cigar) check(w.ctx, bella_hip_trace_pairs(w.ctx, &p, o.trace_band, 1, &ntr, &nops), "bella_hip_trace_pairs");
+                // (--gfa alone: the records are all the graph reads; no run is written or staged)
+                else if (o.gfa) check(w.ctx, bella_hip_trace_pairs_flags(w.ctx, &p, o.trace_band, BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS, &ntr, &nops), "bella_hip_trace_pairs_flags");
+                if (o.gfa) check(w.ctx, bella_hip_graph_add_traced(w.ctx, nullptr), "bella_hip_graph_add_traced");
                 if (o.cigar) {
                     w.traces.resize(w.nnzc);
                     w.ops.resize(nops);                                       // (host memory: 4 bytes per run; -m stages bound it as they bound the records)
@@ -204,6 +260,7 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         }
     };
     if (o.correct) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_pileup_reset(W[(size_t)g].ctx), "bella_hip_pileup_reset"); });
+    if (o.gfa) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_graph_reset(W[(size_t)g].ctx), "bella_hip_graph_reset"); });
     CallStats& cs = last_call_stats();
     cs = CallStats();
     const double free_memory = o.total_memory_mb * 1024 * 1024;               // estimateMemory, overlap.hpp:365-404 (no LINUX/OSX define)
@@ -312,6 +369,7 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         BELLA_HIP_LOGT(tag, OutputtingTime);
     }
     if (o.correct) write_corrected(W, o, names, lens);
+    if (o.gfa) write_graph(W, o, names, lens);
     cs.nreads = nreads; cs.stages = stages; cs.contexts = N; cs.nnzc = nnzc;
     for (auto& w : W) {
         bella_timings tm;

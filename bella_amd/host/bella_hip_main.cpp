@@ -37,12 +37,14 @@
 namespace {
 
 struct Options {
-    std::string fastq_list, output, tuples, correct;
+    std::string fastq_list, output, tuples, correct, gfa;
     int kmer = 17, xdrop = 7, memory = 8000, bin_size = 500, gpus = 1, split_count = 1, window = 0, upper = 8, lower = 2;
     double error = 0.15, deviation = 0.1;
     bool estimate = false, skip_alignment = false, paf = false, hopc = false, syncmer = false, help = false, exact = false, cigar = false;
     int trace_band = 0, min_depth = 3;
     bool min_depth_given = false;
+    int gfa_fuzz = 1000, gfa_max_overhang = 1000, gfa_min_overlap = 1000;
+    bool gfa_no_seq = false, gfa_param_given = false;
 };
 
 const char* kHelp =
@@ -73,6 +75,11 @@ const char* kHelp =
     "      --trace-band arg       first band of the base-level alignments, in diagonals (default: 256; doubled where a path touches it)\n"
     "      --correct arg          corrected reads (FASTA): per-read pileup of the base-level alignments on the device, majority consensus\n"
     "      --min-depth arg        with --correct: votes a position needs before it is changed (default: 3)\n"
+    "      --gfa arg              string graph (GFA 1): overlap classes, contained reads dropped, transitive reduction, on the device\n"
+    "      --gfa-min-overlap arg  with --gfa: shortest overlap that counts (default: 1000)\n"
+    "      --gfa-max-overhang arg with --gfa: longest unaligned end of a dovetail or containment (default: 1000)\n"
+    "      --gfa-fuzz arg         with --gfa: slack of the transitive reduction, in bases (default: 1000)\n"
+    "      --gfa-no-seq           with --gfa: '*' instead of the reads' bases in the S lines\n"
     "  -h, --help                 Usage\n";
 
 [[noreturn]] void die(const std::string& msg) {
@@ -91,6 +98,8 @@ Options parse(int argc, char** argv) {
         {"split-count", 0, 1, &o.split_count}, {"hopc", 0, 0, &o.hopc}, {"window", 'w', 1, &o.window}, {"syncmer", 's', 0, &o.syncmer},
         {"upper-freq", 'u', 1, &o.upper}, {"lower-freq", 'l', 1, &o.lower}, {"tuples", 0, 3, &o.tuples}, {"exact-xdrop", 0, 0, &o.exact}, {"cigar", 0, 0, &o.cigar}, {"trace-band", 0, 1, &o.trace_band},
         {"correct", 0, 3, &o.correct}, {"min-depth", 0, 1, &o.min_depth},
+        {"gfa", 0, 3, &o.gfa}, {"gfa-fuzz", 0, 1, &o.gfa_fuzz}, {"gfa-max-overhang", 0, 1, &o.gfa_max_overhang}, {"gfa-min-overlap", 0, 1, &o.gfa_min_overlap},
+        {"gfa-no-seq", 0, 0, &o.gfa_no_seq},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
         char* end = nullptr;
@@ -117,6 +126,7 @@ Options parse(int argc, char** argv) {
         if (sp->kind == 0) {
             if (val) die("option " + a + " takes no value");
             *(bool*)sp->dst = true;
+            if (sp->dst == &o.gfa_no_seq) o.gfa_param_given = true;
             continue;
         }
         if (!val) {
@@ -125,6 +135,7 @@ Options parse(int argc, char** argv) {
         }
         assign(*sp, val, a);
         if (sp->dst == &o.min_depth) o.min_depth_given = true;
+        if (sp->dst == &o.gfa_fuzz || sp->dst == &o.gfa_max_overhang || sp->dst == &o.gfa_min_overlap) o.gfa_param_given = true;
     }
     return o;
 }
@@ -178,7 +189,10 @@ int main(int argc, char** argv) {
     if (o.cigar && !o.paf) die("--cigar needs --paf (the base-level alignment is written as PAF columns 10-11 and the cg:Z: tag)");
     if (o.cigar && o.skip_alignment) die("--cigar cannot be combined with --skip-alignment (there is no alignment to trace)");
     if (o.trace_band < 0 || o.trace_band > (1 << 18)) die("--trace-band must be in [0, 262144]");
-    if (o.trace_band && !o.cigar && o.correct.empty()) die("--trace-band needs --cigar or --correct");
+    if (o.trace_band && !o.cigar && o.correct.empty() && o.gfa.empty()) die("--trace-band needs --cigar, --correct or --gfa");
+    if (!o.gfa.empty() && o.skip_alignment) die("--gfa cannot be combined with --skip-alignment (the graph is made of base-level alignments)");
+    if (o.gfa_param_given && o.gfa.empty()) die("--gfa-fuzz, --gfa-max-overhang, --gfa-min-overlap and --gfa-no-seq need --gfa");
+    if (o.gfa_fuzz < 0 || o.gfa_max_overhang < 0 || o.gfa_min_overlap < 0) die("--gfa-fuzz, --gfa-max-overhang and --gfa-min-overlap must not be negative");
     if (!o.correct.empty() && o.skip_alignment) die("--correct cannot be combined with --skip-alignment (the pileup is made of base-level alignments)");
     if (o.min_depth_given && o.min_depth < 1) die("--min-depth must be at least 1");
     if (o.min_depth_given && o.correct.empty()) die("--min-depth needs --correct");
@@ -318,6 +332,11 @@ int main(int argc, char** argv) {
     so.trace_band = (uint32_t)o.trace_band;
     so.correct = o.correct.empty() ? nullptr : o.correct.c_str();
     so.min_depth = (uint32_t)o.min_depth;
+    so.gfa = o.gfa.empty() ? nullptr : o.gfa.c_str();
+    so.gfa_fuzz = (uint32_t)o.gfa_fuzz;
+    so.gfa_max_overhang = (uint32_t)o.gfa_max_overhang;
+    so.gfa_min_overlap = (uint32_t)o.gfa_min_overlap;
+    so.gfa_no_seq = o.gfa_no_seq ? 1 : 0;
     const double t_stages = now_s();
     run_stages(W, so, names.data(), lens.data());
     {

@@ -91,6 +91,12 @@ void HashSpGEMM(const CSC<uint32_t, unsigned short>& A, const CSC<uint32_t, unsi
         if (*e && !bpars.skipAlignment) o.correct = e;
         else if (*e) std::cerr << "bella_hip: BELLA_HIP_CORRECT is set but ignored: it needs an alignment (no --skip-alignment)" << std::endl;
     }
+    // BELLA_HIP_GFA=<path>: the string graph of the passed pairs as GFA 1; BELLA_HIP_GFA_NO_SEQ=1: '*' sequences
+    if (const char* e = std::getenv("BELLA_HIP_GFA")) {
+        if (*e && !bpars.skipAlignment) o.gfa = e;
+        else if (*e) std::cerr << "bella_hip: BELLA_HIP_GFA is set but ignored: it needs an alignment (no --skip-alignment)" << std::endl;
+    }
+    if (const char* e = std::getenv("BELLA_HIP_GFA_NO_SEQ")) o.gfa_no_seq = (*e && *e != '0') ? 1 : 0;
     if (const char* e = std::getenv("BELLA_HIP_MIN_DEPTH")) {
         const unsigned long v = std::strtoul(e, nullptr, 10);
         if (v < 1 || v > 0xFFFFFFFFul) std::cerr << "bella_hip: BELLA_HIP_MIN_DEPTH must be at least 1: ignored" << std::endl;

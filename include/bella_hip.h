@@ -408,6 +408,92 @@ int bella_hip_get_consensus(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases, b
 /* ">name\n" + one sequence line per read, in input order.  append == 0 truncates the file.  Plain host code, no context. */
 int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* names, const uint64_t* offsets, const uint8_t* bases, int append);
 
+/* ---- string graph: overlap classes, containment, transitive reduction, GFA (no counterpart in the reference) ----
+ * Vertices: two per read, 2 r + o, o = 0 the read as given, o = 1 its reverse complement; twin(v -> w) = (w ^ 1 -> v ^ 1).  An overlap
+ * record is a pair's end points on V = read cid and on H' = read rid oriented by the strand (the convention of bella_aln / bella_trace).
+ * Class of a record with b1, e1 on V (length l1) and b2, e2 on H' (length l2), tested in this order:
+ *   1. e1 - b1 < min_overlap or e2 - b2 < min_overlap: SHORT, dropped;
+ *   2. overhang = min(b1, b2) + min(l1 - e1, l2 - e2), maplen = max(e1 - b1, e2 - b2); overhang > max_overhang or
+ *      1000 overhang > overhang_permille maplen: INTERNAL, dropped;
+ *   3. b1 <= b2 and l1 - e1 <= l2 - e2: V CONTAINED;          4. b1 >= b2 and l1 - e1 >= l2 - e2: H CONTAINED;
+ *   5. b1 > b2: edge (V,0) -> (H,strand), len = b1 - b2, and its twin (H,strand^1) -> (V,1), len = (l2 - e2) - (l1 - e1);
+ *   6. else:    edge (H,strand) -> (V,0), len = b2 - b1, and its twin (V,1) -> (H,strand^1), len = (l1 - e1) - (l2 - e2).
+ * A read that any record puts in class 3 or 4 on its side is contained; every edge with a contained end is removed.  The out-edges of a
+ * vertex are ordered by (len, dst) ascending; two edges with the same (src, dst) -- two records of one read pair -- fail the build.
+ * Reduction (Myers 2005 as miniasm states it), for every vertex v with out-edges: (1) its out-neighbours are INPLAY, L = the largest len
+ * of v's list + fuzz; (2) for v -> w in list order, skipped unless w is INPLAY at that moment: for w -> x in list order, stopping at the
+ * first with len(v -> w) + len(w -> x) > L: an INPLAY x becomes ELIMINATED; (3) for every v -> w, whatever its mark, and w -> x at index
+ * j of w's list with j == 0 or len(w -> x) < fuzz: an INPLAY x becomes ELIMINATED; (4) the edges v -> x with x ELIMINATED are reduced.
+ * An edge leaves the graph when it OR ITS TWIN is reduced.  No tip clipping, bubble popping or unitig compaction. */
+typedef struct {
+    uint32_t cid, rid;            /* V, H                                                                       */
+    int32_t begV, endV;           /* on V                                                                       */
+    int32_t begH, endH;           /* on H' (H reverse-complemented when strand == 1)                             */
+    int32_t score;                /* carried, not read                                                          */
+    uint8_t strand;               /* 0 or 1                                                                     */
+    uint8_t pad[3];
+} bella_overlap;
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_graph_params) of the caller's header (the struct may grow)     */
+    uint32_t min_overlap;         /* documented default 1000                                                    */
+    uint32_t max_overhang;        /* 1000                                                                       */
+    uint32_t overhang_permille;   /* 800                                                                        */
+    uint32_t fuzz;                /* 1000                                                                       */
+} bella_graph_params;
+#define BELLA_GRAPH_EDGE_TWIN 1u  /* bella_graph_edge::flags bit0: the edge is the second ("its twin") of its record's class 5 / 6 line */
+typedef struct {
+    uint32_t src, dst;            /* vertices                                                                   */
+    uint32_t len;                 /* bases of src's read before dst's read begins                               */
+    uint32_t ovl;                 /* length of src's read - len                                                 */
+    uint32_t rec;                 /* index of the edge's record among the accumulated records                   */
+    uint32_t flags;
+} bella_graph_edge;
+/* What the last bella_hip_graph_build did.  A sized struct: bella_hip_graph_get_stats writes at most struct_size bytes. */
+typedef struct {
+    uint64_t records, n_short, n_internal;
+    uint64_t contained_reads;
+    uint64_t edges_all;           /* directed edges of classes 5 and 6 (two per record)                          */
+    uint64_t edges_kept;          /* ... without a contained end: what the reduction runs on                     */
+    uint64_t edges_reduced;       /* edges step (4) marked                                                      */
+    uint64_t edges_final;         /* edges_kept minus the edges that were reduced or whose twin was              */
+    uint32_t max_degree;          /* largest out-degree among the kept edges                                    */
+    uint32_t overcap_vertices;    /* vertices whose neighbour set did not fit the wavefront's LDS table (global-memory path) */
+    double classify_ms, sort_ms, reduce_ms;   /* device time: classes + flags; filter, degrees, scan, sorts, lists; reduction, twin pass, compaction */
+    double host_ms;               /* the whole call on the host clock                                           */
+} bella_graph_stats;
+/* Drops the accumulated records and the last graph.  Loading other reads does the same. */
+int bella_hip_graph_reset(bella_ctx* ctx);
+/* Appends explicit records.  BELLA_ERR_BAD_ARG (nothing is appended) when a record has cid == rid, an id >= nreads, beg >= end, beg < 0,
+ * end > the read's length or strand > 1.  Records accumulate over calls (stages, column ranges) until the next reset. */
+int bella_hip_graph_add_overlaps(bella_ctx* ctx, const bella_overlap* recs, uint64_t n);
+/* Appends one record per passed pair with a trace (nops > 0) of the context's last alignment + trace, in pair order, from the trace's end
+ * points (tbegV .. tendH), score = the X-drop's.  *added (nullable) = how many.  BELLA_ERR_STATE without traces. */
+int bella_hip_graph_add_traced(bella_ctx* ctx, uint64_t* added);
+/* The accumulated records: *n = their number; out (nullable) receives them.  How several contexts merge: one of them adds the others'. */
+int bella_hip_graph_get_overlaps(bella_ctx* ctx, bella_overlap* out, uint64_t* n);
+/* Classifies, builds the lists, reduces (all on the device).  params == NULL: the documented defaults.  An empty record set gives an empty graph. */
+int bella_hip_graph_build(bella_ctx* ctx, const bella_graph_params* params);
+/* *nvertices = 2 nreads, *nedges = final edges (size query: every other pointer NULL); offsets[2 nreads + 1] (CSR over the vertices),
+ * edges[nedges] in list order, contained[nreads] (0 / 1).  Any pointer may be NULL.  BELLA_ERR_STATE without a built graph. */
+int bella_hip_graph_get(bella_ctx* ctx, uint32_t* nvertices, uint64_t* nedges, uint64_t* offsets, bella_graph_edge* edges, uint8_t* contained);
+int bella_hip_graph_get_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+/* What bella_hip_trace_pairs does, steered by flags: bit0 = passed pairs only; bit1 = the runs are DROPPED: not staged on the host, and
+ * when nothing else reads them (no bit2) not written at all -- the records (end points, counts, nops, op_off as they would be) are all a
+ * caller such as bella_hip_graph_add_traced needs; bella_hip_get_traces then takes ops == NULL only; bit2 = the runs vote into the pileup
+ * table (needs bit0 and a table).  flags = 1 is bella_hip_trace_pairs(passed_only = 1), 5 / 7 are bella_hip_trace_pairs_pileup with
+ * keep_ops 1 / 0. */
+#define BELLA_TRACE_PASSED_ONLY 1u
+#define BELLA_TRACE_DROP_OPS 2u
+#define BELLA_TRACE_PILEUP 4u
+int bella_hip_trace_pairs_flags(bella_ctx* ctx, const bella_params* p, uint32_t band0, uint32_t flags, uint64_t* ntraced, uint64_t* nops);
+/* The loaded reads as upper-case ASCII: offsets[nreads + 1] into bases[total bases].  Either may be NULL. */
+int bella_hip_get_read_bases(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases);
+/* GFA 1: "H\tVN:Z:1.0"; one "S\tname\tsequence\tLN:i:len" per non-contained read in input order (sequence = base_offsets / bases, or "*"
+ * when bases == NULL); one "L\tsrc\t+/-\tdst\t+/-\t<ovl>M\tel:i:<len>\trc:i:<rec>" per edge in CSR order.  Truncates the file.  Plain host
+ * code, no context. */
+int bella_hip_write_gfa(const char* path, uint32_t nreads, const char* const* names, const uint32_t* lens, const uint64_t* base_offsets,
+                        const uint8_t* bases, const uint64_t* offsets, const bella_graph_edge* edges, const uint8_t* contained);
+
 /* ---- multi-GPU: one context per GPU, RCCL over xGMI ------------------------------------------------
  * The reference's multi-GPU path hands alignment batches to the devices inside one call (loganGPU/functions.cuh:441-443,
  * 498-637; include/align.hpp:226-229) and has no collective.  Here reads are 1D row-block partitioned: context r assembles the
@@ -472,7 +558,8 @@ int bella_hip_get_memory_sized(bella_ctx* ctx, void* m, uint64_t struct_size);
  * cache: an entry whose k-mer has exactly one later read carries that read instead of an index into A'; the plain form is also that of
  * inputs with 2^30 reads or 2^31 nonzeros and more); bit16 (same moment) = tests: that inline form on inputs of any size;
  * bit18 = tests: inside bella_hip_allgather_panels this rank fails after the ranks agreed on the shared formation of A' and before its own
- * share begins (every rank must leave the call with an error, none may wait) */
+ * share begins (every rank must leave the call with an error, none may wait); bit19 = tests: bella_hip_graph_build reduces every vertex
+ * on the global-memory path of the vertices whose neighbours do not fit the LDS table */
 int bella_hip_set_debug(bella_ctx* ctx, uint32_t flags);
 /* Reserve device memory up front: ONE slab of `bytes` taken from the driver (and touched) now, from which the stages' buffers are cut
  * afterwards.  The reference has no counterpart (its vectors grow on the host); here the first hipMalloc of a multi-GB buffer costs

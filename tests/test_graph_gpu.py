@@ -1,0 +1,300 @@
+"""GPU tests of the string graph: overlap classes, containment, lists and the transitive reduction on the device,
+EQUAL to the numpy mirror (bella_testkit/graph_mirror.py) -- CSR, edges, contained flags and every count -- on the traced alignments of
+all golden sets, on exact overlaps of reads on a line, on a vertex with more neighbours than the LDS table holds, and on 2,000 synthetic
+reads; bella-hip --gfa end to end."""
+import gzip
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from bella_amd import BellaPars, Engine, _lib, api
+from bella_testkit import graph_mirror as G
+from bella_testkit import synth
+from conftest import GOLD, ROOT, load_golden
+
+pytestmark = pytest.mark.gpu
+
+LOOSE = dict(min_overlap=0, fuzz=10)          # the toy reads are short: the defaults call most of their overlaps SHORT
+FORCE_GLOBAL = 1 << 19                        # bella_hip_set_debug: every vertex on the over-cap path
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = Engine(0)
+    yield e
+    e.close()
+
+
+def _aligned(eng, g):
+    eng.set_reads(g.rs)
+    eng.assemble_tuples(g.k, g.nkmers, g.tk, g.tr, g.tp)
+    pars = BellaPars(kmerSize=g.k, errorRate=g.err)
+    eng.overlap(pars)
+    pairs, _, _ = eng.get_pairs()
+    eng.align_pairs(pars)
+    return pars, pairs, eng.get_alignments()
+
+
+def _records(pairs, alns, tr):
+    m = (alns["passed"] == 1) & (tr["nops"] > 0)
+    recs = np.zeros(int(m.sum()), G.OVL_DT)
+    recs["cid"], recs["rid"] = pairs["cid"][m], pairs["rid"][m]
+    for f, t in (("begV", "tbegV"), ("endV", "tendV"), ("begH", "tbegH"), ("endH", "tendH")):
+        recs[f] = tr[t][m]
+    recs["score"], recs["strand"] = alns["score"][m], alns["strand"][m]
+    return recs
+
+
+def _invariants(off, e, cont, lens):
+    off = off.astype(np.int64)
+    assert off[0] == 0 and off[-1] == len(e) and len(off) == 2 * len(lens) + 1 and np.all(np.diff(off) >= 0)
+    src, dst = e["src"].astype(np.int64), e["dst"].astype(np.int64)
+    assert np.array_equal(src, np.repeat(np.arange(2 * len(lens)), np.diff(off)))
+    assert not cont[src >> 1].any() and not cont[dst >> 1].any()                          # no contained end
+    assert np.array_equal(e["ovl"].astype(np.int64) + e["len"], np.asarray(lens, np.int64)[src >> 1])
+    have = set(zip(src.tolist(), dst.tolist()))
+    assert len(have) == len(e) and all((d ^ 1, s ^ 1) in have for s, d in have)         # every edge has its twin
+    key = src << 48 | e["len"].astype(np.int64) << 31 | dst
+    assert np.all(np.diff(key) > 0)                                                       # lists ordered by (len, dst)
+
+
+def _same(eng, recs, lens, **params):
+    """device == mirror, on the LDS path and with every vertex on the global-memory path"""
+    m = G.build(recs, lens, **params)
+    out = None
+    for dbg in (0, FORCE_GLOBAL):
+        eng.set_debug(dbg)
+        try:
+            eng.graph_build(**params)
+        finally:
+            eng.set_debug(0)
+        off, e, cont = eng.graph()
+        st = eng.graph_stats()
+        assert np.array_equal(off, m["offsets"]) and e.tobytes() == m["edges"].tobytes() and np.array_equal(cont, m["contained"])
+        assert {k: st[k] for k in m["stats"]} == m["stats"]
+        _invariants(off, e, cont, lens)
+        out = out or st
+    return m, out
+
+
+def test_golden_sets_equal_the_mirror(eng, golden):
+    """align -> trace (runs dropped) -> graph_add_traced -> graph_build with the defaults and with min_overlap 0, fuzz 10.  The records
+    are those rebuilt in numpy from get_pairs / get_alignments / the traces; graph, flags and counts are the mirror's.  With the loose
+    setting edges are left on the sets named in HAS_EDGES (the mirror says so)."""
+    g = golden
+    pars, pairs, alns = _aligned(eng, g)
+    tr = eng.trace_pairs_records(pars)
+    st = eng.trace_stats()
+    assert st.ops_host_bytes == 0 and st.ops > 0
+    tr_full, _ = eng.trace_pairs(pars)                                # the records are bella_hip_trace_pairs' own
+    assert tr.tobytes() == tr_full.tobytes()
+    eng.graph_reset()
+    n = eng.graph_add_traced()
+    want = _records(pairs, alns, tr)
+    got = eng.graph_overlaps()
+    assert n == len(want) and got.tobytes() == want.tobytes()
+    lens = g.rs.lengths
+    for params in ({}, LOOSE):
+        m, s = _same(eng, want, lens, **params)
+        print("GRAPH %s %s: %s; classify %.3f sort %.3f reduce %.3f ms" % (g.name, params or "defaults", m["stats"], s["classify_ms"], s["sort_ms"], s["reduce_ms"]))
+        if params and g.name in HAS_EDGES:
+            assert m["stats"]["edges_final"] > 0
+
+
+HAS_EDGES = ("toy120", "toylen80", "toyhifi50", "toyrep90", "toysync60", "toymin70", "toyjunk220")      # every set but sanity3 (3 records, 2 of them containments)
+
+
+def test_truth_chain_on_the_device(eng):
+    starts, lens, strands, recs = G.truth_chain()
+    rs = synth.ReadSet.from_strings([b"A" * int(n) for n in lens])
+    eng.set_reads(rs)
+    eng.graph_add_overlaps(recs)
+    for fuzz in (0, 1000):
+        m, _ = _same(eng, recs, lens, fuzz=fuzz)
+        off, e, cont = eng.graph()
+        assert np.diff(off.astype(np.int64)).max() <= 1
+        order = [r for r in np.argsort(starts).tolist() if not cont[r]]
+        got = G.walk(off, e, 2 * order[0] + int(strands[order[0]]))
+        assert [v >> 1 for v in got] == order and [v & 1 for v in got] == [int(strands[r]) for r in order]
+
+
+def _hub_and_band(nreads=3000, hub=700, band=8, L=20000):
+    out = []
+    for j in range(1, hub + 1):                                       # read 0's suffix on the prefix of the reads 1 .. hub
+        out.append((0, j, L // 2 + j, L, 0, L // 2 - j, 0, j & 1, (0, 0, 0)))
+    for i in range(1, nreads - band):
+        for d in range(1, band + 1):
+            out.append((i, i + d, 1000 * d, L, 0, L - 1000 * d, 0, (i + d) % 3 == 0, (0, 0, 0)))
+    out.append((nreads - 2, nreads - 1, 0, L, 0, L, 0, 0, (0, 0, 0)))  # a contained read
+    return np.array(out, G.OVL_DT), np.full(nreads, L, np.int64)
+
+
+def test_a_vertex_with_more_neighbours_than_the_lds_table(eng):
+    """3,000 dummy reads, explicit records: read 0 overlaps 700 reads (its vertex takes the global-memory path), every read the next
+    eight.  The result is the mirror's, and the same with every vertex forced onto that path"""
+    recs, lens = _hub_and_band()
+    eng.set_reads(synth.ReadSet.from_strings([b"C" * int(n) for n in lens]))
+    eng.graph_add_overlaps(recs)
+    for fuzz in (1000, 0):
+        m, st = _same(eng, recs, lens, fuzz=fuzz)
+        assert st["max_degree"] >= 700 and st["overcap_vertices"] >= 1 and 0 < st["edges_final"] < st["edges_kept"]
+        print("HUB fuzz %d: %s" % (fuzz, {k: st[k] for k in st}))
+
+
+def test_accumulation_round_trip_and_errors(eng):
+    g = load_golden("toy120")
+    pars, pairs, alns = _aligned(eng, g)
+    eng.graph_reset()
+    eng.trace_pairs_records(pars)
+    eng.graph_add_traced()
+    whole = eng.graph_overlaps()
+    eng.graph_build(**LOOSE)
+    off0, e0, c0 = eng.graph()
+    # stages: two column ranges, added one after the other
+    eng.graph_reset()
+    half = g.rs.nreads // 2
+    try:
+        for lo, n in ((0, half), (half, g.rs.nreads - half)):
+            eng.set_column_range(lo, n)
+            eng.overlap(pars)
+            eng.align_pairs(pars)
+            eng.trace_pairs_records(pars)
+            eng.graph_add_traced()
+    finally:
+        eng.set_column_range(0, 0xFFFFFFFF)
+    assert eng.graph_overlaps().tobytes() == whole.tobytes()
+    eng.graph_build(**LOOSE)
+    off1, e1, c1 = eng.graph()
+    assert np.array_equal(off0, off1) and e0.tobytes() == e1.tobytes() and np.array_equal(c0, c1)
+    # get -> reset -> add in two calls
+    eng.graph_reset()
+    assert len(eng.graph_overlaps()) == 0
+    with pytest.raises(api.BellaHipError) as ex:
+        eng.graph()
+    assert ex.value.code == -7
+    eng.graph_add_overlaps(whole[:len(whole) // 3])
+    eng.graph_add_overlaps(whole[len(whole) // 3:])
+    assert eng.graph_overlaps().tobytes() == whole.tobytes()
+    eng.graph_build(**LOOSE)
+    off2, e2, c2 = eng.graph()
+    assert np.array_equal(off0, off2) and e0.tobytes() == e2.tobytes() and np.array_equal(c0, c2)
+    # a duplicate pair fails the build, on both paths
+    eng.graph_add_overlaps(whole[G.classify(whole, g.rs.lengths, **LOOSE)[0] >= G.EDGE_V_FIRST][:1])
+    for dbg in (0, FORCE_GLOBAL):
+        eng.set_debug(dbg)
+        try:
+            with pytest.raises(api.BellaHipError) as ex:
+                eng.graph_build(**LOOSE)
+            assert ex.value.code == -3
+        finally:
+            eng.set_debug(0)
+    # bad records are refused and nothing is appended
+    eng.graph_reset()
+    L0, L1 = int(g.rs.lengths[0]), int(g.rs.lengths[1])
+    for bad in ((0, 0, 0, 10, 0, 10, 0, 0), (0, g.rs.nreads, 0, 10, 0, 10, 0, 0), (0, 1, 10, 10, 0, 10, 0, 0), (0, 1, 0, L0 + 1, 0, 10, 0, 0),
+                (0, 1, 0, 10, 0, L1 + 1, 0, 0), (0, 1, -1, 10, 0, 10, 0, 0), (0, 1, 0, 10, 0, 10, 0, 2)):
+        with pytest.raises(api.BellaHipError) as ex:
+            eng.graph_add_overlaps(np.array([bad + ((0, 0, 0),)], G.OVL_DT))
+        assert ex.value.code == -3
+    assert len(eng.graph_overlaps()) == 0
+    eng.graph_build()                                                 # no records: an empty graph
+    off, e, cont = eng.graph()
+    assert len(e) == 0 and not off.any() and not cont.any()
+    eng.set_reads(g.rs)                                               # other reads drop records and graph
+    with pytest.raises(api.BellaHipError) as ex:
+        eng.graph()
+    assert ex.value.code == -7
+
+
+def _figures(nreads, off, e, cont, truly):
+    deg = np.diff(off.astype(np.int64))
+    live = np.repeat(~cont.astype(bool), 2)
+    ok = sum(1 for s, d in zip((e["src"] >> 1).tolist(), (e["dst"] >> 1).tolist()) if truly(s, d))
+    return (ok / max(len(e), 1), float((deg[live] <= 1).mean()) if live.any() else 1.0, G.components(nreads, e, cont))
+
+
+def test_synthetic_10kb_reads(eng):
+    """2,000 synthetic reads of 10 kb at 15 % error, 30x (the set of the trace and correction tests): device == mirror, and the reduction
+    removes edges.  Printed, not asserted (recorded in DESIGN.md section 11): the share of final edges whose reads truly overlap, the
+    share of vertices of non-contained reads with out-degree <= 1, the weakly connected components among non-contained reads -- and the
+    same for the graph of the reads' true intervals."""
+    nreads, read_len, seed = 2000, 10000, 21
+    rs = synth.make_reads(nreads, read_len=read_len, err=0.15, seed=seed)
+    eng.set_reads(rs)
+    eng.count_kmers(17, 2, 8)
+    eng.assemble_counted()
+    pars = BellaPars()
+    eng.overlap(pars)
+    pairs, _, _ = eng.get_pairs(ext=False)
+    eng.align_pairs(pars)
+    alns = eng.get_alignments()
+    tr = eng.trace_pairs_records(pars)
+    ts = eng.trace_stats()
+    eng.graph_reset()
+    eng.graph_add_traced()
+    recs = eng.graph_overlaps()
+    assert recs.tobytes() == _records(pairs, alns, tr).tobytes()
+    m, st = _same(eng, recs, rs.lengths)
+    assert st["edges_final"] < st["edges_kept"]
+    meta = np.array([[int(x) for x in n.split("_")[1:]] for n in rs.names], np.int64)      # (start, length, strand)
+    a, b = meta[:, 0], meta[:, 0] + meta[:, 1]
+    truly = lambda s, d: min(b[s], b[d]) > max(a[s], a[d])
+    off, e, cont = eng.graph()
+    fig = _figures(nreads, off, e, cont, truly)
+    t = G.build(G.truth_records(meta[:, 0], meta[:, 1], meta[:, 2]), meta[:, 1])
+    tfig = _figures(nreads, t["offsets"], t["edges"], t["contained"], truly)
+    print("SYNTH 2000 x 10 kb: %s; classify %.3f sort %.3f reduce %.3f ms (trace dp %.1f walk %.1f ms)" % (m["stats"], st["classify_ms"], st["sort_ms"], st["reduce_ms"], ts.dp_ms, ts.walk_ms))
+    print("SYNTH device graph: true-overlap share of final edges %.4f, vertices with out-degree <= 1 %.4f, components %d" % fig)
+    print("SYNTH truth graph %s: true-overlap share %.4f, vertices with out-degree <= 1 %.4f, components %d" % ((t["stats"],) + tfig))
+
+
+# ---- command line ----------------------------------------------------------------------------------------------------------------
+def _run(fastqs, flags, cwd, env_extra=None):
+    exe = os.path.join(ROOT, "bella_amd", "bin", "bella-hip")
+    os.makedirs(cwd, exist_ok=True)
+    with open(os.path.join(cwd, "in.txt"), "w") as f:
+        f.write("".join(p + "\n" for p in fastqs))
+    env = dict(os.environ)
+    env.update(env_extra or {})
+    p = subprocess.run([exe, "-f", "in.txt", "-o", "out"] + list(flags), cwd=cwd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
+    rd = lambda n: open(os.path.join(cwd, n), "rb").read() if os.path.exists(os.path.join(cwd, n)) else None
+    return rd("out.out"), rd("g.gfa"), rd("c.fasta")
+
+
+def test_cli_gfa_end_to_end(eng, tmp_path):
+    """bella-hip --gfa on a golden set: the file is the mirror's GFA text of the Python path's records; the -o file is what it is without
+    --gfa; -m 1 (stages) and -g 2 (two contexts on the one GPU) give the same GFA; --gfa-no-seq; with --paf --cigar --correct those files
+    are what they are without --gfa"""
+    g = load_golden("toy120")
+    pars, pairs, alns = _aligned(eng, g)
+    recs = _records(pairs, alns, eng.trace_pairs_records(pars))
+    m = G.build(recs, g.rs.lengths, **LOOSE)
+    want = G.gfa_text(g.names, g.rs.lengths, g.seqs, m["offsets"], m["edges"], m["contained"])
+    want_noseq = G.gfa_text(g.names, g.rs.lengths, None, m["offsets"], m["edges"], m["contained"])
+    assert m["stats"]["edges_final"] > 0 and want.count(b"\nL\t") == m["stats"]["edges_final"]
+    fq = str(tmp_path / "reads.fastq")
+    with gzip.open(os.path.join(GOLD, g.name, "reads.fastq.gz"), "rb") as src, open(fq, "wb") as dst:
+        dst.write(src.read())
+    mtx = str(tmp_path / "readbykmers.mtx")
+    with open(mtx, "w") as f:
+        f.write("%d\t%d\t%d\n" % (g.rs.nreads, g.nkmers, len(g.tk)))
+        f.write("".join("%d\t%d\t%d\n" % (r + 1, k + 1, q) for k, r, q in zip(g.tk.tolist(), g.tr.tolist(), g.tp.tolist())))
+    base = g.meta["flags"] + ["--tuples", mtx]
+    gfa = ["--gfa", "g.gfa", "--gfa-min-overlap", "0", "--gfa-fuzz", "10"]
+    over = {"BELLA_HIP_OVERSUBSCRIBE": "1"}
+    out0, none, _ = _run([fq], base, str(tmp_path / "plain"))
+    assert none is None and out0 == g.out["align"]
+    assert _run([fq], base + gfa, str(tmp_path / "gfa"))[:2] == (out0, want)
+    assert _run([fq], base + gfa + ["--gfa-no-seq"], str(tmp_path / "noseq"))[:2] == (out0, want_noseq)
+    assert _run([fq], base + gfa + ["-m", "1"], str(tmp_path / "m1"))[:2] == (out0, want)
+    assert _run([fq], base + gfa + ["-g", "2"], str(tmp_path / "g2"), over)[:2] == (out0, want)
+    assert _run([fq], base + gfa + ["-m", "1", "-g", "2"], str(tmp_path / "m1g2"), over)[:2] == (out0, want)
+    d = G.build(recs, g.rs.lengths)                                   # the defaults reach the build when no --gfa-* is given
+    assert _run([fq], base + ["--gfa", "g.gfa"], str(tmp_path / "dflt"))[1] == G.gfa_text(g.names, g.rs.lengths, g.seqs, d["offsets"], d["edges"], d["contained"])
+    full = ["--paf", "--cigar", "--correct", "c.fasta"]
+    cg, _, fa = _run([fq], base + full, str(tmp_path / "full"))
+    assert _run([fq], base + full + gfa, str(tmp_path / "fullgfa")) == (cg, want, fa)
+    assert _run([fq], base + full + gfa + ["-g", "2", "-m", "1"], str(tmp_path / "fullgfag2"), over) == (cg, want, fa)

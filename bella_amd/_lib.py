@@ -26,6 +26,9 @@ OVL_DT = np.dtype([("cid", "<u4"), ("rid", "<u4"), ("begV", "<i4"), ("endV", "<i
                    ("strand", "u1"), ("pad", "u1", (3,))])
 EDGE_DT = np.dtype([("src", "<u4"), ("dst", "<u4"), ("len", "<u4"), ("ovl", "<u4"), ("rec", "<u4"), ("flags", "<u4")])
 assert OVL_DT.itemsize == 32 and EDGE_DT.itemsize == 24
+LINK_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("ovl", "<u4"), ("rec", "<u4"), ("flags", "<u4"), ("edge", "<u4")])
+assert LINK_DT.itemsize == 24
+LINK_A_MINUS, LINK_B_MINUS, MAX_TIP_ROUNDS = 1, 2, 16
 TRACE_PASSED_ONLY, TRACE_DROP_OPS, TRACE_PILEUP = 1, 2, 4
 PILEUP_COUNTERS = 9      # per base: votes for A C G T, del, one inserted A C G T in the junction before the base
 assert PAIR_DT.itemsize == 16 and EXT_DT.itemsize == 8 and ALN_DT.itemsize == 32 and SEED_DT.itemsize == 12
@@ -82,6 +85,17 @@ class GraphStats(C.Structure):
                 ("edges_all", C.c_uint64), ("edges_kept", C.c_uint64), ("edges_reduced", C.c_uint64), ("edges_final", C.c_uint64),
                 ("max_degree", C.c_uint32), ("overcap_vertices", C.c_uint32), ("classify_ms", C.c_double), ("sort_ms", C.c_double),
                 ("reduce_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+class GraphCleanParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_tip_reads", C.c_uint32), ("tip_rounds", C.c_uint32)]
+
+
+class UnitigStats(C.Structure):
+    _fields_ = [("unitigs", C.c_uint64), ("vertices", C.c_uint64), ("links", C.c_uint64), ("total_bases", C.c_uint64), ("circular", C.c_uint64),
+                ("largest", C.c_uint64), ("n50", C.c_uint64), ("reads_removed", C.c_uint64), ("edges_removed", C.c_uint64), ("rounds", C.c_uint32),
+                ("rank_rounds", C.c_uint32), ("tips_per_round", C.c_uint32 * MAX_TIP_ROUNDS), ("reads_per_round", C.c_uint32 * MAX_TIP_ROUNDS),
+                ("cycle_vertices", C.c_uint64), ("gather_bytes", C.c_uint64), ("clean_ms", C.c_double), ("rank_ms", C.c_double), ("gather_ms", C.c_double)]
 
 
 # every symbol include/bella_hip.h declares: (name, restype, argtypes)
@@ -163,6 +177,13 @@ SIGNATURES = [
     ("bella_hip_trace_pairs_flags", C.c_int, [vp, C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("bella_hip_get_read_bases", C.c_int, [vp, vp, vp]),
     ("bella_hip_write_gfa", C.c_int, [C.c_char_p, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+    ("bella_hip_graph_clean", C.c_int, [vp, C.POINTER(GraphCleanParams)]),
+    ("bella_hip_graph_get_removed", C.c_int, [vp, vp]),
+    ("bella_hip_graph_unitigs", C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("bella_hip_graph_get_unitigs", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    ("bella_hip_graph_get_unitig_bases", C.c_int, [vp, vp, vp]),
+    ("bella_hip_graph_get_unitig_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_write_unitig_gfa", C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
     ("bella_hip_get_timings", C.c_int, [vp, C.POINTER(Timings)]),
     ("bella_hip_get_memory", C.c_int, [vp, C.POINTER(Memory)]),
     ("bella_hip_get_memory_sized", C.c_int, [vp, vp, C.c_uint64]),

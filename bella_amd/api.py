@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, OVL_DT, PAIR_DT, GraphParams, GraphStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
+from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, GraphCleanParams, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
 class BellaHipError(RuntimeError):
@@ -431,6 +431,52 @@ class Engine:
         self._chk(self.lib.bella_hip_graph_get_stats(self.h, C.byref(st), C.sizeof(st)))
         return {k: getattr(st, k) for k, _ in st._fields_}
 
+    # ---- unitigs: tip clipping, compaction, sequences ----
+    CLEAN_DEFAULTS = dict(max_tip_reads=4, tip_rounds=3)
+
+    def graph_clean(self, **params):
+        """clips tips off the current graph (on the device) and replaces it: graph() then returns the cleaned one.  max_tip_reads
+        (0 = off) and tip_rounds default to 4 and 3"""
+        p = dict(self.CLEAN_DEFAULTS)
+        for k, v in params.items():
+            if k not in p:
+                raise TypeError("unknown clean parameter %r" % k)
+            p[k] = int(v)
+        cp = GraphCleanParams(C.sizeof(GraphCleanParams), p["max_tip_reads"], p["tip_rounds"])
+        self._chk(self.lib.bella_hip_graph_clean(self.h, C.byref(cp)))
+
+    def graph_removed(self) -> np.ndarray:
+        """uint8[nreads]: the reads graph_clean took out since the last graph_build"""
+        out = np.zeros(self.nreads, np.uint8)
+        self._chk(self.lib.bella_hip_graph_get_removed(self.h, _p(out)))
+        return out
+
+    def graph_unitigs(self) -> dict:
+        """unitigs of the current graph (on the device): voff uint64[n + 1] into verts uint32 / pos uint64 / nbases uint32, len uint64[n],
+        circular uint8[n], links of LINK_DT"""
+        n, nv, nl, tb = (C.c_uint64(0) for _ in range(4))
+        self._chk(self.lib.bella_hip_graph_unitigs(self.h, C.byref(n), C.byref(nv), C.byref(nl), C.byref(tb)))
+        u = dict(voff=np.zeros(n.value + 1, np.uint64), verts=np.zeros(nv.value, np.uint32), pos=np.zeros(nv.value, np.uint64), nbases=np.zeros(nv.value, np.uint32),
+                 len=np.zeros(n.value, np.uint64), circular=np.zeros(n.value, np.uint8), links=np.zeros(nl.value, LINK_DT))
+        self._chk(self.lib.bella_hip_graph_get_unitigs(self.h, *(_p(u[k]) for k in ("voff", "verts", "pos", "nbases", "len", "circular", "links"))))
+        u["total_bases"] = tb.value
+        return u
+
+    def unitig_bases(self):
+        """(offsets uint64[nunitigs + 1], bases uint8 ASCII) of the last graph_unitigs"""
+        st = self.unitig_stats()
+        offs = np.zeros(st["unitigs"] + 1, np.uint64)
+        bases = np.zeros(st["total_bases"], np.uint8)
+        self._chk(self.lib.bella_hip_graph_get_unitig_bases(self.h, offs.ctypes.data, _p(bases)))
+        return offs, bases
+
+    def unitig_stats(self) -> dict:
+        st = UnitigStats()
+        self._chk(self.lib.bella_hip_graph_get_unitig_stats(self.h, C.byref(st), C.sizeof(st)))
+        out = {k: getattr(st, k) for k, _ in st._fields_}
+        out["tips_per_round"], out["reads_per_round"] = list(st.tips_per_round)[:st.rounds], list(st.reads_per_round)[:st.rounds]
+        return out
+
     def read_bases(self):
         """(offsets uint64[nreads + 1], bases uint8 ASCII) of the loaded reads"""
         offs = np.zeros(self.nreads + 1, np.uint64)
@@ -595,6 +641,32 @@ def write_gfa(filename: str, names, lengths, offsets, edges, contained, seqs=Non
                                  (bases.ctypes.data if len(bases) else boffs.ctypes.data) if bases is not None else None, offs.ctypes.data, _p(edges), _p(cont))
     if rc:
         raise BellaHipError(rc, "bella_hip_write_gfa failed")
+
+
+def unitig_names(circular) -> list:
+    return ["utg%06d%s" % (k + 1, "c" if c else "l") for k, c in enumerate(np.asarray(circular).tolist())]
+
+
+def write_unitig_gfa(filename: str, names, unitigs: dict, offsets=None, bases=None) -> None:
+    """bella_hip_write_unitig_gfa: GFA 1 of what Engine.graph_unitigs returned: S and a lines per unitig, L lines per link; with the
+    unitigs' bases (what Engine.unitig_bases returned) or '*'"""
+    lib = _lib.load()
+    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    u = unitigs
+    a = {k: np.ascontiguousarray(u[k], dt) for k, dt in (("voff", np.uint64), ("verts", np.uint32), ("pos", np.uint64), ("nbases", np.uint32), ("len", np.uint64),
+                                                         ("circular", np.uint8), ("links", LINK_DT))}
+    boffs = b = None
+    if bases is not None:
+        boffs, b = np.ascontiguousarray(offsets, np.uint64), np.ascontiguousarray(bases, np.uint8)
+        assert len(boffs) == len(a["len"]) + 1
+        if not len(b):
+            b = np.zeros(1, np.uint8)                                 # (no bases at all: still a pointer, NULL would mean '*')
+    rc = lib.bella_hip_write_unitig_gfa(os.fsencode(filename), len(enc), C.cast(arr, C.c_void_p), len(a["len"]), a["voff"].ctypes.data, _p(a["verts"]), _p(a["pos"]),
+                                        _p(a["nbases"]), _p(a["len"]), _p(a["circular"]), boffs.ctypes.data if boffs is not None else None,
+                                        b.ctypes.data if b is not None else None, len(a["links"]), _p(a["links"]))
+    if rc:
+        raise BellaHipError(rc, "bella_hip_write_unitig_gfa failed")
 
 
 def hash_spgemm(engine: Engine, pars: BellaPars, filename: str, stdout=sys.stdout, stages: int = 1):

@@ -29,6 +29,7 @@
 #include "pileup.hpp"
 #include "spgemm.hpp"
 #include "trace.hpp"
+#include "unitig.hpp"
 #include "util.hpp"
 #include "wide.hpp"
 #include "writer.hpp"
@@ -210,6 +211,14 @@ struct bella_ctx {
     std::vector<bella_graph_edge> g_edges;
     std::vector<uint8_t> g_cont;
     bella_graph_stats g_stats{};
+    // unitigs (unitig.hpp): what bella_hip_graph_clean removed from the graph above, and the last unitigs (on the host)
+    std::vector<uint8_t> g_removed;
+    bool have_unitigs = false;
+    std::vector<uint64_t> u_voff, u_pos, u_len, u_boff;
+    std::vector<uint32_t> u_verts, u_nb;
+    std::vector<uint8_t> u_circ, u_bases;
+    std::vector<bella_unitig_link> u_links;
+    bella_unitig_stats u_stats{};
     bella_timings tm{};
     hipEvent_t ev[12]{};
     uint32_t* pinned = nullptr;          // 128 host words the per-pass read backs land in
@@ -947,7 +956,7 @@ static int set_reads_impl(bella_ctx* c, const uint64_t* offsets, uint32_t nreads
     for (Buf* b : {&c->pile, &c->cons_out, &c->cons_offs, &c->cons_stats}) release(*b);      // (the pileup belongs to the reads it was sized for)
     c->have_pile = c->have_cons = false;
     c->g_recs.clear();                                                // (so do the overlap records and the graph)
-    c->have_graph = false;
+    c->have_graph = c->have_unitigs = false;
     return 0;
 }
 
@@ -4067,7 +4076,7 @@ struct KeepU32 {
 int bella_hip_graph_reset(bella_ctx* c) {
     if (!c) return BELLA_ERR_BAD_ARG;
     std::vector<bella_overlap>().swap(c->g_recs);
-    c->have_graph = false;
+    c->have_graph = c->have_unitigs = false;
     return 0;
 }
 
@@ -4085,7 +4094,7 @@ int bella_hip_graph_add_overlaps(bella_ctx* c, const bella_overlap* recs, uint64
                         r.endH, (long long)l2);
     }
     c->g_recs.insert(c->g_recs.end(), recs, recs + n);
-    c->have_graph = false;
+    c->have_graph = c->have_unitigs = false;
     return 0;
 }
 
@@ -4137,7 +4146,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
     HIPCHK(c, hipSetDevice(c->device));
     const auto t_begin = clk::now();
-    c->have_graph = false;
+    c->have_graph = c->have_unitigs = false;
     const uint32_t nr = c->nreads, nv = 2 * nr;
     const uint32_t n = (uint32_t)c->g_recs.size(), nc = 2 * n;
     if (nr >= (1u << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 reads");
@@ -4271,6 +4280,8 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     st.classify_ms = ev_ms(e0, e1); st.sort_ms = ev_ms(e1, e2); st.reduce_ms = ev_ms(e2, e3);
     st.host_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
     c->g_stats = st;
+    c->g_removed.assign(nr, 0);
+    c->u_stats = bella_unitig_stats{};
     c->have_graph = true;
     return 0;
 }
@@ -4290,6 +4301,375 @@ int bella_hip_graph_get_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     if (!c || !out) return BELLA_ERR_BAD_ARG;
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
     std::memcpy(out, &c->g_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_graph_stats)));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- unitigs (unitig.hpp) -----------------------------------------------------------------------------------------
+namespace {
+struct BufGuard {
+    std::vector<Buf*> v;
+    ~BufGuard() { for (Buf* b : v) release(*b); }
+};
+struct EventSet {
+    hipEvent_t a = nullptr, b = nullptr, d = nullptr, e = nullptr;
+    ~EventSet() { for (hipEvent_t x : {a, b, d, e}) if (x) (void)hipEventDestroy(x); }
+};
+
+// the context's current graph on the device: 32-bit offsets, the edges
+int graph_upload(bella_ctx* c, Buf& off, Buf& edges) {
+    const size_t nv1 = c->g_off.size(), m = c->g_edges.size();
+    std::vector<uint32_t> off32(nv1);
+    for (size_t i = 0; i < nv1; ++i) off32[i] = (uint32_t)c->g_off[i];
+    ENSURE(c, off, 4 * nv1);
+    ENSURE(c, edges, sizeof(bella_graph_edge) * m);
+    HIPCHK(c, c->stager.h2d(off.p, off32.data(), 4 * nv1, c->stream));
+    if (m) HIPCHK(c, c->stager.h2d(edges.p, c->g_edges.data(), sizeof(bella_graph_edge) * m, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                       // (off32 leaves scope)
+    return 0;
+}
+
+int scan_flags(bella_ctx* c, const uint8_t* in, uint32_t* out, size_t n) {
+    hipcub::TransformInputIterator<uint32_t, KeepU32, const uint8_t*> it(in, KeepU32());
+    size_t tb = 0;
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, out, (int)n, c->stream));
+    ENSURE(c, c->cubtmp, tb);
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, out, (int)n, c->stream));
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int bella_hip_graph_clean(bella_ctx* c, const bella_graph_clean_params* params) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    bella_graph_clean_params cp{(uint32_t)sizeof(bella_graph_clean_params), 4, 3};
+    if (params) {
+        if (params->struct_size < sizeof(bella_graph_clean_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_graph_clean_params: struct_size %u is too small", params->struct_size);
+        cp = *params;
+    }
+    if (cp.tip_rounds > BELLA_MAX_TIP_ROUNDS) return fail(c, BELLA_ERR_BAD_ARG, "tip_rounds %u: at most %d", cp.tip_rounds, BELLA_MAX_TIP_ROUNDS);
+    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->have_unitigs = false;
+    bella_unitig_stats st{};
+    const uint32_t nr = c->nreads, nv = 2 * nr;
+    uint32_t m = (uint32_t)c->g_edges.size();
+    if (!cp.max_tip_reads || !cp.tip_rounds) { c->u_stats = st; return 0; }
+    if (!m) { st.rounds = 1; c->u_stats = st; return 0; }             // (a round over no edges finds nothing)
+    Buf off, off2, E, E2, hit, rem, keep, scan, cnt;
+    BufGuard guard{{&off, &off2, &E, &E2, &hit, &rem, &keep, &scan, &cnt}};
+    int rc = graph_upload(c, off, E);
+    if (rc) return rc;
+    ENSURE(c, off2, 4 * ((size_t)nv + 1));
+    ENSURE(c, E2, sizeof(bella_graph_edge) * (size_t)m);
+    ENSURE(c, hit, nr); ENSURE(c, rem, nr);
+    ENSURE(c, keep, (size_t)m + 1);
+    ENSURE(c, scan, 4 * ((size_t)m + 1));
+    ENSURE(c, cnt, 4 * kUcCount);
+    HIPCHK(c, hipMemcpyAsync(rem.p, c->g_removed.data(), nr, hipMemcpyHostToDevice, c->stream));
+    EventSet ev;
+    HIPCHK(c, hipEventCreate(&ev.a)); HIPCHK(c, hipEventCreate(&ev.b));
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    const uint32_t m0 = m;
+    for (uint32_t round = 0; round < cp.tip_rounds; ++round) {
+        uint32_t hc[kUcCount] = {};
+        HIPCHK(c, hipMemsetAsync(hit.p, 0, nr, c->stream));
+        HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kUcCount, c->stream));
+        k_tip_walk<<<nblk(nv), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<bella_graph_edge>(E), nv, cp.max_tip_reads, ptr<uint8_t>(hit), ptr<uint32_t>(cnt));
+        KCHK(c);
+        k_tip_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(hit), nr, ptr<uint8_t>(rem), ptr<uint32_t>(cnt));
+        KCHK(c);
+        HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kUcCount, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.tips_per_round[round] = hc[kUcTips];
+        st.reads_per_round[round] = hc[kUcReads];
+        st.rounds = round + 1;
+        st.reads_removed += hc[kUcReads];
+        if (!hc[kUcReads]) break;
+        k_tip_filter<<<nblk((uint64_t)m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), m, ptr<uint8_t>(hit), ptr<uint8_t>(keep));
+        KCHK(c);
+        rc = scan_flags(c, ptr<uint8_t>(keep), ptr<uint32_t>(scan), (size_t)m + 1);
+        if (rc) return rc;
+        uint32_t nm = 0;
+        HIPCHK(c, hipMemcpyAsync(&nm, ptr<uint32_t>(scan) + m, 4, hipMemcpyDeviceToHost, c->stream));
+        k_graph_compact<<<nblk(m), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), ptr<uint8_t>(keep), ptr<uint32_t>(scan), m, ptr<bella_graph_edge>(E2));
+        KCHK(c);
+        k_utg_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint32_t>(off2));
+        KCHK(c);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::swap(E, E2);
+        std::swap(off, off2);
+        m = nm;
+    }
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    std::vector<uint32_t> off32((size_t)nv + 1);
+    std::vector<bella_graph_edge> edges(m);
+    std::vector<uint8_t> removed(nr);
+    HIPCHK(c, hipMemcpyAsync(off32.data(), off.p, 4 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
+    if (m) HIPCHK(c, c->stager.d2h(edges.data(), E.p, sizeof(bella_graph_edge) * (size_t)m, c->stream));
+    HIPCHK(c, hipMemcpyAsync(removed.data(), rem.p, nr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i <= nv; ++i) c->g_off[i] = off32[i];
+    c->g_edges.swap(edges);
+    c->g_removed.swap(removed);
+    st.edges_removed = m0 - m;
+    st.clean_ms = ev_ms(ev.a, ev.b);
+    c->u_stats = st;
+    return 0;
+}
+
+int bella_hip_graph_get_removed(bella_ctx* c, uint8_t* removed) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    if (removed && !c->g_removed.empty()) std::memcpy(removed, c->g_removed.data(), c->g_removed.size());
+    return 0;
+}
+
+int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertices, uint64_t* nlinks, uint64_t* total_bases) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->have_unitigs = false;
+    const uint32_t nr = c->nreads, nv = 2 * nr, m = (uint32_t)c->g_edges.size();
+    bella_unitig_stats& st = c->u_stats;                              // (the clean's figures stay)
+    st.unitigs = st.vertices = st.links = st.total_bases = st.circular = st.largest = st.n50 = st.cycle_vertices = st.gather_bytes = 0;
+    st.rank_rounds = 0;
+    st.rank_ms = st.gather_ms = 0;
+    std::vector<uint8_t> dead(nr);
+    uint32_t nlive = 0;
+    for (uint32_t r = 0; r < nr; ++r) { dead[r] = (c->g_cont[r] | c->g_removed[r]) ? 1 : 0; nlive += dead[r] ? 0u : 1u; }
+    c->u_voff.assign(1, 0); c->u_boff.assign(1, 0);
+    c->u_pos.clear(); c->u_len.clear(); c->u_verts.clear(); c->u_nb.clear(); c->u_circ.clear(); c->u_bases.clear(); c->u_links.clear();
+    uint32_t nutg = 0, nverts = 0, nlk = 0;
+    uint64_t total = 0;
+    if (nlive) {
+        Buf off, E, dd, succ, pred, outlen, inlen, ra, rb, ma, mb, cut, cmin2, tail_of, cnt_of, emit, nvert, uid, voff, cnt, verts, pos, nb, slot_utg, uvoff, ulen, uboff, ucirc,
+            gseg, lflag, lscan, links, out;
+        BufGuard guard{{&off, &E, &dd, &succ, &pred, &outlen, &inlen, &ra, &rb, &ma, &mb, &cut, &cmin2, &tail_of, &cnt_of, &emit, &nvert, &uid, &voff, &cnt, &verts, &pos,
+                        &nb, &slot_utg, &uvoff, &ulen, &uboff, &ucirc, &gseg, &lflag, &lscan, &links, &out}};
+        int rc = graph_upload(c, off, E);
+        if (rc) return rc;
+        ENSURE(c, dd, nr);
+        for (Buf* b : {&succ, &pred, &outlen, &inlen, &tail_of, &cnt_of}) ENSURE(c, *b, 4 * (size_t)nv);
+        for (Buf* b : {&emit, &nvert, &uid, &voff}) ENSURE(c, *b, 4 * ((size_t)nv + 1));
+        ENSURE(c, ra, sizeof(UtgRank) * (size_t)nv); ENSURE(c, rb, sizeof(UtgRank) * (size_t)nv);
+        ENSURE(c, cnt, 4 * kUcCount);
+        ENSURE(c, lflag, (size_t)m + 1);
+        ENSURE(c, lscan, 4 * ((size_t)m + 1));
+        HIPCHK(c, hipMemcpyAsync(dd.p, dead.data(), nr, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(pred.p, 0xFF, 4 * (size_t)nv, c->stream));
+        HIPCHK(c, hipMemsetAsync(inlen.p, 0, 4 * (size_t)nv, c->stream));
+        HIPCHK(c, hipMemsetAsync(tail_of.p, 0, 4 * (size_t)nv, c->stream));
+        HIPCHK(c, hipMemsetAsync(cnt_of.p, 0, 4 * (size_t)nv, c->stream));
+        HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kUcCount, c->stream));
+        EventSet ev;
+        HIPCHK(c, hipEventCreate(&ev.a)); HIPCHK(c, hipEventCreate(&ev.b)); HIPCHK(c, hipEventCreate(&ev.d)); HIPCHK(c, hipEventCreate(&ev.e));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        const uint32_t* const d_off = ptr<uint32_t>(off);
+        const bella_graph_edge* const d_E = ptr<bella_graph_edge>(E);
+        k_utg_succ<<<nblk(nv), 256, 0, c->stream>>>(d_off, d_E, nv, ptr<uint32_t>(succ), ptr<uint32_t>(pred), ptr<uint32_t>(outlen), ptr<uint32_t>(inlen));
+        KCHK(c);
+        uint32_t rounds = 1;
+        while ((1ull << rounds) < nv) ++rounds;
+        st.rank_rounds = rounds;
+        const uint8_t* d_cut = nullptr;
+        UtgRank* rank = nullptr;                                      // the ranking's result
+        auto do_rank = [&]() -> int {
+            UtgRank *a = ptr<UtgRank>(ra), *b = ptr<UtgRank>(rb);
+            k_utg_rank_init<<<nblk(nv), 256, 0, c->stream>>>(ptr<uint32_t>(pred), ptr<uint32_t>(inlen), d_cut, nv, a);
+            KCHK(c);
+            for (uint32_t i = 0; i < rounds; ++i) {
+                k_utg_rank_jump<<<nblk(nv), 256, 0, c->stream>>>(a, b, nv);
+                KCHK(c);
+                std::swap(a, b);
+            }
+            rank = a;
+            return 0;
+        };
+        if ((rc = do_rank())) return rc;
+        uint32_t hc[kUcCount] = {};
+        k_utg_cycle_count<<<nblk(nv), 256, 0, c->stream>>>(rank, ptr<uint32_t>(pred), nv, ptr<uint32_t>(cnt));
+        KCHK(c);
+        HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kUcCount, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.cycle_vertices = hc[kUcCycle];
+        if (hc[kUcCycle]) {                                           // all-mergeable cycles: their smallest vertex becomes the head
+            ENSURE(c, ma, sizeof(UtgMin) * (size_t)nv); ENSURE(c, mb, sizeof(UtgMin) * (size_t)nv);
+            ENSURE(c, cut, nv); ENSURE(c, cmin2, 4 * (size_t)nv);
+            UtgMin *a = ptr<UtgMin>(ma), *b = ptr<UtgMin>(mb);
+            k_utg_min_init<<<nblk(nv), 256, 0, c->stream>>>(ptr<uint32_t>(pred), nv, a);
+            KCHK(c);
+            for (uint32_t i = 0; i < rounds; ++i) {
+                k_utg_min_jump<<<nblk(nv), 256, 0, c->stream>>>(a, b, nv);
+                KCHK(c);
+                std::swap(a, b);
+            }
+            k_utg_cut<<<nblk(nv), 256, 0, c->stream>>>(rank, a, ptr<uint32_t>(pred), nv, ptr<uint8_t>(cut), ptr<uint32_t>(cmin2));
+            KCHK(c);
+            d_cut = ptr<uint8_t>(cut);
+            if ((rc = do_rank())) return rc;
+        }
+        const uint32_t* const d_cmin2 = d_cut ? ptr<uint32_t>(cmin2) : nullptr;
+        k_utg_tail<<<nblk(nv), 256, 0, c->stream>>>(rank, ptr<uint32_t>(succ), d_cut, ptr<uint8_t>(dd), nv, ptr<uint32_t>(tail_of), ptr<uint32_t>(cnt_of));
+        KCHK(c);
+        k_utg_select<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(pred), d_cut, d_cmin2, ptr<uint8_t>(dd), ptr<uint32_t>(tail_of), ptr<uint32_t>(cnt_of), nv,
+                                                                   ptr<uint32_t>(emit), ptr<uint32_t>(nvert));
+        KCHK(c);
+        if ((rc = scan_u32(c, ptr<uint32_t>(emit), ptr<uint32_t>(uid), (size_t)nv + 1))) return rc;
+        if ((rc = scan_u32(c, ptr<uint32_t>(nvert), ptr<uint32_t>(voff), (size_t)nv + 1))) return rc;
+        k_utg_linkflag<<<nblk((uint64_t)m + 1), 256, 0, c->stream>>>(d_E, m, ptr<uint32_t>(succ), ptr<uint8_t>(lflag));
+        KCHK(c);
+        if ((rc = scan_flags(c, ptr<uint8_t>(lflag), ptr<uint32_t>(lscan), (size_t)m + 1))) return rc;
+        HIPCHK(c, hipMemcpyAsync(&nutg, ptr<uint32_t>(uid) + nv, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&nverts, ptr<uint32_t>(voff) + nv, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&nlk, ptr<uint32_t>(lscan) + m, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (nverts != nlive) return fail(c, BELLA_ERR_BAD_ARG, "unitigs: %u vertices for %u live reads (the graph is not twin-symmetric)", nverts, nlive);
+        ENSURE(c, verts, 4 * (size_t)nverts); ENSURE(c, nb, 4 * (size_t)nverts); ENSURE(c, slot_utg, 4 * (size_t)nverts);
+        ENSURE(c, pos, 8 * (size_t)nverts);
+        ENSURE(c, gseg, 8 * ((size_t)nverts + 1));
+        ENSURE(c, uvoff, 8 * ((size_t)nutg + 1)); ENSURE(c, ulen, 8 * ((size_t)nutg + 1)); ENSURE(c, uboff, 8 * ((size_t)nutg + 1));
+        ENSURE(c, ucirc, nutg);
+        ENSURE(c, links, sizeof(bella_unitig_link) * (size_t)nlk);
+        HIPCHK(c, hipMemsetAsync(ulen.p, 0, 8 * ((size_t)nutg + 1), c->stream));
+        k_utg_scatter<<<nblk(nv), 256, 0, c->stream>>>(rank, ptr<uint32_t>(succ), ptr<uint32_t>(outlen), ptr<uint32_t>(inlen), d_cut, ptr<uint8_t>(dd), ptr<uint64_t>(c->roff),
+                                                       ptr<uint32_t>(emit), ptr<uint32_t>(uid), ptr<uint32_t>(voff), nv, ptr<uint32_t>(verts), ptr<uint64_t>(pos),
+                                                       ptr<uint32_t>(nb), ptr<uint32_t>(slot_utg), ptr<uint64_t>(uvoff), ptr<uint64_t>(ulen), ptr<uint8_t>(ucirc));
+        KCHK(c);
+        {
+            size_t tb = 0;
+            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ptr<uint64_t>(ulen), ptr<uint64_t>(uboff), (int)(nutg + 1), c->stream));
+            ENSURE(c, c->cubtmp, tb);
+            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, ptr<uint64_t>(ulen), ptr<uint64_t>(uboff), (int)(nutg + 1), c->stream));
+        }
+        k_utg_segoff<<<nblk((uint64_t)nverts + 1), 256, 0, c->stream>>>(ptr<uint32_t>(slot_utg), ptr<uint64_t>(pos), ptr<uint64_t>(uboff), nverts, nutg, ptr<uint64_t>(gseg));
+        KCHK(c);
+        if (nlk) {
+            k_utg_links<<<nblk(m), 256, 0, c->stream>>>(d_E, ptr<uint8_t>(lflag), ptr<uint32_t>(lscan), m, rank, ptr<uint32_t>(uid), ptr<uint32_t>(tail_of),
+                                                        ptr<bella_unitig_link>(links));
+            KCHK(c);
+        }
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&total, ptr<uint64_t>(uboff) + nutg, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const uint64_t nlanes = (total + kUtgBasesPerLane - 1) / kUtgBasesPerLane;
+        ENSURE(c, out, (size_t)(nlanes * kUtgBasesPerLane));
+        HIPCHK(c, hipEventRecord(ev.d, c->stream));
+        if (total) {
+            k_utg_gather<<<nblk(nlanes), 256, 0, c->stream>>>(ptr<uint64_t>(gseg), ptr<uint32_t>(verts), ptr<uint32_t>(nb), nverts, total, ptr<uint64_t>(c->roff),
+                                                              ptr<uint32_t>(c->packed), ptr<uint4>(out));
+            KCHK(c);
+        }
+        HIPCHK(c, hipEventRecord(ev.e, c->stream));
+        c->u_voff.assign((size_t)nutg + 1, 0); c->u_boff.assign((size_t)nutg + 1, 0);
+        c->u_len.assign(nutg, 0); c->u_circ.assign(nutg, 0);
+        c->u_verts.assign(nverts, 0); c->u_nb.assign(nverts, 0); c->u_pos.assign(nverts, 0);
+        c->u_links.assign(nlk, bella_unitig_link{});
+        c->u_bases.assign((size_t)total, 0);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.rank_ms = ev_ms(ev.a, ev.b);
+        st.gather_ms = ev_ms(ev.d, ev.e);
+        if (nutg) {
+            HIPCHK(c, hipMemcpy(c->u_voff.data(), uvoff.p, 8 * (size_t)nutg, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(c->u_boff.data(), uboff.p, 8 * ((size_t)nutg + 1), hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(c->u_len.data(), ulen.p, 8 * (size_t)nutg, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(c->u_circ.data(), ucirc.p, nutg, hipMemcpyDeviceToHost));
+        }
+        c->u_voff[nutg] = nverts;
+        if (nverts) {
+            HIPCHK(c, c->stager.d2h(c->u_verts.data(), verts.p, 4 * (size_t)nverts, c->stream));
+            HIPCHK(c, c->stager.d2h(c->u_nb.data(), nb.p, 4 * (size_t)nverts, c->stream));
+            HIPCHK(c, c->stager.d2h(c->u_pos.data(), pos.p, 8 * (size_t)nverts, c->stream));
+        }
+        if (nlk) HIPCHK(c, c->stager.d2h(c->u_links.data(), links.p, sizeof(bella_unitig_link) * (size_t)nlk, c->stream));
+        if (total) HIPCHK(c, c->stager.d2h(c->u_bases.data(), out.p, (size_t)total, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    st.unitigs = nutg; st.vertices = nverts; st.links = nlk; st.total_bases = total; st.gather_bytes = total;
+    {
+        std::vector<uint64_t> sorted(c->u_len);
+        std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
+        uint64_t acc = 0;
+        for (uint64_t l : sorted) { acc += l; if (2 * acc >= total) { st.n50 = l; break; } }
+        st.largest = sorted.empty() ? 0 : sorted[0];
+        for (uint8_t f : c->u_circ) st.circular += f;
+    }
+    c->have_unitigs = true;
+    if (nunitigs) *nunitigs = nutg;
+    if (nvertices) *nvertices = nverts;
+    if (nlinks) *nlinks = nlk;
+    if (total_bases) *total_bases = total;
+    return 0;
+}
+
+int bella_hip_graph_get_unitigs(bella_ctx* c, uint64_t* vertex_offsets, uint32_t* vertices, uint64_t* pos, uint32_t* nbases, uint64_t* len, uint8_t* circular,
+                                bella_unitig_link* links) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph || !c->have_unitigs) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_unitigs first");
+    auto copy = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) std::memcpy(dst, src, bytes); };
+    copy(vertex_offsets, c->u_voff.data(), 8 * c->u_voff.size());
+    copy(vertices, c->u_verts.data(), 4 * c->u_verts.size());
+    copy(pos, c->u_pos.data(), 8 * c->u_pos.size());
+    copy(nbases, c->u_nb.data(), 4 * c->u_nb.size());
+    copy(len, c->u_len.data(), 8 * c->u_len.size());
+    copy(circular, c->u_circ.data(), c->u_circ.size());
+    copy(links, c->u_links.data(), sizeof(bella_unitig_link) * c->u_links.size());
+    return 0;
+}
+
+int bella_hip_graph_get_unitig_bases(bella_ctx* c, uint64_t* offsets, uint8_t* bases) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph || !c->have_unitigs) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_unitigs first");
+    if (offsets) std::memcpy(offsets, c->u_boff.data(), 8 * c->u_boff.size());
+    if (bases && !c->u_bases.empty()) std::memcpy(bases, c->u_bases.data(), c->u_bases.size());
+    return 0;
+}
+
+int bella_hip_graph_get_unitig_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    std::memcpy(out, &c->u_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_unitig_stats)));
+    return 0;
+}
+
+int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,
+                               const uint64_t* pos, const uint32_t* nbases, const uint64_t* len, const uint8_t* circular, const uint64_t* base_offsets,
+                               const uint8_t* bases, uint64_t nlinks, const bella_unitig_link* links) {
+    if (!path || (nreads && !names) || (nunitigs && (!vertex_offsets || !vertices || !pos || !nbases || !len || !circular)) || (bases && !base_offsets) || (nlinks && !links)) {
+        fprintf(stderr, "bella_hip_write_unitig_gfa: null argument\n");
+        return BELLA_ERR_BAD_ARG;
+    }
+    const uint64_t nvert = nunitigs ? vertex_offsets[nunitigs] : 0;
+    for (uint64_t i = 0; i < nvert; ++i)
+        if (vertices[i] >= 2 * (uint64_t)nreads || !names[vertices[i] >> 1]) { fprintf(stderr, "bella_hip_write_unitig_gfa: vertex %llu out of range\n", (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
+    for (uint64_t i = 0; i < nlinks; ++i)
+        if (links[i].a >= nunitigs || links[i].b >= nunitigs) { fprintf(stderr, "bella_hip_write_unitig_gfa: link %llu out of range\n", (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
+    FILE* f = std::fopen(path, "wb");
+    if (!f) { fprintf(stderr, "bella_hip_write_unitig_gfa: cannot open %s\n", path); return BELLA_ERR_BAD_ARG; }
+    std::vector<char> buf((size_t)4 << 20);
+    std::setvbuf(f, buf.data(), _IOFBF, buf.size());
+    bool ok = std::fputs("H\tVN:Z:1.0\n", f) != EOF;
+    char name[32], other[32];
+    auto mk = [&](char* dst, uint64_t u) { std::snprintf(dst, 32, "utg%06llu%c", (unsigned long long)(u + 1), circular[u] ? 'c' : 'l'); };
+    for (uint64_t u = 0; u < nunitigs && ok; ++u) {
+        mk(name, u);
+        ok = std::fprintf(f, "S\t%s\t", name) > 0;
+        if (ok && bases) { const size_t n = (size_t)(base_offsets[u + 1] - base_offsets[u]); ok = n == 0 || std::fwrite(bases + base_offsets[u], 1, n, f) == n; }
+        else if (ok) ok = std::fputc('*', f) != EOF;
+        ok = ok && std::fprintf(f, "\tLN:i:%llu\tRC:i:%llu\n", (unsigned long long)len[u], (unsigned long long)(vertex_offsets[u + 1] - vertex_offsets[u])) > 0;
+        for (uint64_t i = vertex_offsets[u]; i < vertex_offsets[u + 1] && ok; ++i)
+            ok = std::fprintf(f, "a\t%s\t%llu\t%s\t%c\t%u\n", name, (unsigned long long)pos[i], names[vertices[i] >> 1], (vertices[i] & 1) ? '-' : '+', nbases[i]) > 0;
+    }
+    for (uint64_t i = 0; i < nlinks && ok; ++i) {
+        const bella_unitig_link& l = links[i];
+        mk(name, l.a); mk(other, l.b);
+        ok = std::fprintf(f, "L\t%s\t%c\t%s\t%c\t%uM\trc:i:%u\n", name, (l.flags & BELLA_UNITIG_LINK_A_MINUS) ? '-' : '+', other, (l.flags & BELLA_UNITIG_LINK_B_MINUS) ? '-' : '+', l.ovl,
+                         l.rec) > 0;
+    }
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) { fprintf(stderr, "bella_hip_write_unitig_gfa: writing %s failed\n", path); return BELLA_ERR_BAD_ARG; }
     return 0;
 }
 

@@ -114,6 +114,11 @@ struct StageOpts {
                                      // built on the device after the last stage and written to this GFA 1 file (needs alignment)
     uint32_t gfa_min_overlap = 1000, gfa_max_overhang = 1000, gfa_fuzz = 1000;
     int gfa_no_seq = 0;              // S lines carry '*' instead of the reads' bases
+    const char* unitigs = nullptr;   // unitigs: tips are clipped off the graph, the unitigs of the cleaned graph are written as GFA 1 ...
+    const char* unitigs_fasta = nullptr;   // ... and / or as FASTA; either one builds the graph, with or without gfa
+    uint32_t tip_reads = 4, tip_rounds = 3;
+    int gfa_clean = 0;               // the gfa file shows the cleaned graph (removed reads' S lines dropped like contained ones)
+    bool graph() const { return gfa || unitigs || unitigs_fasta; }
 };
 
 // The string graph after the last stage: the records of the contexts 1 .. N-1 (each added its own columns' pairs) are gathered into
@@ -139,30 +144,75 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
     gp.struct_size = (uint32_t)sizeof(gp);
     gp.min_overlap = o.gfa_min_overlap; gp.max_overhang = o.gfa_max_overhang; gp.overhang_permille = 800; gp.fuzz = o.gfa_fuzz;
     check(c0, bella_hip_graph_build(c0, &gp), "bella_hip_graph_build");
-    uint32_t nv = 0;
-    uint64_t ne = 0;
-    check(c0, bella_hip_graph_get(c0, &nv, &ne, nullptr, nullptr, nullptr), "bella_hip_graph_get");
-    std::vector<uint64_t> offs((size_t)nv + 1, 0);
-    std::vector<bella_graph_edge> edges((size_t)ne);
-    std::vector<uint8_t> contained(o.nreads, 0);
-    check(c0, bella_hip_graph_get(c0, nullptr, nullptr, offs.data(), edges.data(), contained.data()), "bella_hip_graph_get");
     std::vector<uint64_t> boffs;
     RawBuf<uint8_t> bases;
-    if (!o.gfa_no_seq) {
-        boffs.assign((size_t)o.nreads + 1, 0);
-        check(c0, bella_hip_get_read_bases(c0, boffs.data(), nullptr), "bella_hip_get_read_bases");
-        bases.resize((size_t)boffs[o.nreads] + 1);
-        check(c0, bella_hip_get_read_bases(c0, nullptr, bases.data()), "bella_hip_get_read_bases");
-    }
-    const int wrc = bella_hip_write_gfa(o.gfa, o.nreads, names, lens, o.gfa_no_seq ? nullptr : boffs.data(), o.gfa_no_seq ? nullptr : bases.data(), offs.data(), edges.data(),
-                                        contained.data());
-    if (wrc) check(nullptr, wrc, "bella_hip_write_gfa");
+    auto write_gfa = [&]() {                                          // the context's current graph
+        uint32_t nv = 0;
+        uint64_t ne = 0;
+        check(c0, bella_hip_graph_get(c0, &nv, &ne, nullptr, nullptr, nullptr), "bella_hip_graph_get");
+        std::vector<uint64_t> offs((size_t)nv + 1, 0);
+        std::vector<bella_graph_edge> edges((size_t)ne);
+        std::vector<uint8_t> contained(o.nreads, 0), removed(o.nreads, 0);
+        check(c0, bella_hip_graph_get(c0, nullptr, nullptr, offs.data(), edges.data(), contained.data()), "bella_hip_graph_get");
+        check(c0, bella_hip_graph_get_removed(c0, removed.data()), "bella_hip_graph_get_removed");
+        for (uint32_t r = 0; r < o.nreads; ++r) contained[r] |= removed[r];
+        if (!o.gfa_no_seq) {
+            boffs.assign((size_t)o.nreads + 1, 0);
+            check(c0, bella_hip_get_read_bases(c0, boffs.data(), nullptr), "bella_hip_get_read_bases");
+            bases.resize((size_t)boffs[o.nreads] + 1);
+            check(c0, bella_hip_get_read_bases(c0, nullptr, bases.data()), "bella_hip_get_read_bases");
+        }
+        const int wrc = bella_hip_write_gfa(o.gfa, o.nreads, names, lens, o.gfa_no_seq ? nullptr : boffs.data(), o.gfa_no_seq ? nullptr : bases.data(), offs.data(), edges.data(),
+                                            contained.data());
+        if (wrc) check(nullptr, wrc, "bella_hip_write_gfa");
+    };
+    if (o.gfa && !o.gfa_clean) write_gfa();
     bella_graph_stats st;
     check(c0, bella_hip_graph_get_stats(c0, &st, sizeof(st)), "bella_hip_graph_get_stats");
     const std::string StringGraph = std::to_string(st.records) + " records (" + std::to_string(st.n_short) + " short, " + std::to_string(st.n_internal) + " internal), " +
                                     std::to_string(st.contained_reads) + " contained reads, " + std::to_string(st.edges_kept) + " edges, " + std::to_string(st.edges_reduced) +
                                     " reduced, " + std::to_string(st.edges_final) + " final";
     BELLA_HIP_LOGT(o.tag, StringGraph);
+    if (!o.unitigs && !o.unitigs_fasta && !o.gfa_clean) return;
+    bella_graph_clean_params cp;
+    cp.struct_size = (uint32_t)sizeof(cp);
+    cp.max_tip_reads = o.tip_reads; cp.tip_rounds = o.tip_rounds;
+    check(c0, bella_hip_graph_clean(c0, &cp), "bella_hip_graph_clean");
+    if (o.gfa && o.gfa_clean) write_gfa();
+    if (!o.unitigs && !o.unitigs_fasta) return;
+    uint64_t nu = 0, nuv = 0, nl = 0, tb = 0;
+    check(c0, bella_hip_graph_unitigs(c0, &nu, &nuv, &nl, &tb), "bella_hip_graph_unitigs");
+    std::vector<uint64_t> voff((size_t)nu + 1, 0), pos((size_t)nuv), ulen((size_t)nu), uboff((size_t)nu + 1, 0);
+    std::vector<uint32_t> verts((size_t)nuv), nb((size_t)nuv);
+    std::vector<uint8_t> circ((size_t)nu);
+    std::vector<bella_unitig_link> links((size_t)nl);
+    RawBuf<uint8_t> ubases;
+    ubases.resize((size_t)tb + 1);
+    check(c0, bella_hip_graph_get_unitigs(c0, voff.data(), verts.data(), pos.data(), nb.data(), ulen.data(), circ.data(), links.data()), "bella_hip_graph_get_unitigs");
+    check(c0, bella_hip_graph_get_unitig_bases(c0, uboff.data(), ubases.data()), "bella_hip_graph_get_unitig_bases");
+    if (o.unitigs) {
+        const int wrc = bella_hip_write_unitig_gfa(o.unitigs, o.nreads, names, nu, voff.data(), verts.data(), pos.data(), nb.data(), ulen.data(), circ.data(),
+                                                   o.gfa_no_seq ? nullptr : uboff.data(), o.gfa_no_seq ? nullptr : ubases.data(), nl, links.data());
+        if (wrc) check(nullptr, wrc, "bella_hip_write_unitig_gfa");
+    }
+    if (o.unitigs_fasta) {
+        std::vector<std::string> unames((size_t)nu);
+        std::vector<const char*> uptr((size_t)nu);
+        for (uint64_t u = 0; u < nu; ++u) {
+            char buf[32];
+            std::snprintf(buf, sizeof(buf), "utg%06llu%c", (unsigned long long)(u + 1), circ[(size_t)u] ? 'c' : 'l');
+            unames[(size_t)u] = buf;
+            uptr[(size_t)u] = unames[(size_t)u].c_str();
+        }
+        const int wrc = bella_hip_write_fasta(o.unitigs_fasta, (uint32_t)nu, uptr.data(), uboff.data(), ubases.data(), 0);
+        if (wrc) check(nullptr, wrc, "bella_hip_write_fasta");
+    }
+    bella_unitig_stats us;
+    check(c0, bella_hip_graph_get_unitig_stats(c0, &us, sizeof(us)), "bella_hip_graph_get_unitig_stats");
+    const std::string Unitigs = std::to_string(us.reads_removed) + " reads clipped in " + std::to_string(us.rounds) + " rounds, " + std::to_string(us.unitigs) + " unitigs (" +
+                                std::to_string(us.circular) + " circular) of " + std::to_string(us.vertices) + " reads, " + std::to_string(us.links) + " links, " +
+                                std::to_string(us.total_bases) + " bases, largest " + std::to_string(us.largest) + ", N50 " + std::to_string(us.n50);
+    BELLA_HIP_LOGT(o.tag, Unitigs);
 }
 
 // Read correction after the last stage: the tables of the contexts 1 .. N-1 (each piled up its own columns) are added into context 0 in
@@ -242,8 +292,8 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
                 if (o.correct) check(w.ctx, bella_hip_trace_pairs_pileup(w.ctx, &p, o.trace_band, o.cigar ? 1 : 0, &ntr, &nops), "bella_hip_trace_pairs_pileup");
                 else if (o.cigar) check(w.ctx, bella_hip_trace_pairs(w.ctx, &p, o.trace_band, 1, &ntr, &nops), "bella_hip_trace_pairs");
                 // (--gfa alone: the records are all the graph reads; no run is written or staged)
-                else if (o.gfa) check(w.ctx, bella_hip_trace_pairs_flags(w.ctx, &p, o.trace_band, BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS, &ntr, &nops), "bella_hip_trace_pairs_flags");
-                if (o.gfa) check(w.ctx, bella_hip_graph_add_traced(w.ctx, nullptr), "bella_hip_graph_add_traced");
+                else if (o.graph()) check(w.ctx, bella_hip_trace_pairs_flags(w.ctx, &p, o.trace_band, BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS, &ntr, &nops), "bella_hip_trace_pairs_flags");
+                if (o.graph()) check(w.ctx, bella_hip_graph_add_traced(w.ctx, nullptr), "bella_hip_graph_add_traced");
                 if (o.cigar) {
                     w.traces.resize(w.nnzc);
                     w.ops.resize(nops);                                       // (host memory: 4 bytes per run; -m stages bound it as they bound the records)
@@ -260,7 +310,7 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         }
     };
     if (o.correct) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_pileup_reset(W[(size_t)g].ctx), "bella_hip_pileup_reset"); });
-    if (o.gfa) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_graph_reset(W[(size_t)g].ctx), "bella_hip_graph_reset"); });
+    if (o.graph()) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_graph_reset(W[(size_t)g].ctx), "bella_hip_graph_reset"); });
     CallStats& cs = last_call_stats();
     cs = CallStats();
     const double free_memory = o.total_memory_mb * 1024 * 1024;               // estimateMemory, overlap.hpp:365-404 (no LINUX/OSX define)
@@ -369,7 +419,7 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         BELLA_HIP_LOGT(tag, OutputtingTime);
     }
     if (o.correct) write_corrected(W, o, names, lens);
-    if (o.gfa) write_graph(W, o, names, lens);
+    if (o.graph()) write_graph(W, o, names, lens);
     cs.nreads = nreads; cs.stages = stages; cs.contexts = N; cs.nnzc = nnzc;
     for (auto& w : W) {
         bella_timings tm;

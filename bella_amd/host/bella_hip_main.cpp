@@ -37,7 +37,7 @@
 namespace {
 
 struct Options {
-    std::string fastq_list, output, tuples, correct, gfa;
+    std::string fastq_list, output, tuples, correct, gfa, unitigs, unitigs_fasta;
     int kmer = 17, xdrop = 7, memory = 8000, bin_size = 500, gpus = 1, split_count = 1, window = 0, upper = 8, lower = 2;
     double error = 0.15, deviation = 0.1;
     bool estimate = false, skip_alignment = false, paf = false, hopc = false, syncmer = false, help = false, exact = false, cigar = false;
@@ -45,6 +45,9 @@ struct Options {
     bool min_depth_given = false;
     int gfa_fuzz = 1000, gfa_max_overhang = 1000, gfa_min_overlap = 1000;
     bool gfa_no_seq = false, gfa_param_given = false;
+    int tip_reads = 4, tip_rounds = 3;
+    bool gfa_clean = false, tip_param_given = false;
+    bool graph() const { return !gfa.empty() || !unitigs.empty() || !unitigs_fasta.empty(); }
 };
 
 const char* kHelp =
@@ -79,7 +82,12 @@ const char* kHelp =
     "      --gfa-min-overlap arg  with --gfa: shortest overlap that counts (default: 1000)\n"
     "      --gfa-max-overhang arg with --gfa: longest unaligned end of a dovetail or containment (default: 1000)\n"
     "      --gfa-fuzz arg         with --gfa: slack of the transitive reduction, in bases (default: 1000)\n"
-    "      --gfa-no-seq           with --gfa: '*' instead of the reads' bases in the S lines\n"
+    "      --gfa-no-seq           with --gfa / --unitigs: '*' instead of the bases in the S lines\n"
+    "      --unitigs arg          unitigs of the string graph (GFA 1: S, a and L lines): tips clipped, maximal non-branching paths compacted, on the device\n"
+    "      --unitigs-fasta arg    the unitigs' sequences (FASTA); both build the graph (the --gfa-* parameters apply), --gfa is not required\n"
+    "      --tip-reads arg        with --unitigs / --unitigs-fasta / --gfa-clean: longest tip that is clipped, in reads (default: 4; 0: no clipping)\n"
+    "      --tip-rounds arg       ... and the number of clipping rounds (default: 3)\n"
+    "      --gfa-clean            with --gfa: the file shows the graph after tip clipping\n"
     "  -h, --help                 Usage\n";
 
 [[noreturn]] void die(const std::string& msg) {
@@ -100,6 +108,7 @@ Options parse(int argc, char** argv) {
         {"correct", 0, 3, &o.correct}, {"min-depth", 0, 1, &o.min_depth},
         {"gfa", 0, 3, &o.gfa}, {"gfa-fuzz", 0, 1, &o.gfa_fuzz}, {"gfa-max-overhang", 0, 1, &o.gfa_max_overhang}, {"gfa-min-overlap", 0, 1, &o.gfa_min_overlap},
         {"gfa-no-seq", 0, 0, &o.gfa_no_seq},
+        {"unitigs", 0, 3, &o.unitigs}, {"unitigs-fasta", 0, 3, &o.unitigs_fasta}, {"tip-reads", 0, 1, &o.tip_reads}, {"tip-rounds", 0, 1, &o.tip_rounds}, {"gfa-clean", 0, 0, &o.gfa_clean},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
         char* end = nullptr;
@@ -136,6 +145,7 @@ Options parse(int argc, char** argv) {
         assign(*sp, val, a);
         if (sp->dst == &o.min_depth) o.min_depth_given = true;
         if (sp->dst == &o.gfa_fuzz || sp->dst == &o.gfa_max_overhang || sp->dst == &o.gfa_min_overlap) o.gfa_param_given = true;
+        if (sp->dst == &o.tip_reads || sp->dst == &o.tip_rounds) o.tip_param_given = true;
     }
     return o;
 }
@@ -189,9 +199,12 @@ int main(int argc, char** argv) {
     if (o.cigar && !o.paf) die("--cigar needs --paf (the base-level alignment is written as PAF columns 10-11 and the cg:Z: tag)");
     if (o.cigar && o.skip_alignment) die("--cigar cannot be combined with --skip-alignment (there is no alignment to trace)");
     if (o.trace_band < 0 || o.trace_band > (1 << 18)) die("--trace-band must be in [0, 262144]");
-    if (o.trace_band && !o.cigar && o.correct.empty() && o.gfa.empty()) die("--trace-band needs --cigar, --correct or --gfa");
-    if (!o.gfa.empty() && o.skip_alignment) die("--gfa cannot be combined with --skip-alignment (the graph is made of base-level alignments)");
-    if (o.gfa_param_given && o.gfa.empty()) die("--gfa-fuzz, --gfa-max-overhang, --gfa-min-overlap and --gfa-no-seq need --gfa");
+    if (o.trace_band && !o.cigar && o.correct.empty() && !o.graph()) die("--trace-band needs --cigar, --correct, --gfa, --unitigs or --unitigs-fasta");
+    if (o.graph() && o.skip_alignment) die("--gfa, --unitigs and --unitigs-fasta cannot be combined with --skip-alignment (the graph is made of base-level alignments)");
+    if (o.gfa_param_given && !o.graph()) die("--gfa-fuzz, --gfa-max-overhang, --gfa-min-overlap and --gfa-no-seq need --gfa or --unitigs or --unitigs-fasta");
+    if (o.gfa_clean && o.gfa.empty()) die("--gfa-clean needs --gfa");
+    if (o.tip_param_given && o.unitigs.empty() && o.unitigs_fasta.empty() && !o.gfa_clean) die("--tip-reads and --tip-rounds need --unitigs, --unitigs-fasta or --gfa-clean");
+    if (o.tip_reads < 0 || o.tip_rounds < 0 || o.tip_rounds > BELLA_MAX_TIP_ROUNDS) die("--tip-reads must not be negative and --tip-rounds must be in [0, " + std::to_string(BELLA_MAX_TIP_ROUNDS) + "]");
     if (o.gfa_fuzz < 0 || o.gfa_max_overhang < 0 || o.gfa_min_overlap < 0) die("--gfa-fuzz, --gfa-max-overhang and --gfa-min-overlap must not be negative");
     if (!o.correct.empty() && o.skip_alignment) die("--correct cannot be combined with --skip-alignment (the pileup is made of base-level alignments)");
     if (o.min_depth_given && o.min_depth < 1) die("--min-depth must be at least 1");
@@ -337,6 +350,10 @@ int main(int argc, char** argv) {
     so.gfa_max_overhang = (uint32_t)o.gfa_max_overhang;
     so.gfa_min_overlap = (uint32_t)o.gfa_min_overlap;
     so.gfa_no_seq = o.gfa_no_seq ? 1 : 0;
+    so.unitigs = o.unitigs.empty() ? nullptr : o.unitigs.c_str();
+    so.unitigs_fasta = o.unitigs_fasta.empty() ? nullptr : o.unitigs_fasta.c_str();
+    so.tip_reads = (uint32_t)o.tip_reads; so.tip_rounds = (uint32_t)o.tip_rounds;
+    so.gfa_clean = o.gfa_clean ? 1 : 0;
     const double t_stages = now_s();
     run_stages(W, so, names.data(), lens.data());
     {

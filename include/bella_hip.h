@@ -424,7 +424,8 @@ int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* 
  * of v's list + fuzz; (2) for v -> w in list order, skipped unless w is INPLAY at that moment: for w -> x in list order, stopping at the
  * first with len(v -> w) + len(w -> x) > L: an INPLAY x becomes ELIMINATED; (3) for every v -> w, whatever its mark, and w -> x at index
  * j of w's list with j == 0 or len(w -> x) < fuzz: an INPLAY x becomes ELIMINATED; (4) the edges v -> x with x ELIMINATED are reduced.
- * An edge leaves the graph when it OR ITS TWIN is reduced.  No tip clipping, bubble popping or unitig compaction. */
+ * An edge leaves the graph when it OR ITS TWIN is reduced.  Tip clipping and unitig compaction work on this graph (the next section); no
+ * bubble popping. */
 typedef struct {
     uint32_t cid, rid;            /* V, H                                                                       */
     int32_t begV, endV;           /* on V                                                                       */
@@ -493,6 +494,77 @@ int bella_hip_get_read_bases(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases);
  * code, no context. */
 int bella_hip_write_gfa(const char* path, uint32_t nreads, const char* const* names, const uint32_t* lens, const uint64_t* base_offsets,
                         const uint8_t* bases, const uint64_t* offsets, const bella_graph_edge* edges, const uint8_t* contained);
+
+/* ---- unitigs: tip clipping, compaction, sequences (no counterpart in the reference) -----------------------------
+ * On the graph of the last bella_hip_graph_build, in its notation; in-degree(v) = out-degree(v ^ 1) because the graph is twin-symmetric.
+ * Tip clipping, one round, on a snapshot of the current graph: every vertex v with in-degree 0 and out-degree >= 1 starts a walk,
+ * chain = [v], cur = v; tested in this order: out-degree(cur) == 0: END; out-degree(cur) > 1: OUT; w = the single out-neighbour,
+ * in-degree(w) != 1: IN; len(chain) == max_tip_reads: LONG; else w is appended and cur = w.  Chains that stop with IN or OUT are tips:
+ * every read with a vertex in one is removed, in both orientations, with every edge that touches it.  END chains (a short isolated chain
+ * is a contig) and LONG chains stay.  Rounds repeat until tip_rounds or until one removes nothing.  A small Y-shaped component can vanish
+ * whole in one round (all three arms are tips of each other), as with miniasm's asg_cut_tip.
+ * Unitigs: edge v -> w is mergeable iff out-degree(v) == 1 and in-degree(w) == 1.  The maximal mergeable paths and all-mergeable cycles
+ * partition the vertices of the live reads (neither contained nor removed; a live read without edges is a one-vertex path).  Path
+ * v0 .. vk has the mirror vk^1 .. v0^1 and is emitted iff v0 <= vk^1; a cycle is rotated to its smallest vertex m, is emitted iff
+ * m <= min(v^1 over the cycle) and is flagged circular.  Unitigs are ordered by first vertex and named utg%06d{l|c}, counting from 1.
+ * Vertex i of a unitig contributes the first nbases[i] bases of its read in the vertex's orientation (1 = reverse complement), at offset
+ * pos[i]: nbases = the len of the edge to the next vertex (the closing edge for the last vertex of a cycle), the whole read for the last
+ * vertex of a path; len = their sum.  Every edge that is not mergeable joins the last vertex of a path to the first of another and is a
+ * link, in CSR order, a link and its twin both listed; MINUS = that end is on the emitted unitig's mirror path. */
+#define BELLA_MAX_TIP_ROUNDS 16
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_graph_clean_params) of the caller's header (the struct may grow)          */
+    uint32_t max_tip_reads;       /* documented default 4; 0 = no clipping                                                 */
+    uint32_t tip_rounds;          /* 3; at most BELLA_MAX_TIP_ROUNDS                                                        */
+} bella_graph_clean_params;
+#define BELLA_UNITIG_LINK_A_MINUS 1u
+#define BELLA_UNITIG_LINK_B_MINUS 2u
+typedef struct {
+    uint32_t a, b;                /* unitigs: the edge leaves a, enters b                                                  */
+    uint32_t ovl, rec;            /* the edge's                                                                            */
+    uint32_t flags;               /* BELLA_UNITIG_LINK_*                                                                   */
+    uint32_t edge;                /* the edge's position in the CSR                                                        */
+} bella_unitig_link;
+/* What the last bella_hip_graph_clean (rounds .. edges_removed, clean_ms; zero without one) and bella_hip_graph_unitigs did.  A sized
+ * struct: bella_hip_graph_get_unitig_stats writes at most struct_size bytes. */
+typedef struct {
+    uint64_t unitigs, vertices, links, total_bases, circular;
+    uint64_t largest, n50;        /* n50: the length at which the lengths, largest first, sum to half of total_bases or more */
+    uint64_t reads_removed, edges_removed;
+    uint32_t rounds;              /* tip rounds that ran (the last may have removed nothing)                               */
+    uint32_t rank_rounds;         /* pointer-jumping rounds of one ranking                                                 */
+    uint32_t tips_per_round[BELLA_MAX_TIP_ROUNDS], reads_per_round[BELLA_MAX_TIP_ROUNDS];
+    uint64_t cycle_vertices;      /* vertices on all-mergeable cycles                                                      */
+    uint64_t gather_bytes;        /* bytes the sequence gather wrote                                                       */
+    double clean_ms, rank_ms, gather_ms;      /* between two events on the stream: tip rounds; succ .. links; the gather.      */
+                                              /* gather_ms is one launch, so device time.  clean_ms and rank_ms span the host's */
+                                              /* small read-backs (one per tip round, three per compaction) and the buffers     */
+                                              /* allocated between them: time on the stream, an upper bound of device time      */
+} bella_unitig_stats;
+/* Clips tips off the context's current graph (on the device) and REPLACES it: bella_hip_graph_get then returns the cleaned CSR -- the same
+ * order, the deleted edges compacted out.  params == NULL: the documented defaults.  BELLA_ERR_STATE without a built graph; BELLA_ERR_BAD_ARG
+ * for a struct_size too small or tip_rounds > BELLA_MAX_TIP_ROUNDS.  Drops the unitigs.  A second call clips the cleaned graph further. */
+int bella_hip_graph_clean(bella_ctx* ctx, const bella_graph_clean_params* params);
+/* removed[nreads] (0 / 1): the reads the clean calls since the last build took out (all 0 without one).  BELLA_ERR_STATE without a graph. */
+int bella_hip_graph_get_removed(bella_ctx* ctx, uint8_t* removed);
+/* Unitigs, links and unitig bases of the current graph (cleaned or not), on the device; the results are kept on the host until the graph
+ * changes.  Every count pointer may be NULL.  An empty graph (no live read) launches nothing and gives zero unitigs; live reads without
+ * edges are one-vertex unitigs with bases, and for those the kernels run. */
+int bella_hip_graph_unitigs(bella_ctx* ctx, uint64_t* nunitigs, uint64_t* nvertices, uint64_t* nlinks, uint64_t* total_bases);
+/* vertex_offsets[nunitigs + 1] into vertices / pos / nbases [nvertices]; len[nunitigs], circular[nunitigs] (0 / 1), links[nlinks].  Any
+ * pointer may be NULL.  BELLA_ERR_STATE without bella_hip_graph_unitigs. */
+int bella_hip_graph_get_unitigs(bella_ctx* ctx, uint64_t* vertex_offsets, uint32_t* vertices, uint64_t* pos, uint32_t* nbases, uint64_t* len, uint8_t* circular,
+                                bella_unitig_link* links);
+/* offsets[nunitigs + 1] into bases[total_bases] (upper-case ASCII).  Either may be NULL. */
+int bella_hip_graph_get_unitig_bases(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases);
+int bella_hip_graph_get_unitig_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+/* GFA 1 of the unitigs: "H\tVN:Z:1.0"; per unitig "S\tutg%06d{l|c}\t<bases or *>\tLN:i:<len>\tRC:i:<reads>" (RC = the unitig's reads; '*'
+ * when bases == NULL) followed by one "a\tutg...\t<pos>\t<read name>\t+/-\t<nbases>" per vertex; then one
+ * "L\tutgA\t+/-\tutgB\t+/-\t<ovl>M\trc:i:<rec>" per link.  Truncates the file.  Plain host code, no context.  FASTA: bella_hip_write_fasta
+ * with the same names. */
+int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,
+                               const uint64_t* pos, const uint32_t* nbases, const uint64_t* len, const uint8_t* circular, const uint64_t* base_offsets,
+                               const uint8_t* bases, uint64_t nlinks, const bella_unitig_link* links);
 
 /* ---- multi-GPU: one context per GPU, RCCL over xGMI ------------------------------------------------
  * The reference's multi-GPU path hands alignment batches to the devices inside one call (loganGPU/functions.cuh:441-443,

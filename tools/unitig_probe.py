@@ -1,0 +1,69 @@
+"""Cost and outcome of tip clipping, unitig compaction and the sequence gather next to the graph build that feeds them: writes
+profiles/unitig_probe.json.
+
+For every set (default: 2,000 x 10 kb and the bench set of 10k reads, both at 15 % error): count, assemble, overlap, align, one trace
+with the runs dropped, graph_add_traced, graph_build, graph_clean, graph_unitigs, all with the defaults.  Reported per set: reads removed
+per round, unitigs, largest unitig, N50 and their total length against the genome's, the clean, rank and gather timers (the first two
+span the host's read-backs: bella_unitig_stats in include/bella_hip.h) next to the build's classify + sort + reduce of the same run,
+and the gather's bytes over its time (one byte written per base, a quarter byte read)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: F401,E402  (first: one HIP runtime per process)
+from bella_amd import BellaPars, Engine  # noqa: E402
+from bella_testkit import synth  # noqa: E402
+
+
+def probe(nreads, seed, repeats, fast):
+    rs = (synth.make_reads_fast if fast else synth.make_reads)(nreads, read_len=10000, err=0.15, seed=seed)
+    meta = [[int(x) for x in n.split("_")[1:]] for n in rs.names]     # (start, length, strand)
+    span = max(m[0] + m[1] for m in meta) - min(m[0] for m in meta)
+    eng = Engine(0)
+    eng.reserve(44 * int(rs.offsets[-1]))
+    eng.set_reads(rs)
+    eng.count_kmers(17, 2, 8)
+    eng.assemble_counted()
+    pars = BellaPars()
+    eng.overlap(pars)
+    eng.align_pairs(pars)
+    eng.trace_pairs_records(pars)
+    eng.graph_reset()
+    eng.graph_add_traced()
+    runs = []
+    for _ in range(repeats):                                          # (the first run pays the allocations)
+        eng.graph_build()
+        gs = eng.graph_stats()
+        eng.graph_clean()
+        eng.graph_unitigs()
+        runs.append((gs, eng.unitig_stats()))
+    gs, us = min(runs, key=lambda r: r[1]["rank_ms"] + r[1]["gather_ms"])
+    build_ms = gs["classify_ms"] + gs["sort_ms"] + gs["reduce_ms"]
+    out = dict(reads=nreads, bases=int(rs.offsets[-1]), genome_span=int(span), edges_final=int(gs["edges_final"]), contained_reads=int(gs["contained_reads"]),
+               tips_per_round=us["tips_per_round"], reads_per_round=us["reads_per_round"], reads_removed=int(us["reads_removed"]), edges_removed=int(us["edges_removed"]),
+               unitigs=int(us["unitigs"]), circular=int(us["circular"]), links=int(us["links"]), largest=int(us["largest"]), n50=int(us["n50"]),
+               total_bases=int(us["total_bases"]), total_over_span=us["total_bases"] / max(1, span), rank_rounds=int(us["rank_rounds"]),
+               clean_ms=us["clean_ms"], rank_ms=us["rank_ms"], gather_ms=us["gather_ms"], build_ms=build_ms,
+               unitigs_over_build=(us["clean_ms"] + us["rank_ms"] + us["gather_ms"]) / max(1e-9, build_ms),
+               gather_bytes=int(us["gather_bytes"] * 5 // 4), gather_gb_per_s=us["gather_bytes"] * 1.25 / max(1e-9, us["gather_ms"] * 1e6))
+    eng.close()
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sets", nargs="+", default=["2000:21:exact", "10000:1:fast"], help="reads:seed:exact|fast (the generator: synth.make_reads / make_reads_fast)")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "unitig_probe.json"))
+    a = ap.parse_args()
+    res = []
+    for s in a.sets:
+        n, seed, gen = s.split(":")
+        res.append(probe(int(n), int(seed), a.repeats, gen == "fast"))
+        print(json.dumps(res[-1]), flush=True)
+    with open(a.out, "w") as f:
+        json.dump(dict(sets=res), f, indent=1)
+        f.write("\n")

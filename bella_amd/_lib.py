@@ -98,6 +98,20 @@ class UnitigStats(C.Structure):
                 ("cycle_vertices", C.c_uint64), ("gather_bytes", C.c_uint64), ("clean_ms", C.c_double), ("rank_ms", C.c_double), ("gather_ms", C.c_double)]
 
 
+MAX_BUBBLE_READS = 255
+MAX_BUBBLE_ROUNDS = 16
+
+
+class GraphBubbleParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_bubble_reads", C.c_uint32), ("max_bubble_dist", C.c_uint32), ("bubble_rounds", C.c_uint32)]
+
+
+class BubbleStats(C.Structure):
+    _fields_ = [("reads_removed", C.c_uint64), ("edges_removed", C.c_uint64), ("rounds", C.c_uint32), ("pad", C.c_uint32),
+                ("sources", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("found", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("popped", C.c_uint32 * MAX_BUBBLE_ROUNDS),
+                ("reads_per_round", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("edges_per_round", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("pop_ms", C.c_double)]
+
+
 # every symbol include/bella_hip.h declares: (name, restype, argtypes)
 vp = C.c_void_p
 SIGNATURES = [
@@ -183,6 +197,8 @@ SIGNATURES = [
     ("bella_hip_graph_get_unitigs", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     ("bella_hip_graph_get_unitig_bases", C.c_int, [vp, vp, vp]),
     ("bella_hip_graph_get_unitig_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_graph_pop_bubbles", C.c_int, [vp, C.POINTER(GraphBubbleParams)]),
+    ("bella_hip_graph_get_bubble_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_write_unitig_gfa", C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
     ("bella_hip_get_timings", C.c_int, [vp, C.POINTER(Timings)]),
     ("bella_hip_get_memory", C.c_int, [vp, C.POINTER(Memory)]),

@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, GraphCleanParams, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
+from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
 class BellaHipError(RuntimeError):
@@ -446,9 +446,32 @@ class Engine:
         self._chk(self.lib.bella_hip_graph_clean(self.h, C.byref(cp)))
 
     def graph_removed(self) -> np.ndarray:
-        """uint8[nreads]: the reads graph_clean took out since the last graph_build"""
+        """uint8[nreads]: the reads graph_clean and graph_pop_bubbles took out since the last graph_build"""
         out = np.zeros(self.nreads, np.uint8)
         self._chk(self.lib.bella_hip_graph_get_removed(self.h, _p(out)))
+        return out
+
+    # ---- bubble popping (DESIGN.md section 13) ----
+    BUBBLE_DEFAULTS = dict(max_bubble_reads=64, max_bubble_dist=50000, bubble_rounds=3)
+
+    def graph_pop_bubbles(self, **params):
+        """pops bubbles of the current graph (on the device) and replaces it, as graph_clean does; the popped reads show in
+        graph_removed().  max_bubble_reads (0 = off, at most 255), max_bubble_dist and bubble_rounds default to 64, 50,000 and 3"""
+        p = dict(self.BUBBLE_DEFAULTS)
+        for k, v in params.items():
+            if k not in p:
+                raise TypeError("unknown bubble parameter %r" % k)
+            p[k] = int(v)
+        bp = GraphBubbleParams(C.sizeof(GraphBubbleParams), p["max_bubble_reads"], p["max_bubble_dist"], p["bubble_rounds"])
+        self._chk(self.lib.bella_hip_graph_pop_bubbles(self.h, C.byref(bp)))
+
+    def bubble_stats(self) -> dict:
+        """of the last graph_pop_bubbles: totals, and per round sources / found / popped / reads_per_round / edges_per_round"""
+        st = BubbleStats()
+        self._chk(self.lib.bella_hip_graph_get_bubble_stats(self.h, C.byref(st), C.sizeof(st)))
+        out = dict(reads_removed=st.reads_removed, edges_removed=st.edges_removed, rounds=st.rounds, pop_ms=st.pop_ms)
+        for k in ("sources", "found", "popped", "reads_per_round", "edges_per_round"):
+            out[k] = list(getattr(st, k))[:st.rounds]
         return out
 
     def graph_unitigs(self) -> dict:

@@ -30,6 +30,7 @@
 #include "spgemm.hpp"
 #include "trace.hpp"
 #include "unitig.hpp"
+#include "bubble.hpp"
 #include "util.hpp"
 #include "wide.hpp"
 #include "writer.hpp"
@@ -219,6 +220,7 @@ struct bella_ctx {
     std::vector<uint8_t> u_circ, u_bases;
     std::vector<bella_unitig_link> u_links;
     bella_unitig_stats u_stats{};
+    bella_bubble_stats b_stats{};        // of the last bella_hip_graph_pop_bubbles (bubble.hpp)
     bella_timings tm{};
     hipEvent_t ev[12]{};
     uint32_t* pinned = nullptr;          // 128 host words the per-pass read backs land in
@@ -4282,6 +4284,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     c->g_stats = st;
     c->g_removed.assign(nr, 0);
     c->u_stats = bella_unitig_stats{};
+    c->b_stats = bella_bubble_stats{};
     c->have_graph = true;
     return 0;
 }
@@ -4424,6 +4427,103 @@ int bella_hip_graph_get_removed(bella_ctx* c, uint8_t* removed) {
     if (!c) return BELLA_ERR_BAD_ARG;
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
     if (removed && !c->g_removed.empty()) std::memcpy(removed, c->g_removed.data(), c->g_removed.size());
+    return 0;
+}
+
+// ---- bubble popping (bubble.hpp) ----
+int bella_hip_graph_pop_bubbles(bella_ctx* c, const bella_graph_bubble_params* params) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    bella_graph_bubble_params bp{(uint32_t)sizeof(bella_graph_bubble_params), 64, 50000, 3};
+    if (params) {
+        if (params->struct_size < sizeof(bella_graph_bubble_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_graph_bubble_params: struct_size %u is too small", params->struct_size);
+        bp = *params;
+    }
+    if (bp.bubble_rounds > BELLA_MAX_BUBBLE_ROUNDS) return fail(c, BELLA_ERR_BAD_ARG, "bubble_rounds %u: at most %d", bp.bubble_rounds, BELLA_MAX_BUBBLE_ROUNDS);
+    if (bp.max_bubble_reads > BELLA_MAX_BUBBLE_READS) return fail(c, BELLA_ERR_BAD_ARG, "max_bubble_reads %u: at most %d", bp.max_bubble_reads, BELLA_MAX_BUBBLE_READS);
+    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->have_unitigs = false;
+    bella_bubble_stats st{};
+    const uint32_t nr = c->nreads, nv = 2 * nr;
+    uint32_t m = (uint32_t)c->g_edges.size();
+    if (!bp.max_bubble_reads || !bp.bubble_rounds) { c->b_stats = st; return 0; }
+    if (!m) { st.rounds = 1; c->b_stats = st; return 0; }             // (a round over no edges finds nothing)
+    Buf off, off2, E, E2, list, claim, hit, ekill, rem, keep, scan, cnt;
+    BufGuard guard{{&off, &off2, &E, &E2, &list, &claim, &hit, &ekill, &rem, &keep, &scan, &cnt}};
+    int rc = graph_upload(c, off, E);
+    if (rc) return rc;
+    ENSURE(c, off2, 4 * ((size_t)nv + 1));
+    ENSURE(c, E2, sizeof(bella_graph_edge) * (size_t)m);
+    ENSURE(c, list, 4 * (size_t)nv);
+    ENSURE(c, claim, 4 * (size_t)nr);
+    ENSURE(c, hit, nr); ENSURE(c, rem, nr);
+    ENSURE(c, ekill, (size_t)m + 1);
+    ENSURE(c, keep, (size_t)m + 1);
+    ENSURE(c, scan, 4 * ((size_t)m + 1));
+    ENSURE(c, cnt, 4 * kBcCount);
+    HIPCHK(c, hipMemcpyAsync(rem.p, c->g_removed.data(), nr, hipMemcpyHostToDevice, c->stream));
+    EventSet ev;
+    HIPCHK(c, hipEventCreate(&ev.a)); HIPCHK(c, hipEventCreate(&ev.b));
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    const uint32_t m0 = m;
+    for (uint32_t round = 0; round < bp.bubble_rounds; ++round) {
+        uint32_t hc[kBcCount] = {}, nm = 0;
+        HIPCHK(c, hipMemsetAsync(hit.p, 0, nr, c->stream));
+        HIPCHK(c, hipMemsetAsync(ekill.p, 0, (size_t)m + 1, c->stream));
+        HIPCHK(c, hipMemsetAsync(claim.p, 0xFF, 4 * (size_t)nr, c->stream));
+        HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kBcCount, c->stream));
+        k_bub_sources<<<nblk(nv), 256, 0, c->stream>>>(ptr<uint32_t>(off), nv, ptr<uint32_t>(list), ptr<uint32_t>(cnt));
+        KCHK(c);
+        // one wavefront per listed source; the grid covers every vertex and the wavefronts past the list leave at once
+        k_bub_detect<<<nblk(nv, kBubBlock / 64), kBubBlock, 0, c->stream>>>(ptr<uint32_t>(off), ptr<bella_graph_edge>(E), ptr<uint32_t>(list), bp.max_bubble_reads,
+                                                                            bp.max_bubble_dist, ptr<uint32_t>(claim), ptr<uint32_t>(cnt));
+        KCHK(c);
+        k_bub_apply<<<nblk(nv, kBubBlock / 64), kBubBlock, 0, c->stream>>>(ptr<uint32_t>(off), ptr<bella_graph_edge>(E), ptr<uint32_t>(list), bp.max_bubble_reads,
+                                                                           bp.max_bubble_dist, ptr<uint32_t>(claim), ptr<uint8_t>(hit), ptr<uint8_t>(ekill), ptr<uint32_t>(cnt));
+        KCHK(c);
+        k_bub_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(hit), nr, ptr<uint8_t>(rem), ptr<uint32_t>(cnt));
+        KCHK(c);
+        k_bub_filter<<<nblk((uint64_t)m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), m, ptr<uint8_t>(hit), ptr<uint8_t>(ekill), ptr<uint8_t>(keep));
+        KCHK(c);
+        rc = scan_flags(c, ptr<uint8_t>(keep), ptr<uint32_t>(scan), (size_t)m + 1);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(&nm, ptr<uint32_t>(scan) + m, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kBcCount, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));                   // the round's one read-back
+        st.sources[round] = hc[kBcSources]; st.found[round] = hc[kBcFound]; st.popped[round] = hc[kBcPopped];
+        st.reads_per_round[round] = hc[kBcReads]; st.edges_per_round[round] = m - nm;
+        st.rounds = round + 1;
+        st.reads_removed += hc[kBcReads];
+        if (!hc[kBcPopped]) break;
+        k_graph_compact<<<nblk(m), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), ptr<uint8_t>(keep), ptr<uint32_t>(scan), m, ptr<bella_graph_edge>(E2));
+        KCHK(c);
+        k_utg_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint32_t>(off2));
+        KCHK(c);
+        std::swap(E, E2);
+        std::swap(off, off2);
+        m = nm;
+    }
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    std::vector<uint32_t> off32((size_t)nv + 1);
+    std::vector<bella_graph_edge> edges(m);
+    std::vector<uint8_t> removed(nr);
+    HIPCHK(c, hipMemcpyAsync(off32.data(), off.p, 4 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
+    if (m) HIPCHK(c, c->stager.d2h(edges.data(), E.p, sizeof(bella_graph_edge) * (size_t)m, c->stream));
+    HIPCHK(c, hipMemcpyAsync(removed.data(), rem.p, nr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i <= nv; ++i) c->g_off[i] = off32[i];
+    c->g_edges.swap(edges);
+    c->g_removed.swap(removed);
+    st.edges_removed = m0 - m;
+    st.pop_ms = ev_ms(ev.a, ev.b);
+    c->b_stats = st;
+    return 0;
+}
+
+int bella_hip_graph_get_bubble_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    std::memcpy(out, &c->b_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_bubble_stats)));
     return 0;
 }
 

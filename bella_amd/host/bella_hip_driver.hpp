@@ -118,6 +118,8 @@ struct StageOpts {
     const char* unitigs_fasta = nullptr;   // ... and / or as FASTA; either one builds the graph, with or without gfa
     uint32_t tip_reads = 4, tip_rounds = 3;
     int gfa_clean = 0;               // the gfa file shows the cleaned graph (removed reads' S lines dropped like contained ones)
+    int pop_bubbles = 0;             // bubble popping after the tip clipping, before the unitigs and the cleaned gfa file
+    uint32_t bubble_reads = 64, bubble_dist = 50000, bubble_rounds = 3;
     bool graph() const { return gfa || unitigs || unitigs_fasta; }
 };
 
@@ -178,6 +180,14 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
     cp.struct_size = (uint32_t)sizeof(cp);
     cp.max_tip_reads = o.tip_reads; cp.tip_rounds = o.tip_rounds;
     check(c0, bella_hip_graph_clean(c0, &cp), "bella_hip_graph_clean");
+    bella_bubble_stats bs{};
+    if (o.pop_bubbles) {                                              // (popping cannot create a tip: a bubble is closed)
+        bella_graph_bubble_params bp;
+        bp.struct_size = (uint32_t)sizeof(bp);
+        bp.max_bubble_reads = o.bubble_reads; bp.max_bubble_dist = o.bubble_dist; bp.bubble_rounds = o.bubble_rounds;
+        check(c0, bella_hip_graph_pop_bubbles(c0, &bp), "bella_hip_graph_pop_bubbles");
+        check(c0, bella_hip_graph_get_bubble_stats(c0, &bs, sizeof(bs)), "bella_hip_graph_get_bubble_stats");
+    }
     if (o.gfa && o.gfa_clean) write_gfa();
     if (!o.unitigs && !o.unitigs_fasta) return;
     uint64_t nu = 0, nuv = 0, nl = 0, tb = 0;
@@ -209,7 +219,10 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
     }
     bella_unitig_stats us;
     check(c0, bella_hip_graph_get_unitig_stats(c0, &us, sizeof(us)), "bella_hip_graph_get_unitig_stats");
-    const std::string Unitigs = std::to_string(us.reads_removed) + " reads clipped in " + std::to_string(us.rounds) + " rounds, " + std::to_string(us.unitigs) + " unitigs (" +
+    uint64_t npopped = 0;
+    for (uint32_t r = 0; r < bs.rounds; ++r) npopped += bs.popped[r];
+    const std::string Popped = o.pop_bubbles ? std::to_string(npopped) + " bubbles popped, " + std::to_string(bs.reads_removed) + " reads, " : std::string();
+    const std::string Unitigs = std::to_string(us.reads_removed) + " reads clipped in " + std::to_string(us.rounds) + " rounds, " + Popped + std::to_string(us.unitigs) + " unitigs (" +
                                 std::to_string(us.circular) + " circular) of " + std::to_string(us.vertices) + " reads, " + std::to_string(us.links) + " links, " +
                                 std::to_string(us.total_bases) + " bases, largest " + std::to_string(us.largest) + ", N50 " + std::to_string(us.n50);
     BELLA_HIP_LOGT(o.tag, Unitigs);

@@ -47,6 +47,8 @@ struct Options {
     bool gfa_no_seq = false, gfa_param_given = false;
     int tip_reads = 4, tip_rounds = 3;
     bool gfa_clean = false, tip_param_given = false;
+    int bubble_reads = 64, bubble_dist = 50000, bubble_rounds = 3;
+    bool pop_bubbles = false, bubble_param_given = false;
     bool graph() const { return !gfa.empty() || !unitigs.empty() || !unitigs_fasta.empty(); }
 };
 
@@ -87,7 +89,11 @@ const char* kHelp =
     "      --unitigs-fasta arg    the unitigs' sequences (FASTA); both build the graph (the --gfa-* parameters apply), --gfa is not required\n"
     "      --tip-reads arg        with --unitigs / --unitigs-fasta / --gfa-clean: longest tip that is clipped, in reads (default: 4; 0: no clipping)\n"
     "      --tip-rounds arg       ... and the number of clipping rounds (default: 3)\n"
-    "      --gfa-clean            with --gfa: the file shows the graph after tip clipping\n"
+    "      --gfa-clean            with --gfa: the file shows the graph after tip clipping (and bubble popping)\n"
+    "      --pop-bubbles          with --unitigs / --unitigs-fasta / --gfa-clean: pop bubbles after the tip clipping, on the device\n"
+    "      --bubble-reads arg     with --pop-bubbles: largest bubble that is popped, in reads (default: 64; at most 255; 0: no popping)\n"
+    "      --bubble-dist arg      ... its largest distance from the source, in bases (default: 50000)\n"
+    "      --bubble-rounds arg    ... and the number of popping rounds (default: 3)\n"
     "  -h, --help                 Usage\n";
 
 [[noreturn]] void die(const std::string& msg) {
@@ -109,6 +115,7 @@ Options parse(int argc, char** argv) {
         {"gfa", 0, 3, &o.gfa}, {"gfa-fuzz", 0, 1, &o.gfa_fuzz}, {"gfa-max-overhang", 0, 1, &o.gfa_max_overhang}, {"gfa-min-overlap", 0, 1, &o.gfa_min_overlap},
         {"gfa-no-seq", 0, 0, &o.gfa_no_seq},
         {"unitigs", 0, 3, &o.unitigs}, {"unitigs-fasta", 0, 3, &o.unitigs_fasta}, {"tip-reads", 0, 1, &o.tip_reads}, {"tip-rounds", 0, 1, &o.tip_rounds}, {"gfa-clean", 0, 0, &o.gfa_clean},
+        {"pop-bubbles", 0, 0, &o.pop_bubbles}, {"bubble-reads", 0, 1, &o.bubble_reads}, {"bubble-dist", 0, 1, &o.bubble_dist}, {"bubble-rounds", 0, 1, &o.bubble_rounds},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
         char* end = nullptr;
@@ -146,6 +153,7 @@ Options parse(int argc, char** argv) {
         if (sp->dst == &o.min_depth) o.min_depth_given = true;
         if (sp->dst == &o.gfa_fuzz || sp->dst == &o.gfa_max_overhang || sp->dst == &o.gfa_min_overlap) o.gfa_param_given = true;
         if (sp->dst == &o.tip_reads || sp->dst == &o.tip_rounds) o.tip_param_given = true;
+        if (sp->dst == &o.bubble_reads || sp->dst == &o.bubble_dist || sp->dst == &o.bubble_rounds) o.bubble_param_given = true;
     }
     return o;
 }
@@ -205,6 +213,11 @@ int main(int argc, char** argv) {
     if (o.gfa_clean && o.gfa.empty()) die("--gfa-clean needs --gfa");
     if (o.tip_param_given && o.unitigs.empty() && o.unitigs_fasta.empty() && !o.gfa_clean) die("--tip-reads and --tip-rounds need --unitigs, --unitigs-fasta or --gfa-clean");
     if (o.tip_reads < 0 || o.tip_rounds < 0 || o.tip_rounds > BELLA_MAX_TIP_ROUNDS) die("--tip-reads must not be negative and --tip-rounds must be in [0, " + std::to_string(BELLA_MAX_TIP_ROUNDS) + "]");
+    if (o.bubble_param_given && !o.pop_bubbles) die("--bubble-reads, --bubble-dist and --bubble-rounds need --pop-bubbles");
+    if (o.pop_bubbles && o.unitigs.empty() && o.unitigs_fasta.empty() && !o.gfa_clean) die("--pop-bubbles needs --unitigs, --unitigs-fasta or --gfa-clean");
+    if (o.bubble_reads < 0 || o.bubble_reads > BELLA_MAX_BUBBLE_READS || o.bubble_dist < 0 || o.bubble_rounds < 0 || o.bubble_rounds > BELLA_MAX_BUBBLE_ROUNDS)
+        die("--bubble-reads must be in [0, " + std::to_string(BELLA_MAX_BUBBLE_READS) + "], --bubble-dist must not be negative and --bubble-rounds must be in [0, " +
+            std::to_string(BELLA_MAX_BUBBLE_ROUNDS) + "]");
     if (o.gfa_fuzz < 0 || o.gfa_max_overhang < 0 || o.gfa_min_overlap < 0) die("--gfa-fuzz, --gfa-max-overhang and --gfa-min-overlap must not be negative");
     if (!o.correct.empty() && o.skip_alignment) die("--correct cannot be combined with --skip-alignment (the pileup is made of base-level alignments)");
     if (o.min_depth_given && o.min_depth < 1) die("--min-depth must be at least 1");
@@ -354,6 +367,8 @@ int main(int argc, char** argv) {
     so.unitigs_fasta = o.unitigs_fasta.empty() ? nullptr : o.unitigs_fasta.c_str();
     so.tip_reads = (uint32_t)o.tip_reads; so.tip_rounds = (uint32_t)o.tip_rounds;
     so.gfa_clean = o.gfa_clean ? 1 : 0;
+    so.pop_bubbles = o.pop_bubbles ? 1 : 0;
+    so.bubble_reads = (uint32_t)o.bubble_reads; so.bubble_dist = (uint32_t)o.bubble_dist; so.bubble_rounds = (uint32_t)o.bubble_rounds;
     const double t_stages = now_s();
     run_stages(W, so, names.data(), lens.data());
     {

@@ -424,8 +424,8 @@ int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* 
  * of v's list + fuzz; (2) for v -> w in list order, skipped unless w is INPLAY at that moment: for w -> x in list order, stopping at the
  * first with len(v -> w) + len(w -> x) > L: an INPLAY x becomes ELIMINATED; (3) for every v -> w, whatever its mark, and w -> x at index
  * j of w's list with j == 0 or len(w -> x) < fuzz: an INPLAY x becomes ELIMINATED; (4) the edges v -> x with x ELIMINATED are reduced.
- * An edge leaves the graph when it OR ITS TWIN is reduced.  Tip clipping and unitig compaction work on this graph (the next section); no
- * bubble popping. */
+ * An edge leaves the graph when it OR ITS TWIN is reduced.  Tip clipping, unitig compaction (the next section) and bubble popping (the
+ * one after it) work on this graph. */
 typedef struct {
     uint32_t cid, rid;            /* V, H                                                                       */
     int32_t begV, endV;           /* on V                                                                       */
@@ -545,7 +545,7 @@ typedef struct {
  * order, the deleted edges compacted out.  params == NULL: the documented defaults.  BELLA_ERR_STATE without a built graph; BELLA_ERR_BAD_ARG
  * for a struct_size too small or tip_rounds > BELLA_MAX_TIP_ROUNDS.  Drops the unitigs.  A second call clips the cleaned graph further. */
 int bella_hip_graph_clean(bella_ctx* ctx, const bella_graph_clean_params* params);
-/* removed[nreads] (0 / 1): the reads the clean calls since the last build took out (all 0 without one).  BELLA_ERR_STATE without a graph. */
+/* removed[nreads] (0 / 1): the reads the clean and pop calls since the last build took out (all 0 without one).  BELLA_ERR_STATE without a graph. */
 int bella_hip_graph_get_removed(bella_ctx* ctx, uint8_t* removed);
 /* Unitigs, links and unitig bases of the current graph (cleaned or not), on the device; the results are kept on the host until the graph
  * changes.  Every count pointer may be NULL.  An empty graph (no live read) launches nothing and gives zero unitigs; live reads without
@@ -565,6 +565,51 @@ int bella_hip_graph_get_unitig_stats(bella_ctx* ctx, void* out, uint64_t struct_
 int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,
                                const uint64_t* pos, const uint32_t* nbases, const uint64_t* len, const uint8_t* circular, const uint64_t* base_offsets,
                                const uint8_t* bases, uint64_t nlinks, const bella_unitig_link* links);
+
+/* ---- bubble popping (no counterpart in the reference; the pass is miniasm's asg_pop_bubble) -----------------------
+ * One round works on a snapshot of the current graph.  Every vertex s with out-degree >= 2 runs detect(s), a Kahn traversal: each visited
+ * vertex carries r (in-edges not yet seen), d (smallest distance from s) and (c, D, p), its best path: reads on it, its length, its
+ * predecessor.  visited = {s: r = 0, d = 0, c = 0, D = 0}, stack = [s], pending = 0.  While the stack is not empty: v = pop; out-degree(v)
+ * == 0 fails (a tip inside); for v -> w of length l in list order: w == s or w ^ 1 visited fails (a cycle; both orientations of a read);
+ * d(v) + l > max_bubble_dist fails; a new w fails when visited - {s} already holds max_bubble_reads vertices, else it is visited with
+ * r = in-degree(w), d = d(v) + l, (c, D, p) = (c(v) + 1, D(v) + l, v) and pending += 1; a known w takes d = min(d, d(v) + l) and the new
+ * (c, D, p) when (c(v) + 1, D(v) + l) is lexicographically larger than (c(w), D(w)), or equal with v < p(w); then r(w) -= 1 and, at 0, w is
+ * pushed and pending -= 1.  After v's edges: stack == [t] and pending == 0 is SUCCESS (t is not expanded).  An empty stack fails (an
+ * in-edge from outside keeps a vertex waiting).  Success, t, the visited set and every (d, c, D, p) do not depend on which ready vertex
+ * is popped first; the reason of a failure can, and is not reported.
+ * Only the side of a bubble with s < t ^ 1 acts.  Interior I = visited - {s, t}; kept path K = t, p(t), p(p(t)), ... s.  Every acting
+ * bubble claims the reads of I: claim[read] = min(claim[read], s); it is ACCEPTED iff it holds the claim on every read of I (nested
+ * bubbles and bubbles that meet in opposite orientations are settled so; the smallest s always wins).  An accepted bubble removes the
+ * reads of I - K, in both orientations, with every edge that touches them, and every edge v -> w with v, w in visited that is not an edge
+ * of K, with its twin.  The round's result is the CSR in the old order with the deleted edges compacted out; the removed reads are OR-ed
+ * into what bella_hip_graph_get_removed returns, so the unitigs treat them as dead.  Rounds repeat until bubble_rounds or until one
+ * accepts nothing (that round is counted). */
+#define BELLA_MAX_BUBBLE_READS 255
+#define BELLA_MAX_BUBBLE_ROUNDS 16
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_graph_bubble_params) of the caller's header (the struct may grow)         */
+    uint32_t max_bubble_reads;    /* documented default 64; at most BELLA_MAX_BUBBLE_READS; 0 = no popping                  */
+    uint32_t max_bubble_dist;     /* 50000 bases (miniasm's default)                                                       */
+    uint32_t bubble_rounds;       /* 3; at most BELLA_MAX_BUBBLE_ROUNDS                                                     */
+} bella_graph_bubble_params;
+/* What the last bella_hip_graph_pop_bubbles did (zero without one since the build).  A sized struct: bella_hip_graph_get_bubble_stats
+ * writes at most struct_size bytes. */
+typedef struct {
+    uint64_t reads_removed, edges_removed;    /* over all rounds                                                               */
+    uint32_t rounds;                          /* rounds that ran (the last may have accepted nothing)                          */
+    uint32_t pad;
+    uint32_t sources[BELLA_MAX_BUBBLE_ROUNDS];        /* per round: vertices with out-degree >= 2                              */
+    uint32_t found[BELLA_MAX_BUBBLE_ROUNDS];          /* successes of detect with s < t ^ 1                                    */
+    uint32_t popped[BELLA_MAX_BUBBLE_ROUNDS];         /* accepted bubbles                                                      */
+    uint32_t reads_per_round[BELLA_MAX_BUBBLE_ROUNDS], edges_per_round[BELLA_MAX_BUBBLE_ROUNDS];
+    double pop_ms;                            /* between two events on the stream: all rounds, their read-backs included       */
+} bella_bubble_stats;
+/* Pops bubbles of the context's current graph (on the device) and REPLACES it, as bella_hip_graph_clean does; the popped reads show in
+ * bella_hip_graph_get_removed.  params == NULL: the defaults.  BELLA_ERR_STATE without a built graph; BELLA_ERR_BAD_ARG for a struct_size
+ * too small, bubble_rounds > BELLA_MAX_BUBBLE_ROUNDS or max_bubble_reads > BELLA_MAX_BUBBLE_READS.  Drops the unitigs.  A graph without
+ * edges, max_bubble_reads == 0 or bubble_rounds == 0 launch nothing.  Bubbles of more than max_bubble_reads reads are left alone. */
+int bella_hip_graph_pop_bubbles(bella_ctx* ctx, const bella_graph_bubble_params* params);
+int bella_hip_graph_get_bubble_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 
 /* ---- multi-GPU: one context per GPU, RCCL over xGMI ------------------------------------------------
  * The reference's multi-GPU path hands alignment batches to the devices inside one call (loganGPU/functions.cuh:441-443,

@@ -1,11 +1,13 @@
-"""Cost and outcome of tip clipping, unitig compaction and the sequence gather next to the graph build that feeds them: writes
-profiles/unitig_probe.json.
+"""Cost and outcome of tip clipping, bubble popping, unitig compaction and the sequence gather next to the graph build that feeds them:
+writes profiles/unitig_probe.json.
 
 For every set (default: 2,000 x 10 kb and the bench set of 10k reads, both at 15 % error): count, assemble, overlap, align, one trace
 with the runs dropped, graph_add_traced, graph_build, graph_clean, graph_unitigs, all with the defaults.  Reported per set: reads removed
 per round, unitigs, largest unitig, N50 and their total length against the genome's, the clean, rank and gather timers (the first two
 span the host's read-backs: bella_unitig_stats in include/bella_hip.h) next to the build's classify + sort + reduce of the same run,
-and the gather's bytes over its time (one byte written per base, a quarter byte read)."""
+and the gather's bytes over its time (one byte written per base, a quarter byte read).  Then the same with graph_pop_bubbles between the
+clean and the unitigs: sources / found / popped / reads removed per round, pop_ms, and unitigs, largest and N50
+with the stage next to those without it."""
 import argparse
 import json
 import os
@@ -39,8 +41,15 @@ def probe(nreads, seed, repeats, fast):
         gs = eng.graph_stats()
         eng.graph_clean()
         eng.graph_unitigs()
-        runs.append((gs, eng.unitig_stats()))
-    gs, us = min(runs, key=lambda r: r[1]["rank_ms"] + r[1]["gather_ms"])
+        us = eng.unitig_stats()
+        eng.graph_build()
+        eng.graph_clean()
+        eng.graph_pop_bubbles()
+        bs = eng.bubble_stats()
+        eng.graph_unitigs()
+        runs.append((gs, us, bs, eng.unitig_stats()))
+    gs, us, _, _ = min(runs, key=lambda r: r[1]["rank_ms"] + r[1]["gather_ms"])
+    _, _, bs, ps = min(runs, key=lambda r: r[2]["pop_ms"])
     build_ms = gs["classify_ms"] + gs["sort_ms"] + gs["reduce_ms"]
     out = dict(reads=nreads, bases=int(rs.offsets[-1]), genome_span=int(span), edges_final=int(gs["edges_final"]), contained_reads=int(gs["contained_reads"]),
                tips_per_round=us["tips_per_round"], reads_per_round=us["reads_per_round"], reads_removed=int(us["reads_removed"]), edges_removed=int(us["edges_removed"]),
@@ -49,6 +58,10 @@ def probe(nreads, seed, repeats, fast):
                clean_ms=us["clean_ms"], rank_ms=us["rank_ms"], gather_ms=us["gather_ms"], build_ms=build_ms,
                unitigs_over_build=(us["clean_ms"] + us["rank_ms"] + us["gather_ms"]) / max(1e-9, build_ms),
                gather_bytes=int(us["gather_bytes"] * 5 // 4), gather_gb_per_s=us["gather_bytes"] * 1.25 / max(1e-9, us["gather_ms"] * 1e6))
+    out["pop"] = dict(rounds=int(bs["rounds"]), sources=bs["sources"], found=bs["found"], popped=bs["popped"], reads_per_round=bs["reads_per_round"],
+                      edges_per_round=bs["edges_per_round"], reads_removed=int(bs["reads_removed"]), edges_removed=int(bs["edges_removed"]), pop_ms=bs["pop_ms"],
+                      pop_over_build=bs["pop_ms"] / max(1e-9, build_ms), unitigs=int(ps["unitigs"]), largest=int(ps["largest"]), n50=int(ps["n50"]),
+                      total_bases=int(ps["total_bases"]), unitigs_without=int(us["unitigs"]), largest_without=int(us["largest"]), n50_without=int(us["n50"]))
     eng.close()
     return out
 

@@ -29,6 +29,9 @@ assert OVL_DT.itemsize == 32 and EDGE_DT.itemsize == 24
 LINK_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("ovl", "<u4"), ("rec", "<u4"), ("flags", "<u4"), ("edge", "<u4")])
 assert LINK_DT.itemsize == 24
 LINK_A_MINUS, LINK_B_MINUS, MAX_TIP_ROUNDS = 1, 2, 16
+POLISH_DT = np.dtype([("len_before", "<u8"), ("len_after", "<u8"), ("substituted", "<u8"), ("deleted", "<u8"), ("inserted", "<u8"), ("covered", "<u8"),
+                      ("depth_sum", "<u8")])
+assert POLISH_DT.itemsize == 56
 TRACE_PASSED_ONLY, TRACE_DROP_OPS, TRACE_PILEUP = 1, 2, 4
 PILEUP_COUNTERS = 9      # per base: votes for A C G T, del, one inserted A C G T in the junction before the base
 assert PAIR_DT.itemsize == 16 and EXT_DT.itemsize == 8 and ALN_DT.itemsize == 32 and SEED_DT.itemsize == 12
@@ -110,6 +113,16 @@ class BubbleStats(C.Structure):
     _fields_ = [("reads_removed", C.c_uint64), ("edges_removed", C.c_uint64), ("rounds", C.c_uint32), ("pad", C.c_uint32),
                 ("sources", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("found", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("popped", C.c_uint32 * MAX_BUBBLE_ROUNDS),
                 ("reads_per_round", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("edges_per_round", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("pop_ms", C.c_double)]
+
+
+class PolishParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_depth", C.c_uint32)]
+
+
+class PolishStats(C.Structure):
+    _fields_ = [("unitigs", C.c_uint64), ("vertices", C.c_uint64), ("bases_before", C.c_uint64), ("bases_after", C.c_uint64), ("substituted", C.c_uint64),
+                ("deleted", C.c_uint64), ("inserted", C.c_uint64), ("covered", C.c_uint64), ("depth_sum", C.c_uint64), ("table_bytes", C.c_uint64),
+                ("min_depth", C.c_uint32), ("tiles", C.c_uint32), ("decide_ms", C.c_double), ("write_ms", C.c_double)]
 
 
 # every symbol include/bella_hip.h declares: (name, restype, argtypes)
@@ -199,6 +212,9 @@ SIGNATURES = [
     ("bella_hip_graph_get_unitig_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_graph_pop_bubbles", C.c_int, [vp, C.POINTER(GraphBubbleParams)]),
     ("bella_hip_graph_get_bubble_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_graph_polish_unitigs", C.c_int, [vp, C.POINTER(PolishParams), C.POINTER(C.c_uint64)]),
+    ("bella_hip_graph_get_polished", C.c_int, [vp, vp, vp, vp, vp, vp]),
+    ("bella_hip_graph_get_polish_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_write_unitig_gfa", C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
     ("bella_hip_get_timings", C.c_int, [vp, C.POINTER(Timings)]),
     ("bella_hip_get_memory", C.c_int, [vp, C.POINTER(Memory)]),

@@ -14,7 +14,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
+from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, POLISH_DT, PolishParams, PolishStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
 class BellaHipError(RuntimeError):
@@ -499,6 +499,24 @@ class Engine:
         out = {k: getattr(st, k) for k, _ in st._fields_}
         out["tips_per_round"], out["reads_per_round"] = list(st.tips_per_round)[:st.rounds], list(st.reads_per_round)[:st.rounds]
         return out
+
+    # ---- unitig consensus ----
+    def graph_polish_unitigs(self, min_depth: int = 3) -> dict:
+        """polishes the unitigs of the last graph_unitigs with the pileup table (on the device): offsets uint64[n + 1] into bases (uint8
+        ASCII), pos uint64 / nbases uint32 per vertex in polished coordinates, stats of POLISH_DT per unitig"""
+        pp = PolishParams(C.sizeof(PolishParams), min_depth)
+        tot = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_graph_polish_unitigs(self.h, C.byref(pp), C.byref(tot)))
+        st = self.polish_stats()
+        out = dict(offsets=np.zeros(st["unitigs"] + 1, np.uint64), bases=np.zeros(tot.value, np.uint8), pos=np.zeros(st["vertices"], np.uint64),
+                   nbases=np.zeros(st["vertices"], np.uint32), stats=np.zeros(st["unitigs"], POLISH_DT))
+        self._chk(self.lib.bella_hip_graph_get_polished(self.h, *(_p(out[k]) for k in ("offsets", "bases", "pos", "nbases", "stats"))))
+        return out
+
+    def polish_stats(self) -> dict:
+        st = PolishStats()
+        self._chk(self.lib.bella_hip_graph_get_polish_stats(self.h, C.byref(st), C.sizeof(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
 
     def read_bases(self):
         """(offsets uint64[nreads + 1], bases uint8 ASCII) of the loaded reads"""

@@ -27,6 +27,7 @@
 #include "logan.hpp"
 #include "order.hpp"
 #include "pileup.hpp"
+#include "polish.hpp"
 #include "spgemm.hpp"
 #include "trace.hpp"
 #include "unitig.hpp"
@@ -221,6 +222,13 @@ struct bella_ctx {
     std::vector<bella_unitig_link> u_links;
     bella_unitig_stats u_stats{};
     bella_bubble_stats b_stats{};        // of the last bella_hip_graph_pop_bubbles (bubble.hpp)
+    // unitig consensus (polish.hpp): the last bella_hip_graph_polish_unitigs (on the host, like the unitigs)
+    bool have_polish = false;
+    std::vector<uint64_t> p_offs, p_pos;
+    std::vector<uint32_t> p_nb;
+    std::vector<uint8_t> p_bases;
+    std::vector<bella_polish_unitig> p_recs;
+    bella_polish_stats p_stats{};
     bella_timings tm{};
     hipEvent_t ev[12]{};
     uint32_t* pinned = nullptr;          // 128 host words the per-pass read backs land in
@@ -958,7 +966,7 @@ static int set_reads_impl(bella_ctx* c, const uint64_t* offsets, uint32_t nreads
     for (Buf* b : {&c->pile, &c->cons_out, &c->cons_offs, &c->cons_stats}) release(*b);      // (the pileup belongs to the reads it was sized for)
     c->have_pile = c->have_cons = false;
     c->g_recs.clear();                                                // (so do the overlap records and the graph)
-    c->have_graph = c->have_unitigs = false;
+    c->have_graph = c->have_unitigs = c->have_polish = false;
     return 0;
 }
 
@@ -3839,7 +3847,7 @@ static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0,
     std::vector<bella_trace> tr(jobs.size());
     c->trace_ops.clear();
     if (!keep_ops) std::vector<uint32_t>().swap(c->trace_ops);
-    if (vote) c->have_cons = false;
+    if (vote) c->have_cons = c->have_polish = false;
     rc = run_trace(c, p, jobs, band0, tr.data(), c->trace_ops, c->trace_stats, vote, keep_ops);
     trace_release(c);
     if (vote) release(c->pile_pairs);
@@ -3928,7 +3936,7 @@ int bella_hip_pileup_reset(bella_ctx* c) {
     if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->total_bases * kPileCounters * 4;
-    c->have_pile = c->have_cons = false;
+    c->have_pile = c->have_cons = c->have_polish = false;
     if (ensure_bytes(c, c->pile, bytes))
         return fail(c, BELLA_ERR_NOMEM, "the pileup table needs %zu bytes of device memory (36 per base of %llu bases) and they do not fit", bytes,
                     (unsigned long long)c->total_bases);
@@ -3976,7 +3984,7 @@ int bella_hip_add_pileup(bella_ctx* c, uint32_t first_read, uint32_t nreads, con
     if (!count) return 0;
     if (!in) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_cons = false;
+    c->have_cons = c->have_polish = false;
     constexpr uint64_t kChunk = 16ull << 20;                          // counters per step: 64 MB of device scratch whatever the range
     ENSURE(c, c->pile_tmp, 4 * (size_t)std::min(kChunk, count));
     for (uint64_t o = 0; o < count; o += kChunk) {
@@ -4078,7 +4086,7 @@ struct KeepU32 {
 int bella_hip_graph_reset(bella_ctx* c) {
     if (!c) return BELLA_ERR_BAD_ARG;
     std::vector<bella_overlap>().swap(c->g_recs);
-    c->have_graph = c->have_unitigs = false;
+    c->have_graph = c->have_unitigs = c->have_polish = false;
     return 0;
 }
 
@@ -4096,7 +4104,7 @@ int bella_hip_graph_add_overlaps(bella_ctx* c, const bella_overlap* recs, uint64
                         r.endH, (long long)l2);
     }
     c->g_recs.insert(c->g_recs.end(), recs, recs + n);
-    c->have_graph = c->have_unitigs = false;
+    c->have_graph = c->have_unitigs = c->have_polish = false;
     return 0;
 }
 
@@ -4148,7 +4156,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
     HIPCHK(c, hipSetDevice(c->device));
     const auto t_begin = clk::now();
-    c->have_graph = c->have_unitigs = false;
+    c->have_graph = c->have_unitigs = c->have_polish = false;
     const uint32_t nr = c->nreads, nv = 2 * nr;
     const uint32_t n = (uint32_t)c->g_recs.size(), nc = 2 * n;
     if (nr >= (1u << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 reads");
@@ -4355,7 +4363,7 @@ int bella_hip_graph_clean(bella_ctx* c, const bella_graph_clean_params* params) 
     if (cp.tip_rounds > BELLA_MAX_TIP_ROUNDS) return fail(c, BELLA_ERR_BAD_ARG, "tip_rounds %u: at most %d", cp.tip_rounds, BELLA_MAX_TIP_ROUNDS);
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_unitigs = false;
+    c->have_unitigs = c->have_polish = false;
     bella_unitig_stats st{};
     const uint32_t nr = c->nreads, nv = 2 * nr;
     uint32_t m = (uint32_t)c->g_edges.size();
@@ -4442,7 +4450,7 @@ int bella_hip_graph_pop_bubbles(bella_ctx* c, const bella_graph_bubble_params* p
     if (bp.max_bubble_reads > BELLA_MAX_BUBBLE_READS) return fail(c, BELLA_ERR_BAD_ARG, "max_bubble_reads %u: at most %d", bp.max_bubble_reads, BELLA_MAX_BUBBLE_READS);
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_unitigs = false;
+    c->have_unitigs = c->have_polish = false;
     bella_bubble_stats st{};
     const uint32_t nr = c->nreads, nv = 2 * nr;
     uint32_t m = (uint32_t)c->g_edges.size();
@@ -4531,7 +4539,7 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
     if (!c) return BELLA_ERR_BAD_ARG;
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_unitigs = false;
+    c->have_unitigs = c->have_polish = false;
     const uint32_t nr = c->nreads, nv = 2 * nr, m = (uint32_t)c->g_edges.size();
     bella_unitig_stats& st = c->u_stats;                              // (the clean's figures stay)
     st.unitigs = st.vertices = st.links = st.total_bases = st.circular = st.largest = st.n50 = st.cycle_vertices = st.gather_bytes = 0;
@@ -4731,6 +4739,122 @@ int bella_hip_graph_get_unitig_stats(bella_ctx* c, void* out, uint64_t struct_si
     if (!c || !out) return BELLA_ERR_BAD_ARG;
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
     std::memcpy(out, &c->u_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_unitig_stats)));
+    return 0;
+}
+
+// ---- unitig consensus (polish.hpp) ---------------------------------------------------------------------------------
+struct TileCount {
+    __host__ __device__ uint64_t operator()(const uint32_t& v) const { return (uint64_t)v; }
+};
+
+int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* params, uint64_t* total_bases) {
+    if (!c || !params) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
+    if (params->struct_size < sizeof(bella_polish_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_polish_params: struct_size %u is too small", params->struct_size);
+    if (params->min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
+    if (!c->have_graph || !c->have_unitigs) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_unitigs first");
+    if (!c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->have_polish = false;
+    const uint32_t nutg = (uint32_t)c->u_len.size(), nseg = (uint32_t)c->u_verts.size();
+    const uint64_t total = c->u_boff[nutg];
+    bella_polish_stats st{};
+    st.unitigs = nutg; st.vertices = nseg; st.bases_before = total; st.min_depth = params->min_depth;
+    c->p_offs.assign((size_t)nutg + 1, 0);
+    c->p_pos.assign(nseg, 0); c->p_nb.assign(nseg, 0);
+    c->p_recs.assign(nutg, bella_polish_unitig{});
+    c->p_bases.clear();
+    uint64_t nout = 0;
+    if (total) {                                                      // (no unitig position: nothing is launched)
+        const uint64_t ntiles = (total + kPolTile - 1) / kPolTile;
+        if (ntiles >= 0x7FFFFFFFull) return fail(c, BELLA_ERR_BAD_ARG, "polish: fewer than 2^31 tiles of unitig positions");
+        st.tiles = (uint32_t)ntiles;
+        st.table_bytes = total * kPileCounters * 4;
+        std::vector<uint32_t> slot(nseg);
+        for (uint32_t u = 0; u < nutg; ++u)
+            for (uint64_t i = c->u_voff[u]; i < c->u_voff[u + 1]; ++i) slot[(size_t)i] = u;
+        Buf verts, slot_utg, pos, uvoff, uboff, gseg, emit, tcnt, tpref, gp, ppos, pnb, poffs, recs, out;
+        BufGuard guard{{&verts, &slot_utg, &pos, &uvoff, &uboff, &gseg, &emit, &tcnt, &tpref, &gp, &ppos, &pnb, &poffs, &recs, &out}};
+        ENSURE(c, verts, 4 * (size_t)nseg); ENSURE(c, slot_utg, 4 * (size_t)nseg); ENSURE(c, pnb, 4 * (size_t)nseg);
+        ENSURE(c, pos, 8 * (size_t)nseg); ENSURE(c, ppos, 8 * (size_t)nseg);
+        ENSURE(c, gseg, 8 * ((size_t)nseg + 1)); ENSURE(c, gp, 8 * ((size_t)nseg + 1));
+        ENSURE(c, uvoff, 8 * ((size_t)nutg + 1)); ENSURE(c, uboff, 8 * ((size_t)nutg + 1)); ENSURE(c, poffs, 8 * ((size_t)nutg + 1));
+        ENSURE(c, recs, sizeof(bella_polish_unitig) * (size_t)nutg);
+        ENSURE(c, emit, (size_t)(ntiles * kPolTile));
+        ENSURE(c, tcnt, 4 * ((size_t)ntiles + 1)); ENSURE(c, tpref, 8 * ((size_t)ntiles + 1));
+        HIPCHK(c, c->stager.h2d(verts.p, c->u_verts.data(), 4 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(slot_utg.p, slot.data(), 4 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(pos.p, c->u_pos.data(), 8 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(uvoff.p, c->u_voff.data(), 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, c->stager.h2d(uboff.p, c->u_boff.data(), 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, hipMemsetAsync(recs.p, 0, sizeof(bella_polish_unitig) * (size_t)nutg, c->stream));
+        HIPCHK(c, hipMemsetAsync(ptr<uint32_t>(tcnt) + ntiles, 0, 4, c->stream));
+        k_utg_segoff<<<nblk((uint64_t)nseg + 1), 256, 0, c->stream>>>(ptr<uint32_t>(slot_utg), ptr<uint64_t>(pos), ptr<uint64_t>(uboff), nseg, nutg, ptr<uint64_t>(gseg));
+        KCHK(c);
+        EventSet ev;
+        HIPCHK(c, hipEventCreate(&ev.a)); HIPCHK(c, hipEventCreate(&ev.b)); HIPCHK(c, hipEventCreate(&ev.d)); HIPCHK(c, hipEventCreate(&ev.e));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        k_pol_decide<<<(uint32_t)ntiles, kPolBlock, 0, c->stream>>>(ptr<uint64_t>(gseg), ptr<uint32_t>(verts), ptr<uint32_t>(slot_utg), nseg, total, ptr<uint64_t>(c->roff),
+                                                                    ptr<uint32_t>(c->packed), ptr<uint32_t>(c->pile), params->min_depth, ptr<uint8_t>(emit),
+                                                                    ptr<bella_polish_unitig>(recs), ptr<uint32_t>(tcnt));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        {
+            hipcub::TransformInputIterator<uint64_t, TileCount, const uint32_t*> it(ptr<uint32_t>(tcnt), TileCount());
+            size_t tb = 0;
+            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, ptr<uint64_t>(tpref), (int)(ntiles + 1), c->stream));
+            ENSURE(c, c->cubtmp, tb);
+            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, ptr<uint64_t>(tpref), (int)(ntiles + 1), c->stream));
+        }
+        k_pol_segoff<<<nblk(((uint64_t)nseg + 1) * 64, kPolBlock), kPolBlock, 0, c->stream>>>(ptr<uint64_t>(gseg), nseg, ptr<uint8_t>(emit), ptr<uint64_t>(tpref),
+                                                                                              ptr<uint64_t>(gp));
+        KCHK(c);
+        k_pol_finish<<<nblk((uint64_t)std::max(nseg, nutg) + 1), 256, 0, c->stream>>>(ptr<uint64_t>(gp), ptr<uint32_t>(slot_utg), ptr<uint64_t>(uvoff), ptr<uint64_t>(uboff), nseg,
+                                                                                       nutg, ptr<uint64_t>(ppos), ptr<uint32_t>(pnb), ptr<uint64_t>(poffs),
+                                                                                       ptr<bella_polish_unitig>(recs));
+        KCHK(c);
+        HIPCHK(c, hipMemcpyAsync(&nout, ptr<uint64_t>(tpref) + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        ENSURE(c, out, (size_t)((nout + 15) / 16 * 16 + 16));
+        HIPCHK(c, hipEventRecord(ev.d, c->stream));
+        k_pol_write<<<(uint32_t)ntiles, kPolBlock, 0, c->stream>>>(ptr<uint8_t>(emit), ptr<uint64_t>(tpref), ptr<uint8_t>(out));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.e, c->stream));
+        c->p_bases.assign((size_t)nout, 0);
+        HIPCHK(c, c->stager.d2h(c->p_offs.data(), poffs.p, 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, c->stager.d2h(c->p_recs.data(), recs.p, sizeof(bella_polish_unitig) * (size_t)nutg, c->stream));
+        HIPCHK(c, c->stager.d2h(c->p_pos.data(), ppos.p, 8 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.d2h(c->p_nb.data(), pnb.p, 4 * (size_t)nseg, c->stream));
+        if (nout) HIPCHK(c, c->stager.d2h(c->p_bases.data(), out.p, (size_t)nout, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.decide_ms = ev_ms(ev.a, ev.b);
+        st.write_ms = ev_ms(ev.d, ev.e);
+    }
+    st.bases_after = nout;
+    for (const bella_polish_unitig& r : c->p_recs) {
+        st.substituted += r.substituted; st.deleted += r.deleted; st.inserted += r.inserted; st.covered += r.covered; st.depth_sum += r.depth_sum;
+    }
+    c->p_stats = st;
+    c->have_polish = true;
+    if (total_bases) *total_bases = nout;
+    return 0;
+}
+
+int bella_hip_graph_get_polished(bella_ctx* c, uint64_t* offsets, uint8_t* bases, uint64_t* ppos, uint32_t* pnbases, bella_polish_unitig* per_unitig) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph || !c->have_unitigs || !c->have_polish) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_polish_unitigs first");
+    auto copy = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) std::memcpy(dst, src, bytes); };
+    copy(offsets, c->p_offs.data(), 8 * c->p_offs.size());
+    copy(bases, c->p_bases.data(), c->p_bases.size());
+    copy(ppos, c->p_pos.data(), 8 * c->p_pos.size());
+    copy(pnbases, c->p_nb.data(), 4 * c->p_nb.size());
+    copy(per_unitig, c->p_recs.data(), sizeof(bella_polish_unitig) * c->p_recs.size());
+    return 0;
+}
+
+int bella_hip_graph_get_polish_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    if (!c->have_graph || !c->have_unitigs || !c->have_polish) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_polish_unitigs first");
+    std::memcpy(out, &c->p_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_polish_stats)));
     return 0;
 }
 

@@ -131,26 +131,19 @@ __global__ void k_pile_add(uint32_t* table, const uint32_t* add, uint64_t n) {
 }
 
 // ---- consensus ------------------------------------------------------------------------------------------------------------------
-// Per position g (a row of the table): emit[g] = count | first base << 2 | second base << 4.  A junction's inserted base comes before
-// the position's own.  Per-read statistics: a wavefront whose 64 positions lie in one read reduces across its lanes first.
-__global__ __launch_bounds__(256) void k_cons_decide(const uint32_t* table, const uint32_t* packed, const uint64_t* roff, uint32_t nreads, uint64_t total,
-                                                     uint32_t min_depth, uint8_t* emit, bella_consensus_read* stats) {
-    const uint64_t g0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = g0 < total;
-    const uint64_t g = live ? g0 : total - 1;
-    const int lane = (int)(threadIdx.x & 63);
-    uint32_t lo = 0, hi = nreads;                                     // the read of g: the last r with roff[r] <= g
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (roff[mid] <= g) lo = mid; else hi = mid;
-    }
-    const uint32_t r = lo;
-    const uint32_t p = (uint32_t)(g - roff[r]);
-    const uint32_t* const row = table + g * kPileCounters;
+// What the rule of DESIGN.md section 10 decides at one position: the emit byte and the position's share of the statistics.
+struct ConsDecision {
+    uint32_t emit;                     // count | first base << 2 | second base << 4: a junction's inserted base comes before the position's own
+    uint32_t sub, del, ins, cov;       // 0 / 1 each
+    uint64_t depth;
+};
+
+// row: the nine counters of the position; p: its index in its read (the junction before it reads the row before: p >= 1 only); own: the
+// read's base there.  The one statement of the rule on the device: k_cons_decide (read space) and k_pol_decide (unitig space) call it.
+__device__ __forceinline__ ConsDecision cons_decide_at(const uint32_t* row, uint32_t p, uint32_t own, uint32_t min_depth) {
     uint32_t cb[4] = {row[0], row[1], row[2], row[3]};
     const uint32_t del = row[kPileDel];
     const uint64_t depth = (uint64_t)cb[0] + cb[1] + cb[2] + cb[3] + del;
-    const uint32_t own = pile_base(packed, g);
     uint32_t n = 0, code = 0, n_ins = 0, n_del = 0, n_sub = 0, cov = 0;
     if (p >= 1) {                                                     // the junction before p
         const uint32_t* const pr = row - kPileCounters;
@@ -180,16 +173,35 @@ __global__ __launch_bounds__(256) void k_cons_decide(const uint32_t* table, cons
             n_sub = best != own ? 1u : 0u;
         }
     }
-    if (live) emit[g] = (uint8_t)(code | n);
+    return ConsDecision{code | n, n_sub, n_del, n_ins, cov, depth};
+}
+
+// Per position g (a row of the table): emit[g].  Per-read statistics: a wavefront whose 64 positions lie in one read reduces across its
+// lanes first.
+__global__ __launch_bounds__(256) void k_cons_decide(const uint32_t* table, const uint32_t* packed, const uint64_t* roff, uint32_t nreads, uint64_t total,
+                                                     uint32_t min_depth, uint8_t* emit, bella_consensus_read* stats) {
+    const uint64_t g0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = g0 < total;
+    const uint64_t g = live ? g0 : total - 1;
+    const int lane = (int)(threadIdx.x & 63);
+    uint32_t lo = 0, hi = nreads;                                     // the read of g: the last r with roff[r] <= g
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (roff[mid] <= g) lo = mid; else hi = mid;
+    }
+    const uint32_t r = lo;
+    const uint32_t p = (uint32_t)(g - roff[r]);
+    const ConsDecision d = cons_decide_at(table + g * kPileCounters, p, pile_base(packed, g), min_depth);
+    if (live) emit[g] = (uint8_t)d.emit;
     // statistics
-    uint32_t s_sub = live ? n_sub : 0u, s_del = live ? n_del : 0u, s_ins = live ? n_ins : 0u, s_cov = live ? cov : 0u;
-    unsigned long long s_depth = live ? depth : 0ull;
+    uint32_t s_sub = live ? d.sub : 0u, s_del = live ? d.del : 0u, s_ins = live ? d.ins : 0u, s_cov = live ? d.cov : 0u;
+    unsigned long long s_depth = live ? d.depth : 0ull;
     const uint32_t r0 = __shfl(r, 0, 64);
     if (__all(!live || r == r0)) {
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            s_sub += __shfl_xor(s_sub, d, 64); s_del += __shfl_xor(s_del, d, 64); s_ins += __shfl_xor(s_ins, d, 64); s_cov += __shfl_xor(s_cov, d, 64);
-            s_depth += __shfl_xor(s_depth, d, 64);
+        for (int m = 1; m < 64; m <<= 1) {
+            s_sub += __shfl_xor(s_sub, m, 64); s_del += __shfl_xor(s_del, m, 64); s_ins += __shfl_xor(s_ins, m, 64); s_cov += __shfl_xor(s_cov, m, 64);
+            s_depth += __shfl_xor(s_depth, m, 64);
         }
         if (lane != 0) return;
     }

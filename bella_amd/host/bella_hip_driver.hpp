@@ -120,7 +120,10 @@ struct StageOpts {
     int gfa_clean = 0;               // the gfa file shows the cleaned graph (removed reads' S lines dropped like contained ones)
     int pop_bubbles = 0;             // bubble popping after the tip clipping, before the unitigs and the cleaned gfa file
     uint32_t bubble_reads = 64, bubble_dist = 50000, bubble_rounds = 3;
+    int polish = 0;                  // unitig consensus: every stage's traced pairs vote as with correct; the unitigs files carry the
+    uint32_t polish_min_depth = 3;   // polished sequences and coordinates
     bool graph() const { return gfa || unitigs || unitigs_fasta; }
+    bool pileup() const { return correct || polish; }
 };
 
 // The string graph after the last stage: the records of the contexts 1 .. N-1 (each added its own columns' pairs) are gathered into
@@ -200,6 +203,19 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
     ubases.resize((size_t)tb + 1);
     check(c0, bella_hip_graph_get_unitigs(c0, voff.data(), verts.data(), pos.data(), nb.data(), ulen.data(), circ.data(), links.data()), "bella_hip_graph_get_unitigs");
     check(c0, bella_hip_graph_get_unitig_bases(c0, uboff.data(), ubases.data()), "bella_hip_graph_get_unitig_bases");
+    bella_polish_stats ps{};
+    if (o.polish) {                                                   // the files take the polished coordinates and bases in place of the raw ones
+        bella_polish_params pp;
+        pp.struct_size = (uint32_t)sizeof(pp);
+        pp.min_depth = o.polish_min_depth;
+        uint64_t ptotal = 0;
+        check(c0, bella_hip_graph_polish_unitigs(c0, &pp, &ptotal), "bella_hip_graph_polish_unitigs");
+        std::vector<bella_polish_unitig> pu((size_t)nu);
+        ubases.resize((size_t)ptotal + 1);
+        check(c0, bella_hip_graph_get_polished(c0, uboff.data(), ubases.data(), pos.data(), nb.data(), pu.data()), "bella_hip_graph_get_polished");
+        for (uint64_t u = 0; u < nu; ++u) ulen[(size_t)u] = pu[(size_t)u].len_after;
+        check(c0, bella_hip_graph_get_polish_stats(c0, &ps, sizeof(ps)), "bella_hip_graph_get_polish_stats");
+    }
     if (o.unitigs) {
         const int wrc = bella_hip_write_unitig_gfa(o.unitigs, o.nreads, names, nu, voff.data(), verts.data(), pos.data(), nb.data(), ulen.data(), circ.data(),
                                                    o.gfa_no_seq ? nullptr : uboff.data(), o.gfa_no_seq ? nullptr : ubases.data(), nl, links.data());
@@ -224,13 +240,14 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
     const std::string Popped = o.pop_bubbles ? std::to_string(npopped) + " bubbles popped, " + std::to_string(bs.reads_removed) + " reads, " : std::string();
     const std::string Unitigs = std::to_string(us.reads_removed) + " reads clipped in " + std::to_string(us.rounds) + " rounds, " + Popped + std::to_string(us.unitigs) + " unitigs (" +
                                 std::to_string(us.circular) + " circular) of " + std::to_string(us.vertices) + " reads, " + std::to_string(us.links) + " links, " +
-                                std::to_string(us.total_bases) + " bases, largest " + std::to_string(us.largest) + ", N50 " + std::to_string(us.n50);
+                                std::to_string(us.total_bases) + " bases, largest " + std::to_string(us.largest) + ", N50 " + std::to_string(us.n50) +
+                                (o.polish ? ", polished " + std::to_string(ps.bases_before) + " -> " + std::to_string(ps.bases_after) + " bases" : std::string());
     BELLA_HIP_LOGT(o.tag, Unitigs);
 }
 
-// Read correction after the last stage: the tables of the contexts 1 .. N-1 (each piled up its own columns) are added into context 0 in
-// chunks of whole reads of at most ~4 M bases (144 MB on the host, whatever the read set), then the consensus and the FASTA file.
-inline void write_corrected(std::vector<Worker>& W, const StageOpts& o, const char* const* names, const uint32_t* lens) {
+// The pileup after the last stage: the tables of the contexts 1 .. N-1 (each piled up its own columns) are added into context 0 in
+// chunks of whole reads of at most ~4 M bases (144 MB on the host, whatever the read set).  Once, before the consensus and the polish.
+inline void merge_pileups(std::vector<Worker>& W, const StageOpts& o, const uint32_t* lens) {
     const uint32_t nreads = o.nreads;
     bella_ctx* const c0 = W[0].ctx;
     if (o.N > 1) {
@@ -248,6 +265,12 @@ inline void write_corrected(std::vector<Worker>& W, const StageOpts& o, const ch
             lo = hi;
         }
     }
+}
+
+// Read correction: the consensus of every read from context 0's (merged) table, and the FASTA file.
+inline void write_corrected(std::vector<Worker>& W, const StageOpts& o, const char* const* names) {
+    const uint32_t nreads = o.nreads;
+    bella_ctx* const c0 = W[0].ctx;
     bella_consensus_params cp;
     cp.struct_size = (uint32_t)sizeof(cp);
     cp.min_depth = o.min_depth;
@@ -301,8 +324,8 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
                 w.alns.resize(w.nnzc);
                 if (w.nnzc) check(w.ctx, bella_hip_get_alignments(w.ctx, w.alns.data()), "bella_hip_get_alignments");
                 uint64_t ntr = 0, nops = 0;
-                // (--correct: the stage's runs vote on the device; they come to the host only when the true PAF wants them too)
-                if (o.correct) check(w.ctx, bella_hip_trace_pairs_pileup(w.ctx, &p, o.trace_band, o.cigar ? 1 : 0, &ntr, &nops), "bella_hip_trace_pairs_pileup");
+                // (--correct / --polish: the stage's runs vote on the device; they come to the host only when the true PAF wants them too)
+                if (o.pileup()) check(w.ctx, bella_hip_trace_pairs_pileup(w.ctx, &p, o.trace_band, o.cigar ? 1 : 0, &ntr, &nops), "bella_hip_trace_pairs_pileup");
                 else if (o.cigar) check(w.ctx, bella_hip_trace_pairs(w.ctx, &p, o.trace_band, 1, &ntr, &nops), "bella_hip_trace_pairs");
                 // (--gfa alone: the records are all the graph reads; no run is written or staged)
                 else if (o.graph()) check(w.ctx, bella_hip_trace_pairs_flags(w.ctx, &p, o.trace_band, BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS, &ntr, &nops), "bella_hip_trace_pairs_flags");
@@ -322,7 +345,7 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
             colptrC[i + 1] = colptrC[i] + (w.colptr[i + 1] - w.colptr[i]);
         }
     };
-    if (o.correct) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_pileup_reset(W[(size_t)g].ctx), "bella_hip_pileup_reset"); });
+    if (o.pileup()) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_pileup_reset(W[(size_t)g].ctx), "bella_hip_pileup_reset"); });
     if (o.graph()) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_graph_reset(W[(size_t)g].ctx), "bella_hip_graph_reset"); });
     CallStats& cs = last_call_stats();
     cs = CallStats();
@@ -431,7 +454,8 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         const std::string OutputtingTime = std::to_string(ws.seconds) + " seconds";
         BELLA_HIP_LOGT(tag, OutputtingTime);
     }
-    if (o.correct) write_corrected(W, o, names, lens);
+    if (o.pileup()) merge_pileups(W, o, lens);
+    if (o.correct) write_corrected(W, o, names);
     if (o.graph()) write_graph(W, o, names, lens);
     cs.nreads = nreads; cs.stages = stages; cs.contexts = N; cs.nnzc = nnzc;
     for (auto& w : W) {

@@ -19,6 +19,9 @@
 // --correct FILE: read correction: every stage's traced pairs vote into a per-read pileup on the device, the
 // consensus of every read goes to FILE as FASTA after the last stage; the main output file is what it is without the option.
 //
+// --polish: unitig consensus: every stage's traced pairs vote as with --correct, the unitigs are polished from
+// the pileup on the device after the last stage; --unitigs / --unitigs-fasta then carry the polished sequences and coordinates.
+//
 // Not built (rejected loudly): --hopc, --estimate, --split-count > 1.
 #include <sys/stat.h>
 #include <chrono>
@@ -49,6 +52,8 @@ struct Options {
     bool gfa_clean = false, tip_param_given = false;
     int bubble_reads = 64, bubble_dist = 50000, bubble_rounds = 3;
     bool pop_bubbles = false, bubble_param_given = false;
+    int polish_min_depth = 3;
+    bool polish = false, polish_param_given = false;
     bool graph() const { return !gfa.empty() || !unitigs.empty() || !unitigs_fasta.empty(); }
 };
 
@@ -94,6 +99,8 @@ const char* kHelp =
     "      --bubble-reads arg     with --pop-bubbles: largest bubble that is popped, in reads (default: 64; at most 255; 0: no popping)\n"
     "      --bubble-dist arg      ... its largest distance from the source, in bases (default: 50000)\n"
     "      --bubble-rounds arg    ... and the number of popping rounds (default: 3)\n"
+    "      --polish               with --unitigs / --unitigs-fasta: unitig consensus from the pileup of the base-level alignments, on the device\n"
+    "      --polish-min-depth arg with --polish: votes a position needs before it is changed (default: 3)\n"
     "  -h, --help                 Usage\n";
 
 [[noreturn]] void die(const std::string& msg) {
@@ -116,6 +123,7 @@ Options parse(int argc, char** argv) {
         {"gfa-no-seq", 0, 0, &o.gfa_no_seq},
         {"unitigs", 0, 3, &o.unitigs}, {"unitigs-fasta", 0, 3, &o.unitigs_fasta}, {"tip-reads", 0, 1, &o.tip_reads}, {"tip-rounds", 0, 1, &o.tip_rounds}, {"gfa-clean", 0, 0, &o.gfa_clean},
         {"pop-bubbles", 0, 0, &o.pop_bubbles}, {"bubble-reads", 0, 1, &o.bubble_reads}, {"bubble-dist", 0, 1, &o.bubble_dist}, {"bubble-rounds", 0, 1, &o.bubble_rounds},
+        {"polish", 0, 0, &o.polish}, {"polish-min-depth", 0, 1, &o.polish_min_depth},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
         char* end = nullptr;
@@ -154,6 +162,7 @@ Options parse(int argc, char** argv) {
         if (sp->dst == &o.gfa_fuzz || sp->dst == &o.gfa_max_overhang || sp->dst == &o.gfa_min_overlap) o.gfa_param_given = true;
         if (sp->dst == &o.tip_reads || sp->dst == &o.tip_rounds) o.tip_param_given = true;
         if (sp->dst == &o.bubble_reads || sp->dst == &o.bubble_dist || sp->dst == &o.bubble_rounds) o.bubble_param_given = true;
+        if (sp->dst == &o.polish_min_depth) o.polish_param_given = true;
     }
     return o;
 }
@@ -218,6 +227,10 @@ int main(int argc, char** argv) {
     if (o.bubble_reads < 0 || o.bubble_reads > BELLA_MAX_BUBBLE_READS || o.bubble_dist < 0 || o.bubble_rounds < 0 || o.bubble_rounds > BELLA_MAX_BUBBLE_ROUNDS)
         die("--bubble-reads must be in [0, " + std::to_string(BELLA_MAX_BUBBLE_READS) + "], --bubble-dist must not be negative and --bubble-rounds must be in [0, " +
             std::to_string(BELLA_MAX_BUBBLE_ROUNDS) + "]");
+    if (o.polish_param_given && !o.polish) die("--polish-min-depth needs --polish");
+    if (o.polish && o.unitigs.empty() && o.unitigs_fasta.empty()) die("--polish needs --unitigs or --unitigs-fasta");
+    if (o.polish && o.gfa_no_seq && o.unitigs_fasta.empty()) die("--polish with --gfa-no-seq needs --unitigs-fasta (there is no sequence to polish into)");
+    if (o.polish && o.polish_min_depth < 1) die("--polish-min-depth must be at least 1");
     if (o.gfa_fuzz < 0 || o.gfa_max_overhang < 0 || o.gfa_min_overlap < 0) die("--gfa-fuzz, --gfa-max-overhang and --gfa-min-overlap must not be negative");
     if (!o.correct.empty() && o.skip_alignment) die("--correct cannot be combined with --skip-alignment (the pileup is made of base-level alignments)");
     if (o.min_depth_given && o.min_depth < 1) die("--min-depth must be at least 1");
@@ -369,6 +382,8 @@ int main(int argc, char** argv) {
     so.gfa_clean = o.gfa_clean ? 1 : 0;
     so.pop_bubbles = o.pop_bubbles ? 1 : 0;
     so.bubble_reads = (uint32_t)o.bubble_reads; so.bubble_dist = (uint32_t)o.bubble_dist; so.bubble_rounds = (uint32_t)o.bubble_rounds;
+    so.polish = o.polish ? 1 : 0;
+    so.polish_min_depth = (uint32_t)o.polish_min_depth;
     const double t_stages = now_s();
     run_stages(W, so, names.data(), lens.data());
     {

@@ -1,5 +1,5 @@
-"""numpy / plain-Python statement of tip clipping, unitig compaction and unitig sequences, on the reduced string
-graph of graph_mirror (section 11's notation: vertex 2 r + o, twin(v -> w) = (w ^ 1 -> v ^ 1), in-degree(v) = out-degree(v ^ 1)).
+"""numpy / plain-Python statement of tip clipping, unitig compaction and unitig sequences and of the unitig
+consensus (section 14), on the reduced string graph of graph_mirror (section 11's notation: vertex 2 r + o, twin(v -> w) = (w ^ 1 -> v ^ 1), in-degree(v) = out-degree(v ^ 1)).
 Written straight from the definition; everything is an integer, so the device result must EQUAL it."""
 from __future__ import annotations
 
@@ -228,6 +228,148 @@ def fasta_text(u, offsets, bases) -> bytes:
     return b"".join(b">%s\n%s\n" % (n.encode(), bytes(bases[int(offsets[k]):int(offsets[k + 1])])) for k, n in enumerate(unitig_names(u)))
 
 
+# ---- unitig consensus ----------------------------------------------------------------------------------------------
+POLISH_DT = np.dtype([("len_before", "<u8"), ("len_after", "<u8"), ("substituted", "<u8"), ("deleted", "<u8"), ("inserted", "<u8"), ("covered", "<u8"),
+                      ("depth_sum", "<u8")])
+_CODE = np.full(256, 255, np.uint8)
+for _i, _c in enumerate(b"ACGT"):
+    _CODE[_c] = _i
+_ASCII = np.frombuffer(b"ACGT", np.uint8)
+BRANCHES = ("depth0", "below", "at", "del_major", "del_tie", "ins_major", "ins_tie", "sub", "tie_own", "tie_other")
+
+
+def decisions(read: bytes, rows, min_depth: int = 3):
+    """Section 10's rule at every position p of one read, from ITS rows of the table ((len, 9)): dict of per-position arrays --
+    ins (bool: the junction before p emits), ins_base, keep (bool: the position emits), base (codes), sub / cov (bool), depth -- and
+    `branch`, which branches of the rule the rows took (BRANCHES -> count)."""
+    own = _CODE[np.frombuffer(bytes(read), np.uint8)].astype(np.int64)
+    n = len(own)
+    T = np.asarray(rows, np.int64).reshape(n, 9)
+    p = np.arange(n)
+    depth = T[:, 0:4].sum(1) + T[:, 4]
+    prev = np.concatenate([[0], depth[:-1]])
+    c = np.minimum(prev, depth)
+    I = T[:, 5:9].sum(1)
+    junction = (p >= 1) & (c >= min_depth)
+    ins = junction & (2 * I > c + 1)
+    ins_base = T[:, 5:9].argmax(1) if n else np.zeros(0, np.int64)               # the first maximum: ties go to the smallest code
+    cov = depth >= min_depth
+    dele = cov & (2 * T[:, 4] > depth + 1)
+    w = T[:, 0:4].copy()
+    w[p, own] += 1
+    mx = w.max(1) if n else np.zeros(0, np.int64)
+    own_max = w[p, own] == mx
+    call = np.where(own_max, own, w.argmax(1) if n else own)
+    base = np.where(cov, call, own)
+    voted = cov & ~dele
+    nmax = (w == mx[:, None]).sum(1) if n else np.zeros(0, np.int64)
+    branch = dict(depth0=int((depth == 0).sum()), below=int(((depth > 0) & ~cov).sum()), at=int((depth == min_depth).sum()), del_major=int(dele.sum()),
+                  del_tie=int((cov & (2 * T[:, 4] == depth + 1)).sum()), ins_major=int(ins.sum()), ins_tie=int((junction & (2 * I == c + 1)).sum()),
+                  sub=int((voted & (base != own)).sum()), tie_own=int((voted & (nmax > 1) & own_max).sum()), tie_other=int((voted & (nmax > 1) & ~own_max).sum()))
+    return dict(ins=ins, ins_base=ins_base, keep=~dele, base=base, sub=voted & (base != own), cov=cov, depth=depth, dele=dele, branch=branch)
+
+
+def polished(u, seqs, table, min_depth: int = 3):
+    """bella_hip_graph_polish_unitigs: -> dict(offsets uint64[n + 1], bases, pos uint64 / nbases uint32 per vertex in polished coordinates,
+    len uint64[n], stats of POLISH_DT per unitig).  table: (total bases, 9), the rows of all reads in read order.  Vertex i = 2 r + o
+    with n = nbases[i] contributes E(0) .. E(n - 1) for o = 0 and rc(E(L - 1)) .. rc(E(L - n)) for o = 1, E(p) = the decision string
+    at position p of read r: the junction's base if it fires, then the position's base unless it is deleted."""
+    lens = np.array([len(x) for x in seqs], np.int64)
+    roff = np.concatenate([[0], np.cumsum(lens)])
+    T = np.asarray(table).reshape(-1, 9)
+    assert len(T) == roff[-1] and min_depth >= 1
+    dec = {}
+    voff = u["voff"].astype(np.int64).tolist()
+    out, offs, pos, nb, stats = [], [0], [], [], np.zeros(len(u["len"]), POLISH_DT)
+    for k in range(len(u["len"])):
+        at = 0
+        for v, n in zip(u["verts"][voff[k]:voff[k + 1]].tolist(), u["nbases"][voff[k]:voff[k + 1]].tolist()):
+            r, L = v >> 1, int(lens[v >> 1])
+            if r not in dec:
+                dec[r] = decisions(seqs[r], T[roff[r]:roff[r + 1]], min_depth)
+            d = dec[r]
+            idx = np.arange(L - 1, L - 1 - n, -1) if v & 1 else np.arange(n)
+            slots, use = np.empty(2 * n, np.int64), np.empty(2 * n, bool)
+            if v & 1:                                                 # rc of a decision string: the position's base first, then the junction's
+                slots[0::2], slots[1::2] = 3 - d["base"][idx], 3 - d["ins_base"][idx]
+                use[0::2], use[1::2] = d["keep"][idx], d["ins"][idx]
+            else:
+                slots[0::2], slots[1::2] = d["ins_base"][idx], d["base"][idx]
+                use[0::2], use[1::2] = d["ins"][idx], d["keep"][idx]
+            seg = _ASCII[slots[use]].tobytes()
+            out.append(seg); pos.append(at); nb.append(len(seg))
+            at += len(seg)
+            st = stats[k]
+            st["substituted"] += int(d["sub"][idx].sum()); st["deleted"] += int(d["dele"][idx].sum()); st["inserted"] += int(d["ins"][idx].sum())
+            st["covered"] += int(d["cov"][idx].sum()); st["depth_sum"] += int(d["depth"][idx].sum())
+        stats[k]["len_before"], stats[k]["len_after"] = int(u["len"][k]), at
+        offs.append(offs[-1] + at)
+    return dict(offsets=np.array(offs, np.uint64), bases=b"".join(out), pos=np.array(pos, np.uint64), nbases=np.array(nb, np.uint32),
+                len=stats["len_after"].astype(np.uint64), stats=stats)
+
+
+def polished_unitigs(u, p):
+    """the unitig dict with its coordinates replaced by the polished ones: what unitig_gfa_text / fasta_text take with p's offsets and bases"""
+    q = dict(u)
+    q["pos"], q["nbases"], q["len"] = p["pos"], p["nbases"], p["len"]
+    return q
+
+
+def branch_counts(seqs, table, min_depth: int = 3):
+    """BRANCHES -> how many positions of the read set took that branch of the rule"""
+    lens = np.array([len(x) for x in seqs], np.int64)
+    roff = np.concatenate([[0], np.cumsum(lens)])
+    T = np.asarray(table).reshape(-1, 9)
+    tot = dict.fromkeys(BRANCHES, 0)
+    for r, s in enumerate(seqs):
+        for k, x in decisions(s, T[roff[r]:roff[r + 1]], min_depth)["branch"].items():
+            tot[k] += x
+    return tot
+
+
+def random_table(lens, seed, min_depth: int = 3):
+    """A seeded (total bases, 9) uint32 table whose rows are drawn so that every branch of the rule occurs at `min_depth`: depth 0, depth
+    below and exactly at min_depth, deletion majorities and exact ties (2 del == depth + 1), insertion majorities and ties, and small
+    base counts, where two equal maxima with and without the read's own base among them are common."""
+    rng = np.random.default_rng(seed)
+    n = int(np.sum(lens))
+    T = np.zeros((n, 9), np.int64)
+    kind = rng.integers(0, 10, n)
+    one_hot = lambda m: np.eye(4, dtype=np.int64)[rng.integers(0, 4, m)]
+    sel = lambda k: np.flatnonzero(kind == k)
+    i = sel(1); T[i, 0:4] = one_hot(len(i)) * rng.integers(1, max(min_depth, 2), len(i))[:, None]             # below min_depth (min_depth 1: none)
+    i = sel(2); T[i, 0:4] = one_hot(len(i)) * min_depth                                                        # exactly at it
+    i = sel(3); T[i, 0:4] = rng.integers(0, 3, (len(i), 4)); T[i, 4] = T[i, 0:4].sum(1) + rng.integers(2, 9, len(i)) + min_depth      # deletion majority
+    i = sel(4); T[i, 0:4] = rng.integers(0, 3, (len(i), 4)) + one_hot(len(i)) * min_depth; T[i, 4] = T[i, 0:4].sum(1) + 1             # 2 del == depth + 1
+    i = sel(5); T[i, 0:4] = rng.integers(0, 4, (len(i), 4)); T[i, 4] = rng.integers(0, 2, len(i))                                     # small counts: ties
+    i = sel(6); T[i, 0:4] = one_hot(len(i)) * rng.integers(min_depth, min_depth + 30, len(i))[:, None] + rng.integers(0, 3, (len(i), 4))   # one clear base
+    i = np.flatnonzero(kind >= 7); T[i, 0:4] = rng.integers(0, 20, (len(i), 4)); T[i, 4] = rng.integers(0, 12, len(i))                # anything
+    i = np.flatnonzero(rng.integers(0, 8, n) == 0); T[i, 0:5] *= 10                                                                  # some deep rows
+    depth = T[:, 0:5].sum(1)
+    c = np.minimum(np.concatenate([[0], depth[:-1]]), depth)                          # (a read's first row has no junction: its counters are just data)
+    how = rng.integers(0, 4, n)                                                      # 0: none, 1: an exact tie where c is odd, 2: one over it, 3: anything
+    I = np.select([how == 1, how == 2, how == 3], [(c + 1) // 2, (c + 1) // 2 + 1, rng.integers(0, 25, n)], 0)
+    first = rng.integers(0, I + 1)                                                   # split I over two bases: equal ins maxima occur
+    a, b = rng.integers(0, 4, n), rng.integers(0, 4, n)
+    np.add.at(T, (np.arange(n), 5 + a), first)
+    np.add.at(T, (np.arange(n), 5 + b), I - first)
+    return T.astype(np.uint32)
+
+
+def window_distance(window: bytes, template: bytes) -> int:
+    """Levenshtein distance (unit costs) of `window` to the best PREFIX of `template`: the window is consumed whole, the template's end
+    is free -- the minimum of the last row of pileup_mirror.edit_distance's table."""
+    x, y = np.frombuffer(window, np.uint8), np.frombuffer(template, np.uint8)
+    idx = np.arange(len(y) + 1, dtype=np.int64)
+    prev = idx.copy()
+    for i in range(1, len(x) + 1):
+        cand = np.empty(len(y) + 1, np.int64)
+        cand[0] = i
+        np.minimum(prev[:-1] + (y != x[i - 1]), prev[1:] + 1, out=cand[1:])
+        prev = np.minimum.accumulate(cand - idx) + idx
+    return int(prev.min())
+
+
 # ---- inputs of the tests ----------------------------------------------------------------------------------------------------------------
 def tip_input():
     """40 reads of 10 kb every 2,000 bases on a line (random strands, seed 3) plus two reads at 41,000 and 42,500; the records between
@@ -288,3 +430,41 @@ def circle_input(nreads=60, read_len=10000, step=2000, seed=5, fan=4):
             out.append((v, h, cv[0], cv[1], ch[0], ch[1], read_len - sh, int(strands[v] ^ strands[h]), (0, 0, 0)))
     recs = np.array(out, G.OVL_DT)
     return genome, seqs, strands, recs[np.lexsort((recs["rid"], recs["cid"]))]
+
+
+def short_segment_input(n=400, seed=17):
+    """reads of 40 to 70 bases every 1 to 20 bases on a line, mixed strands, exact records: segments of 1 to 20 bases
+    -> (starts, lens, strands, recs); built with min_overlap = 0, fuzz = 0 and no clipping it is one unitig"""
+    rng = np.random.default_rng(seed)
+    starts = np.cumsum(rng.integers(1, 21, n))
+    lens = rng.integers(40, 71, n)
+    strands = rng.integers(0, 2, n)
+    return starts, lens, strands, G.truth_records(starts, lens, strands, min_overlap=1)
+
+
+def polish_cases():
+    """the layouts the polish tests share: -> [(name, seqs, recs, graph parameters, clean parameters)] -- the tip input (one unitig of
+    88,000 bases; unclipped with max_tip_reads = 1 it is three unitigs), the circle, the two-round input and the short segments"""
+    def cut(starts, lens, strands, seed):
+        genome = random_genome(int((np.asarray(starts) + np.asarray(lens)).max()), seed)
+        return reads_from_genome(genome, starts, lens, strands)
+    out = []
+    starts, lens, strands, recs = tip_input()
+    seqs = cut(starts, lens, strands, 33)
+    out.append(("tip", seqs, recs, {}, {}))
+    out.append(("tip3", seqs, recs, {}, dict(max_tip_reads=1)))
+    _, seqs, _, recs = circle_input()
+    out.append(("circle", seqs, recs, {}, {}))
+    lens, recs = two_round_input()
+    out.append(("two_round", [random_genome(int(n), 40 + i) for i, n in enumerate(lens)], recs, {}, {}))
+    starts, lens, strands, recs = short_segment_input()
+    out.append(("short", cut(starts, lens, strands, 34), recs, dict(min_overlap=0, fuzz=0), dict(max_tip_reads=0)))
+    return out
+
+
+def case_unitigs(seqs, recs, graph, clean_params):
+    """graph_mirror.build -> clean -> unitigs of one polish case: -> (graph, cleaned, unitigs)"""
+    lens = np.array([len(x) for x in seqs], np.int64)
+    m = G.build(recs, lens, **graph)
+    c = clean(m["offsets"], m["edges"], m["contained"], **clean_params)
+    return m, c, unitigs(c["offsets"], c["edges"], m["contained"], c["removed"], lens)

@@ -611,6 +611,46 @@ typedef struct {
 int bella_hip_graph_pop_bubbles(bella_ctx* ctx, const bella_graph_bubble_params* params);
 int bella_hip_graph_get_bubble_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 
+/* ---- unitig consensus: the pileup's majority vote per position of the backbone reads (no counterpart in the
+ * reference) -----------------------------------------------------------------------------------------------------------------------
+ * Needs the unitigs of bella_hip_graph_unitigs and the pileup table of the read-correction section, both on this context.  The DECISION
+ * at position p of read r is the string E_r(p) of 0, 1 or 2 bases that bella_hip_consensus's rule emits for p: the junction's base of
+ * step (1) if it fires (p >= 1 only), then the position's base of step (2) unless it is deleted; E_r(0) .. E_r(len - 1) is the read's
+ * bella_hip_consensus output.  Vertex i of a unitig (v = 2 r + o, n = nbases[i], L = the read's length) contributes
+ *   o == 0: E(0) E(1) .. E(n - 1);      o == 1: rc(E(L - 1)) rc(E(L - 2)) .. rc(E(L - n)), rc = the reverse complement of a decision string,
+ * and the polished unitig is the concatenation of its vertices' segments, circular unitigs alike.  A segment takes the decisions of its
+ * own positions and nothing else (the junction in front of the first position behind a forward segment is not part of it: an edge effect
+ * of at most one base per segment).  With an all-zero table the result is the raw unitigs.  Limits as in the read correction: one
+ * inserted base per junction, plain majority; the segment boundaries stay where the raw unitig has them; the links keep their raw
+ * overlaps; there is no second round and no re-alignment of reads to the unitig. */
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_polish_params) of the caller's header (the struct may grow)               */
+    uint32_t min_depth;           /* >= 1; the documented default is 3                                                     */
+} bella_polish_params;
+typedef struct {                  /* bella_consensus_read's fields, summed over the unitig's positions                     */
+    uint64_t len_before, len_after;
+    uint64_t substituted, deleted, inserted, covered, depth_sum;
+} bella_polish_unitig;
+/* What the last bella_hip_graph_polish_unitigs did.  A sized struct: bella_hip_graph_get_polish_stats writes at most struct_size bytes. */
+typedef struct {
+    uint64_t unitigs, vertices;
+    uint64_t bases_before, bases_after;
+    uint64_t substituted, deleted, inserted, covered, depth_sum;
+    uint64_t table_bytes;         /* bytes of table rows the decision read: 36 per unitig position                          */
+    uint32_t min_depth, tiles;    /* tiles of 4,096 unitig positions                                                       */
+    double decide_ms, write_ms;   /* one event pair around the one launch each: device time                                */
+} bella_polish_stats;
+/* Polishes the unitigs of the last bella_hip_graph_unitigs with the context's pileup table, on the device; the result stays with the
+ * context until the unitigs are dropped, the table changes (bella_hip_pileup_reset, bella_hip_add_pileup, a trace that votes) or reads
+ * are loaded.  BELLA_ERR_STATE without unitigs or without a table; BELLA_ERR_BAD_ARG for min_depth < 1 or a struct_size too small.  Zero
+ * unitigs launch nothing and give empty results.  total_bases may be NULL. */
+int bella_hip_graph_polish_unitigs(bella_ctx* ctx, const bella_polish_params* params, uint64_t* total_bases);
+/* offsets[nunitigs + 1] into bases[total_bases] (upper-case ASCII); ppos[nvertices] / pnbases[nvertices]: where every vertex's segment
+ * starts inside its polished unitig and how long it is; per_unitig[nunitigs].  Any pointer may be NULL.  bella_hip_write_unitig_gfa takes
+ * them in place of pos / nbases / len / base_offsets / bases. */
+int bella_hip_graph_get_polished(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases, uint64_t* ppos, uint32_t* pnbases, bella_polish_unitig* per_unitig);
+int bella_hip_graph_get_polish_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+
 /* ---- multi-GPU: one context per GPU, RCCL over xGMI ------------------------------------------------
  * The reference's multi-GPU path hands alignment batches to the devices inside one call (loganGPU/functions.cuh:441-443,
  * 498-637; include/align.hpp:226-229) and has no collective.  Here reads are 1D row-block partitioned: context r assembles the

@@ -2,12 +2,13 @@
 writes profiles/unitig_probe.json.
 
 For every set (default: 2,000 x 10 kb and the bench set of 10k reads, both at 15 % error): count, assemble, overlap, align, one trace
-with the runs dropped, graph_add_traced, graph_build, graph_clean, graph_unitigs, all with the defaults.  Reported per set: reads removed
+that votes into the pileup table (the runs are not staged), graph_add_traced, graph_build, graph_clean, graph_unitigs, all with the defaults.  Reported per set: reads removed
 per round, unitigs, largest unitig, N50 and their total length against the genome's, the clean, rank and gather timers (the first two
 span the host's read-backs: bella_unitig_stats in include/bella_hip.h) next to the build's classify + sort + reduce of the same run,
 and the gather's bytes over its time (one byte written per base, a quarter byte read).  Then the same with graph_pop_bubbles between the
 clean and the unitigs: sources / found / popped / reads removed per round, pop_ms, and unitigs, largest and N50
-with the stage next to those without it."""
+with the stage next to those without it.  Last, the unitig consensus of those unitigs: decide_ms and write_ms (one
+launch each), the table bytes the decision read over its time, and the unitigs' total length raw and polished against the genome span."""
 import argparse
 import json
 import os
@@ -32,7 +33,8 @@ def probe(nreads, seed, repeats, fast):
     pars = BellaPars()
     eng.overlap(pars)
     eng.align_pairs(pars)
-    eng.trace_pairs_records(pars)
+    eng.pileup_reset()
+    eng.trace_pairs(pars, pileup=True, keep_ops=False)
     eng.graph_reset()
     eng.graph_add_traced()
     runs = []
@@ -47,9 +49,11 @@ def probe(nreads, seed, repeats, fast):
         eng.graph_pop_bubbles()
         bs = eng.bubble_stats()
         eng.graph_unitigs()
-        runs.append((gs, us, bs, eng.unitig_stats()))
-    gs, us, _, _ = min(runs, key=lambda r: r[1]["rank_ms"] + r[1]["gather_ms"])
-    _, _, bs, ps = min(runs, key=lambda r: r[2]["pop_ms"])
+        eng.graph_polish_unitigs()
+        runs.append((gs, us, bs, eng.unitig_stats(), eng.polish_stats()))
+    gs, us, _, _, _ = min(runs, key=lambda r: r[1]["rank_ms"] + r[1]["gather_ms"])
+    _, _, bs, ps, _ = min(runs, key=lambda r: r[2]["pop_ms"])
+    pol = min((r[4] for r in runs), key=lambda q: q["decide_ms"] + q["write_ms"])
     build_ms = gs["classify_ms"] + gs["sort_ms"] + gs["reduce_ms"]
     out = dict(reads=nreads, bases=int(rs.offsets[-1]), genome_span=int(span), edges_final=int(gs["edges_final"]), contained_reads=int(gs["contained_reads"]),
                tips_per_round=us["tips_per_round"], reads_per_round=us["reads_per_round"], reads_removed=int(us["reads_removed"]), edges_removed=int(us["edges_removed"]),
@@ -62,6 +66,13 @@ def probe(nreads, seed, repeats, fast):
                       edges_per_round=bs["edges_per_round"], reads_removed=int(bs["reads_removed"]), edges_removed=int(bs["edges_removed"]), pop_ms=bs["pop_ms"],
                       pop_over_build=bs["pop_ms"] / max(1e-9, build_ms), unitigs=int(ps["unitigs"]), largest=int(ps["largest"]), n50=int(ps["n50"]),
                       total_bases=int(ps["total_bases"]), unitigs_without=int(us["unitigs"]), largest_without=int(us["largest"]), n50_without=int(us["n50"]))
+    out["polish"] = dict(min_depth=int(pol["min_depth"]), unitigs=int(pol["unitigs"]), vertices=int(pol["vertices"]), tiles=int(pol["tiles"]),
+                         bases_before=int(pol["bases_before"]), bases_after=int(pol["bases_after"]), before_over_span=pol["bases_before"] / max(1, span),
+                         after_over_span=pol["bases_after"] / max(1, span), substituted=int(pol["substituted"]), deleted=int(pol["deleted"]),
+                         inserted=int(pol["inserted"]), covered=int(pol["covered"]), decide_ms=pol["decide_ms"], write_ms=pol["write_ms"],
+                         gather_ms=ps["gather_ms"], table_bytes=int(pol["table_bytes"]),
+                         decide_gb_per_s=(pol["table_bytes"] + pol["bases_before"]) / max(1e-9, pol["decide_ms"] * 1e6),
+                         write_gb_per_s=(pol["bases_before"] + pol["bases_after"]) / max(1e-9, pol["write_ms"] * 1e6))
     eng.close()
     return out
 

@@ -360,6 +360,18 @@ void release(Buf& b) {
     b.cap = 0;
 }
 
+// A function's own device buffer: a Buf that is released when its scope ends, on every way out.  reset() gives it up earlier (where peak
+// memory or what the pool holds afterwards depends on the point); give_to() hands the allocation to a Buf the context owns.
+struct TmpBuf : Buf {
+    TmpBuf() = default;
+    TmpBuf(const TmpBuf&) = delete;
+    TmpBuf& operator=(const TmpBuf&) = delete;
+    ~TmpBuf() { release(*this); }
+    void reset() { release(*this); }
+    void swap(TmpBuf& o) { std::swap<Buf>(*this, o); }
+    void give_to(Buf& dst) { release(dst); dst = *this; p = nullptr; cap = 0; }
+};
+
 template <class T>
 T* ptr(const Buf& b) { return (T*)b.p; }
 
@@ -382,20 +394,39 @@ int status_to_error(bella_ctx* c, uint32_t st) {
     return 0;
 }
 
+// hipCUB's two-phase call, written once: `fn(tmp, bytes)` is asked for its size with tmp == nullptr, the context's scratch grows to
+// that (plus `slack`), and the call runs.  CUB(c, function, its arguments after the first two) returns from the caller on failure, like HIPCHK.
+template <class Fn>
+int cub_call(bella_ctx* c, const char* what, int line, Fn&& fn, size_t slack = 0) {
+    size_t tb = 0;
+    hipError_t e = fn(nullptr, tb);
+    if (e == hipSuccess) {
+        ENSURE(c, c->cubtmp, tb + slack);
+        e = fn(c->cubtmp.p, tb);
+    }
+    if (e != hipSuccess) return fail(c, BELLA_ERR_HIP, "%s failed: %s (%s:%d)", what, hipGetErrorString(e), __FILE__, line);
+    return 0;
+}
+#define CUB_SLACK(c, slack, fn, ...)                                                                                         \
+    do {                                                                                                                     \
+        int r_ = cub_call(c, #fn, __LINE__, [&](void* t_, size_t& n_) { return fn(t_, n_, __VA_ARGS__); }, slack);           \
+        if (r_) return r_;                                                                                                   \
+    } while (0)
+#define CUB(c, fn, ...) CUB_SLACK(c, 0, fn, __VA_ARGS__)
+
 // exclusive scans (rocPRIM through hipCUB: plumbing, not a hot op)
 int scan_u32(bella_ctx* c, const uint32_t* in, uint32_t* out, uint64_t n) {
-    size_t tb = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, c->stream));
-    ENSURE(c, c->cubtmp, tb);
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, in, out, (int)n, c->stream));
+    CUB(c, hipcub::DeviceScan::ExclusiveSum, in, out, (int)n, c->stream);
     return 0;
 }
 int scan_u32_to_u64(bella_ctx* c, const uint32_t* in, uint64_t* out, uint64_t n) {
     hipcub::TransformInputIterator<uint64_t, CastU64, const uint32_t*> it(in, CastU64());
-    size_t tb = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, out, (int)n, c->stream));
-    ENSURE(c, c->cubtmp, tb);
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, out, (int)n, c->stream));
+    CUB(c, hipcub::DeviceScan::ExclusiveSum, it, out, (int)n, c->stream);
+    return 0;
+}
+int scan_u8_to_u32(bella_ctx* c, const uint8_t* in, uint32_t* out, uint64_t n) {
+    hipcub::TransformInputIterator<uint32_t, CastU8, const uint8_t*> it(in, CastU8());
+    CUB(c, hipcub::DeviceScan::ExclusiveSum, it, out, (int)n, c->stream);
     return 0;
 }
 
@@ -404,6 +435,51 @@ float ev_ms(hipEvent_t a, hipEvent_t b) {
     (void)hipEventElapsedTime(&ms, a, b);
     return ms;
 }
+
+// a function's own timing events: create(n) makes the first n of a, b, d, e; all of them go with the scope
+struct EventSet {
+    hipEvent_t a = nullptr, b = nullptr, d = nullptr, e = nullptr;
+    ~EventSet() { for (hipEvent_t x : {a, b, d, e}) if (x) (void)hipEventDestroy(x); }
+    int create(bella_ctx* c, int n) {
+        hipEvent_t* const all[4] = {&a, &b, &d, &e};
+        for (int i = 0; i < n; ++i) HIPCHK(c, hipEventCreate(all[i]));
+        return 0;
+    }
+};
+
+// The ABI's sized structs: struct_size in, at most struct_size bytes out.  take_params: the caller's struct over `p` (which holds the
+// defaults) when there is one -- longer than this library's is fine, shorter is refused; put_sized: a result struct, cut to the caller's size.
+template <class P>
+int take_params(bella_ctx* c, P& p, const P* given, const char* name) {
+    if (!given) return 0;
+    if (given->struct_size < sizeof(P)) return fail(c, BELLA_ERR_BAD_ARG, "%s: struct_size %u is too small", name, given->struct_size);
+    p = *given;
+    return 0;
+}
+template <class S>
+int put_sized(void* out, uint64_t struct_size, const S& s) {
+    std::memcpy(out, &s, (size_t)std::min<uint64_t>(struct_size, sizeof(S)));
+    return 0;
+}
+
+// A text file one of the writers fills: opened with a 4 MB buffer; close(ok) is the writer's result -- `ok` and the close itself.  Both
+// ways to fail are reported on stderr under the writer's name.
+struct TextFile {
+    const char *who, *path;
+    FILE* f;
+    std::vector<char> buf;
+    TextFile(const char* who_, const char* path_, const char* mode) : who(who_), path(path_), f(std::fopen(path_, mode)), buf((size_t)4 << 20) {
+        if (f) std::setvbuf(f, buf.data(), _IOFBF, buf.size());
+        else fprintf(stderr, "%s: cannot open %s\n", who, path);
+    }
+    ~TextFile() { if (f) (void)std::fclose(f); }
+    int close(bool ok) {
+        if (std::fclose(f) != 0) ok = false;
+        f = nullptr;
+        if (!ok) { fprintf(stderr, "%s: writing %s failed\n", who, path); return BELLA_ERR_BAD_ARG; }
+        return 0;
+    }
+};
 
 // the row pointers the passes index B' with: the rows of the context's own columns (build_layout; the other rows are empty)
 inline const uint32_t* layout_bptr(const bella_ctx* c) { return ptr<uint32_t>(c->Bloc); }
@@ -523,10 +599,7 @@ int build_layout(bella_ctx* c, bool collective = false) {
         if (rc0) return rc0;
         hipcub::DoubleBuffer<uint32_t> dk(ptr<uint32_t>(c->lk_key), ptr<uint32_t>(c->lk_key2));
         hipcub::DoubleBuffer<uint64_t> dv(ptr<uint64_t>(c->lk_val), ptr<uint64_t>(c->lk_val2));
-        size_t tb = 0;
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, (uint64_t)nnz, 0, kbits, c->stream));
-        ENSURE(c, c->cubtmp, tb);
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, tb, dk, dv, (uint64_t)nnz, 0, kbits, c->stream));
+        CUB(c, hipcub::DeviceRadixSort::SortPairs, dk, dv, (uint64_t)nnz, 0, kbits, c->stream);
         skey = dk.Current();
         sval = dv.Current();
         if (!by_kmer) {
@@ -559,12 +632,7 @@ int build_layout(bella_ctx* c, bool collective = false) {
             while (ebits < 32 && (1ull << ebits) < nown_nnz) ++ebits;
             hipcub::DoubleBuffer<uint32_t> ek(ekey, const_cast<uint32_t*>(skey));
             hipcub::DoubleBuffer<uint64_t> ev(eval, const_cast<uint64_t*>(sval));
-            if (ebits > 12) {
-                size_t tb2 = 0;
-                HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, ek, ev, (uint64_t)nown_nnz, ebits - 8, ebits, c->stream));
-                ENSURE(c, c->cubtmp, tb2);
-                HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, tb2, ek, ev, (uint64_t)nown_nnz, ebits - 8, ebits, c->stream));
-            }
+            if (ebits > 12) CUB(c, hipcub::DeviceRadixSort::SortPairs, ek, ev, (uint64_t)nown_nnz, ebits - 8, ebits, c->stream);
             k_layout_place<<<((nblk(nown_nnz) + 7u) / 8u) * 8u, 256, 0, c->stream>>>(ek.Current(), ev.Current(), nown_nnz, ptr<uint2>(c->Bent));
             KCHK(c);
         }
@@ -588,15 +656,13 @@ int build_layout(bella_ctx* c, bool collective = false) {
                 uint32_t live = 0;
                 HIPCHK(c, hipMemcpyAsync(&live, bnew + c->nreads, 4, hipMemcpyDeviceToHost, c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->stream));
-                Buf out;
-                rc = ensure_bytes(c, out, 8 * (size_t)live);
-                if (rc) return rc;
+                TmpBuf out;
+                ENSURE(c, out, 8 * (size_t)live);
                 k_layout_compact<<<nblk(c->nreads, kWaves), kBlock, 0, c->stream>>>(Bloc, bnew, ptr<uint2>(c->Bent), c->nreads, inl, ptr<uint2>(out));
-                if (hipGetLastError() != hipSuccess) { release(out); return fail(c, BELLA_ERR_HIP, "k_layout_compact failed to launch"); }
+                if (hipGetLastError() != hipSuccess) return fail(c, BELLA_ERR_HIP, "k_layout_compact failed to launch");
                 HIPCHK(c, hipMemcpyAsync(c->Bloc.p, bnew, 4 * ((size_t)c->nreads + 1), hipMemcpyDeviceToDevice, c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->stream));
-                std::swap(c->Bent, out);
-                release(out);
+                out.give_to(c->Bent);                              // (the uncompacted B' goes here, not at the end of the call)
                 c->live_nnz = live;
             }
         }
@@ -936,23 +1002,21 @@ static int set_reads_impl(bella_ctx* c, const uint64_t* offsets, uint32_t nreads
     const uint64_t nwords = (total + 15) / 16;
     ENSURE(c, c->packed, 4 * (nwords + 16));
     ENSURE(c, c->roff, 8 * ((size_t)nreads + 1));
-    Buf raw;
-    int rc = ensure_bytes(c, raw, total);
-    if (rc) return rc;
-    hipError_t e = total ? c->stager.h2d_fill(raw.p, total, c->stream, fill) : hipSuccess;
-    if (e == hipSuccess) e = hipMemcpyAsync(c->roff.p, offsets, 8 * ((size_t)nreads + 1), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->packed.p, 0, 4 * (nwords + 16), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->status.p, 0, 4, c->stream);
-    if (e == hipSuccess && nwords) {
+    TmpBuf raw;
+    ENSURE(c, raw, total);
+    if (total) HIPCHK(c, c->stager.h2d_fill(raw.p, total, c->stream, fill));
+    HIPCHK(c, hipMemcpyAsync(c->roff.p, offsets, 8 * ((size_t)nreads + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->packed.p, 0, 4 * (nwords + 16), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->status.p, 0, 4, c->stream));
+    if (nwords) {
         k_pack_reads<<<nblk(nwords), 256, 0, c->stream>>>(ptr<uint8_t>(raw), total, ptr<uint32_t>(c->packed), nwords,
                                                           ptr<uint32_t>(c->status));
-        e = hipGetLastError();
+        KCHK(c);
     }
     uint32_t st = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&st, c->status.p, 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release(raw);
-    if (e != hipSuccess) return fail(c, BELLA_ERR_HIP, "set_reads: %s", hipGetErrorString(e));
+    int rc = read_status(c, &st);
+    if (rc) return rc;
+    raw.reset();
     rc = status_to_error(c, st);
     if (rc) return rc;
     c->nreads = nreads;
@@ -1247,13 +1311,11 @@ int bella_hip_assemble_tuples(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers,
 // ---- k-mer counting, dictionary, tuples (kcount.hpp) ----------------------------------------------------------------------
 static int grow_keep(bella_ctx* c, Buf& b, size_t need, size_t used) {
     if (b.cap >= need) return 0;
-    Buf nb;
-    int rc = ensure_bytes(c, nb, need + need / 4);
-    if (rc) return rc;
+    TmpBuf nb;
+    ENSURE(c, nb, need + need / 4);
     if (used) HIPCHK(c, hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    release(b);
-    b = nb;
+    nb.give_to(b);
     return 0;
 }
 
@@ -1396,13 +1458,10 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
         KCHK(c);
         mark("alloc + emit codes");
         hipcub::DoubleBuffer<uint64_t> db(ptr<uint64_t>(c->kc_keys), ptr<uint64_t>(c->kc_alt));
-        size_t tb = 0;
         // (with the positions in the keys the run kernels handle groups of four neighbouring words: the sort may leave out the word's
         // two lowest bits, and does when that saves it a pass of eight bits -- 32 instead of 34 bits for k = 17)
         const uint32_t gb = fast && 2 * k >= 10 && (2 * k + 7) / 8 > (2 * k - 2 + 7) / 8 ? 2u : 0u;
-        HIPCHK(c, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, db, (int)np, (int)(pb + gb), (int)pb + 2 * (int)k, c->stream));
-        ENSURE(c, c->cubtmp, tb);
-        HIPCHK(c, hipcub::DeviceRadixSort::SortKeys(c->cubtmp.p, tb, db, (int)np, (int)(pb + gb), (int)pb + 2 * (int)k, c->stream));
+        CUB(c, hipcub::DeviceRadixSort::SortKeys, db, (int)np, (int)(pb + gb), (int)pb + 2 * (int)k, c->stream);
         uint64_t* sorted = db.Current();
         mark("sort");
         if (fast) {
@@ -1424,10 +1483,7 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
             if (rc) return rc;
             {
                 hipcub::TransformInputIterator<uint64_t, CastU64, const uint32_t*> hit(tile_heads, CastU64());
-                size_t tb4 = 0;
-                HIPCHK(c, hipcub::DeviceReduce::Sum(nullptr, tb4, hit, ptr<uint64_t>(c->kc_cursor), (int)ntile, c->stream));
-                ENSURE(c, c->cubtmp, tb4);
-                HIPCHK(c, hipcub::DeviceReduce::Sum(c->cubtmp.p, tb4, hit, ptr<uint64_t>(c->kc_cursor), (int)ntile, c->stream));
+                CUB(c, hipcub::DeviceReduce::Sum, hit, ptr<uint64_t>(c->kc_cursor), (int)ntile, c->stream);
             }
             uint32_t nrel = 0, nwords = 0;
             uint64_t nruns = 0;
@@ -1469,12 +1525,7 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
             continue;
         }
         uint64_t* run_code = sorted == ptr<uint64_t>(c->kc_keys) ? ptr<uint64_t>(c->kc_alt) : ptr<uint64_t>(c->kc_keys);
-        size_t tb2 = 0;
-        HIPCHK(c, hipcub::DeviceRunLengthEncode::Encode(nullptr, tb2, sorted, run_code, ptr<uint32_t>(c->kc_runlen),
-                                                       ptr<uint32_t>(c->kc_nruns), (int)np, c->stream));
-        ENSURE(c, c->cubtmp, tb2);
-        HIPCHK(c, hipcub::DeviceRunLengthEncode::Encode(c->cubtmp.p, tb2, sorted, run_code, ptr<uint32_t>(c->kc_runlen),
-                                                       ptr<uint32_t>(c->kc_nruns), (int)np, c->stream));
+        CUB(c, hipcub::DeviceRunLengthEncode::Encode, sorted, run_code, ptr<uint32_t>(c->kc_runlen), ptr<uint32_t>(c->kc_nruns), (int)np, c->stream);
         uint32_t nruns = 0;
         HIPCHK(c, hipMemcpyAsync(&nruns, c->kc_nruns.p, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1516,12 +1567,12 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
         std::vector<uint64_t> off((size_t)NR + 1, 0);
         uint64_t nd_all = 0;
         for (int r = 0; r < NR; ++r) { off[r + 1] = off[r] + meta[4 * r]; nd_all += meta[4 * r + 1]; }
-        Buf ncode, ncount;
+        TmpBuf ncode, ncount;
         int r2 = off[NR] >= 0xFFFFFFF0ull ? fail(c, BELLA_ERR_BAD_ARG, "more than 2^32 reliable k-mers") : 0;
         if (!r2) r2 = ensure_bytes(c, ncode, 8 * off[NR]);
         if (!r2) r2 = ensure_bytes(c, ncount, 2 * off[NR] + 16);
         r2 = comm_agree(c, r2);                                    // all ranks hold their receive buffers, or all leave
-        if (r2) { release(ncode); release(ncount); return r2; }
+        if (r2) return r2;
         hipError_t he = hipSuccess;
         if (nk_total) {
             he = hipMemcpyAsync(ptr<uint64_t>(ncode) + off[me], c->kc_dcode.p, 8 * nk_total, hipMemcpyDeviceToDevice, c->stream);
@@ -1544,13 +1595,10 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
             const ncclResult_t ge = c->api->GroupEnd();
             if (nr2 == ncclSuccess) nr2 = ge;
         }
-        if (he == hipSuccess && nr2 == ncclSuccess) { const int sr = comm_sync(c, "dictionary exchange"); if (sr) { release(ncode); release(ncount); return sr; } }
-        if (nr2 != ncclSuccess || he != hipSuccess) {
-            release(ncode); release(ncount);
+        if (he == hipSuccess && nr2 == ncclSuccess) { const int sr = comm_sync(c, "dictionary exchange"); if (sr) return sr; }
+        if (nr2 != ncclSuccess || he != hipSuccess)
             return fail(c, BELLA_ERR_HIP, "dictionary exchange failed: %s", nr2 != ncclSuccess ? (c->api->GetErrorString ? c->api->GetErrorString(nr2) : "RCCL error") : hipGetErrorString(he));
-        }
-        release(c->kc_dcode); release(c->kc_dcount);
-        c->kc_dcode = ncode; c->kc_dcount = ncount;
+        ncode.give_to(c->kc_dcode); ncount.give_to(c->kc_dcount);
         nk_total = off[NR];
         ndistinct = nd_all;
     }
@@ -1569,10 +1617,7 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
             }
             hipcub::DoubleBuffer<uint32_t> dk(occ_pos, occ_pos2);
             hipcub::DoubleBuffer<uint32_t> dv(occ_id, occ_id2);
-            size_t tb = 0;
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, (uint64_t)nocc, 0, (int)pb, c->stream));
-            ENSURE(c, c->cubtmp, tb);
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, tb, dk, dv, (uint64_t)nocc, 0, (int)pb, c->stream));
+            CUB(c, hipcub::DeviceRadixSort::SortPairs, dk, dv, (uint64_t)nocc, 0, (int)pb, c->stream);
             spos = dk.Current();
             sid = dv.Current();
             mark("sort occurrences");
@@ -1849,23 +1894,20 @@ int bella_hip_set_B_device(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, co
     c->have_matrix = c->have_pairs = c->have_alns = false;
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     // the sources may alias our own panel buffers: stage through fresh allocations
-    Buf nBptr, nBk, nBpos;
-    int rc = ensure_bytes(c, nBptr, 4 * ((size_t)c->nreads + 2));
-    if (!rc) rc = ensure_bytes(c, nBk, 4 * nnz);
-    if (!rc) rc = ensure_bytes(c, nBpos, 2 * nnz);
-    if (rc) { release(nBptr); release(nBk); release(nBpos); return rc; }
-    hipError_t e = hipMemcpyAsync(nBptr.p, d_colptr, 4 * ((size_t)c->nreads + 1), hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(nBk.p, d_rowids, 4 * nnz, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(nBpos.p, d_values, 2 * nnz, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { release(nBptr); release(nBk); release(nBpos); return fail(c, BELLA_ERR_HIP, "set_B_device: %s", hipGetErrorString(e)); }
-    release(c->Bptr); release(c->Bk); release(c->Bpos);
-    c->Bptr = nBptr; c->Bk = nBk; c->Bpos = nBpos;
+    TmpBuf nBptr, nBk, nBpos;
+    ENSURE(c, nBptr, 4 * ((size_t)c->nreads + 2));
+    ENSURE(c, nBk, 4 * nnz);
+    ENSURE(c, nBpos, 2 * nnz);
+    HIPCHK(c, hipMemcpyAsync(nBptr.p, d_colptr, 4 * ((size_t)c->nreads + 1), hipMemcpyDeviceToDevice, c->stream));
+    if (nnz) HIPCHK(c, hipMemcpyAsync(nBk.p, d_rowids, 4 * nnz, hipMemcpyDeviceToDevice, c->stream));
+    if (nnz) HIPCHK(c, hipMemcpyAsync(nBpos.p, d_values, 2 * nnz, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    nBptr.give_to(c->Bptr); nBk.give_to(c->Bk); nBpos.give_to(c->Bpos);
     c->have_panel = false;
     c->nkmers = nkmers;
     c->nnz = nnz;
     c->kmer_size = kmer_size;
-    rc = build_layout(c);
+    int rc = build_layout(c);
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     HIPCHK(c, hipEventSynchronize(c->ev[1]));
@@ -2027,8 +2069,7 @@ int layout_dist(bella_ctx* c, uint64_t nown_nnz, uint32_t rmask, uint32_t inl, i
     const uint32_t klo = (uint32_t)((uint64_t)nk * (uint64_t)me / (uint64_t)N), khi = (uint32_t)((uint64_t)nk * (uint64_t)(me + 1) / (uint64_t)N);
     const uint32_t M = (nr + (uint32_t)N - 1) / (uint32_t)N;      // rows per owner, at most
     const size_t W = (size_t)N + 3;                               // words of a rank's line of the metadata exchange
-    Buf pbuf, sbuf, hbuf;                                         // owner-major row lengths + their scan; per-owner counters and cursors
-    auto done = [&](int rc) { release(pbuf); release(sbuf); release(hbuf); return rc; };
+    TmpBuf pbuf, sbuf, hbuf;                                      // owner-major row lengths + their scan; per-owner counters and cursors
     // (1) this rank's entries: per row how many, where they go, how many for the rows of each rank.  Host synchronisations of the
     // whole formation: this read-back, the metadata exchange, the end of the data exchange, the closing agreement.
     int rc = ensure_bytes(c, pbuf, 4 * ((size_t)N * M + 2));
@@ -2066,7 +2107,7 @@ int layout_dist(bella_ctx* c, uint64_t nown_nnz, uint32_t rmask, uint32_t inl, i
     if (!rc) rc = ensure_bytes(c, c->lk_val, 8 * cap);
     if (!rc) rc = ensure_bytes(c, c->lk_val2, 8 * cap);
     // (3) every rank's line to every rank: all take the same decision from the same table
-    if (!c->comm_meta.p) return done(rc ? rc : BELLA_ERR_NOMEM);  // (nothing to exchange through: cannot happen after the first collective call)
+    if (!c->comm_meta.p) return rc ? rc : BELLA_ERR_NOMEM;        // (nothing to exchange through: cannot happen after the first collective call)
     uint64_t* d_meta = ptr<uint64_t>(c->comm_meta);
     line[0] = rc ? 1 : 0; line[1] = nsel; line[2] = nown_nnz;
     std::vector<uint64_t> T(W * (size_t)N, 0);
@@ -2074,27 +2115,27 @@ int layout_dist(bella_ctx* c, uint64_t nown_nnz, uint32_t rmask, uint32_t inl, i
         hipError_t e = hipMemcpyAsync(d_meta + W * (size_t)N, line.data(), 8 * W, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         const ncclResult_t r = c->api->AllGather(d_meta + W * (size_t)N, d_meta, W, ncclUint64, c->comm, c->stream);
-        if (r != ncclSuccess) return done(rc ? rc : fail(c, BELLA_ERR_HIP, "layout metadata exchange failed"));
+        if (r != ncclSuccess) return rc ? rc : fail(c, BELLA_ERR_HIP, "layout metadata exchange failed");
         if (e == hipSuccess) e = hipMemcpyAsync(T.data(), d_meta, 8 * W * (size_t)N, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) return done(rc ? rc : fail(c, BELLA_ERR_HIP, "layout metadata exchange: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return rc ? rc : fail(c, BELLA_ERR_HIP, "layout metadata exchange: %s", hipGetErrorString(e));
         const int sr = comm_sync(c, "layout metadata");
-        if (sr) return done(rc ? rc : sr);
+        if (sr) return rc ? rc : sr;
     }
-    if (rc) return done(rc);
+    if (rc) return rc;
     std::vector<uint64_t> abase((size_t)N + 1, 0), roffs((size_t)N + 1, 0), ooff((size_t)N + 1, 0);
     for (int p = 0; p < N; ++p) {
-        if (T[W * (size_t)p]) return done(fail(c, BELLA_ERR_STATE, "rank %d failed inside the collective call; all ranks leave it", p));
+        if (T[W * (size_t)p]) return fail(c, BELLA_ERR_STATE, "rank %d failed inside the collective call; all ranks leave it", p);
         abase[(size_t)p + 1] = abase[(size_t)p] + T[W * (size_t)p + 1];
     }
     if (abase[(size_t)N] != nnz)
-        return done(fail(c, BELLA_ERR_STATE, "the ranks' slices hold %llu of %llu entries (different matrices or dictionaries?)",
-                         (unsigned long long)abase[(size_t)N], (unsigned long long)nnz));
+        return fail(c, BELLA_ERR_STATE, "the ranks' slices hold %llu of %llu entries (different matrices or dictionaries?)",
+                    (unsigned long long)abase[(size_t)N], (unsigned long long)nnz);
     for (int q = 0; q < N; ++q) {                                 // (every rank checks every rank's rows: the same verdict everywhere)
         uint64_t got = 0;
         for (int p = 0; p < N; ++p) got += T[W * (size_t)p + 3 + (size_t)q];
         if (got != T[W * (size_t)q + 2])
-            return done(fail(c, BELLA_ERR_STATE, "the ranks hold %llu entries for the rows of rank %d, its rows have %llu", (unsigned long long)got, q,
-                             (unsigned long long)T[W * (size_t)q + 2]));
+            return fail(c, BELLA_ERR_STATE, "the ranks hold %llu entries for the rows of rank %d, its rows have %llu", (unsigned long long)got, q,
+                        (unsigned long long)T[W * (size_t)q + 2]);
     }
     auto S = [&](int p, int q) { return T[W * (size_t)p + 3 + (size_t)q]; };    // entries rank p holds for the rows of rank q
     for (int p = 0; p < N; ++p) { roffs[(size_t)p + 1] = roffs[(size_t)p] + S(p, me); ooff[(size_t)p + 1] = ooff[(size_t)p] + S(me, p); }
@@ -2110,10 +2151,7 @@ int layout_dist(bella_ctx* c, uint64_t nown_nnz, uint32_t rmask, uint32_t inl, i
                                                                            ptr<uint32_t>(c->packed), ptr<uint64_t>(c->roff), c->kmer_size, nk, klo, khi,
                                                                            rowbase, dk.Current(), dv.Current(), ptr<uint32_t>(c->status));
             KCHK(c);
-            size_t tb = 0;
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, (uint64_t)nsel, 0, kbits, c->stream));
-            ENSURE(c, c->cubtmp, tb);
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, tb, dk, dv, (uint64_t)nsel, 0, kbits, c->stream));
+            CUB(c, hipcub::DeviceRadixSort::SortPairs, dk, dv, (uint64_t)nsel, 0, kbits, c->stream);
         }
         // (5) where a row starts in ITS owner's B': owner-major lengths, one scan
         uint2* rinfo = ptr<uint2>(c->lk_rinfo);
@@ -2178,9 +2216,9 @@ int layout_dist(bella_ctx* c, uint64_t nown_nnz, uint32_t rmask, uint32_t inl, i
         if (!rc) rc = status_to_error(c, st);
     }
     rc = comm_agree(c, rc);                                       // all ranks hold the layout's inputs, or all leave
-    if (rc) return done(rc);
+    if (rc) return rc;
     *ekey_out = rkey; *eval_out = rval; *fkey_out = okey; *fval_out = oval;
-    return done(0);
+    return 0;
 }
 }  // namespace
 }  // extern "C++"
@@ -2221,13 +2259,13 @@ int bella_hip_allgather_panels(bella_ctx* c) {
     if (roff[N] != c->nreads) return fail(c, BELLA_ERR_BAD_ARG, "the panels cover %llu of %u reads", (unsigned long long)roff[N], c->nreads);
     const uint64_t nnz = eoff[N];
     if (nnz >= 0xFFFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "nnz(A) must be < 2^32");
-    Buf nCnt, nBk, nBpos, nBptr;
+    TmpBuf nCnt, nBk, nBpos, nBptr;
     rc = ensure_bytes(c, nCnt, 4 * ((size_t)c->nreads + 2));
     if (!rc) rc = ensure_bytes(c, nBptr, 4 * ((size_t)c->nreads + 2));
     if (!rc) rc = ensure_bytes(c, nBk, 4 * nnz);
     if (!rc) rc = ensure_bytes(c, nBpos, 2 * nnz + 16);
     rc = comm_agree(c, rc);                                       // all ranks hold the full arrays, or all leave
-    if (rc) { release(nCnt); release(nBk); release(nBpos); release(nBptr); return rc; }
+    if (rc) return rc;
     // one grouped exchange: to every peer my block, from every peer its block, straight to its place in the full arrays
     uint32_t* cnt = ptr<uint32_t>(nCnt);
     uint32_t* bk = ptr<uint32_t>(nBk);
@@ -2258,15 +2296,13 @@ int bella_hip_allgather_panels(bella_ctx* c) {
     }
     if (nr2 != ncclSuccess || he != hipSuccess) {
         (void)hipStreamSynchronize(c->stream);
-        release(nCnt); release(nBk); release(nBpos); release(nBptr);
         return fail(c, BELLA_ERR_HIP, "panel exchange failed: %s", nr2 != ncclSuccess ? (c->api->GetErrorString ? c->api->GetErrorString(nr2) : "RCCL error") : hipGetErrorString(he));
     }
     rc = scan_u32(c, cnt, ptr<uint32_t>(nBptr), (uint64_t)c->nreads + 1);
     if (!rc) rc = comm_sync(c, "panel exchange");
-    release(nCnt);
-    if (rc) { release(nBk); release(nBpos); release(nBptr); return rc; }
-    release(c->Bptr); release(c->Bk); release(c->Bpos);
-    c->Bptr = nBptr; c->Bk = nBk; c->Bpos = nBpos;
+    nCnt.reset();
+    if (rc) return rc;
+    nBptr.give_to(c->Bptr); nBk.give_to(c->Bk); nBpos.give_to(c->Bpos);
     c->have_panel = false;
     c->have_matrix = c->have_pairs = c->have_alns = false;
     c->nnz = nnz;
@@ -2457,16 +2493,10 @@ static int wide_batch_finish(bella_ctx* c, WideBatch& wb, bool sync_at_end) {
             using K = decltype(key_tag);
             hipcub::DoubleBuffer<K> dk((K*)c->w_key.p, (K*)c->w_key2.p);
             hipcub::DoubleBuffer<uint32_t> dv(ptr<uint32_t>(c->w_idx), ptr<uint32_t>(c->w_idx2));
-            size_t tb = 0;
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, (int)T, 0, rbits + seg_bits, c->stream));
-            ENSURE(c, c->cubtmp, tb);
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, tb, dk, dv, (int)T, 0, rbits + seg_bits, c->stream));
+            CUB(c, hipcub::DeviceRadixSort::SortPairs, dk, dv, (int)T, 0, rbits + seg_bits, c->stream);
             a.S_key = dk.Current(); a.S_idx = dv.Current();
             K* rkey = dk.Current() == (K*)c->w_key.p ? (K*)c->w_key2.p : (K*)c->w_key.p;
-            size_t tb2 = 0;
-            HIPCHK(c, hipcub::DeviceRunLengthEncode::Encode(nullptr, tb2, (const K*)a.S_key, rkey, ptr<uint32_t>(c->w_rlen), ptr<uint32_t>(c->w_nruns), (int)T, c->stream));
-            ENSURE(c, c->cubtmp, tb2);
-            HIPCHK(c, hipcub::DeviceRunLengthEncode::Encode(c->cubtmp.p, tb2, (const K*)a.S_key, rkey, ptr<uint32_t>(c->w_rlen), ptr<uint32_t>(c->w_nruns), (int)T, c->stream));
+            CUB(c, hipcub::DeviceRunLengthEncode::Encode, (const K*)a.S_key, rkey, ptr<uint32_t>(c->w_rlen), ptr<uint32_t>(c->w_nruns), (int)T, c->stream);
             a.R_key = rkey;
             return 0;
         };
@@ -3125,11 +3155,7 @@ int bella_hip_count_pairs(bella_ctx* c, const bella_params* p, uint64_t* colptrC
         }
         hipcub::TransformInputIterator<uint64_t, CastU64, const uint32_t*> it(ptr<uint32_t>(c->flopsr), CastU64());
         uint64_t* d_sum = ptr<uint64_t>(c->colptrC);
-        size_t tb = 0;
-        HIPCHK(c, hipcub::DeviceReduce::Sum(nullptr, tb, it, d_sum, (int)nr + 1, c->stream));
-        ENSURE(c, c->cubtmp, tb + 256);
-        tb = c->cubtmp.cap;
-        HIPCHK(c, hipcub::DeviceReduce::Sum(c->cubtmp.p, tb, it, d_sum, (int)nr + 1, c->stream));
+        CUB_SLACK(c, 256, hipcub::DeviceReduce::Sum, it, d_sum, (int)nr + 1, c->stream);
         uint64_t F = 0;
         HIPCHK(c, hipMemcpyAsync(&F, d_sum, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3164,11 +3190,7 @@ int bella_hip_count_pairs(bella_ctx* c, const bella_params* p, uint64_t* colptrC
     }
     {
         hipcub::TransformInputIterator<uint64_t, CountU64, const uint32_t*> it(ptr<uint32_t>(c->nnzC), CountU64());
-        size_t tb = 0;
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, ptr<uint64_t>(c->colptrC), (int)nr + 1, c->stream));
-        ENSURE(c, c->cubtmp, tb + 256);
-        tb = c->cubtmp.cap;
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, ptr<uint64_t>(c->colptrC), (int)nr + 1, c->stream));
+        CUB_SLACK(c, 256, hipcub::DeviceScan::ExclusiveSum, it, ptr<uint64_t>(c->colptrC), (int)nr + 1, c->stream);
     }
     HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
     uint64_t tot[2] = {0, 0};
@@ -3190,8 +3212,7 @@ int bella_hip_get_memory_sized(bella_ctx* c, void* out, uint64_t struct_size) {
     bella_memory m{};
     const int rc = get_memory_impl(c, &m);
     if (rc) return rc;
-    std::memcpy(out, &m, (size_t)std::min<uint64_t>(struct_size, sizeof(m)));
-    return 0;
+    return put_sized(out, struct_size, m);
 }
 int bella_hip_get_memory(bella_ctx* c, bella_memory* m) { return get_memory_impl(c, m); }
 static int get_memory_impl(bella_ctx* c, bella_memory* m) {
@@ -3331,14 +3352,8 @@ static int run_xdrop(bella_ctx* c, const bella_params* p, const bella_seed* d_se
             HIPCHK(c, hipMemsetAsync(c->xres.p, 0xFF, 16 * ne, c->stream));   // (a result nobody wrote is not a result of an earlier call)
             k_xdrop_plan<<<nblk(ne), 256, 0, c->stream>>>(sa);
             KCHK(c);
-            size_t tb = 0;
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, ptr<uint32_t>(c->xest), ptr<uint32_t>(c->xest2),
-                                                                  ptr<uint32_t>(c->xids), ptr<uint32_t>(c->xorder), (int)ne, 0, 18,
-                                                                  c->stream));
-            ENSURE(c, c->cubtmp, tb);
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairsDescending(c->cubtmp.p, tb, ptr<uint32_t>(c->xest), ptr<uint32_t>(c->xest2),
-                                                                  ptr<uint32_t>(c->xids), ptr<uint32_t>(c->xorder), (int)ne, 0, 18,
-                                                                  c->stream));
+            CUB(c, hipcub::DeviceRadixSort::SortPairsDescending, ptr<uint32_t>(c->xest), ptr<uint32_t>(c->xest2), ptr<uint32_t>(c->xids), ptr<uint32_t>(c->xorder),
+                (int)ne, 0, 18, c->stream);
             // In one launch a wavefront runs until its longest lane ends; chance pairs (one shared k-mer: 92 % of the pairs of the 100k-read
             // set) end long before the step bound they are scheduled by, and their wavefronts idle behind the few lanes that run on: 5.2 s
             // against 3.1 s in slices on the 100k set, 75.3 against 71.4 ms on the 10k set.
@@ -3559,21 +3574,15 @@ static int xdrop_batch_impl(bella_ctx* c, const bella_seed* seeds, uint64_t n, c
         if ((uint64_t)s.seedH + p->kmer_size > lh || (uint64_t)s.seedV + p->kmer_size > lv)
             return fail(c, BELLA_ERR_BAD_ARG, "seed %llu: k-mer past the end of a read", (unsigned long long)i);
     }
-    Buf dalns;
+    TmpBuf dalns;
     ENSURE(c, c->seeds, sizeof(bella_seed) * n);
-    int rc = ensure_bytes(c, dalns, sizeof(bella_aln) * n);
+    ENSURE(c, dalns, sizeof(bella_aln) * n);
+    if (n) HIPCHK(c, hipMemcpyAsync(c->seeds.p, seeds, sizeof(bella_seed) * n, hipMemcpyHostToDevice, c->stream));
+    const int rc = exact ? run_logan(c, p, ptr<bella_seed>(c->seeds), nullptr, n, ptr<bella_aln>(dalns))
+                         : run_xdrop(c, p, ptr<bella_seed>(c->seeds), nullptr, n, ptr<bella_aln>(dalns));
     if (rc) return rc;
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemcpyAsync(c->seeds.p, seeds, sizeof(bella_seed) * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        rc = exact ? run_logan(c, p, ptr<bella_seed>(c->seeds), nullptr, n, ptr<bella_aln>(dalns))
-                   : run_xdrop(c, p, ptr<bella_seed>(c->seeds), nullptr, n, ptr<bella_aln>(dalns));
-        if (rc == 0 && n) e = hipMemcpyAsync(out, dalns.p, sizeof(bella_aln) * n, hipMemcpyDeviceToHost, c->stream);
-        if (rc == 0 && e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    release(dalns);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(c, BELLA_ERR_HIP, "xdrop_batch: %s", hipGetErrorString(e));
+    if (n) HIPCHK(c, hipMemcpyAsync(out, dalns.p, sizeof(bella_aln) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -3656,9 +3665,8 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
     constexpr uint32_t kMaxBatchPairs = 1u << 20;
     std::vector<uint32_t> queue(n), next;
     for (size_t q = 0; q < n; ++q) queue[q] = (uint32_t)q;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1)); HIPCHK(c, hipEventCreate(&e2)); HIPCHK(c, hipEventCreate(&e3));
-    struct EvGuard { hipEvent_t a, b, d, e; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(d); (void)hipEventDestroy(e); } } evg{e0, e1, e2, e3};
+    EventSet ev;
+    if (int r = ev.create(c, 4)) return r;
     std::vector<TraceExt> exts;
     std::vector<uint32_t> lists[4];
     std::vector<TracePairRes> pres;
@@ -3725,23 +3733,23 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
             const uint32_t* const dl = ptr<uint32_t>(c->tr_lists);
             uint8_t* const ddirs = ptr<uint8_t>(c->tr_dirs);
             TraceExtRes* const dres = ptr<TraceExtRes>(c->tr_res);
-            HIPCHK(c, hipEventRecord(e0, c->stream));
+            HIPCHK(c, hipEventRecord(ev.a, c->stream));
             const uint32_t wpb = kTraceBlock / 64;
             if (lo[1] > lo[0]) { k_trace_dp<4><<<nblk(lo[1] - lo[0], wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[0], lo[1] - lo[0], packed, ddirs, dres); KCHK(c); }
             if (lo[2] > lo[1]) { k_trace_dp<8><<<nblk(lo[2] - lo[1], wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[1], lo[2] - lo[1], packed, ddirs, dres); KCHK(c); }
             if (lo[3] > lo[2]) { k_trace_dp<16><<<nblk(lo[3] - lo[2], wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[2], lo[3] - lo[2], packed, ddirs, dres); KCHK(c); }
             if (lo[4] > lo[3]) { k_trace_dp_wide<<<lo[4] - lo[3], 64, 0, c->stream>>>(dex, dl + lo[3], lo[4] - lo[3], packed, ddirs, ptr<int>(c->tr_scr), dres); KCHK(c); }
-            HIPCHK(c, hipEventRecord(e1, c->stream));
+            HIPCHK(c, hipEventRecord(ev.b, c->stream));
             k_trace_count<<<nblk(nb, 64), 64, 0, c->stream>>>(dex, dres, nb, packed, ddirs, (int)k, ptr<TracePairRes>(c->tr_pres));
             KCHK(c);
-            HIPCHK(c, hipEventRecord(e2, c->stream));
+            HIPCHK(c, hipEventRecord(ev.d, c->stream));
             pres.resize(nb);
             eres.resize(exts.size());
             HIPCHK(c, hipMemcpyAsync(pres.data(), c->tr_pres.p, sizeof(TracePairRes) * nb, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(eres.data(), c->tr_res.p, sizeof(TraceExtRes) * exts.size(), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            st.dp_ms += ev_ms(e0, e1);
-            st.walk_ms += ev_ms(e1, e2);
+            st.dp_ms += ev_ms(ev.a, ev.b);
+            st.walk_ms += ev_ms(ev.b, ev.d);
             // ---- who is done, who goes again
             opoff.assign(nb, ~0ull);
             votep.clear();
@@ -3779,19 +3787,19 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
             } else if (bops) {
                 ENSURE(c, c->tr_ops, 4 * (size_t)bops);
                 HIPCHK(c, hipMemcpyAsync(c->tr_opoff.p, opoff.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipEventRecord(e0, c->stream));
+                HIPCHK(c, hipEventRecord(ev.a, c->stream));
                 k_trace_write<<<nblk(nb, 64), 64, 0, c->stream>>>(dex, dres, nb, packed, ddirs, (int)k, ptr<uint64_t>(c->tr_opoff), ptr<TracePairRes>(c->tr_pres),
                                                                   ptr<uint32_t>(c->tr_ops));
                 KCHK(c);
-                HIPCHK(c, hipEventRecord(e1, c->stream));
+                HIPCHK(c, hipEventRecord(ev.b, c->stream));
                 if (vote && !votep.empty()) {                           // the batch's runs vote while they are in device memory
                     ENSURE(c, c->pile_pairs, sizeof(PilePair) * votep.size());
                     HIPCHK(c, hipMemcpyAsync(c->pile_pairs.p, votep.data(), sizeof(PilePair) * votep.size(), hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipEventRecord(e2, c->stream));
+                    HIPCHK(c, hipEventRecord(ev.d, c->stream));
                     k_pile_vote<<<nblk(votep.size(), kPileBlock / 64), kPileBlock, 0, c->stream>>>(ptr<PilePair>(c->pile_pairs), (uint32_t)votep.size(), ptr<uint32_t>(c->tr_ops),
                                                                                                    packed, ptr<uint32_t>(c->pile), ptr<unsigned long long>(c->pile_cnt));
                     KCHK(c);
-                    HIPCHK(c, hipEventRecord(e3, c->stream));
+                    HIPCHK(c, hipEventRecord(ev.e, c->stream));
                 }
                 if (keep_ops) {
                     const size_t base = ops.size();
@@ -3800,8 +3808,8 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                     st.ops_host_bytes += 4 * bops;
                 }
                 HIPCHK(c, hipStreamSynchronize(c->stream));              // (votep and opoff are reused by the next batch)
-                st.walk_ms += ev_ms(e0, e1);
-                if (vote && !votep.empty()) st.vote_ms += ev_ms(e2, e3);
+                st.walk_ms += ev_ms(ev.a, ev.b);
+                if (vote && !votep.empty()) st.vote_ms += ev_ms(ev.d, ev.e);
                 ops_seen += bops;
                 st.ops += bops;
             }
@@ -3922,8 +3930,7 @@ int bella_hip_get_batch_ops(bella_ctx* c, uint32_t* ops, uint64_t ops_cap) {
 
 int bella_hip_get_trace_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     if (!c || !out) return BELLA_ERR_BAD_ARG;
-    std::memcpy(out, &c->trace_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_trace_stats)));
-    return 0;
+    return put_sized(out, struct_size, c->trace_stats);
 }
 
 // ---- read correction (pileup.hpp) ----------------------------------------------------------------------------
@@ -4000,8 +4007,9 @@ int bella_hip_add_pileup(bella_ctx* c, uint32_t first_read, uint32_t nreads, con
 
 int bella_hip_consensus(bella_ctx* c, const bella_consensus_params* params, uint64_t* total_bases) {
     if (!c || !params) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (params->struct_size < sizeof(bella_consensus_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_consensus_params: struct_size %u is too small", params->struct_size);
-    if (params->min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
+    bella_consensus_params cp{};                                      // (no defaults: NULL was refused)
+    if (int r = take_params(c, cp, params, "bella_consensus_params")) return r;
+    if (cp.min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
     if (!c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
     HIPCHK(c, hipSetDevice(c->device));
     c->have_cons = false;
@@ -4015,16 +4023,13 @@ int bella_hip_consensus(bella_ctx* c, const bella_consensus_params* params, uint
     HIPCHK(c, hipMemsetAsync(c->cons_stats.p, 0, sizeof(bella_consensus_read) * std::max<size_t>(nr, 1), c->stream));
     HIPCHK(c, hipMemsetAsync(ptr<uint8_t>(c->cons_emit) + total, 0, 1, c->stream));
     if (total) {
-        k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(c->pile), ptr<uint32_t>(c->packed), ptr<uint64_t>(c->roff), nr, total, params->min_depth,
+        k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(c->pile), ptr<uint32_t>(c->packed), ptr<uint64_t>(c->roff), nr, total, cp.min_depth,
                                                           ptr<uint8_t>(c->cons_emit), ptr<bella_consensus_read>(c->cons_stats));
         KCHK(c);
     }
     {
         hipcub::TransformInputIterator<uint64_t, EmitCount, const uint8_t*> it(ptr<uint8_t>(c->cons_emit), EmitCount());
-        size_t tb = 0;
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, ptr<uint64_t>(c->cons_scan), (int)(total + 1), c->stream));
-        ENSURE(c, c->cubtmp, tb);
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, ptr<uint64_t>(c->cons_scan), (int)(total + 1), c->stream));
+        CUB(c, hipcub::DeviceScan::ExclusiveSum, it, ptr<uint64_t>(c->cons_scan), (int)(total + 1), c->stream);
     }
     uint64_t nout = 0;
     HIPCHK(c, hipMemcpyAsync(&nout, ptr<uint64_t>(c->cons_scan) + total, 8, hipMemcpyDeviceToHost, c->stream));
@@ -4062,10 +4067,9 @@ int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* 
         fprintf(stderr, "bella_hip_write_fasta: null argument\n");
         return BELLA_ERR_BAD_ARG;
     }
-    FILE* f = std::fopen(path, append ? "ab" : "wb");
-    if (!f) { fprintf(stderr, "bella_hip_write_fasta: cannot open %s\n", path); return BELLA_ERR_BAD_ARG; }
-    std::vector<char> buf((size_t)4 << 20);
-    std::setvbuf(f, buf.data(), _IOFBF, buf.size());
+    TextFile file("bella_hip_write_fasta", path, append ? "ab" : "wb");
+    FILE* const f = file.f;
+    if (!f) return BELLA_ERR_BAD_ARG;
     bool ok = true;
     for (uint32_t r = 0; r < nreads && ok; ++r) {
         if (!names[r] || offsets[r + 1] < offsets[r]) { ok = false; break; }
@@ -4073,16 +4077,10 @@ int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* 
         ok = std::fputc('>', f) != EOF && std::fputs(names[r], f) != EOF && std::fputc('\n', f) != EOF && (n == 0 || std::fwrite(bases + offsets[r], 1, n, f) == n) &&
              std::fputc('\n', f) != EOF;
     }
-    if (std::fclose(f) != 0) ok = false;
-    if (!ok) { fprintf(stderr, "bella_hip_write_fasta: writing %s failed\n", path); return BELLA_ERR_BAD_ARG; }
-    return 0;
+    return file.close(ok);
 }
 
 // ---- string graph (graph.hpp) ----------------------------------------------------------------------------------
-struct KeepU32 {
-    __host__ __device__ uint32_t operator()(const uint8_t& v) const { return (uint32_t)v; }
-};
-
 int bella_hip_graph_reset(bella_ctx* c) {
     if (!c) return BELLA_ERR_BAD_ARG;
     std::vector<bella_overlap>().swap(c->g_recs);
@@ -4149,10 +4147,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     using clk = std::chrono::steady_clock;
     if (!c) return BELLA_ERR_BAD_ARG;
     bella_graph_params gp{(uint32_t)sizeof(bella_graph_params), 1000, 1000, 800, 1000};
-    if (params) {
-        if (params->struct_size < sizeof(bella_graph_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_graph_params: struct_size %u is too small", params->struct_size);
-        gp = *params;
-    }
+    if (int r = take_params(c, gp, params, "bella_graph_params")) return r;
     if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
     HIPCHK(c, hipSetDevice(c->device));
     const auto t_begin = clk::now();
@@ -4162,9 +4157,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     if (nr >= (1u << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 reads");
     bella_graph_stats st{};
     st.records = n;
-    Buf recs, cand, cont, cnt, ok, deg, off, key1, key1b, idx, idxb, key2, key2b, edges, pos, bykey, bykeyb, gmark, red, keep, scan, fin, foff;
-    struct Guard { std::vector<Buf*> v; ~Guard() { for (Buf* b : v) release(*b); } } guard{{&recs, &cand, &cont, &cnt, &ok, &deg, &off, &key1, &key1b, &idx, &idxb, &key2, &key2b,
-                                                                                           &edges, &pos, &bykey, &bykeyb, &gmark, &red, &keep, &scan, &fin, &foff}};
+    TmpBuf recs, cand, cont, cnt, ok, deg, off, key1, key1b, idx, idxb, key2, key2b, edges, pos, bykey, bykeyb, gmark, red, keep, scan, fin, foff;
     ENSURE(c, recs, sizeof(bella_overlap) * (size_t)n);
     ENSURE(c, cand, sizeof(bella_graph_edge) * (size_t)nc);
     ENSURE(c, cont, 4 * (size_t)nr);
@@ -4177,44 +4170,33 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     ENSURE(c, key2, 8 * (size_t)nc); ENSURE(c, key2b, 8 * (size_t)nc);
     ENSURE(c, pos, 4 * (size_t)nc);
     uint32_t* const d_cnt = ptr<uint32_t>(cnt);
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1)); HIPCHK(c, hipEventCreate(&e2)); HIPCHK(c, hipEventCreate(&e3));
-    struct EvGuard { hipEvent_t a, b, d, e; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(d); (void)hipEventDestroy(e); } } evg{e0, e1, e2, e3};
+    EventSet ev;
+    if (int r = ev.create(c, 4)) return r;
     if (n) HIPCHK(c, c->stager.h2d(recs.p, c->g_recs.data(), sizeof(bella_overlap) * (size_t)n, c->stream));
     HIPCHK(c, hipMemsetAsync(cont.p, 0, std::max<size_t>(4 * (size_t)nr, 16), c->stream));
     HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kGcCount, c->stream));
     HIPCHK(c, hipMemsetAsync(deg.p, 0, 4 * ((size_t)nv + 1), c->stream));
     // ---- classes
-    HIPCHK(c, hipEventRecord(e0, c->stream));
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
     if (n) {
         k_graph_classify<<<nblk(n), 256, 0, c->stream>>>(ptr<bella_overlap>(recs), n, ptr<uint64_t>(c->roff), gp.min_overlap, gp.max_overhang, gp.overhang_permille,
                                                          ptr<bella_graph_edge>(cand), ptr<uint32_t>(cont), d_cnt);
         KCHK(c);
     }
-    HIPCHK(c, hipEventRecord(e1, c->stream));
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
     // ---- lists: filter, degrees, scan, two stable sorts, gather
     if (nc) {
         k_graph_filter<<<nblk(nc), 256, 0, c->stream>>>(ptr<bella_graph_edge>(cand), nc, ptr<uint32_t>(cont), ptr<uint8_t>(ok), ptr<uint32_t>(deg), ptr<uint32_t>(key1),
                                                         ptr<uint32_t>(idx), d_cnt);
         KCHK(c);
     }
-    {
-        size_t tb = 0;
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ptr<uint32_t>(deg), ptr<uint32_t>(off), (int)(nv + 1), c->stream));
-        ENSURE(c, c->cubtmp, tb);
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, ptr<uint32_t>(deg), ptr<uint32_t>(off), (int)(nv + 1), c->stream));
-    }
+    int rc = scan_u32(c, ptr<uint32_t>(deg), ptr<uint32_t>(off), (uint64_t)nv + 1);
+    if (rc) return rc;
     if (nc) {
-        size_t tb = 0;
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, ptr<uint32_t>(key1), ptr<uint32_t>(key1b), ptr<uint32_t>(idx), ptr<uint32_t>(idxb), (int)nc, 0, 32, c->stream));
-        ENSURE(c, c->cubtmp, tb);
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, tb, ptr<uint32_t>(key1), ptr<uint32_t>(key1b), ptr<uint32_t>(idx), ptr<uint32_t>(idxb), (int)nc, 0, 32, c->stream));
+        CUB(c, hipcub::DeviceRadixSort::SortPairs, ptr<uint32_t>(key1), ptr<uint32_t>(key1b), ptr<uint32_t>(idx), ptr<uint32_t>(idxb), (int)nc, 0, 32, c->stream);
         k_graph_key2<<<nblk(nc), 256, 0, c->stream>>>(ptr<bella_graph_edge>(cand), ptr<uint8_t>(ok), ptr<uint32_t>(idxb), nc, ptr<uint64_t>(key2));
         KCHK(c);
-        tb = 0;
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, ptr<uint64_t>(key2), ptr<uint64_t>(key2b), ptr<uint32_t>(idxb), ptr<uint32_t>(idx), (int)nc, 0, 64, c->stream));
-        ENSURE(c, c->cubtmp, tb);
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, tb, ptr<uint64_t>(key2), ptr<uint64_t>(key2b), ptr<uint32_t>(idxb), ptr<uint32_t>(idx), (int)nc, 0, 64, c->stream));
+        CUB(c, hipcub::DeviceRadixSort::SortPairs, ptr<uint64_t>(key2), ptr<uint64_t>(key2b), ptr<uint32_t>(idxb), ptr<uint32_t>(idx), (int)nc, 0, 64, c->stream);
     }
     uint32_t hc[kGcCount] = {};
     HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kGcCount, hipMemcpyDeviceToHost, c->stream));
@@ -4234,14 +4216,11 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     const bool need_global = m && (force_global || hc[kGcOvercap] != 0);
     const uint64_t* d_bykey = nullptr;
     if (need_global) {                                                    // the over-cap path's neighbour sets: every vertex's dst values, ascending
-        size_t tb = 0;
-        HIPCHK(c, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, ptr<uint64_t>(bykey), ptr<uint64_t>(bykeyb), (int)m, 0, 64, c->stream));
-        ENSURE(c, c->cubtmp, tb);
-        HIPCHK(c, hipcub::DeviceRadixSort::SortKeys(c->cubtmp.p, tb, ptr<uint64_t>(bykey), ptr<uint64_t>(bykeyb), (int)m, 0, 64, c->stream));
+        CUB(c, hipcub::DeviceRadixSort::SortKeys, ptr<uint64_t>(bykey), ptr<uint64_t>(bykeyb), (int)m, 0, 64, c->stream);
         d_bykey = ptr<uint64_t>(bykeyb);
         ENSURE(c, gmark, m);
     }
-    HIPCHK(c, hipEventRecord(e2, c->stream));
+    HIPCHK(c, hipEventRecord(ev.d, c->stream));
     // ---- reduction, twin pass, compaction
     ENSURE(c, red, (size_t)m + 1);
     ENSURE(c, keep, (size_t)m + 1);
@@ -4255,13 +4234,8 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     }
     k_graph_symmetric<<<nblk((uint64_t)m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(edges), m, ptr<uint32_t>(pos), ptr<uint8_t>(red), ptr<uint8_t>(keep));
     KCHK(c);
-    {
-        hipcub::TransformInputIterator<uint32_t, KeepU32, const uint8_t*> it(ptr<uint8_t>(keep), KeepU32());
-        size_t tb = 0;
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, ptr<uint32_t>(scan), (int)(m + 1), c->stream));
-        ENSURE(c, c->cubtmp, tb);
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, ptr<uint32_t>(scan), (int)(m + 1), c->stream));
-    }
+    rc = scan_u8_to_u32(c, ptr<uint8_t>(keep), ptr<uint32_t>(scan), (uint64_t)m + 1);
+    if (rc) return rc;
     uint32_t nfinal = 0;
     HIPCHK(c, hipMemcpyAsync(&nfinal, ptr<uint32_t>(scan) + m, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kGcCount, hipMemcpyDeviceToHost, c->stream));
@@ -4274,7 +4248,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     }
     k_graph_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint64_t>(foff));
     KCHK(c);
-    HIPCHK(c, hipEventRecord(e3, c->stream));
+    HIPCHK(c, hipEventRecord(ev.e, c->stream));
     c->g_off.assign((size_t)nv + 1, 0);
     c->g_edges.assign(nfinal, bella_graph_edge{});
     std::vector<uint32_t> cont32(nr);
@@ -4287,7 +4261,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     st.n_short = hc[kGcShort]; st.n_internal = hc[kGcInternal]; st.contained_reads = hc[kGcContained];
     st.edges_all = hc[kGcEdgesAll]; st.edges_kept = m; st.edges_reduced = hc[kGcReduced]; st.edges_final = nfinal;
     st.max_degree = hc[kGcMaxDegree]; st.overcap_vertices = hc[kGcOvercap];
-    st.classify_ms = ev_ms(e0, e1); st.sort_ms = ev_ms(e1, e2); st.reduce_ms = ev_ms(e2, e3);
+    st.classify_ms = ev_ms(ev.a, ev.b); st.sort_ms = ev_ms(ev.b, ev.d); st.reduce_ms = ev_ms(ev.d, ev.e);
     st.host_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
     c->g_stats = st;
     c->g_removed.assign(nr, 0);
@@ -4311,23 +4285,13 @@ int bella_hip_graph_get(bella_ctx* c, uint32_t* nvertices, uint64_t* nedges, uin
 int bella_hip_graph_get_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     if (!c || !out) return BELLA_ERR_BAD_ARG;
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
-    std::memcpy(out, &c->g_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_graph_stats)));
-    return 0;
+    return put_sized(out, struct_size, c->g_stats);
 }
 
 }  // extern "C"
 
 // ---- unitigs (unitig.hpp) -----------------------------------------------------------------------------------------
 namespace {
-struct BufGuard {
-    std::vector<Buf*> v;
-    ~BufGuard() { for (Buf* b : v) release(*b); }
-};
-struct EventSet {
-    hipEvent_t a = nullptr, b = nullptr, d = nullptr, e = nullptr;
-    ~EventSet() { for (hipEvent_t x : {a, b, d, e}) if (x) (void)hipEventDestroy(x); }
-};
-
 // the context's current graph on the device: 32-bit offsets, the edges
 int graph_upload(bella_ctx* c, Buf& off, Buf& edges) {
     const size_t nv1 = c->g_off.size(), m = c->g_edges.size();
@@ -4341,14 +4305,57 @@ int graph_upload(bella_ctx* c, Buf& off, Buf& edges) {
     return 0;
 }
 
-int scan_flags(bella_ctx* c, const uint8_t* in, uint32_t* out, size_t n) {
-    hipcub::TransformInputIterator<uint32_t, KeepU32, const uint8_t*> it(in, KeepU32());
-    size_t tb = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, out, (int)n, c->stream));
-    ENSURE(c, c->cubtmp, tb);
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, out, (int)n, c->stream));
-    return 0;
-}
+// What tip clipping and bubble popping share: the graph and the removed-read marks on the device, the buffers a round filters and
+// compacts with, the stage's two events.  A stage marks the reads of a round in `hit`, the edges that stay in `keep`, scans `keep`
+// into `scan`, and owns everything else: its kernels, its counters, its read-backs and synchronisations.
+struct GraphRound {
+    TmpBuf off, off2, E, E2, rem, hit, keep, scan;
+    EventSet ev;
+    uint32_t nr = 0, nv = 0, m = 0, m0 = 0;
+    // upload, allocate, start the clock
+    int begin(bella_ctx* c) {
+        nr = c->nreads; nv = 2 * nr;
+        m = m0 = (uint32_t)c->g_edges.size();
+        int rc = graph_upload(c, off, E);
+        if (rc) return rc;
+        ENSURE(c, off2, 4 * ((size_t)nv + 1));
+        ENSURE(c, E2, sizeof(bella_graph_edge) * (size_t)m);
+        ENSURE(c, hit, nr); ENSURE(c, rem, nr);
+        ENSURE(c, keep, (size_t)m + 1);
+        ENSURE(c, scan, 4 * ((size_t)m + 1));
+        HIPCHK(c, hipMemcpyAsync(rem.p, c->g_removed.data(), nr, hipMemcpyHostToDevice, c->stream));
+        if ((rc = ev.create(c, 2))) return rc;
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        return 0;
+    }
+    // the kept edges become the graph (enqueued, not waited for); the caller sets m to the count it read back from scan[m]
+    int apply_keep(bella_ctx* c) {
+        k_graph_compact<<<nblk(m), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), ptr<uint8_t>(keep), ptr<uint32_t>(scan), m, ptr<bella_graph_edge>(E2));
+        KCHK(c);
+        k_utg_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint32_t>(off2));
+        KCHK(c);
+        E.swap(E2);
+        off.swap(off2);
+        return 0;
+    }
+    // stop the clock; the graph and the marks back into the context
+    int finish(bella_ctx* c, uint64_t* edges_removed, double* ms) {
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        std::vector<uint32_t> off32((size_t)nv + 1);
+        std::vector<bella_graph_edge> edges(m);
+        std::vector<uint8_t> removed(nr);
+        HIPCHK(c, hipMemcpyAsync(off32.data(), off.p, 4 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
+        if (m) HIPCHK(c, c->stager.d2h(edges.data(), E.p, sizeof(bella_graph_edge) * (size_t)m, c->stream));
+        HIPCHK(c, hipMemcpyAsync(removed.data(), rem.p, nr, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i <= nv; ++i) c->g_off[i] = off32[i];
+        c->g_edges.swap(edges);
+        c->g_removed.swap(removed);
+        *edges_removed = m0 - m;
+        *ms = ev_ms(ev.a, ev.b);
+        return 0;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -4356,41 +4363,28 @@ extern "C" {
 int bella_hip_graph_clean(bella_ctx* c, const bella_graph_clean_params* params) {
     if (!c) return BELLA_ERR_BAD_ARG;
     bella_graph_clean_params cp{(uint32_t)sizeof(bella_graph_clean_params), 4, 3};
-    if (params) {
-        if (params->struct_size < sizeof(bella_graph_clean_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_graph_clean_params: struct_size %u is too small", params->struct_size);
-        cp = *params;
-    }
+    if (int r = take_params(c, cp, params, "bella_graph_clean_params")) return r;
     if (cp.tip_rounds > BELLA_MAX_TIP_ROUNDS) return fail(c, BELLA_ERR_BAD_ARG, "tip_rounds %u: at most %d", cp.tip_rounds, BELLA_MAX_TIP_ROUNDS);
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
     HIPCHK(c, hipSetDevice(c->device));
     c->have_unitigs = c->have_polish = false;
     bella_unitig_stats st{};
     const uint32_t nr = c->nreads, nv = 2 * nr;
-    uint32_t m = (uint32_t)c->g_edges.size();
+    const uint32_t m = (uint32_t)c->g_edges.size();
     if (!cp.max_tip_reads || !cp.tip_rounds) { c->u_stats = st; return 0; }
     if (!m) { st.rounds = 1; c->u_stats = st; return 0; }             // (a round over no edges finds nothing)
-    Buf off, off2, E, E2, hit, rem, keep, scan, cnt;
-    BufGuard guard{{&off, &off2, &E, &E2, &hit, &rem, &keep, &scan, &cnt}};
-    int rc = graph_upload(c, off, E);
-    if (rc) return rc;
-    ENSURE(c, off2, 4 * ((size_t)nv + 1));
-    ENSURE(c, E2, sizeof(bella_graph_edge) * (size_t)m);
-    ENSURE(c, hit, nr); ENSURE(c, rem, nr);
-    ENSURE(c, keep, (size_t)m + 1);
-    ENSURE(c, scan, 4 * ((size_t)m + 1));
+    TmpBuf cnt;
     ENSURE(c, cnt, 4 * kUcCount);
-    HIPCHK(c, hipMemcpyAsync(rem.p, c->g_removed.data(), nr, hipMemcpyHostToDevice, c->stream));
-    EventSet ev;
-    HIPCHK(c, hipEventCreate(&ev.a)); HIPCHK(c, hipEventCreate(&ev.b));
-    HIPCHK(c, hipEventRecord(ev.a, c->stream));
-    const uint32_t m0 = m;
+    GraphRound g;
+    int rc = g.begin(c);
+    if (rc) return rc;
     for (uint32_t round = 0; round < cp.tip_rounds; ++round) {
         uint32_t hc[kUcCount] = {};
-        HIPCHK(c, hipMemsetAsync(hit.p, 0, nr, c->stream));
+        HIPCHK(c, hipMemsetAsync(g.hit.p, 0, nr, c->stream));
         HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kUcCount, c->stream));
-        k_tip_walk<<<nblk(nv), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<bella_graph_edge>(E), nv, cp.max_tip_reads, ptr<uint8_t>(hit), ptr<uint32_t>(cnt));
+        k_tip_walk<<<nblk(nv), 256, 0, c->stream>>>(ptr<uint32_t>(g.off), ptr<bella_graph_edge>(g.E), nv, cp.max_tip_reads, ptr<uint8_t>(g.hit), ptr<uint32_t>(cnt));
         KCHK(c);
-        k_tip_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(hit), nr, ptr<uint8_t>(rem), ptr<uint32_t>(cnt));
+        k_tip_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(g.hit), nr, ptr<uint8_t>(g.rem), ptr<uint32_t>(cnt));
         KCHK(c);
         HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kUcCount, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4399,34 +4393,17 @@ int bella_hip_graph_clean(bella_ctx* c, const bella_graph_clean_params* params) 
         st.rounds = round + 1;
         st.reads_removed += hc[kUcReads];
         if (!hc[kUcReads]) break;
-        k_tip_filter<<<nblk((uint64_t)m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), m, ptr<uint8_t>(hit), ptr<uint8_t>(keep));
+        k_tip_filter<<<nblk((uint64_t)g.m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(g.E), g.m, ptr<uint8_t>(g.hit), ptr<uint8_t>(g.keep));
         KCHK(c);
-        rc = scan_flags(c, ptr<uint8_t>(keep), ptr<uint32_t>(scan), (size_t)m + 1);
+        rc = scan_u8_to_u32(c, ptr<uint8_t>(g.keep), ptr<uint32_t>(g.scan), (uint64_t)g.m + 1);
         if (rc) return rc;
         uint32_t nm = 0;
-        HIPCHK(c, hipMemcpyAsync(&nm, ptr<uint32_t>(scan) + m, 4, hipMemcpyDeviceToHost, c->stream));
-        k_graph_compact<<<nblk(m), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), ptr<uint8_t>(keep), ptr<uint32_t>(scan), m, ptr<bella_graph_edge>(E2));
-        KCHK(c);
-        k_utg_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint32_t>(off2));
-        KCHK(c);
+        HIPCHK(c, hipMemcpyAsync(&nm, ptr<uint32_t>(g.scan) + g.m, 4, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = g.apply_keep(c))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        std::swap(E, E2);
-        std::swap(off, off2);
-        m = nm;
+        g.m = nm;
     }
-    HIPCHK(c, hipEventRecord(ev.b, c->stream));
-    std::vector<uint32_t> off32((size_t)nv + 1);
-    std::vector<bella_graph_edge> edges(m);
-    std::vector<uint8_t> removed(nr);
-    HIPCHK(c, hipMemcpyAsync(off32.data(), off.p, 4 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
-    if (m) HIPCHK(c, c->stager.d2h(edges.data(), E.p, sizeof(bella_graph_edge) * (size_t)m, c->stream));
-    HIPCHK(c, hipMemcpyAsync(removed.data(), rem.p, nr, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i <= nv; ++i) c->g_off[i] = off32[i];
-    c->g_edges.swap(edges);
-    c->g_removed.swap(removed);
-    st.edges_removed = m0 - m;
-    st.clean_ms = ev_ms(ev.a, ev.b);
+    if ((rc = g.finish(c, &st.edges_removed, &st.clean_ms))) return rc;
     c->u_stats = st;
     return 0;
 }
@@ -4442,10 +4419,7 @@ int bella_hip_graph_get_removed(bella_ctx* c, uint8_t* removed) {
 int bella_hip_graph_pop_bubbles(bella_ctx* c, const bella_graph_bubble_params* params) {
     if (!c) return BELLA_ERR_BAD_ARG;
     bella_graph_bubble_params bp{(uint32_t)sizeof(bella_graph_bubble_params), 64, 50000, 3};
-    if (params) {
-        if (params->struct_size < sizeof(bella_graph_bubble_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_graph_bubble_params: struct_size %u is too small", params->struct_size);
-        bp = *params;
-    }
+    if (int r = take_params(c, bp, params, "bella_graph_bubble_params")) return r;
     if (bp.bubble_rounds > BELLA_MAX_BUBBLE_ROUNDS) return fail(c, BELLA_ERR_BAD_ARG, "bubble_rounds %u: at most %d", bp.bubble_rounds, BELLA_MAX_BUBBLE_ROUNDS);
     if (bp.max_bubble_reads > BELLA_MAX_BUBBLE_READS) return fail(c, BELLA_ERR_BAD_ARG, "max_bubble_reads %u: at most %d", bp.max_bubble_reads, BELLA_MAX_BUBBLE_READS);
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
@@ -4453,77 +4427,50 @@ int bella_hip_graph_pop_bubbles(bella_ctx* c, const bella_graph_bubble_params* p
     c->have_unitigs = c->have_polish = false;
     bella_bubble_stats st{};
     const uint32_t nr = c->nreads, nv = 2 * nr;
-    uint32_t m = (uint32_t)c->g_edges.size();
+    const uint32_t m = (uint32_t)c->g_edges.size();
     if (!bp.max_bubble_reads || !bp.bubble_rounds) { c->b_stats = st; return 0; }
     if (!m) { st.rounds = 1; c->b_stats = st; return 0; }             // (a round over no edges finds nothing)
-    Buf off, off2, E, E2, list, claim, hit, ekill, rem, keep, scan, cnt;
-    BufGuard guard{{&off, &off2, &E, &E2, &list, &claim, &hit, &ekill, &rem, &keep, &scan, &cnt}};
-    int rc = graph_upload(c, off, E);
-    if (rc) return rc;
-    ENSURE(c, off2, 4 * ((size_t)nv + 1));
-    ENSURE(c, E2, sizeof(bella_graph_edge) * (size_t)m);
+    TmpBuf list, claim, ekill, cnt;
     ENSURE(c, list, 4 * (size_t)nv);
     ENSURE(c, claim, 4 * (size_t)nr);
-    ENSURE(c, hit, nr); ENSURE(c, rem, nr);
     ENSURE(c, ekill, (size_t)m + 1);
-    ENSURE(c, keep, (size_t)m + 1);
-    ENSURE(c, scan, 4 * ((size_t)m + 1));
     ENSURE(c, cnt, 4 * kBcCount);
-    HIPCHK(c, hipMemcpyAsync(rem.p, c->g_removed.data(), nr, hipMemcpyHostToDevice, c->stream));
-    EventSet ev;
-    HIPCHK(c, hipEventCreate(&ev.a)); HIPCHK(c, hipEventCreate(&ev.b));
-    HIPCHK(c, hipEventRecord(ev.a, c->stream));
-    const uint32_t m0 = m;
+    GraphRound g;
+    int rc = g.begin(c);
+    if (rc) return rc;
     for (uint32_t round = 0; round < bp.bubble_rounds; ++round) {
         uint32_t hc[kBcCount] = {}, nm = 0;
-        HIPCHK(c, hipMemsetAsync(hit.p, 0, nr, c->stream));
-        HIPCHK(c, hipMemsetAsync(ekill.p, 0, (size_t)m + 1, c->stream));
+        HIPCHK(c, hipMemsetAsync(g.hit.p, 0, nr, c->stream));
+        HIPCHK(c, hipMemsetAsync(ekill.p, 0, (size_t)g.m + 1, c->stream));
         HIPCHK(c, hipMemsetAsync(claim.p, 0xFF, 4 * (size_t)nr, c->stream));
         HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kBcCount, c->stream));
-        k_bub_sources<<<nblk(nv), 256, 0, c->stream>>>(ptr<uint32_t>(off), nv, ptr<uint32_t>(list), ptr<uint32_t>(cnt));
+        k_bub_sources<<<nblk(nv), 256, 0, c->stream>>>(ptr<uint32_t>(g.off), nv, ptr<uint32_t>(list), ptr<uint32_t>(cnt));
         KCHK(c);
         // one wavefront per listed source; the grid covers every vertex and the wavefronts past the list leave at once
-        k_bub_detect<<<nblk(nv, kBubBlock / 64), kBubBlock, 0, c->stream>>>(ptr<uint32_t>(off), ptr<bella_graph_edge>(E), ptr<uint32_t>(list), bp.max_bubble_reads,
+        k_bub_detect<<<nblk(nv, kBubBlock / 64), kBubBlock, 0, c->stream>>>(ptr<uint32_t>(g.off), ptr<bella_graph_edge>(g.E), ptr<uint32_t>(list), bp.max_bubble_reads,
                                                                             bp.max_bubble_dist, ptr<uint32_t>(claim), ptr<uint32_t>(cnt));
         KCHK(c);
-        k_bub_apply<<<nblk(nv, kBubBlock / 64), kBubBlock, 0, c->stream>>>(ptr<uint32_t>(off), ptr<bella_graph_edge>(E), ptr<uint32_t>(list), bp.max_bubble_reads,
-                                                                           bp.max_bubble_dist, ptr<uint32_t>(claim), ptr<uint8_t>(hit), ptr<uint8_t>(ekill), ptr<uint32_t>(cnt));
+        k_bub_apply<<<nblk(nv, kBubBlock / 64), kBubBlock, 0, c->stream>>>(ptr<uint32_t>(g.off), ptr<bella_graph_edge>(g.E), ptr<uint32_t>(list), bp.max_bubble_reads,
+                                                                           bp.max_bubble_dist, ptr<uint32_t>(claim), ptr<uint8_t>(g.hit), ptr<uint8_t>(ekill), ptr<uint32_t>(cnt));
         KCHK(c);
-        k_bub_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(hit), nr, ptr<uint8_t>(rem), ptr<uint32_t>(cnt));
+        k_bub_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(g.hit), nr, ptr<uint8_t>(g.rem), ptr<uint32_t>(cnt));
         KCHK(c);
-        k_bub_filter<<<nblk((uint64_t)m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), m, ptr<uint8_t>(hit), ptr<uint8_t>(ekill), ptr<uint8_t>(keep));
+        k_bub_filter<<<nblk((uint64_t)g.m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(g.E), g.m, ptr<uint8_t>(g.hit), ptr<uint8_t>(ekill), ptr<uint8_t>(g.keep));
         KCHK(c);
-        rc = scan_flags(c, ptr<uint8_t>(keep), ptr<uint32_t>(scan), (size_t)m + 1);
+        rc = scan_u8_to_u32(c, ptr<uint8_t>(g.keep), ptr<uint32_t>(g.scan), (uint64_t)g.m + 1);
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(&nm, ptr<uint32_t>(scan) + m, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&nm, ptr<uint32_t>(g.scan) + g.m, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kBcCount, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));                   // the round's one read-back
         st.sources[round] = hc[kBcSources]; st.found[round] = hc[kBcFound]; st.popped[round] = hc[kBcPopped];
-        st.reads_per_round[round] = hc[kBcReads]; st.edges_per_round[round] = m - nm;
+        st.reads_per_round[round] = hc[kBcReads]; st.edges_per_round[round] = g.m - nm;
         st.rounds = round + 1;
         st.reads_removed += hc[kBcReads];
         if (!hc[kBcPopped]) break;
-        k_graph_compact<<<nblk(m), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), ptr<uint8_t>(keep), ptr<uint32_t>(scan), m, ptr<bella_graph_edge>(E2));
-        KCHK(c);
-        k_utg_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint32_t>(off2));
-        KCHK(c);
-        std::swap(E, E2);
-        std::swap(off, off2);
-        m = nm;
+        if ((rc = g.apply_keep(c))) return rc;
+        g.m = nm;
     }
-    HIPCHK(c, hipEventRecord(ev.b, c->stream));
-    std::vector<uint32_t> off32((size_t)nv + 1);
-    std::vector<bella_graph_edge> edges(m);
-    std::vector<uint8_t> removed(nr);
-    HIPCHK(c, hipMemcpyAsync(off32.data(), off.p, 4 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
-    if (m) HIPCHK(c, c->stager.d2h(edges.data(), E.p, sizeof(bella_graph_edge) * (size_t)m, c->stream));
-    HIPCHK(c, hipMemcpyAsync(removed.data(), rem.p, nr, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i <= nv; ++i) c->g_off[i] = off32[i];
-    c->g_edges.swap(edges);
-    c->g_removed.swap(removed);
-    st.edges_removed = m0 - m;
-    st.pop_ms = ev_ms(ev.a, ev.b);
+    if ((rc = g.finish(c, &st.edges_removed, &st.pop_ms))) return rc;
     c->b_stats = st;
     return 0;
 }
@@ -4531,8 +4478,7 @@ int bella_hip_graph_pop_bubbles(bella_ctx* c, const bella_graph_bubble_params* p
 int bella_hip_graph_get_bubble_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     if (!c || !out) return BELLA_ERR_BAD_ARG;
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
-    std::memcpy(out, &c->b_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_bubble_stats)));
-    return 0;
+    return put_sized(out, struct_size, c->b_stats);
 }
 
 int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertices, uint64_t* nlinks, uint64_t* total_bases) {
@@ -4553,10 +4499,8 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
     uint32_t nutg = 0, nverts = 0, nlk = 0;
     uint64_t total = 0;
     if (nlive) {
-        Buf off, E, dd, succ, pred, outlen, inlen, ra, rb, ma, mb, cut, cmin2, tail_of, cnt_of, emit, nvert, uid, voff, cnt, verts, pos, nb, slot_utg, uvoff, ulen, uboff, ucirc,
-            gseg, lflag, lscan, links, out;
-        BufGuard guard{{&off, &E, &dd, &succ, &pred, &outlen, &inlen, &ra, &rb, &ma, &mb, &cut, &cmin2, &tail_of, &cnt_of, &emit, &nvert, &uid, &voff, &cnt, &verts, &pos,
-                        &nb, &slot_utg, &uvoff, &ulen, &uboff, &ucirc, &gseg, &lflag, &lscan, &links, &out}};
+        TmpBuf off, E, dd, succ, pred, outlen, inlen, ra, rb, ma, mb, cut, cmin2, tail_of, cnt_of, emit, nvert, uid, voff, cnt, verts, pos, nb, slot_utg, uvoff, ulen, uboff,
+            ucirc, gseg, lflag, lscan, links, out;
         int rc = graph_upload(c, off, E);
         if (rc) return rc;
         ENSURE(c, dd, nr);
@@ -4573,7 +4517,7 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
         HIPCHK(c, hipMemsetAsync(cnt_of.p, 0, 4 * (size_t)nv, c->stream));
         HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kUcCount, c->stream));
         EventSet ev;
-        HIPCHK(c, hipEventCreate(&ev.a)); HIPCHK(c, hipEventCreate(&ev.b)); HIPCHK(c, hipEventCreate(&ev.d)); HIPCHK(c, hipEventCreate(&ev.e));
+        if ((rc = ev.create(c, 4))) return rc;
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
         const uint32_t* const d_off = ptr<uint32_t>(off);
         const bella_graph_edge* const d_E = ptr<bella_graph_edge>(E);
@@ -4629,7 +4573,7 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
         if ((rc = scan_u32(c, ptr<uint32_t>(nvert), ptr<uint32_t>(voff), (size_t)nv + 1))) return rc;
         k_utg_linkflag<<<nblk((uint64_t)m + 1), 256, 0, c->stream>>>(d_E, m, ptr<uint32_t>(succ), ptr<uint8_t>(lflag));
         KCHK(c);
-        if ((rc = scan_flags(c, ptr<uint8_t>(lflag), ptr<uint32_t>(lscan), (size_t)m + 1))) return rc;
+        if ((rc = scan_u8_to_u32(c, ptr<uint8_t>(lflag), ptr<uint32_t>(lscan), (size_t)m + 1))) return rc;
         HIPCHK(c, hipMemcpyAsync(&nutg, ptr<uint32_t>(uid) + nv, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(&nverts, ptr<uint32_t>(voff) + nv, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(&nlk, ptr<uint32_t>(lscan) + m, 4, hipMemcpyDeviceToHost, c->stream));
@@ -4646,12 +4590,7 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
                                                        ptr<uint32_t>(emit), ptr<uint32_t>(uid), ptr<uint32_t>(voff), nv, ptr<uint32_t>(verts), ptr<uint64_t>(pos),
                                                        ptr<uint32_t>(nb), ptr<uint32_t>(slot_utg), ptr<uint64_t>(uvoff), ptr<uint64_t>(ulen), ptr<uint8_t>(ucirc));
         KCHK(c);
-        {
-            size_t tb = 0;
-            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ptr<uint64_t>(ulen), ptr<uint64_t>(uboff), (int)(nutg + 1), c->stream));
-            ENSURE(c, c->cubtmp, tb);
-            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, ptr<uint64_t>(ulen), ptr<uint64_t>(uboff), (int)(nutg + 1), c->stream));
-        }
+        CUB(c, hipcub::DeviceScan::ExclusiveSum, ptr<uint64_t>(ulen), ptr<uint64_t>(uboff), (int)(nutg + 1), c->stream);
         k_utg_segoff<<<nblk((uint64_t)nverts + 1), 256, 0, c->stream>>>(ptr<uint32_t>(slot_utg), ptr<uint64_t>(pos), ptr<uint64_t>(uboff), nverts, nutg, ptr<uint64_t>(gseg));
         KCHK(c);
         if (nlk) {
@@ -4738,19 +4677,15 @@ int bella_hip_graph_get_unitig_bases(bella_ctx* c, uint64_t* offsets, uint8_t* b
 int bella_hip_graph_get_unitig_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     if (!c || !out) return BELLA_ERR_BAD_ARG;
     if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
-    std::memcpy(out, &c->u_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_unitig_stats)));
-    return 0;
+    return put_sized(out, struct_size, c->u_stats);
 }
 
 // ---- unitig consensus (polish.hpp) ---------------------------------------------------------------------------------
-struct TileCount {
-    __host__ __device__ uint64_t operator()(const uint32_t& v) const { return (uint64_t)v; }
-};
-
 int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* params, uint64_t* total_bases) {
     if (!c || !params) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (params->struct_size < sizeof(bella_polish_params)) return fail(c, BELLA_ERR_BAD_ARG, "bella_polish_params: struct_size %u is too small", params->struct_size);
-    if (params->min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
+    bella_polish_params pp{};                                         // (no defaults: NULL was refused)
+    if (int r = take_params(c, pp, params, "bella_polish_params")) return r;
+    if (pp.min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
     if (!c->have_graph || !c->have_unitigs) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_unitigs first");
     if (!c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
     HIPCHK(c, hipSetDevice(c->device));
@@ -4758,7 +4693,7 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
     const uint32_t nutg = (uint32_t)c->u_len.size(), nseg = (uint32_t)c->u_verts.size();
     const uint64_t total = c->u_boff[nutg];
     bella_polish_stats st{};
-    st.unitigs = nutg; st.vertices = nseg; st.bases_before = total; st.min_depth = params->min_depth;
+    st.unitigs = nutg; st.vertices = nseg; st.bases_before = total; st.min_depth = pp.min_depth;
     c->p_offs.assign((size_t)nutg + 1, 0);
     c->p_pos.assign(nseg, 0); c->p_nb.assign(nseg, 0);
     c->p_recs.assign(nutg, bella_polish_unitig{});
@@ -4772,8 +4707,7 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
         std::vector<uint32_t> slot(nseg);
         for (uint32_t u = 0; u < nutg; ++u)
             for (uint64_t i = c->u_voff[u]; i < c->u_voff[u + 1]; ++i) slot[(size_t)i] = u;
-        Buf verts, slot_utg, pos, uvoff, uboff, gseg, emit, tcnt, tpref, gp, ppos, pnb, poffs, recs, out;
-        BufGuard guard{{&verts, &slot_utg, &pos, &uvoff, &uboff, &gseg, &emit, &tcnt, &tpref, &gp, &ppos, &pnb, &poffs, &recs, &out}};
+        TmpBuf verts, slot_utg, pos, uvoff, uboff, gseg, emit, tcnt, tpref, gp, ppos, pnb, poffs, recs, out;
         ENSURE(c, verts, 4 * (size_t)nseg); ENSURE(c, slot_utg, 4 * (size_t)nseg); ENSURE(c, pnb, 4 * (size_t)nseg);
         ENSURE(c, pos, 8 * (size_t)nseg); ENSURE(c, ppos, 8 * (size_t)nseg);
         ENSURE(c, gseg, 8 * ((size_t)nseg + 1)); ENSURE(c, gp, 8 * ((size_t)nseg + 1));
@@ -4791,20 +4725,15 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
         k_utg_segoff<<<nblk((uint64_t)nseg + 1), 256, 0, c->stream>>>(ptr<uint32_t>(slot_utg), ptr<uint64_t>(pos), ptr<uint64_t>(uboff), nseg, nutg, ptr<uint64_t>(gseg));
         KCHK(c);
         EventSet ev;
-        HIPCHK(c, hipEventCreate(&ev.a)); HIPCHK(c, hipEventCreate(&ev.b)); HIPCHK(c, hipEventCreate(&ev.d)); HIPCHK(c, hipEventCreate(&ev.e));
+        int rc = ev.create(c, 4);
+        if (rc) return rc;
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
         k_pol_decide<<<(uint32_t)ntiles, kPolBlock, 0, c->stream>>>(ptr<uint64_t>(gseg), ptr<uint32_t>(verts), ptr<uint32_t>(slot_utg), nseg, total, ptr<uint64_t>(c->roff),
-                                                                    ptr<uint32_t>(c->packed), ptr<uint32_t>(c->pile), params->min_depth, ptr<uint8_t>(emit),
+                                                                    ptr<uint32_t>(c->packed), ptr<uint32_t>(c->pile), pp.min_depth, ptr<uint8_t>(emit),
                                                                     ptr<bella_polish_unitig>(recs), ptr<uint32_t>(tcnt));
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.b, c->stream));
-        {
-            hipcub::TransformInputIterator<uint64_t, TileCount, const uint32_t*> it(ptr<uint32_t>(tcnt), TileCount());
-            size_t tb = 0;
-            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, ptr<uint64_t>(tpref), (int)(ntiles + 1), c->stream));
-            ENSURE(c, c->cubtmp, tb);
-            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, tb, it, ptr<uint64_t>(tpref), (int)(ntiles + 1), c->stream));
-        }
+        if ((rc = scan_u32_to_u64(c, ptr<uint32_t>(tcnt), ptr<uint64_t>(tpref), (uint64_t)ntiles + 1))) return rc;
         k_pol_segoff<<<nblk(((uint64_t)nseg + 1) * 64, kPolBlock), kPolBlock, 0, c->stream>>>(ptr<uint64_t>(gseg), nseg, ptr<uint8_t>(emit), ptr<uint64_t>(tpref),
                                                                                               ptr<uint64_t>(gp));
         KCHK(c);
@@ -4854,8 +4783,7 @@ int bella_hip_graph_get_polished(bella_ctx* c, uint64_t* offsets, uint8_t* bases
 int bella_hip_graph_get_polish_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     if (!c || !out) return BELLA_ERR_BAD_ARG;
     if (!c->have_graph || !c->have_unitigs || !c->have_polish) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_polish_unitigs first");
-    std::memcpy(out, &c->p_stats, (size_t)std::min<uint64_t>(struct_size, sizeof(bella_polish_stats)));
-    return 0;
+    return put_sized(out, struct_size, c->p_stats);
 }
 
 int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,
@@ -4870,10 +4798,9 @@ int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* co
         if (vertices[i] >= 2 * (uint64_t)nreads || !names[vertices[i] >> 1]) { fprintf(stderr, "bella_hip_write_unitig_gfa: vertex %llu out of range\n", (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
     for (uint64_t i = 0; i < nlinks; ++i)
         if (links[i].a >= nunitigs || links[i].b >= nunitigs) { fprintf(stderr, "bella_hip_write_unitig_gfa: link %llu out of range\n", (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
-    FILE* f = std::fopen(path, "wb");
-    if (!f) { fprintf(stderr, "bella_hip_write_unitig_gfa: cannot open %s\n", path); return BELLA_ERR_BAD_ARG; }
-    std::vector<char> buf((size_t)4 << 20);
-    std::setvbuf(f, buf.data(), _IOFBF, buf.size());
+    TextFile file("bella_hip_write_unitig_gfa", path, "wb");
+    FILE* const f = file.f;
+    if (!f) return BELLA_ERR_BAD_ARG;
     bool ok = std::fputs("H\tVN:Z:1.0\n", f) != EOF;
     char name[32], other[32];
     auto mk = [&](char* dst, uint64_t u) { std::snprintf(dst, 32, "utg%06llu%c", (unsigned long long)(u + 1), circular[u] ? 'c' : 'l'); };
@@ -4892,9 +4819,7 @@ int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* co
         ok = std::fprintf(f, "L\t%s\t%c\t%s\t%c\t%uM\trc:i:%u\n", name, (l.flags & BELLA_UNITIG_LINK_A_MINUS) ? '-' : '+', other, (l.flags & BELLA_UNITIG_LINK_B_MINUS) ? '-' : '+', l.ovl,
                          l.rec) > 0;
     }
-    if (std::fclose(f) != 0) ok = false;
-    if (!ok) { fprintf(stderr, "bella_hip_write_unitig_gfa: writing %s failed\n", path); return BELLA_ERR_BAD_ARG; }
-    return 0;
+    return file.close(ok);
 }
 
 int bella_hip_get_read_bases(bella_ctx* c, uint64_t* offsets, uint8_t* bases) {
@@ -4924,10 +4849,9 @@ int bella_hip_write_gfa(const char* path, uint32_t nreads, const char* const* na
     const uint64_t ne = offsets[2 * (size_t)nreads];
     for (uint64_t i = 0; i < ne; ++i)
         if (edges[i].src >= 2 * (uint64_t)nreads || edges[i].dst >= 2 * (uint64_t)nreads) { fprintf(stderr, "bella_hip_write_gfa: edge %llu: vertex out of range\n", (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
-    FILE* f = std::fopen(path, "wb");
-    if (!f) { fprintf(stderr, "bella_hip_write_gfa: cannot open %s\n", path); return BELLA_ERR_BAD_ARG; }
-    std::vector<char> buf((size_t)4 << 20);
-    std::setvbuf(f, buf.data(), _IOFBF, buf.size());
+    TextFile file("bella_hip_write_gfa", path, "wb");
+    FILE* const f = file.f;
+    if (!f) return BELLA_ERR_BAD_ARG;
     bool ok = std::fputs("H\tVN:Z:1.0\n", f) != EOF;
     for (uint32_t r = 0; r < nreads && ok; ++r) {
         if (contained[r]) continue;
@@ -4941,9 +4865,7 @@ int bella_hip_write_gfa(const char* path, uint32_t nreads, const char* const* na
         const bella_graph_edge& e = edges[i];
         ok = std::fprintf(f, "L\t%s\t%c\t%s\t%c\t%uM\tel:i:%u\trc:i:%u\n", names[e.src >> 1], (e.src & 1) ? '-' : '+', names[e.dst >> 1], (e.dst & 1) ? '-' : '+', e.ovl, e.len, e.rec) > 0;
     }
-    if (std::fclose(f) != 0) ok = false;
-    if (!ok) { fprintf(stderr, "bella_hip_write_gfa: writing %s failed\n", path); return BELLA_ERR_BAD_ARG; }
-    return 0;
+    return file.close(ok);
 }
 
 int bella_hip_write_output_traced(const char* path, const bella_params* p, uint32_t nreads, const char* const* names, const uint32_t* lens, const bella_pair* pairs,

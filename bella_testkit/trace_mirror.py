@@ -9,7 +9,12 @@ V = read cid, H' = read rid, reverse-complemented when strand == 1, the seed at 
 nothing: the left rectangle then reaches to the reads' starts)
 An extension is a DP with S[0][0] = 0, S[i][0] = -i, S[0][j] = -j, S[i][j] = max(S[i-1][j-1] +- 1, S[i-1][j] - 1, S[i][j-1] - 1); it
 ends at the cell with the largest S, ties to the smallest i + j, then the smallest i (i counts bases of V, j bases of H').
-Ops: 0 '=' 1 'X' (one base of each), 2 'I' (a base of V only), 3 'D' (a base of H' only)."""
+Ops: 0 '=' 1 'X' (one base of each), 2 'I' (a base of V only), 3 'D' (a base of H' only).
+
+Band.  On B diagonals only the cells with p = j - i + B/2 in [0, B) exist (everything else is minus infinity), rows 0 .. min(n, m + B/2).
+Every cell stores the FIRST of diagonal, up ('I'), left ('D') that attains its score; the walk from the best cell back to (0, 0)
+follows them (up along j == 0, left along i == 0), and a side whose walk visits p <= 0 or p >= B - 1 (the anchor excluded) has touched.
+banded_extension() is that definition for any even B; trace_expect_banded() is the pair-level rule with its widening, op for op."""
 from __future__ import annotations
 
 import numpy as np
@@ -81,6 +86,120 @@ def trace_expect(seqH: bytes, seqV: bytes, seedH: int, seedV: int, k: int, aln):
     sr, ir, jr = extension_optimum(Hp[sH + k:sH + k + mr], seqV[sV + k:sV + k + nr])
     seed = sum(1 if Hp[sH + t] == seqV[sV + t] else -1 for t in range(k))
     return dict(score=sl + seed + sr, tbegH=sH - jl, tbegV=sV - il, tendH=sH + k + jr, tendV=sV + k + ir)
+
+
+TOUCH_LOW, TOUCH_HIGH = 1, 2           # which edge a walk visited: p <= 0 (the path drifted towards V), p >= B - 1 (towards H')
+_NEGB = -(1 << 29)                     # minus infinity of the banded DP: no sum of it with a column or a step reaches a real score
+
+
+def banded_extension(h: bytes, v: bytes, B: int):
+    """The extension on a band of B diagonals (B even, >= 2): (score, (i, j), ops, touch).  ops: one op code per step of the walk, the
+    far end first; touch: 0, or TOUCH_LOW | TOUCH_HIGH for the edges the walk visited (truthy when the side has touched).
+    Row by row over the columns of the band: with a linear gap S[i][j] = max_{j' <= j}(cand[j'] + j') - j, cand = max(diagonal, up)."""
+    if B < 2 or B & 1:
+        raise ValueError("the band must be even and >= 2")
+    n, m, half = len(v), len(h), B // 2
+    rows = min(n, m + half)
+    hv = np.frombuffer(h, np.uint8)
+    sub = {b: np.where(hv == b, 1, -1).astype(np.int32) for b in set(v[:rows])}
+    J = np.arange(m + 1, dtype=np.int32)
+    prev = np.full(m + 1, _NEGB, np.int32)          # S[i - 1][j]; minus infinity where row i - 1 has no cell
+    top = min(m, half - 1)
+    prev[:top + 1] = -J[:top + 1]
+    best, bi, bj = 0, 0, 0
+    dirs = [None]                                   # dirs[i] = (first column of row i, its directions)
+    for i in range(1, rows + 1):
+        lo, hi = max(0, i - half), min(m, i + half - 1)
+        a = max(lo, 1)
+        cu = prev[lo:hi + 1] - 1                    # (i - 1, j): one diagonal higher, absent for the band's last diagonal
+        cd = np.full(hi - lo + 1, _NEGB, np.int32)
+        cd[a - lo:] = prev[a - 1:hi] + sub[v[i - 1]][a - 1:hi]
+        jj = J[lo:hi + 1]
+        s = np.maximum.accumulate(np.maximum(cd, cu) + jj) - jj
+        dirs.append((lo, np.where(s == cd, 0, np.where(s == cu, 1, 2)).astype(np.uint8)))
+        prev[lo:hi + 1] = s
+        mx = int(s.max())
+        if mx >= best:
+            j = lo + int(np.argmax(s))              # first maximum of the row: its smallest i + j
+            if mx > best or i + j < bi + bj:        # (rows come in order of i: on equal score and i + j the earlier row stays)
+                best, bi, bj = mx, i, j
+    ops, touch = [], 0
+    i, j = bi, bj
+    while i or j:
+        p = j - i + half
+        if p <= 0:
+            touch |= TOUCH_LOW
+        if p >= B - 1:
+            touch |= TOUCH_HIGH
+        d = 2 if i == 0 else 1 if j == 0 else int(dirs[i][1][j - dirs[i][0]])
+        if d == 0:
+            ops.append(0 if h[j - 1] == v[i - 1] else 1)
+            i, j = i - 1, j - 1
+        elif d == 1:
+            ops.append(2)
+            i -= 1
+        else:
+            ops.append(3)
+            j -= 1
+    return best, (bi, bj), ops, touch
+
+
+def trace_cover_band(n: int, m: int) -> int:
+    """the smallest band the device has (a power of two >= 256) that holds the whole rectangle: B >= 2 max(n, m + 1)"""
+    b = 256
+    while b < 2 * max(n, m + 1):
+        b <<= 1
+    return b
+
+
+def first_band(band0: int) -> int:
+    b0 = 256
+    while b0 < max(band0 or 256, 256) and b0 < (1 << 18):
+        b0 <<= 1
+    return b0
+
+
+def run_lengths(op_list):
+    """op codes -> uint32 words len << 4 | op, adjacent equal ops merged"""
+    a = np.asarray(op_list, np.int64)
+    if not len(a):
+        return np.zeros(0, np.uint32)
+    cut = np.flatnonzero(np.concatenate([[True], a[1:] != a[:-1]]))
+    ln = np.diff(np.concatenate([cut, [len(a)]]))
+    return (ln << 4 | a[cut]).astype(np.uint32)
+
+
+def trace_expect_banded(seqH: bytes, seqV: bytes, seedH: int, seedV: int, k: int, aln, band0: int, ext=banded_extension):
+    """What a trace that starts with band0 must report, complete: (record, ops, steps).  record: dict(score, tbegH, tendH, tbegV,
+    tendV, n_eq, n_x, n_ins, n_del, band, widened); ops: uint32 run-length words in V order (left part, seed, right part, merged
+    across both seams); steps: per side (left, right) the list of (band, touch) of every DP the pair ran -- a pair one of whose sides
+    touched below its covering band runs again as a whole, every such side with its band doubled.
+    ext: the side DP (tests pass a memoising wrapper)."""
+    Hp = oriented(seqH, int(aln["strand"]))
+    sH, (ml, nl), (mr, nr) = rectangles(len(seqH), len(seqV), seedH, seedV, k, aln)
+    sV = seedV
+    sides = [(Hp[sH - ml:sH][::-1], seqV[sV - nl:sV][::-1]), (Hp[sH + k:sH + k + mr], seqV[sV + k:sV + k + nr])]
+    cover = [trace_cover_band(len(v), len(h)) for h, v in sides]
+    band = [min(first_band(band0), c) for c in cover]
+    steps, widened = ([], []), 0
+    while True:
+        res = [ext(h, v, b) for (h, v), b in zip(sides, band)]
+        again = False
+        for sd in range(2):
+            steps[sd].append((band[sd], res[sd][3]))
+            if res[sd][3] and band[sd] < cover[sd]:
+                band[sd] *= 2
+                widened += 1
+                again = True
+        if not again:
+            break
+    (sl, (il, jl), ol, _), (sr, (ir, jr), orr, _) = res
+    seed = [0 if Hp[sH + t] == seqV[sV + t] else 1 for t in range(k)]
+    allops = list(ol) + seed + list(orr)[::-1]
+    cnt = np.bincount(np.asarray(allops, np.int64), minlength=4)
+    rec = dict(score=sl + sr + sum(1 if o == 0 else -1 for o in seed), tbegH=sH - jl, tendH=sH + k + jr, tbegV=sV - il, tendV=sV + k + ir,
+               n_eq=int(cnt[0]), n_x=int(cnt[1]), n_ins=int(cnt[2]), n_del=int(cnt[3]), band=max(band), widened=widened)
+    return rec, run_lengths(allops), steps
 
 
 def unpack_ops(ops):

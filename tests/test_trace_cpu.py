@@ -1,5 +1,6 @@
-"""CPU tests of the traced alignments: the numpy mirror against a scalar DP, the replay checker, the true-PAF
-writer (plain host code), the command line's --cigar rules and the ABI additions.  No device."""
+"""CPU tests of the traced alignments: the numpy mirrors (full rectangle and banded) against scalar DPs, the
+replay checker, the hand-made case list of the banded GPU tests, the true-PAF writer (plain host code), the command line's --cigar
+rules and the ABI additions.  No device."""
 import ctypes
 import os
 import subprocess
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 
 from bella_amd import _lib, api
+from bella_testkit import trace_cases as T
 from bella_testkit import trace_mirror as M
 from conftest import ROOT
 
@@ -223,3 +225,174 @@ def test_trace_structs_as_a_c_compiler_sees_them(tmp_path):
     assert lib.bella_hip_abi_version() == 6
     for name in ("bella_hip_trace_pairs", "bella_hip_get_traces", "bella_hip_trace_batch", "bella_hip_get_batch_ops", "bella_hip_get_trace_stats", "bella_hip_write_output_traced"):
         assert hasattr(lib, name), name
+
+
+# ---- the banded mirror -----------------------------------------------------------------------------------------------------------
+def _brute_banded(h, v, B):
+    """the banded definition, cell by cell: (score, (i, j), ops far end first, touch, the cells that hold the best score)"""
+    n, m, half = len(v), len(h), B // 2
+    rows = min(n, m + half)
+    S, D = {(0, 0): 0}, {}
+    for i in range(rows + 1):
+        for j in range(m + 1):
+            if not 0 <= j - i + half < B or (i == 0 and j == 0):
+                continue
+            c = []                                           # in the order of preference: diagonal, up, left
+            if (i - 1, j - 1) in S:
+                c.append((S[i - 1, j - 1] + (1 if v[i - 1] == h[j - 1] else -1), 0))
+            if (i - 1, j) in S:
+                c.append((S[i - 1, j] - 1, 1))
+            if (i, j - 1) in S:
+                c.append((S[i, j - 1] - 1, 2))
+            S[i, j] = max(x for x, _ in c)
+            D[i, j] = next(d for x, d in c if x == S[i, j])
+    _, _, bi, bj = min((-s, i + j, i, j) for (i, j), s in S.items())
+    ops, touch = [], 0
+    i, j = bi, bj
+    while i or j:
+        p = j - i + half
+        touch |= (M.TOUCH_LOW if p <= 0 else 0) | (M.TOUCH_HIGH if p >= B - 1 else 0)
+        d = 2 if i == 0 else 1 if j == 0 else D[i, j]
+        if d == 0:
+            ops.append(0 if h[j - 1] == v[i - 1] else 1)
+        else:
+            ops.append(d + 1)
+        i, j = i - (d != 2), j - (d != 1)
+    return S[bi, bj], (bi, bj), ops, touch, sorted(c for c, s in S.items() if s == S[bi, bj])
+
+
+def _mutated(rng, v, rate):
+    out = []
+    for c in v:
+        u = rng.random()
+        if u < rate:
+            continue
+        out.append(int(rng.choice(np.frombuffer(b"ACGT", np.uint8))) if u < 2 * rate else c)
+        if u > 1 - rate:
+            out.append(int(rng.choice(np.frombuffer(b"ACGT", np.uint8))))
+    return bytes(out)
+
+
+def test_banded_mirror_equals_the_scalar_banded_dp():
+    """score, best cell, every op of the walk and the touched edges, on bands of 2 .. 32 diagonals: random, related, empty sides,
+    n >> m, m >> n, homopolymers, dinucleotide repeats.  Small bands put most paths on an edge and most cells into a tie."""
+    rng = np.random.default_rng(31)
+    cases = [(b"", b""), (b"ACGT", b""), (b"", b"ACGT"), (b"AAAA", b"CCCC"), (b"A", b"A"), (b"ACGTACGT", b"ACGTACGT"), (b"A" * 40, b"A"), (b"A", b"A" * 40),
+             (b"A" * 30, b"A" * 22), (b"A" * 19, b"A" * 33), (b"AC" * 15, b"AC" * 11), (b"AC" * 9 + b"A", b"CA" * 14), (b"ACG" * 8, b"ACG" * 12 + b"T"),
+             (b"A" * 10 + b"C" + b"A" * 12, b"A" * 14 + b"C" + b"A" * 9)]
+    for t in range(360):
+        n, m = int(rng.integers(0, 40)), int(rng.integers(0, 40))
+        kind = t % 6
+        if kind == 0:
+            h, v = _rand(rng, m), _rand(rng, n)
+        elif kind == 1:
+            v = _rand(rng, n)
+            h = _mutated(rng, v, 0.1)
+        elif kind == 2:
+            h, v = _rand(rng, m, b"AC"), _rand(rng, n, b"AC")
+        elif kind == 3:                          # n >> m
+            v = _rand(rng, 40 + n)
+            h = _mutated(rng, v[:int(rng.integers(0, 6))], 0.1)
+        elif kind == 4:                          # m >> n
+            h = _rand(rng, 40 + m)
+            v = _mutated(rng, h[:int(rng.integers(0, 6))], 0.1)
+        else:                                    # one gap of a few bases inside a repeat
+            u = [b"A", b"AC", b"GAT"][t % 3]
+            v = u * (n // len(u)) + b"T" + u * (m // len(u))
+            h = u * (m // len(u)) + b"T" + u * (n // len(u))
+        cases.append((h, v))
+    bands, touched, tied = set(), 0, 0
+    for q, (h, v) in enumerate(cases):
+        for B in {2, 32, 2 * int(rng.integers(1, 17)), 2 * int(rng.integers(1, 17))}:
+            want = _brute_banded(h, v, B)
+            assert M.banded_extension(h, v, B) == want[:4], (h, v, B)
+            bands.add(B)
+            touched += bool(want[3])
+            tied += len(want[4]) > 1
+    assert bands == set(range(2, 33, 2)) and touched > 200 and tied > 200
+    with pytest.raises(ValueError):
+        M.banded_extension(b"A", b"A", 3)
+
+
+def test_banded_mirror_on_the_covering_band_is_the_full_rectangle():
+    """B = the covering band: score and best cell are extension_optimum's, and nothing touches unless the path runs along an axis"""
+    rng = np.random.default_rng(32)
+    for t in range(40):
+        v = _rand(rng, int(rng.integers(0, 200)))
+        h = _mutated(rng, v, 0.08) if t % 2 else _rand(rng, int(rng.integers(0, 200)))
+        B = M.trace_cover_band(len(v), len(h))
+        assert B >= 2 * max(len(v), len(h) + 1) and (B == 256 or B // 2 < 2 * max(len(v), len(h) + 1))
+        s, cell, ops, touch = M.banded_extension(h, v, B)
+        assert (s, *cell) == M.extension_optimum(h, v), (h, v)
+        assert not touch
+    assert [M.first_band(b) for b in (0, 1, 256, 257, 300, 512, 1024, 2048, 1 << 18, 1 << 20)] == [256, 256, 256, 512, 512, 512, 1024, 2048, 1 << 18, 1 << 18]
+
+
+@pytest.fixture(scope="module")
+def listed():
+    cases = T.build_cases()
+    return cases, T.expectations(cases)
+
+
+def test_case_list_is_deterministic_and_its_reads_hit_every_packed_offset():
+    a, b = T.build_cases(), T.build_cases()
+    assert [(c.name, c.H, c.V, c.seedH, c.seedV, c.strand, c.aln) for c in a] == [(c.name, c.H, c.V, c.seedH, c.seedV, c.strand, c.aln) for c in b]
+    assert len({c.name for c in a}) == len(a)
+    rs = T.read_set(a)
+    assert rs.nreads == 2 * len(a) and not (rs.lengths % 16 == 0).any() and int(rs.lengths.max()) <= 4500
+    assert set((rs.offsets[:-1] % 16).tolist()) == set(range(16))
+    assert {c.strand for c in a} == {0, 1}
+    for c in a:                                              # the seed lies in both reads, the rectangle in the reads
+        sH, (ml, nl), (mr, nr) = M.rectangles(len(c.H), len(c.V), c.seedH, c.seedV, T.K, c.aln)
+        assert 0 <= c.seedH <= len(c.H) - T.K and 0 <= c.seedV <= len(c.V) - T.K
+        assert (ml, nl, mr, nr) == (sH - c.aln["begH"], c.seedV - c.aln["begV"], c.aln["endH"] - sH - T.K, c.aln["endV"] - c.seedV - T.K)
+    by = {c.name: c for c in a}
+    assert by["tall0_right0"].seedV == 0 and by["tall1_left0"].seedV == len(by["tall1_left0"].V) - T.K      # a seed at position 0 and at len - k
+
+
+def test_case_list_meets_its_coverage_conditions(listed):
+    """on the mirror alone: what the GPU test of the list relies on to reach every kernel below its cover, both edges, every widening"""
+    cases, expect = listed
+    cov = T.coverage(cases, expect)
+    print("TRACE case list: %d cases; side DPs taller than their band %s; touches (low, high) %s; short without widening %d; bookkeeping %s"
+          % (len(cases), cov["tall"], cov["touches"], cov["short"], {b0: T.bookkeeping(expect[b0]) for b0 in T.BAND0S}))
+    T.check_coverage(cov)
+    e0 = {c.name: expect[0][q] for q, c in enumerate(cases)}
+    ec = {c.name: expect[T.BAND0S[-1]][q] for q, c in enumerate(cases)}
+    for total, last in ((130, 512), (260, 1024), (520, 2048)):           # the drift families widen step by step, on either edge, up to the optimum
+        for on, edge in (("V", M.TOUCH_LOW), ("H", M.TOUCH_HIGH)):
+            for name, sd in (("drift%d%s_right0" % (total, on), 1), ("drift%d%s_left1" % (total, on), 0)):
+                rec, _, steps = e0[name]
+                assert [b for b, _ in steps[sd]] == [256 << s for s in range(rec["widened"] + 1)] and steps[sd][-1] == (last, 0), (name, steps)
+                assert all(t == edge for _, t in steps[sd][:-1]) and all(s == (256, 0) for s in steps[1 - sd]) and len(steps[0]) == len(steps[1])
+                assert rec["score"] == ec[name][0]["score"] and rec["band"] == last
+    assert e0["drift_both130_0"][2] == ([(256, M.TOUCH_LOW), (512, 0)], [(256, M.TOUCH_HIGH), (512, 0)])          # two doublings, one repeat
+    assert e0["drift_130H_260V_1"][2] == ([(256, M.TOUCH_HIGH), (512, 0), (512, 0)], [(256, M.TOUCH_LOW), (512, M.TOUCH_LOW), (1024, 0)])
+    assert T.bookkeeping(expect[0])["widened_extensions"] > T.bookkeeping(expect[0])["repeated_pairs"]
+    rec, _, steps = e0["block128V_right0"]                               # 128 reaches p = 0 and widens; 140 stays inside, short of the optimum
+    assert steps[1] == [(256, M.TOUCH_LOW), (512, 0)] and rec["score"] == ec["block128V_right0"][0]["score"]
+    rec, _, steps = e0["block140V_right1"]
+    assert steps == ([(256, 0)], [(256, 0)]) and rec["widened"] == 0 and rec["score"] < ec["block140V_right1"][0]["score"] - 300
+    # the two co-optimal cells of tie_shift lie on one anti-diagonal: the smaller i wins
+    c = next(c for c in cases if c.name == "tie_shift_right0")
+    sH, _, (mr, nr) = M.rectangles(len(c.H), len(c.V), c.seedH, c.seedV, T.K, c.aln)
+    s, cell, _, _, cells = _brute_banded(c.H[sH + T.K:sH + T.K + mr], c.V[c.seedV + T.K:c.seedV + T.K + nr], 256)
+    assert len(cells) == 2 and sum(cells[0]) == sum(cells[1]) and cell == cells[0] and M.banded_extension(c.H[sH + T.K:sH + T.K + mr], c.V[c.seedV + T.K:c.seedV + T.K + nr], 256)[1] == cell
+
+
+def test_pair_level_ops_replay_with_the_records_counters(listed):
+    """every case at every first band: the op words replay on the reads between the record's end points, and counters and score
+    are the ops' own; the seams are merged (replay refuses two adjacent runs with one op)"""
+    cases, expect = listed
+    merged = 0
+    for b0 in T.BAND0S:
+        for c, (rec, ops, steps) in zip(cases, expect[b0]):
+            got = M.replay(ops, M.oriented(c.H, c.strand), c.V, rec["tbegH"], rec["tendH"], rec["tbegV"], rec["tendV"])
+            assert got == {f: rec[f] for f in got}, (c.name, b0)
+            assert rec["band"] == max(s[-1][0] for s in steps) and rec["widened"] == sum(1 for s in steps for a, b in zip(s, s[1:]) if b[0] == 2 * a[0])
+            assert len(steps[0]) == len(steps[1])
+            merged += len(ops) == 1
+    assert merged >= 2 * len(T.BAND0S)                                   # seam_equal_*: one '=' run through both seams
+    seams = {c.name: M.cigar(expect[0][q][1]) for q, c in enumerate(cases) if c.name.startswith("seam")}
+    assert seams["seam_xx_both_0"] == "179=2X7=1X7=2X209=" and seams["seam_all_x_0"] == "180=17X210=", seams
+

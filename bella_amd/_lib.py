@@ -125,6 +125,24 @@ class PolishStats(C.Structure):
                 ("min_depth", C.c_uint32), ("tiles", C.c_uint32), ("decide_ms", C.c_double), ("write_ms", C.c_double)]
 
 
+class GraphTrimParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_depth", C.c_uint32), ("end_clip", C.c_uint32), ("min_span", C.c_uint32)]
+
+
+class ReadClip(C.Structure):
+    _fields_ = [("beg", C.c_uint32), ("end", C.c_uint32), ("nregions", C.c_uint32), ("max_depth", C.c_uint32)]
+
+
+CLIP_DT = np.dtype([("beg", "<u4"), ("end", "<u4"), ("nregions", "<u4"), ("max_depth", "<u4")])
+assert CLIP_DT.itemsize == 16 == C.sizeof(ReadClip)
+
+
+class TrimStats(C.Structure):
+    _fields_ = [("intervals", C.c_uint64), ("reads_clipped", C.c_uint64), ("reads_uncovered", C.c_uint64), ("reads_multi", C.c_uint64),
+                ("bases_before", C.c_uint64), ("bases_after", C.c_uint64), ("records_outside", C.c_uint64), ("events_ms", C.c_double),
+                ("sort_ms", C.c_double), ("sweep_ms", C.c_double), ("host_ms", C.c_double)]
+
+
 # every symbol include/bella_hip.h declares: (name, restype, argtypes)
 vp = C.c_void_p
 SIGNATURES = [
@@ -215,6 +233,10 @@ SIGNATURES = [
     ("bella_hip_graph_polish_unitigs", C.c_int, [vp, C.POINTER(PolishParams), C.POINTER(C.c_uint64)]),
     ("bella_hip_graph_get_polished", C.c_int, [vp, vp, vp, vp, vp, vp]),
     ("bella_hip_graph_get_polish_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_graph_trim", C.c_int, [vp, C.POINTER(GraphTrimParams)]),
+    ("bella_hip_graph_get_trim", C.c_int, [vp, vp]),
+    ("bella_hip_graph_get_trim_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_graph_untrim", C.c_int, [vp]),
     ("bella_hip_write_unitig_gfa", C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
     ("bella_hip_get_timings", C.c_int, [vp, C.POINTER(Timings)]),
     ("bella_hip_get_memory", C.c_int, [vp, C.POINTER(Memory)]),

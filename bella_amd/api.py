@@ -14,6 +14,7 @@ import sys
 import numpy as np
 
 from . import _lib
+from ._lib import CLIP_DT, GraphTrimParams, TrimStats
 from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, POLISH_DT, PolishParams, PolishStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
@@ -518,6 +519,35 @@ class Engine:
         self._chk(self.lib.bella_hip_graph_get_polish_stats(self.h, C.byref(st), C.sizeof(st)))
         return {k: getattr(st, k) for k, _ in st._fields_}
 
+    # ---- coverage trimming ----
+    TRIM_DEFAULTS = dict(min_depth=3, end_clip=500, min_span=1000)
+
+    def graph_trim(self, **params):
+        """clips every read to its longest stretch that at least min_depth accumulated records cover (on the device); graph_build then
+        cuts the records to the clips, and everything downstream works in clipped coordinates, until graph_untrim, new records or
+        new reads.  min_depth, end_clip and min_span default to 3, 500 and 1000"""
+        p = dict(self.TRIM_DEFAULTS)
+        for k, v in params.items():
+            if k not in p:
+                raise TypeError("unknown trim parameter %r" % k)
+            p[k] = int(v)
+        tp = GraphTrimParams(C.sizeof(GraphTrimParams), p["min_depth"], p["end_clip"], p["min_span"])
+        self._chk(self.lib.bella_hip_graph_trim(self.h, C.byref(tp)))
+
+    def graph_clips(self) -> np.ndarray:
+        """CLIP_DT[nreads] of the last graph_trim: beg, end (0, 0 = uncovered), nregions, max_depth"""
+        out = np.zeros(self.nreads, CLIP_DT)
+        self._chk(self.lib.bella_hip_graph_get_trim(self.h, _p(out)))
+        return out
+
+    def trim_stats(self) -> dict:
+        st = TrimStats()
+        self._chk(self.lib.bella_hip_graph_get_trim_stats(self.h, C.byref(st), C.sizeof(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def graph_untrim(self):
+        self._chk(self.lib.bella_hip_graph_untrim(self.h))
+
     def read_bases(self):
         """(offsets uint64[nreads + 1], bases uint8 ASCII) of the loaded reads"""
         offs = np.zeros(self.nreads + 1, np.uint64)
@@ -682,6 +712,23 @@ def write_gfa(filename: str, names, lengths, offsets, edges, contained, seqs=Non
                                  (bases.ctypes.data if len(bases) else boffs.ctypes.data) if bases is not None else None, offs.ctypes.data, _p(edges), _p(cont))
     if rc:
         raise BellaHipError(rc, "bella_hip_write_gfa failed")
+
+
+def trimmed_reads(offsets, bases, clips):
+    """(offsets uint64[nreads + 1], bases uint8) of the reads cut to their clips (what Engine.graph_clips returned), on the host: an
+    uncovered read becomes empty.  Serves the S lines of the trimmed graph and the FASTA of the trimmed reads."""
+    offs = np.asarray(offsets, np.int64)
+    b = np.asarray(bases, np.uint8)
+    clips = np.asarray(clips)
+    assert len(clips) == len(offs) - 1
+    beg, end = clips["beg"].astype(np.int64), clips["end"].astype(np.int64)
+    assert np.all(beg <= end) and np.all(end <= np.diff(offs))
+    n = end - beg
+    out = np.zeros(len(clips) + 1, np.uint64)
+    out[1:] = np.cumsum(n)
+    first = out[:-1].astype(np.int64)
+    idx = np.arange(int(out[-1]), dtype=np.int64) + np.repeat(offs[:-1] + beg - first, n)
+    return out, b[idx]
 
 
 def unitig_names(circular) -> list:

@@ -23,6 +23,7 @@
 #include "core.hpp"
 #include "fastq.hpp"
 #include "graph.hpp"
+#include "trim.hpp"
 #include "kcount.hpp"
 #include "logan.hpp"
 #include "order.hpp"
@@ -229,6 +230,11 @@ struct bella_ctx {
     std::vector<uint8_t> p_bases;
     std::vector<bella_polish_unitig> p_recs;
     bella_polish_stats p_stats{};
+    // coverage trimming (trim.hpp): the clips of the last bella_hip_graph_trim (on the host, 16 bytes per read).  A
+    // graph in the context was always built in the trim state the context is in now: a trim and an untrim drop it.
+    bool have_trim = false;
+    std::vector<bella_read_clip> t_clips;
+    bella_trim_stats t_stats{};
     bella_timings tm{};
     hipEvent_t ev[12]{};
     uint32_t* pinned = nullptr;          // 128 host words the per-pass read backs land in
@@ -1029,8 +1035,8 @@ static int set_reads_impl(bella_ctx* c, const uint64_t* offsets, uint32_t nreads
     c->have_tuples = false;
     for (Buf* b : {&c->pile, &c->cons_out, &c->cons_offs, &c->cons_stats}) release(*b);      // (the pileup belongs to the reads it was sized for)
     c->have_pile = c->have_cons = false;
-    c->g_recs.clear();                                                // (so do the overlap records and the graph)
-    c->have_graph = c->have_unitigs = c->have_polish = false;
+    c->g_recs.clear();                                                // (so do the overlap records, the clips and the graph)
+    c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;
     return 0;
 }
 
@@ -4084,7 +4090,7 @@ int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* 
 int bella_hip_graph_reset(bella_ctx* c) {
     if (!c) return BELLA_ERR_BAD_ARG;
     std::vector<bella_overlap>().swap(c->g_recs);
-    c->have_graph = c->have_unitigs = c->have_polish = false;
+    c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;
     return 0;
 }
 
@@ -4102,7 +4108,7 @@ int bella_hip_graph_add_overlaps(bella_ctx* c, const bella_overlap* recs, uint64
                         r.endH, (long long)l2);
     }
     c->g_recs.insert(c->g_recs.end(), recs, recs + n);
-    c->have_graph = c->have_unitigs = c->have_polish = false;
+    c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;      // (the clips were those of the records before)
     return 0;
 }
 
@@ -4174,12 +4180,21 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     if (int r = ev.create(c, 4)) return r;
     if (n) HIPCHK(c, c->stager.h2d(recs.p, c->g_recs.data(), sizeof(bella_overlap) * (size_t)n, c->stream));
     HIPCHK(c, hipMemsetAsync(cont.p, 0, std::max<size_t>(4 * (size_t)nr, 16), c->stream));
+    TmpBuf clipb;
+    const bella_read_clip* d_clip = nullptr;                              // the clips of bella_hip_graph_trim, while they exist
+    if (c->have_trim && nr) {
+        ENSURE(c, clipb, sizeof(bella_read_clip) * (size_t)nr);
+        HIPCHK(c, c->stager.h2d(clipb.p, c->t_clips.data(), sizeof(bella_read_clip) * (size_t)nr, c->stream));
+        d_clip = ptr<bella_read_clip>(clipb);
+        k_trim_flags<<<nblk(nr), 256, 0, c->stream>>>(d_clip, nr, ptr<uint32_t>(cont));
+        KCHK(c);
+    }
     HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kGcCount, c->stream));
     HIPCHK(c, hipMemsetAsync(deg.p, 0, 4 * ((size_t)nv + 1), c->stream));
     // ---- classes
     HIPCHK(c, hipEventRecord(ev.a, c->stream));
     if (n) {
-        k_graph_classify<<<nblk(n), 256, 0, c->stream>>>(ptr<bella_overlap>(recs), n, ptr<uint64_t>(c->roff), gp.min_overlap, gp.max_overhang, gp.overhang_permille,
+        k_graph_classify<<<nblk(n), 256, 0, c->stream>>>(ptr<bella_overlap>(recs), n, ptr<uint64_t>(c->roff), d_clip, gp.min_overlap, gp.max_overhang, gp.overhang_permille,
                                                          ptr<bella_graph_edge>(cand), ptr<uint32_t>(cont), d_cnt);
         KCHK(c);
     }
@@ -4257,7 +4272,8 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     if (nr) HIPCHK(c, hipMemcpyAsync(cont32.data(), cont.p, 4 * (size_t)nr, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->g_cont.resize(nr);
-    for (uint32_t r = 0; r < nr; ++r) c->g_cont[r] = cont32[r] ? 1 : 0;
+    for (uint32_t r = 0; r < nr; ++r) c->g_cont[r] = (uint8_t)cont32[r];      // 1 contained; 2 uncovered (only with clips)
+    if (c->have_trim) c->t_stats.records_outside = hc[kGcOutside];
     st.n_short = hc[kGcShort]; st.n_internal = hc[kGcInternal]; st.contained_reads = hc[kGcContained];
     st.edges_all = hc[kGcEdgesAll]; st.edges_kept = m; st.edges_reduced = hc[kGcReduced]; st.edges_final = nfinal;
     st.max_degree = hc[kGcMaxDegree]; st.overcap_vertices = hc[kGcOvercap];
@@ -4288,6 +4304,89 @@ int bella_hip_graph_get_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     return put_sized(out, struct_size, c->g_stats);
 }
 
+// ---- coverage trimming (trim.hpp) ------------------------------------------------------------------------------
+int bella_hip_graph_trim(bella_ctx* c, const bella_graph_trim_params* params) {
+    using clk = std::chrono::steady_clock;
+    if (!c) return BELLA_ERR_BAD_ARG;
+    bella_graph_trim_params tp{(uint32_t)sizeof(bella_graph_trim_params), 3, 500, 1000};
+    if (int r = take_params(c, tp, params, "bella_graph_trim_params")) return r;
+    if (tp.min_depth < 1 || tp.min_depth > 0x7FFFFFFFu) return fail(c, BELLA_ERR_BAD_ARG, "trim: min_depth must be in [1, 2^31)");
+    if (tp.end_clip >= (1u << 16)) tp.end_clip = 1u << 16;            // (no read is that long: the same result, and the sums stay small)
+    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const auto t_begin = clk::now();
+    c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;
+    const uint32_t nr = c->nreads, n = (uint32_t)c->g_recs.size();
+    if (nr >= (1u << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 reads");
+    if (n >= (1u << 29)) return fail(c, BELLA_ERR_BAD_ARG, "trim: fewer than 2^29 overlap records (four sort keys each)");
+    const uint64_t nkeys = 4 * (uint64_t)n;
+    bella_trim_stats st{};
+    c->t_clips.assign(nr, bella_read_clip{0, 0, 0, 0});
+    uint32_t nint = 0;
+    if (n && nr) {
+        TmpBuf recs, keys, keysb, evoff, clip, cnt;
+        ENSURE(c, recs, sizeof(bella_overlap) * (size_t)n);
+        ENSURE(c, keys, 8 * (size_t)nkeys); ENSURE(c, keysb, 8 * (size_t)nkeys);
+        ENSURE(c, evoff, 4 * ((size_t)nr + 1));
+        ENSURE(c, clip, sizeof(bella_read_clip) * (size_t)nr);
+        ENSURE(c, cnt, 4);
+        EventSet ev;
+        if (int r = ev.create(c, 4)) return r;
+        HIPCHK(c, c->stager.h2d(recs.p, c->g_recs.data(), sizeof(bella_overlap) * (size_t)n, c->stream));
+        HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4, c->stream));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        k_trim_events<<<nblk(n), 256, 0, c->stream>>>(ptr<bella_overlap>(recs), n, ptr<uint64_t>(c->roff), tp.end_clip, tp.min_span, ptr<uint64_t>(keys), ptr<uint32_t>(cnt));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        int read_bits = 1;                                            // all ones in the sorted bits lies behind every read id
+        while (((1ull << read_bits) - 1) < nr) ++read_bits;
+        CUB(c, hipcub::DeviceRadixSort::SortKeys, ptr<uint64_t>(keys), ptr<uint64_t>(keysb), (int)nkeys, 0, 32 + read_bits, c->stream);
+        k_trim_offsets<<<nblk((uint64_t)nr + 1), 256, 0, c->stream>>>(ptr<uint64_t>(keysb), nkeys, nr, ptr<uint32_t>(evoff));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.d, c->stream));
+        k_trim_sweep<<<nblk(nr, kTrimBlock / 64), kTrimBlock, 0, c->stream>>>(ptr<uint64_t>(keysb), ptr<uint32_t>(evoff), nr, tp.min_depth, tp.min_span,
+                                                                             ptr<bella_read_clip>(clip));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.e, c->stream));
+        HIPCHK(c, c->stager.d2h(c->t_clips.data(), clip.p, sizeof(bella_read_clip) * (size_t)nr, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&nint, cnt.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.events_ms = ev_ms(ev.a, ev.b); st.sort_ms = ev_ms(ev.b, ev.d); st.sweep_ms = ev_ms(ev.d, ev.e);
+    }
+    st.intervals = nint;
+    for (uint32_t r = 0; r < nr; ++r) {
+        const bella_read_clip& k = c->t_clips[r];
+        st.bases_before += c->host_lens[r];
+        st.bases_after += k.end - k.beg;
+        if (k.end == k.beg) ++st.reads_uncovered;
+        else if (k.beg != 0 || k.end != c->host_lens[r]) ++st.reads_clipped;
+        if (k.nregions >= 2) ++st.reads_multi;
+    }
+    st.host_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    c->t_stats = st;
+    c->have_trim = true;
+    return 0;
+}
+
+int bella_hip_graph_get_trim(bella_ctx* c, bella_read_clip* out) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!c->have_trim) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_trim first");
+    if (out && !c->t_clips.empty()) std::memcpy(out, c->t_clips.data(), sizeof(bella_read_clip) * c->t_clips.size());
+    return 0;
+}
+
+int bella_hip_graph_get_trim_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    if (!c->have_trim) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_trim first");
+    return put_sized(out, struct_size, c->t_stats);
+}
+
+int bella_hip_graph_untrim(bella_ctx* c) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (c->have_trim) c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;
+    return 0;
+}
+
 }  // extern "C"
 
 // ---- unitigs (unitig.hpp) -----------------------------------------------------------------------------------------
@@ -4304,6 +4403,25 @@ int graph_upload(bella_ctx* c, Buf& off, Buf& edges) {
     HIPCHK(c, hipStreamSynchronize(c->stream));                       // (off32 leaves scope)
     return 0;
 }
+
+// Where every read's span begins and ends among all bases, for the kernels that read bases along the unitigs: roff and roff + 1 (whole
+// reads), or the clipped spans while the context holds clips (trim.hpp).
+struct ReadSpans {
+    TmpBuf clipb, begs, ends;
+    const uint64_t *beg = nullptr, *end = nullptr;
+    int make(bella_ctx* c) {
+        const uint32_t nr = c->nreads;
+        beg = ptr<uint64_t>(c->roff); end = ptr<uint64_t>(c->roff) + 1;
+        if (!c->have_trim || !nr) return 0;
+        ENSURE(c, clipb, sizeof(bella_read_clip) * (size_t)nr);
+        ENSURE(c, begs, 8 * (size_t)nr); ENSURE(c, ends, 8 * (size_t)nr);
+        HIPCHK(c, c->stager.h2d(clipb.p, c->t_clips.data(), sizeof(bella_read_clip) * (size_t)nr, c->stream));
+        k_trim_spans<<<nblk(nr), 256, 0, c->stream>>>(ptr<bella_read_clip>(clipb), ptr<uint64_t>(c->roff), nr, ptr<uint64_t>(begs), ptr<uint64_t>(ends));
+        KCHK(c);
+        beg = ptr<uint64_t>(begs); end = ptr<uint64_t>(ends);
+        return 0;
+    }
+};
 
 // What tip clipping and bubble popping share: the graph and the removed-read marks on the device, the buffers a round filters and
 // compacts with, the stage's two events.  A stage marks the reads of a round in `hit`, the edges that stay in `keep`, scans `keep`
@@ -4503,6 +4621,8 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
             ucirc, gseg, lflag, lscan, links, out;
         int rc = graph_upload(c, off, E);
         if (rc) return rc;
+        ReadSpans spans;
+        if ((rc = spans.make(c))) return rc;
         ENSURE(c, dd, nr);
         for (Buf* b : {&succ, &pred, &outlen, &inlen, &tail_of, &cnt_of}) ENSURE(c, *b, 4 * (size_t)nv);
         for (Buf* b : {&emit, &nvert, &uid, &voff}) ENSURE(c, *b, 4 * ((size_t)nv + 1));
@@ -4586,7 +4706,7 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
         ENSURE(c, ucirc, nutg);
         ENSURE(c, links, sizeof(bella_unitig_link) * (size_t)nlk);
         HIPCHK(c, hipMemsetAsync(ulen.p, 0, 8 * ((size_t)nutg + 1), c->stream));
-        k_utg_scatter<<<nblk(nv), 256, 0, c->stream>>>(rank, ptr<uint32_t>(succ), ptr<uint32_t>(outlen), ptr<uint32_t>(inlen), d_cut, ptr<uint8_t>(dd), ptr<uint64_t>(c->roff),
+        k_utg_scatter<<<nblk(nv), 256, 0, c->stream>>>(rank, ptr<uint32_t>(succ), ptr<uint32_t>(outlen), ptr<uint32_t>(inlen), d_cut, ptr<uint8_t>(dd), spans.beg, spans.end,
                                                        ptr<uint32_t>(emit), ptr<uint32_t>(uid), ptr<uint32_t>(voff), nv, ptr<uint32_t>(verts), ptr<uint64_t>(pos),
                                                        ptr<uint32_t>(nb), ptr<uint32_t>(slot_utg), ptr<uint64_t>(uvoff), ptr<uint64_t>(ulen), ptr<uint8_t>(ucirc));
         KCHK(c);
@@ -4605,7 +4725,7 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
         ENSURE(c, out, (size_t)(nlanes * kUtgBasesPerLane));
         HIPCHK(c, hipEventRecord(ev.d, c->stream));
         if (total) {
-            k_utg_gather<<<nblk(nlanes), 256, 0, c->stream>>>(ptr<uint64_t>(gseg), ptr<uint32_t>(verts), ptr<uint32_t>(nb), nverts, total, ptr<uint64_t>(c->roff),
+            k_utg_gather<<<nblk(nlanes), 256, 0, c->stream>>>(ptr<uint64_t>(gseg), ptr<uint32_t>(verts), ptr<uint32_t>(nb), nverts, total, spans.beg, spans.end,
                                                               ptr<uint32_t>(c->packed), ptr<uint4>(out));
             KCHK(c);
         }
@@ -4727,9 +4847,11 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
         EventSet ev;
         int rc = ev.create(c, 4);
         if (rc) return rc;
+        ReadSpans spans;
+        if ((rc = spans.make(c))) return rc;
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
         k_pol_decide<<<(uint32_t)ntiles, kPolBlock, 0, c->stream>>>(ptr<uint64_t>(gseg), ptr<uint32_t>(verts), ptr<uint32_t>(slot_utg), nseg, total, ptr<uint64_t>(c->roff),
-                                                                    ptr<uint32_t>(c->packed), ptr<uint32_t>(c->pile), pp.min_depth, ptr<uint8_t>(emit),
+                                                                    spans.beg, spans.end, ptr<uint32_t>(c->packed), ptr<uint32_t>(c->pile), pp.min_depth, ptr<uint8_t>(emit),
                                                                     ptr<bella_polish_unitig>(recs), ptr<uint32_t>(tcnt));
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.b, c->stream));

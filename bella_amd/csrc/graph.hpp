@@ -4,7 +4,7 @@
 // down in DESIGN.md section 11 and in include/bella_hip.h.  Everything is an integer, so the result is the numpy mirror's exactly.
 //
 // Passes.  k_graph_classify: one thread per record, the class and the record's two edge candidates (2 i and 2 i + 1: an edge's twin is
-// the other candidate of its record), contained flags with ordinary atomics.  k_graph_filter: candidates without a contained end, their
+// the other candidate of its record), contained flags with ordinary atomics; with the clips of trim.hpp the record is cut first.  k_graph_filter: candidates without a contained end, their
 // degrees.  The lists: two stable device radix sorts (by dst, then by src << 32 | len; a dropped candidate's key is all ones and lands
 // behind the kept ones), an exclusive scan of the degrees, a gather that also records where every candidate went (pos: the twin pass
 // finds an edge's twin there without a search).
@@ -32,7 +32,7 @@ constexpr int kGraphBlock = 256;            // four independent wavefronts
 constexpr uint32_t kGraphNone = 0xFFFFFFFFu;
 enum { kGrInplay = 1, kGrEliminated = 2 };
 // device counters of a build (uint32 each)
-enum { kGcShort = 0, kGcInternal, kGcEdgesAll, kGcEdgesKept, kGcReduced, kGcContained, kGcMaxDegree, kGcOvercap, kGcDuplicate, kGcFinal, kGcCount };
+enum { kGcShort = 0, kGcInternal, kGcEdgesAll, kGcEdgesKept, kGcReduced, kGcContained, kGcMaxDegree, kGcOvercap, kGcDuplicate, kGcFinal, kGcOutside, kGcCount };
 
 struct GraphKeyDst {       // the low word of a (src << 32 | dst) key
     __host__ __device__ uint32_t operator()(const uint64_t& v) const { return (uint32_t)v; }
@@ -44,19 +44,36 @@ __device__ __forceinline__ void graph_count(uint32_t* counter, bool pred) {     
     if (m && (threadIdx.x & 63) == (unsigned)__ffsll((long long)m) - 1) atomicAdd(counter, (uint32_t)__popcll(m));
 }
 
-__global__ __launch_bounds__(256) void k_graph_classify(const bella_overlap* recs, uint32_t n, const uint64_t* roff, uint32_t min_overlap, uint32_t max_overhang,
-                                                        uint32_t permille, bella_graph_edge* cand, uint32_t* contained, uint32_t* counters) {
+// clip == nullptr: the records as they are.  Otherwise every record is cut to its reads' clips first (trim.hpp): a
+// record with an uncovered read or an emptied interval is OUTSIDE, gives no candidates and is counted; the others are classified in
+// clipped coordinates with the clipped lengths.
+__global__ __launch_bounds__(256) void k_graph_classify(const bella_overlap* recs, uint32_t n, const uint64_t* roff, const bella_read_clip* clip, uint32_t min_overlap,
+                                                        uint32_t max_overhang, uint32_t permille, bella_graph_edge* cand, uint32_t* contained, uint32_t* counters) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < n;
-    bool is_short = false, is_internal = false;
+    bool is_short = false, is_internal = false, is_outside = false;
     if (live) {
         const bella_overlap r = recs[i];
-        const int64_t l1 = (int64_t)(roff[r.cid + 1] - roff[r.cid]), l2 = (int64_t)(roff[r.rid + 1] - roff[r.rid]);
-        const int64_t b1 = r.begV, e1 = r.endV, b2 = r.begH, e2 = r.endH, t1 = l1 - e1, t2 = l2 - e2;
+        int64_t l1 = (int64_t)(roff[r.cid + 1] - roff[r.cid]), l2 = (int64_t)(roff[r.rid + 1] - roff[r.rid]);
+        int64_t b1 = r.begV, e1 = r.endV, b2 = r.begH, e2 = r.endH;
         const uint32_t s = r.strand ? 1u : 0u;
+        if (clip) {
+            const bella_read_clip c1 = clip[r.cid], c2 = clip[r.rid];
+            if (c1.end == c1.beg || c2.end == c2.beg) is_outside = true;
+            else {
+                const int64_t cs1 = c1.beg, ce1 = c1.end, c2s = s ? l2 - (int64_t)c2.end : (int64_t)c2.beg, c2e = s ? l2 - (int64_t)c2.beg : (int64_t)c2.end;
+                int64_t db = cs1 - b1 > c2s - b2 ? cs1 - b1 : c2s - b2, de = e1 - ce1 > e2 - c2e ? e1 - ce1 : e2 - c2e;
+                db = db > 0 ? db : 0; de = de > 0 ? de : 0;
+                b1 += db; b2 += db; e1 -= de; e2 -= de;
+                if (e1 <= b1 || e2 <= b2) is_outside = true;
+                else { b1 -= cs1; e1 -= cs1; b2 -= c2s; e2 -= c2s; l1 = ce1 - cs1; l2 = c2e - c2s; }
+            }
+        }
+        const int64_t t1 = l1 - e1, t2 = l2 - e2;
         bella_graph_edge a{kGraphNone, kGraphNone, 0, 0, i, 0}, b{kGraphNone, kGraphNone, 0, 0, i, BELLA_GRAPH_EDGE_TWIN};
         const int64_t overhang = (b1 < b2 ? b1 : b2) + (t1 < t2 ? t1 : t2), maplen = e1 - b1 > e2 - b2 ? e1 - b1 : e2 - b2;
-        if (e1 - b1 < (int64_t)min_overlap || e2 - b2 < (int64_t)min_overlap) is_short = true;
+        if (is_outside) {}
+        else if (e1 - b1 < (int64_t)min_overlap || e2 - b2 < (int64_t)min_overlap) is_short = true;
         else if (overhang > (int64_t)max_overhang || (uint64_t)(1000 * overhang) > (uint64_t)permille * (uint64_t)maplen) is_internal = true;
         else if (b1 <= b2 && t1 <= t2) atomicOr(contained + r.cid, 1u);
         else if (b1 >= b2 && t1 >= t2) atomicOr(contained + r.rid, 1u);
@@ -72,6 +89,7 @@ __global__ __launch_bounds__(256) void k_graph_classify(const bella_overlap* rec
     }
     graph_count(counters + kGcShort, is_short);
     graph_count(counters + kGcInternal, is_internal);
+    if (clip) graph_count(counters + kGcOutside, is_outside);
 }
 
 // candidates without a contained end: ok[e], the degree of their source, the first sort's key (dst) and value (e)
@@ -116,7 +134,7 @@ __global__ void k_graph_vertex_stats(const uint32_t* off, uint32_t nv, const uin
     const uint32_t deg = v < nv ? off[v + 1] - off[v] : 0u;
     if (deg) atomicMax(counters + kGcMaxDegree, deg);
     graph_count(counters + kGcOvercap, deg > cap);
-    graph_count(counters + kGcContained, v < nreads && contained[v] != 0);
+    graph_count(counters + kGcContained, v < nreads && (contained[v] & 1u) != 0);      // (bit 1: uncovered, trim.hpp)
 }
 
 __device__ __forceinline__ void graph_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }

@@ -44,10 +44,11 @@ __device__ __forceinline__ uint32_t pol_count4(uint32_t w, uint32_t nb) {
 }
 
 // gseg[nseg + 1]: where every segment's raw bases begin among all unitig positions (k_utg_segoff); emit holds ntiles * kPolTile bytes
-// (the positions behind `total` get 0); recs is zeroed on entry.
+// (the positions behind `total` get 0); recs is zeroed on entry.  rbeg[r] / rend[r]: read r's span among all bases (whole reads: roff and
+// roff + 1; clipped reads: trim.hpp's spans).
 __global__ __launch_bounds__(kPolBlock) void k_pol_decide(const uint64_t* gseg, const uint32_t* verts, const uint32_t* slot_utg, uint32_t nseg, uint64_t total,
-                                                          const uint64_t* roff, const uint32_t* packed, const uint32_t* table, uint32_t min_depth, uint8_t* emit,
-                                                          bella_polish_unitig* recs, uint32_t* tile_cnt) {
+                                                          const uint64_t* roff, const uint64_t* rbeg, const uint64_t* rend, const uint32_t* packed, const uint32_t* table,
+                                                          uint32_t min_depth, uint8_t* emit, bella_polish_unitig* recs, uint32_t* tile_cnt) {
     __shared__ uint32_t wsum[kPolBlock / 64];
     const uint64_t base = (uint64_t)blockIdx.x * kPolTile;
     const int lane = (int)(threadIdx.x & 63);
@@ -69,10 +70,9 @@ __global__ __launch_bounds__(kPolBlock) void k_pol_decide(const uint64_t* gseg, 
         const uint64_t g = live ? g0 : total - 1;
         while (g >= end && s + 1 < nseg) { ++s; beg = end; end = gseg[s + 1]; }
         const uint32_t v = verts[s], r = v >> 1;
-        const uint64_t rb = roff[r];
-        const uint32_t L = (uint32_t)(roff[r + 1] - rb), i = (uint32_t)(g - beg);
-        const uint32_t p = (v & 1u) ? L - 1 - i : i;
-        const uint64_t row = rb + p;
+        const uint64_t i = g - beg;
+        const uint64_t row = (v & 1u) ? rend[r] - 1 - i : rbeg[r] + i;
+        const uint32_t p = (uint32_t)(row - roff[r]);                 // the ORIGINAL position: the junction rule and the table know no clip
         const ConsDecision d = cons_decide_at(table + row * kPileCounters, p, pile_base(packed, row), min_depth);
         uint32_t e = d.emit;
         if (v & 1u) {                                                 // rc of the decision string: the position's base first, then the junction's

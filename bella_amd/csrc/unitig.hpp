@@ -168,8 +168,8 @@ __global__ void k_utg_select(const uint32_t* pred, const uint8_t* cut, const uin
 }
 
 __global__ void k_utg_scatter(const UtgRank* st, const uint32_t* succ, const uint32_t* outlen, const uint32_t* inlen, const uint8_t* cut, const uint8_t* dead,
-                              const uint64_t* roff, const uint32_t* emit, const uint32_t* uid, const uint32_t* voff, uint32_t nv, uint32_t* verts, uint64_t* pos,
-                              uint32_t* nb, uint32_t* slot_utg, uint64_t* u_voff, uint64_t* u_len, uint8_t* u_circ) {
+                              const uint64_t* rbeg, const uint64_t* rend, const uint32_t* emit, const uint32_t* uid, const uint32_t* voff, uint32_t nv, uint32_t* verts,
+                              uint64_t* pos, uint32_t* nb, uint32_t* slot_utg, uint64_t* u_voff, uint64_t* u_len, uint8_t* u_circ) {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= nv || dead[v >> 1]) return;
     const UtgRank s = st[v];
@@ -178,7 +178,7 @@ __global__ void k_utg_scatter(const UtgRank* st, const uint32_t* succ, const uin
     const uint32_t u = uid[h], slot = voff[h] + s.rank;
     const bool tail = utg_is_tail(succ, cut, v), circ = cut && cut[h];
     const uint32_t r = v >> 1;
-    const uint32_t n = tail ? (circ ? inlen[h] : (uint32_t)(roff[r + 1] - roff[r])) : outlen[v];
+    const uint32_t n = tail ? (circ ? inlen[h] : (uint32_t)(rend[r] - rbeg[r])) : outlen[v];
     verts[slot] = v;
     pos[slot] = s.dist;
     nb[slot] = n;
@@ -226,9 +226,10 @@ __device__ __forceinline__ uint32_t utg_codes16(const uint32_t* packed, uint64_t
     return (uint32_t)(two >> sh);
 }
 
-// out holds ceil(total / 16) * 16 bytes; roff / packed: the loaded reads; gseg[nseg + 1], verts[nseg], nb[nseg]
-__global__ __launch_bounds__(256) void k_utg_gather(const uint64_t* gseg, const uint32_t* verts, const uint32_t* nb, uint32_t nseg, uint64_t total, const uint64_t* roff,
-                                                    const uint32_t* packed, uint4* out) {
+// out holds ceil(total / 16) * 16 bytes; packed: the loaded reads; rbeg[r] / rend[r]: where read r's span begins and ends among all
+// bases (whole reads: roff and roff + 1; clipped reads: trim.hpp's spans); gseg[nseg + 1], verts[nseg], nb[nseg]
+__global__ __launch_bounds__(256) void k_utg_gather(const uint64_t* gseg, const uint32_t* verts, const uint32_t* nb, uint32_t nseg, uint64_t total, const uint64_t* rbeg,
+                                                    const uint64_t* rend, const uint32_t* packed, uint4* out) {
     const uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t g0 = lane * kUtgBasesPerLane;
     if (g0 >= total) return;
@@ -243,10 +244,9 @@ __global__ __launch_bounds__(256) void k_utg_gather(const uint64_t* gseg, const 
     if (g0 + kUtgBasesPerLane <= end) {                                 // all 16 bases inside one segment
         const uint32_t v = verts[s], r = v >> 1;
         const uint64_t i = g0 - beg;
-        if (!(v & 1u)) codes = utg_codes16(packed, roff[r] + i);
+        if (!(v & 1u)) codes = utg_codes16(packed, rbeg[r] + i);
         else {
-            const uint64_t L = roff[r + 1] - roff[r];
-            uint32_t x = utg_codes16(packed, roff[r] + L - 16 - i);     // bases L-1-i-15 .. L-1-i, to be reversed and complemented
+            uint32_t x = utg_codes16(packed, rend[r] - 16 - i);         // bases L-1-i-15 .. L-1-i of the span, to be reversed and complemented
             x = __brev(x);
             x = ((x & 0x55555555u) << 1) | ((x >> 1) & 0x55555555u);
             codes = ~x;
@@ -258,8 +258,8 @@ __global__ __launch_bounds__(256) void k_utg_gather(const uint64_t* gseg, const 
             if (g >= total) break;
             while (g >= end && s + 1 < nseg) { ++s; beg = end; end = gseg[s + 1]; }
             const uint32_t v = verts[s], r = v >> 1;
-            const uint64_t i = g - beg, L = roff[r + 1] - roff[r];
-            const uint64_t at = roff[r] + ((v & 1u) ? L - 1 - i : i);
+            const uint64_t i = g - beg;
+            const uint64_t at = (v & 1u) ? rend[r] - 1 - i : rbeg[r] + i;
             uint32_t code = (packed[at >> 4] >> ((uint32_t)(at & 15) * 2)) & 3u;
             if (v & 1u) code ^= 3u;
             codes |= code << (2 * j);

@@ -122,6 +122,9 @@ struct StageOpts {
     uint32_t bubble_reads = 64, bubble_dist = 50000, bubble_rounds = 3;
     int polish = 0;                  // unitig consensus: every stage's traced pairs vote as with correct; the unitigs files carry the
     uint32_t polish_min_depth = 3;   // polished sequences and coordinates
+    int trim = 0;                    // coverage trimming: the reads are clipped to their longest well-covered stretch before the graph
+    uint32_t trim_depth = 3, trim_end_clip = 500;     // is built (min_span = gfa_min_overlap); every graph file is in clipped coordinates
+    const char* trimmed_reads = nullptr;              // the clipped reads as FASTA, in input order, without the uncovered ones
     bool graph() const { return gfa || unitigs || unitigs_fasta; }
     bool pileup() const { return correct || polish; }
 };
@@ -145,12 +148,59 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
         check(c0, bella_hip_graph_reset(c0), "bella_hip_graph_reset");
         check(c0, bella_hip_graph_add_overlaps(c0, all.data(), all.size()), "bella_hip_graph_add_overlaps");
     }
+    std::vector<bella_read_clip> clips;                              // --trim: on context 0, after the records are gathered: -m and -g change nothing
+    if (o.trim) {
+        bella_graph_trim_params tp;
+        tp.struct_size = (uint32_t)sizeof(tp);
+        tp.min_depth = o.trim_depth; tp.end_clip = o.trim_end_clip; tp.min_span = o.gfa_min_overlap;
+        check(c0, bella_hip_graph_trim(c0, &tp), "bella_hip_graph_trim");
+        clips.resize(o.nreads);
+        check(c0, bella_hip_graph_get_trim(c0, clips.data()), "bella_hip_graph_get_trim");
+    }
     bella_graph_params gp;
     gp.struct_size = (uint32_t)sizeof(gp);
     gp.min_overlap = o.gfa_min_overlap; gp.max_overhang = o.gfa_max_overhang; gp.overhang_permille = 800; gp.fuzz = o.gfa_fuzz;
     check(c0, bella_hip_graph_build(c0, &gp), "bella_hip_graph_build");
     std::vector<uint64_t> boffs;
     RawBuf<uint8_t> bases;
+    std::vector<uint32_t> clens;                                      // --trim: the clipped lengths; the reads' bases are cut to the clips in place
+    auto read_bases = [&]() {
+        if (!boffs.empty()) return;
+        boffs.assign((size_t)o.nreads + 1, 0);
+        check(c0, bella_hip_get_read_bases(c0, boffs.data(), nullptr), "bella_hip_get_read_bases");
+        bases.resize((size_t)boffs[o.nreads] + 1);
+        check(c0, bella_hip_get_read_bases(c0, nullptr, bases.data()), "bella_hip_get_read_bases");
+        if (!o.trim) return;
+        uint64_t at = 0;
+        for (uint32_t r = 0; r < o.nreads; ++r) {
+            const uint64_t from = boffs[r] + clips[r].beg, n = clips[r].end - clips[r].beg;
+            std::memmove(bases.data() + at, bases.data() + from, (size_t)n);
+            boffs[r] = at;
+            at += n;
+        }
+        boffs[o.nreads] = at;
+    };
+    if (o.trim) {
+        clens.resize(o.nreads);
+        for (uint32_t r = 0; r < o.nreads; ++r) clens[r] = clips[r].end - clips[r].beg;
+        lens = clens.data();
+        bella_trim_stats ts;
+        check(c0, bella_hip_graph_get_trim_stats(c0, &ts, sizeof(ts)), "bella_hip_graph_get_trim_stats");
+        const std::string Trim = std::to_string(ts.intervals) + " intervals, " + std::to_string(ts.reads_clipped) + " reads clipped, " + std::to_string(ts.reads_uncovered) +
+                                 " uncovered, " + std::to_string(ts.reads_multi) + " with two or more regions, " + std::to_string(ts.bases_before) + " -> " +
+                                 std::to_string(ts.bases_after) + " bases, " + std::to_string(ts.records_outside) + " records outside";
+        BELLA_HIP_LOGT(o.tag, Trim);
+        if (o.trimmed_reads) {
+            read_bases();
+            std::vector<const char*> tnames;
+            std::vector<uint64_t> toffs(1, 0);
+            for (uint32_t r = 0; r < o.nreads; ++r)
+                if (clens[r]) { tnames.push_back(names[r]); toffs.push_back(boffs[r + 1]); }      // (an uncovered read is empty: the offsets stay consecutive)
+            toffs[0] = boffs[0];
+            const int wrc = bella_hip_write_fasta(o.trimmed_reads, (uint32_t)tnames.size(), tnames.data(), toffs.data(), bases.data(), 0);
+            if (wrc) check(nullptr, wrc, "bella_hip_write_fasta");
+        }
+    }
     auto write_gfa = [&]() {                                          // the context's current graph
         uint32_t nv = 0;
         uint64_t ne = 0;
@@ -161,12 +211,7 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
         check(c0, bella_hip_graph_get(c0, nullptr, nullptr, offs.data(), edges.data(), contained.data()), "bella_hip_graph_get");
         check(c0, bella_hip_graph_get_removed(c0, removed.data()), "bella_hip_graph_get_removed");
         for (uint32_t r = 0; r < o.nreads; ++r) contained[r] |= removed[r];
-        if (!o.gfa_no_seq) {
-            boffs.assign((size_t)o.nreads + 1, 0);
-            check(c0, bella_hip_get_read_bases(c0, boffs.data(), nullptr), "bella_hip_get_read_bases");
-            bases.resize((size_t)boffs[o.nreads] + 1);
-            check(c0, bella_hip_get_read_bases(c0, nullptr, bases.data()), "bella_hip_get_read_bases");
-        }
+        if (!o.gfa_no_seq) read_bases();
         const int wrc = bella_hip_write_gfa(o.gfa, o.nreads, names, lens, o.gfa_no_seq ? nullptr : boffs.data(), o.gfa_no_seq ? nullptr : bases.data(), offs.data(), edges.data(),
                                             contained.data());
         if (wrc) check(nullptr, wrc, "bella_hip_write_gfa");

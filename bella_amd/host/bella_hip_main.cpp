@@ -22,6 +22,10 @@
 // --polish: unitig consensus: every stage's traced pairs vote as with --correct, the unitigs are polished from
 // the pileup on the device after the last stage; --unitigs / --unitigs-fasta then carry the polished sequences and coordinates.
 //
+// --trim: coverage trimming: after the last stage every read is clipped, on the device, to its longest stretch that
+// --trim-depth overlap records cover; the graph is built from the records cut to the clips, and --gfa / --unitigs / --unitigs-fasta are in
+// clipped coordinates; --trimmed-reads FILE: the clipped reads as FASTA.
+//
 // Not built (rejected loudly): --hopc, --estimate, --split-count > 1.
 #include <sys/stat.h>
 #include <chrono>
@@ -54,6 +58,9 @@ struct Options {
     bool pop_bubbles = false, bubble_param_given = false;
     int polish_min_depth = 3;
     bool polish = false, polish_param_given = false;
+    int trim_depth = 3, trim_end_clip = 500;
+    std::string trimmed_reads;
+    bool trim = false, trim_param_given = false;
     bool graph() const { return !gfa.empty() || !unitigs.empty() || !unitigs_fasta.empty(); }
 };
 
@@ -101,6 +108,11 @@ const char* kHelp =
     "      --bubble-rounds arg    ... and the number of popping rounds (default: 3)\n"
     "      --polish               with --unitigs / --unitigs-fasta: unitig consensus from the pileup of the base-level alignments, on the device\n"
     "      --polish-min-depth arg with --polish: votes a position needs before it is changed (default: 3)\n"
+    "      --trim                 with --gfa / --unitigs / --unitigs-fasta: clip every read to its longest stretch that --trim-depth overlaps cover, on the\n"
+    "                             device, before the graph is built (shortest stretch: --gfa-min-overlap); the graph files are in clipped coordinates\n"
+    "      --trim-depth arg       with --trim: overlaps a position needs to count as covered (default: 3)\n"
+    "      --trim-end-clip arg    with --trim: bases an overlap's inner ends are shortened by before it is counted (default: 500)\n"
+    "      --trimmed-reads arg    with --trim: the clipped reads (FASTA), in input order, without the uncovered ones\n"
     "  -h, --help                 Usage\n";
 
 [[noreturn]] void die(const std::string& msg) {
@@ -124,6 +136,7 @@ Options parse(int argc, char** argv) {
         {"unitigs", 0, 3, &o.unitigs}, {"unitigs-fasta", 0, 3, &o.unitigs_fasta}, {"tip-reads", 0, 1, &o.tip_reads}, {"tip-rounds", 0, 1, &o.tip_rounds}, {"gfa-clean", 0, 0, &o.gfa_clean},
         {"pop-bubbles", 0, 0, &o.pop_bubbles}, {"bubble-reads", 0, 1, &o.bubble_reads}, {"bubble-dist", 0, 1, &o.bubble_dist}, {"bubble-rounds", 0, 1, &o.bubble_rounds},
         {"polish", 0, 0, &o.polish}, {"polish-min-depth", 0, 1, &o.polish_min_depth},
+        {"trim", 0, 0, &o.trim}, {"trim-depth", 0, 1, &o.trim_depth}, {"trim-end-clip", 0, 1, &o.trim_end_clip}, {"trimmed-reads", 0, 3, &o.trimmed_reads},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
         char* end = nullptr;
@@ -163,6 +176,7 @@ Options parse(int argc, char** argv) {
         if (sp->dst == &o.tip_reads || sp->dst == &o.tip_rounds) o.tip_param_given = true;
         if (sp->dst == &o.bubble_reads || sp->dst == &o.bubble_dist || sp->dst == &o.bubble_rounds) o.bubble_param_given = true;
         if (sp->dst == &o.polish_min_depth) o.polish_param_given = true;
+        if (sp->dst == &o.trim_depth || sp->dst == &o.trim_end_clip || sp->dst == &o.trimmed_reads) o.trim_param_given = true;
     }
     return o;
 }
@@ -231,6 +245,9 @@ int main(int argc, char** argv) {
     if (o.polish && o.unitigs.empty() && o.unitigs_fasta.empty()) die("--polish needs --unitigs or --unitigs-fasta");
     if (o.polish && o.gfa_no_seq && o.unitigs_fasta.empty()) die("--polish with --gfa-no-seq needs --unitigs-fasta (there is no sequence to polish into)");
     if (o.polish && o.polish_min_depth < 1) die("--polish-min-depth must be at least 1");
+    if (o.trim_param_given && !o.trim) die("--trim-depth, --trim-end-clip and --trimmed-reads need --trim");
+    if (o.trim && !o.graph()) die("--trim needs --gfa, --unitigs or --unitigs-fasta");
+    if (o.trim && (o.trim_depth < 1 || o.trim_end_clip < 0)) die("--trim-depth must be at least 1 and --trim-end-clip must not be negative");
     if (o.gfa_fuzz < 0 || o.gfa_max_overhang < 0 || o.gfa_min_overlap < 0) die("--gfa-fuzz, --gfa-max-overhang and --gfa-min-overlap must not be negative");
     if (!o.correct.empty() && o.skip_alignment) die("--correct cannot be combined with --skip-alignment (the pileup is made of base-level alignments)");
     if (o.min_depth_given && o.min_depth < 1) die("--min-depth must be at least 1");
@@ -384,6 +401,9 @@ int main(int argc, char** argv) {
     so.bubble_reads = (uint32_t)o.bubble_reads; so.bubble_dist = (uint32_t)o.bubble_dist; so.bubble_rounds = (uint32_t)o.bubble_rounds;
     so.polish = o.polish ? 1 : 0;
     so.polish_min_depth = (uint32_t)o.polish_min_depth;
+    so.trim = o.trim ? 1 : 0;
+    so.trim_depth = (uint32_t)o.trim_depth; so.trim_end_clip = (uint32_t)o.trim_end_clip;
+    so.trimmed_reads = o.trimmed_reads.empty() ? nullptr : o.trimmed_reads.c_str();
     const double t_stages = now_s();
     run_stages(W, so, names.data(), lens.data());
     {

@@ -97,6 +97,12 @@ void HashSpGEMM(const CSC<uint32_t, unsigned short>& A, const CSC<uint32_t, unsi
         else if (*e) std::cerr << "bella_hip: BELLA_HIP_GFA is set but ignored: it needs an alignment (no --skip-alignment)" << std::endl;
     }
     if (const char* e = std::getenv("BELLA_HIP_GFA_NO_SEQ")) o.gfa_no_seq = (*e && *e != '0') ? 1 : 0;
+    // BELLA_HIP_TRIM=1: the reads are clipped to their well-covered stretch before the graph is built (the defaults)
+    if (const char* e = std::getenv("BELLA_HIP_TRIM")) {
+        const bool want = *e && *e != '0';
+        o.trim = (want && o.gfa) ? 1 : 0;
+        if (want && !o.trim) std::cerr << "bella_hip: BELLA_HIP_TRIM is set but ignored: it needs BELLA_HIP_GFA" << std::endl;
+    }
     if (const char* e = std::getenv("BELLA_HIP_MIN_DEPTH")) {
         const unsigned long v = std::strtoul(e, nullptr, 10);
         if (v < 1 || v > 0xFFFFFFFFul) std::cerr << "bella_hip: BELLA_HIP_MIN_DEPTH must be at least 1: ignored" << std::endl;

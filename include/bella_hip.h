@@ -472,10 +472,12 @@ int bella_hip_graph_add_overlaps(bella_ctx* ctx, const bella_overlap* recs, uint
 int bella_hip_graph_add_traced(bella_ctx* ctx, uint64_t* added);
 /* The accumulated records: *n = their number; out (nullable) receives them.  How several contexts merge: one of them adds the others'. */
 int bella_hip_graph_get_overlaps(bella_ctx* ctx, bella_overlap* out, uint64_t* n);
-/* Classifies, builds the lists, reduces (all on the device).  params == NULL: the documented defaults.  An empty record set gives an empty graph. */
+/* Classifies, builds the lists, reduces (all on the device).  params == NULL: the documented defaults.  An empty record set gives an empty graph.
+ * While the clips of bella_hip_graph_trim exist (the coverage trimming section below) every record is cut to them first. */
 int bella_hip_graph_build(bella_ctx* ctx, const bella_graph_params* params);
 /* *nvertices = 2 nreads, *nedges = final edges (size query: every other pointer NULL); offsets[2 nreads + 1] (CSR over the vertices),
- * edges[nedges] in list order, contained[nreads] (0 / 1).  Any pointer may be NULL.  BELLA_ERR_STATE without a built graph. */
+ * edges[nedges] in list order, contained[nreads] (0 / 1; 2 for an uncovered read, only while the clips of bella_hip_graph_trim exist: such a
+ * read is dead downstream like a contained one).  Any pointer may be NULL.  BELLA_ERR_STATE without a built graph. */
 int bella_hip_graph_get(bella_ctx* ctx, uint32_t* nvertices, uint64_t* nedges, uint64_t* offsets, bella_graph_edge* edges, uint8_t* contained);
 int bella_hip_graph_get_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 /* What bella_hip_trace_pairs does, steered by flags: bit0 = passed pairs only; bit1 = the runs are DROPPED: not staged on the host, and
@@ -650,6 +652,56 @@ int bella_hip_graph_polish_unitigs(bella_ctx* ctx, const bella_polish_params* pa
  * them in place of pos / nbases / len / base_offsets / bases. */
 int bella_hip_graph_get_polished(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases, uint64_t* ppos, uint32_t* pnbases, bella_polish_unitig* per_unitig);
 int bella_hip_graph_get_polish_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+
+/* ---- coverage trimming: clip every read to its longest well-covered stretch before the graph (no counterpart in
+ * the reference; the stage is miniasm's ma_hit_sub / ma_hit_cut) ---------------------------------------------------------------------
+ * Notation of the string graph section.  A record whose e1 - b1 or e2 - b2 is below min_span gives nothing.  Every other record gives
+ * one interval [b, e) to each of its two reads in that read's OWN coordinates (length l): (b1, e1) to V; (b2, e2) to H for strand 0 and
+ * (l2 - e2, l2 - b2) for strand 1.  The interval is shrunk to [s, t): s = b if b <= end_clip else b + end_clip; t = e if l - e <= end_clip
+ * else e - end_clip (an interval that reaches a read end keeps that end); it is dropped when t <= s.  depth(p) = the shrunk intervals
+ * that contain p; a region is a maximal run of positions with depth >= min_depth (two regions that abut are one: depth is judged after
+ * all events of a position).  The clip of a read is its longest region, the leftmost on ties; without a region, or with the longest
+ * shorter than min_span, the read is UNCOVERED and its clip is (0, 0).
+ * While clips exist bella_hip_graph_build CUTS every record first: cs1, ce1 = V's clip; c2s, c2e = H's clip in H' coordinates (mirrored
+ * by l2 for strand 1).  A record with an uncovered read is OUTSIDE.  Otherwise db = max(0, cs1 - b1, c2s - b2), de = max(0, e1 - ce1,
+ * e2 - c2e), the ends become b1 + db, e1 - de, b2 + db, e2 - de (both sides move by the same amount: a record carries no path); a record
+ * with an empty interval is OUTSIDE; otherwise cs1 is subtracted from V's coordinates, c2s from H''s, and the lengths are ce1 - cs1 and
+ * c2e - c2s.  The six rules then run unchanged.  OUTSIDE records give no candidates.  An uncovered read is dead everywhere downstream
+ * (bella_hip_graph_get's contained[] holds 2 for it); edge len / ovl, unitig pos / nbases / len and the unitig bases are in clipped
+ * coordinates: a vertex of read r contributes read[beg + i] (orientation 0) or the complement of read[end - 1 - i] (orientation 1).
+ * bella_hip_graph_polish_unitigs takes its decision at the ORIGINAL position beg + i (resp. end - 1 - i). */
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_graph_trim_params) of the caller's header (the struct may grow)           */
+    uint32_t min_depth;           /* documented default 3; >= 1                                                            */
+    uint32_t end_clip;            /* 500                                                                                   */
+    uint32_t min_span;            /* 1000                                                                                  */
+} bella_graph_trim_params;
+typedef struct {
+    uint32_t beg, end;            /* the clip [beg, end) in the read's own coordinates; (0, 0) = uncovered                 */
+    uint32_t nregions;            /* regions of the read (2 and more: the signature of a chimera)                          */
+    uint32_t max_depth;           /* the largest depth on the read                                                         */
+} bella_read_clip;
+/* What the last bella_hip_graph_trim did.  A sized struct: bella_hip_graph_get_trim_stats writes at most struct_size bytes. */
+typedef struct {
+    uint64_t intervals;           /* shrunk intervals that entered the sweep                                               */
+    uint64_t reads_clipped;       /* covered reads whose clip is not the whole read                                        */
+    uint64_t reads_uncovered;
+    uint64_t reads_multi;         /* reads with two or more regions                                                        */
+    uint64_t bases_before, bases_after;
+    uint64_t records_outside;     /* filled by the next bella_hip_graph_build (0 until then)                               */
+    double events_ms, sort_ms, sweep_ms;      /* between two events on the stream; sort_ms includes the per-read offsets       */
+    double host_ms;               /* the whole call on the host clock                                                      */
+} bella_trim_stats;
+/* Computes the clips from the accumulated records, on the device.  params == NULL: the defaults.  BELLA_ERR_BAD_ARG for a struct_size
+ * too small or min_depth < 1; BELLA_ERR_STATE without reads.  Drops any built graph and any unitigs.  The clips stay until
+ * bella_hip_graph_untrim, until records are added, bella_hip_graph_reset, or reads are loaded; bella_hip_graph_build uses them while
+ * they exist.  Without a trim every entry point behaves as if this section did not exist. */
+int bella_hip_graph_trim(bella_ctx* ctx, const bella_graph_trim_params* params);
+/* out[nreads].  BELLA_ERR_STATE without a trim. */
+int bella_hip_graph_get_trim(bella_ctx* ctx, bella_read_clip* out);
+int bella_hip_graph_get_trim_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+/* Drops the clips, and with them the built graph and the unitigs, which were made with them.  Without a trim nothing happens. */
+int bella_hip_graph_untrim(bella_ctx* ctx);
 
 /* ---- multi-GPU: one context per GPU, RCCL over xGMI ------------------------------------------------
  * The reference's multi-GPU path hands alignment batches to the devices inside one call (loganGPU/functions.cuh:441-443,

@@ -43,6 +43,22 @@ def _p(a):
     return a.ctypes.data if a is not None and a.size else None
 
 
+def _over(defaults, params, what):
+    """`params` over a copy of `defaults`, as ints"""
+    p = dict(defaults)
+    for k, v in params.items():
+        if k not in p:
+            raise TypeError("unknown %s parameter %r" % (what, k))
+        p[k] = int(v)
+    return p
+
+
+def _names(names):
+    """(how many, char*[] of the encoded names for the C ABI: it keeps the strings alive)"""
+    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    return len(enc), C.cast((C.c_char_p * max(len(enc), 1))(*enc), C.c_void_p)
+
+
 _ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 
 
@@ -68,6 +84,12 @@ class Engine:
     def _chk(self, rc):
         if rc:
             raise BellaHipError(rc, self.lib.bella_hip_last_error(self.h).decode() or self.lib.bella_hip_strerror(rc).decode())
+
+    def _stats(self, getter, struct) -> dict:
+        """one of the ABI's sized result structs as a dict of its fields"""
+        st = struct()
+        self._chk(getter(self.h, C.byref(st), C.sizeof(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
 
     # ---- reads (readVector_) ----
     def set_reads(self, rs):
@@ -409,11 +431,7 @@ class Engine:
     def graph_build(self, **params):
         """classifies the accumulated records, drops contained reads, reduces transitively (on the device); min_overlap, max_overhang,
         overhang_permille, fuzz default to 1000, 1000, 800, 1000"""
-        p = dict(self.GRAPH_DEFAULTS)
-        for k, v in params.items():
-            if k not in p:
-                raise TypeError("unknown graph parameter %r" % k)
-            p[k] = int(v)
+        p = _over(self.GRAPH_DEFAULTS, params, "graph")
         gp = GraphParams(C.sizeof(GraphParams), p["min_overlap"], p["max_overhang"], p["overhang_permille"], p["fuzz"])
         self._chk(self.lib.bella_hip_graph_build(self.h, C.byref(gp)))
 
@@ -428,9 +446,7 @@ class Engine:
         return offs, edges, cont
 
     def graph_stats(self) -> dict:
-        st = GraphStats()
-        self._chk(self.lib.bella_hip_graph_get_stats(self.h, C.byref(st), C.sizeof(st)))
-        return {k: getattr(st, k) for k, _ in st._fields_}
+        return self._stats(self.lib.bella_hip_graph_get_stats, GraphStats)
 
     # ---- unitigs: tip clipping, compaction, sequences ----
     CLEAN_DEFAULTS = dict(max_tip_reads=4, tip_rounds=3)
@@ -438,11 +454,7 @@ class Engine:
     def graph_clean(self, **params):
         """clips tips off the current graph (on the device) and replaces it: graph() then returns the cleaned one.  max_tip_reads
         (0 = off) and tip_rounds default to 4 and 3"""
-        p = dict(self.CLEAN_DEFAULTS)
-        for k, v in params.items():
-            if k not in p:
-                raise TypeError("unknown clean parameter %r" % k)
-            p[k] = int(v)
+        p = _over(self.CLEAN_DEFAULTS, params, "clean")
         cp = GraphCleanParams(C.sizeof(GraphCleanParams), p["max_tip_reads"], p["tip_rounds"])
         self._chk(self.lib.bella_hip_graph_clean(self.h, C.byref(cp)))
 
@@ -458,21 +470,16 @@ class Engine:
     def graph_pop_bubbles(self, **params):
         """pops bubbles of the current graph (on the device) and replaces it, as graph_clean does; the popped reads show in
         graph_removed().  max_bubble_reads (0 = off, at most 255), max_bubble_dist and bubble_rounds default to 64, 50,000 and 3"""
-        p = dict(self.BUBBLE_DEFAULTS)
-        for k, v in params.items():
-            if k not in p:
-                raise TypeError("unknown bubble parameter %r" % k)
-            p[k] = int(v)
+        p = _over(self.BUBBLE_DEFAULTS, params, "bubble")
         bp = GraphBubbleParams(C.sizeof(GraphBubbleParams), p["max_bubble_reads"], p["max_bubble_dist"], p["bubble_rounds"])
         self._chk(self.lib.bella_hip_graph_pop_bubbles(self.h, C.byref(bp)))
 
     def bubble_stats(self) -> dict:
         """of the last graph_pop_bubbles: totals, and per round sources / found / popped / reads_per_round / edges_per_round"""
-        st = BubbleStats()
-        self._chk(self.lib.bella_hip_graph_get_bubble_stats(self.h, C.byref(st), C.sizeof(st)))
-        out = dict(reads_removed=st.reads_removed, edges_removed=st.edges_removed, rounds=st.rounds, pop_ms=st.pop_ms)
+        st = self._stats(self.lib.bella_hip_graph_get_bubble_stats, BubbleStats)
+        out = {k: st[k] for k in ("reads_removed", "edges_removed", "rounds", "pop_ms")}
         for k in ("sources", "found", "popped", "reads_per_round", "edges_per_round"):
-            out[k] = list(getattr(st, k))[:st.rounds]
+            out[k] = list(st[k])[:st["rounds"]]
         return out
 
     def graph_unitigs(self) -> dict:
@@ -495,10 +502,9 @@ class Engine:
         return offs, bases
 
     def unitig_stats(self) -> dict:
-        st = UnitigStats()
-        self._chk(self.lib.bella_hip_graph_get_unitig_stats(self.h, C.byref(st), C.sizeof(st)))
-        out = {k: getattr(st, k) for k, _ in st._fields_}
-        out["tips_per_round"], out["reads_per_round"] = list(st.tips_per_round)[:st.rounds], list(st.reads_per_round)[:st.rounds]
+        out = self._stats(self.lib.bella_hip_graph_get_unitig_stats, UnitigStats)
+        for k in ("tips_per_round", "reads_per_round"):
+            out[k] = list(out[k])[:out["rounds"]]
         return out
 
     # ---- unitig consensus ----
@@ -515,9 +521,7 @@ class Engine:
         return out
 
     def polish_stats(self) -> dict:
-        st = PolishStats()
-        self._chk(self.lib.bella_hip_graph_get_polish_stats(self.h, C.byref(st), C.sizeof(st)))
-        return {k: getattr(st, k) for k, _ in st._fields_}
+        return self._stats(self.lib.bella_hip_graph_get_polish_stats, PolishStats)
 
     # ---- coverage trimming ----
     TRIM_DEFAULTS = dict(min_depth=3, end_clip=500, min_span=1000)
@@ -526,11 +530,7 @@ class Engine:
         """clips every read to its longest stretch that at least min_depth accumulated records cover (on the device); graph_build then
         cuts the records to the clips, and everything downstream works in clipped coordinates, until graph_untrim, new records or
         new reads.  min_depth, end_clip and min_span default to 3, 500 and 1000"""
-        p = dict(self.TRIM_DEFAULTS)
-        for k, v in params.items():
-            if k not in p:
-                raise TypeError("unknown trim parameter %r" % k)
-            p[k] = int(v)
+        p = _over(self.TRIM_DEFAULTS, params, "trim")
         tp = GraphTrimParams(C.sizeof(GraphTrimParams), p["min_depth"], p["end_clip"], p["min_span"])
         self._chk(self.lib.bella_hip_graph_trim(self.h, C.byref(tp)))
 
@@ -541,9 +541,7 @@ class Engine:
         return out
 
     def trim_stats(self) -> dict:
-        st = TrimStats()
-        self._chk(self.lib.bella_hip_graph_get_trim_stats(self.h, C.byref(st), C.sizeof(st)))
-        return {k: getattr(st, k) for k, _ in st._fields_}
+        return self._stats(self.lib.bella_hip_graph_get_trim_stats, TrimStats)
 
     def graph_untrim(self):
         self._chk(self.lib.bella_hip_graph_untrim(self.h))
@@ -632,15 +630,14 @@ def format_aligned(names, lengths, pairs, alns, paf=False) -> bytes:
 def write_output(filename: str, pars: BellaPars, names, lengths, pairs, alns=None, nthreads: int = 0) -> WriteStats:
     """bella_hip_write_output: the library's multi-threaded writer (overlap.hpp:603-642); APPENDS to `filename`."""
     lib = _lib.load()
-    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
-    arr = (C.c_char_p * len(enc))(*enc)
+    n, arr = _names(names)
     lens = np.ascontiguousarray(lengths, np.uint32)
     pairs = np.ascontiguousarray(pairs, PAIR_DT)
     st = WriteStats()
     cp = pars.c()
     if alns is not None:
         alns = np.ascontiguousarray(alns, ALN_DT)
-    rc = lib.bella_hip_write_output(filename.encode(), C.byref(cp), 1 if pars.outputPaf else 0, len(enc), C.cast(arr, C.c_void_p),
+    rc = lib.bella_hip_write_output(filename.encode(), C.byref(cp), 1 if pars.outputPaf else 0, n, arr,
                                     lens.ctypes.data, pairs.ctypes.data if len(pairs) else None,
                                     alns.ctypes.data if alns is not None and len(alns) else None, len(pairs), nthreads, C.byref(st))
     if rc:
@@ -663,8 +660,7 @@ def cigar_strings(traces, ops, reverse=None):
 def write_output_traced(filename: str, pars: BellaPars, names, lengths, pairs, alns, traces, ops, nthreads: int = 0) -> WriteStats:
     """bella_hip_write_output_traced: true PAF (columns 10/11 = residue matches / block length, AS ov NM cg tags); APPENDS."""
     lib = _lib.load()
-    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
-    arr = (C.c_char_p * len(enc))(*enc)
+    n, arr = _names(names)
     lens = np.ascontiguousarray(lengths, np.uint32)
     pairs = np.ascontiguousarray(pairs, PAIR_DT)
     alns = np.ascontiguousarray(alns, ALN_DT)
@@ -673,7 +669,7 @@ def write_output_traced(filename: str, pars: BellaPars, names, lengths, pairs, a
     assert len(pairs) == len(alns) == len(traces)
     st = WriteStats()
     cp = pars.c()
-    rc = lib.bella_hip_write_output_traced(filename.encode(), C.byref(cp), len(enc), C.cast(arr, C.c_void_p), lens.ctypes.data, _p(pairs), _p(alns),
+    rc = lib.bella_hip_write_output_traced(filename.encode(), C.byref(cp), n, arr, lens.ctypes.data, _p(pairs), _p(alns),
                                            _p(traces), _p(ops), len(ops), len(pairs), nthreads, C.byref(st))
     if rc:
         raise BellaHipError(rc, "bella_hip_write_output_traced failed")
@@ -683,12 +679,11 @@ def write_output_traced(filename: str, pars: BellaPars, names, lengths, pairs, a
 def write_fasta(filename: str, names, offsets, bases, append: bool = False) -> None:
     """bella_hip_write_fasta: '>name' + one sequence line per read (what Engine.consensus returned), reads in input order."""
     lib = _lib.load()
-    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
-    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    n, arr = _names(names)
     offs = np.ascontiguousarray(offsets, np.uint64)
     b = np.ascontiguousarray(bases, np.uint8)
-    assert len(offs) == len(enc) + 1
-    rc = lib.bella_hip_write_fasta(os.fsencode(filename), len(enc), C.cast(arr, C.c_void_p), offs.ctypes.data, _p(b), 1 if append else 0)
+    assert len(offs) == n + 1
+    rc = lib.bella_hip_write_fasta(os.fsencode(filename), n, arr, offs.ctypes.data, _p(b), 1 if append else 0)
     if rc:
         raise BellaHipError(rc, "bella_hip_write_fasta failed")
 
@@ -697,18 +692,17 @@ def write_gfa(filename: str, names, lengths, offsets, edges, contained, seqs=Non
     """bella_hip_write_gfa: GFA 1 of a graph (what Engine.graph returned): S lines of the non-contained reads in input order -- with the
     reads' own bases (seqs: one bytes per read) or '*' -- and one L line per edge in list order."""
     lib = _lib.load()
-    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
-    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    n, arr = _names(names)
     lens = np.ascontiguousarray(lengths, np.uint32)
     offs = np.ascontiguousarray(offsets, np.uint64)
     edges = np.ascontiguousarray(edges, EDGE_DT)
     cont = np.ascontiguousarray(contained, np.uint8)
-    assert len(offs) == 2 * len(enc) + 1 and len(cont) == len(enc) == len(lens) and int(offs[-1]) == len(edges)
+    assert len(offs) == 2 * n + 1 and len(cont) == n == len(lens) and int(offs[-1]) == len(edges)
     boffs = bases = None
     if seqs is not None:
         boffs = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
         bases = np.frombuffer(b"".join(bytes(s) for s in seqs), np.uint8)
-    rc = lib.bella_hip_write_gfa(os.fsencode(filename), len(enc), C.cast(arr, C.c_void_p), _p(lens), boffs.ctypes.data if boffs is not None else None,
+    rc = lib.bella_hip_write_gfa(os.fsencode(filename), n, arr, _p(lens), boffs.ctypes.data if boffs is not None else None,
                                  (bases.ctypes.data if len(bases) else boffs.ctypes.data) if bases is not None else None, offs.ctypes.data, _p(edges), _p(cont))
     if rc:
         raise BellaHipError(rc, "bella_hip_write_gfa failed")
@@ -739,8 +733,7 @@ def write_unitig_gfa(filename: str, names, unitigs: dict, offsets=None, bases=No
     """bella_hip_write_unitig_gfa: GFA 1 of what Engine.graph_unitigs returned: S and a lines per unitig, L lines per link; with the
     unitigs' bases (what Engine.unitig_bases returned) or '*'"""
     lib = _lib.load()
-    enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
-    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    n, arr = _names(names)
     u = unitigs
     a = {k: np.ascontiguousarray(u[k], dt) for k, dt in (("voff", np.uint64), ("verts", np.uint32), ("pos", np.uint64), ("nbases", np.uint32), ("len", np.uint64),
                                                          ("circular", np.uint8), ("links", LINK_DT))}
@@ -750,7 +743,7 @@ def write_unitig_gfa(filename: str, names, unitigs: dict, offsets=None, bases=No
         assert len(boffs) == len(a["len"]) + 1
         if not len(b):
             b = np.zeros(1, np.uint8)                                 # (no bases at all: still a pointer, NULL would mean '*')
-    rc = lib.bella_hip_write_unitig_gfa(os.fsencode(filename), len(enc), C.cast(arr, C.c_void_p), len(a["len"]), a["voff"].ctypes.data, _p(a["verts"]), _p(a["pos"]),
+    rc = lib.bella_hip_write_unitig_gfa(os.fsencode(filename), n, arr, len(a["len"]), a["voff"].ctypes.data, _p(a["verts"]), _p(a["pos"]),
                                         _p(a["nbases"]), _p(a["len"]), _p(a["circular"]), boffs.ctypes.data if boffs is not None else None,
                                         b.ctypes.data if b is not None else None, len(a["links"]), _p(a["links"]))
     if rc:

@@ -135,6 +135,42 @@ struct CountU64 {                                        // pair counts: without
     __host__ __device__ uint64_t operator()(const uint32_t& v) const { return (uint64_t)(v & ~kOrderedBit); }
 };
 
+// The results of the stages that follow the alignment, one member per stage, and which of them are valid.  All of
+// it lives on the host: the graph is small next to what it was made from, and a stage uploads what it reads.  drop / changed / need
+// (below) are the only code that touches `valid`.
+enum Stage : uint32_t { RECORDS, TRIM, GRAPH, UNITIGS, POLISH, PILE, CONS, kStages };
+struct StageState {
+    uint32_t valid = 1u << RECORDS;          // one bit per Stage (the records are always there: possibly none)
+    std::vector<bella_overlap> records;      // accumulated by bella_hip_graph_add_overlaps (graph.hpp)
+    struct Trim {                            // the clips of the last bella_hip_graph_trim, 16 bytes per read (trim.hpp; section 15).  A graph
+        std::vector<bella_read_clip> clips;  // in the context was always built in the trim state the context is in now
+        bella_trim_stats stats{};
+    } trim;
+    struct Graph {                           // the last build's result, as bella_hip_graph_clean and _pop_bubbles left it (sections 11 to 13)
+        std::vector<uint32_t> off;
+        std::vector<bella_graph_edge> edges;
+        std::vector<uint8_t> contained, removed;
+        bella_graph_stats stats{};
+        bella_unitig_stats clean{};          // the clean's part of bella_unitig_stats (rounds .. edges_removed, clean_ms)
+        bella_bubble_stats bubbles{};
+    } graph;
+    struct Unitigs {                         // the last bella_hip_graph_unitigs (unitig.hpp; section 12)
+        std::vector<uint64_t> voff, pos, len, boff;
+        std::vector<uint32_t> verts, nb;
+        std::vector<uint8_t> circ, bases;
+        std::vector<bella_unitig_link> links;
+        bella_unitig_stats stats{};          // the unitigs' part
+    } unitigs;
+    struct Polish {                          // the last bella_hip_graph_polish_unitigs (polish.hpp; section 14)
+        std::vector<uint64_t> offs, pos;
+        std::vector<uint32_t> nb;
+        std::vector<uint8_t> bases;
+        std::vector<bella_polish_unitig> recs;
+        bella_polish_stats stats{};
+    } polish;
+    // PILE and CONS (pileup.hpp; section 10) are device buffers of the context: only their bits are here
+};
+
 }  // namespace
 
 struct bella_ctx {
@@ -203,38 +239,9 @@ struct bella_ctx {
     Buf tr_exts, tr_lists, tr_res, tr_pres, tr_opoff, tr_dirs, tr_scr, tr_ops;
     bool trace_ops_kept = true;          // false: the last call piled its runs up on the device and did not stage them (keep_ops == 0)
     // read correction (pileup.hpp): the table of the loaded reads, and the last consensus
-    bool have_pile = false, have_cons = false;
     uint64_t cons_total = 0;
     Buf pile, pile_pairs, pile_cnt, pile_tmp, cons_emit, cons_scan, cons_out, cons_offs, cons_stats;
-    // string graph (graph.hpp): the accumulated overlap records, and the last build's result (both on the host: the
-    // graph is small next to what it was made from)
-    std::vector<bella_overlap> g_recs;
-    bool have_graph = false;
-    std::vector<uint64_t> g_off;
-    std::vector<bella_graph_edge> g_edges;
-    std::vector<uint8_t> g_cont;
-    bella_graph_stats g_stats{};
-    // unitigs (unitig.hpp): what bella_hip_graph_clean removed from the graph above, and the last unitigs (on the host)
-    std::vector<uint8_t> g_removed;
-    bool have_unitigs = false;
-    std::vector<uint64_t> u_voff, u_pos, u_len, u_boff;
-    std::vector<uint32_t> u_verts, u_nb;
-    std::vector<uint8_t> u_circ, u_bases;
-    std::vector<bella_unitig_link> u_links;
-    bella_unitig_stats u_stats{};
-    bella_bubble_stats b_stats{};        // of the last bella_hip_graph_pop_bubbles (bubble.hpp)
-    // unitig consensus (polish.hpp): the last bella_hip_graph_polish_unitigs (on the host, like the unitigs)
-    bool have_polish = false;
-    std::vector<uint64_t> p_offs, p_pos;
-    std::vector<uint32_t> p_nb;
-    std::vector<uint8_t> p_bases;
-    std::vector<bella_polish_unitig> p_recs;
-    bella_polish_stats p_stats{};
-    // coverage trimming (trim.hpp): the clips of the last bella_hip_graph_trim (on the host, 16 bytes per read).  A
-    // graph in the context was always built in the trim state the context is in now: a trim and an untrim drop it.
-    bool have_trim = false;
-    std::vector<bella_read_clip> t_clips;
-    bella_trim_stats t_stats{};
+    StageState as;                       // overlap records, clips, graph, unitigs, polish; what of them and of the two above is valid
     bella_timings tm{};
     hipEvent_t ev[12]{};
     uint32_t* pinned = nullptr;          // 128 host words the per-pass read backs land in
@@ -465,6 +472,65 @@ int take_params(bella_ctx* c, P& p, const P* given, const char* name) {
 template <class S>
 int put_sized(void* out, uint64_t struct_size, const S& s) {
     std::memcpy(out, &s, (size_t)std::min<uint64_t>(struct_size, sizeof(S)));
+    return 0;
+}
+
+// ---- stage state --------------------------------------------------------------------------------------------------
+// What is built directly from each stage.  changed(s): s has other contents now, so everything built from it goes, and what was built
+// from that; drop(s): s goes too (a stage drops itself when it starts and comes back with made(s) when it has succeeded).
+constexpr uint32_t stage_bit(Stage s) { return 1u << s; }
+constexpr uint32_t kBuiltFrom[kStages] = {
+    /* RECORDS */ stage_bit(TRIM) | stage_bit(GRAPH),
+    /* TRIM    */ stage_bit(GRAPH),
+    /* GRAPH   */ stage_bit(UNITIGS),
+    /* UNITIGS */ stage_bit(POLISH),
+    /* POLISH  */ 0,
+    /* PILE    */ stage_bit(CONS) | stage_bit(POLISH),
+    /* CONS    */ 0,
+};
+void drop(bella_ctx* c, Stage s);
+void changed(bella_ctx* c, Stage s) {
+    for (uint32_t d = 0; d < kStages; ++d)
+        if (kBuiltFrom[s] & (1u << d)) drop(c, (Stage)d);
+}
+void drop(bella_ctx* c, Stage s) {
+    c->as.valid &= ~stage_bit(s);
+    changed(c, s);
+}
+void made(bella_ctx* c, Stage s) { c->as.valid |= stage_bit(s); }
+bool has(const bella_ctx* c, Stage s) { return (c->as.valid & stage_bit(s)) != 0; }
+// the precondition of a call that reads stage s
+int need(bella_ctx* c, Stage s) {
+    static const char* const first[kStages] = {"", "bella_hip_graph_trim first", "bella_hip_graph_build first", "bella_hip_graph_unitigs first",
+                                               "bella_hip_graph_polish_unitigs first", "bella_hip_pileup_reset first", "bella_hip_consensus first"};
+    return has(c, s) ? 0 : fail(c, BELLA_ERR_STATE, "%s", first[s]);
+}
+
+// a stage's result struct for the caller: get(state) is the struct
+template <class Get>
+int get_stats(bella_ctx* c, Stage s, void* out, uint64_t struct_size, Get get) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, s)) return r;
+    return put_sized(out, struct_size, get(c->as));
+}
+// ... and one of its arrays, when the caller wants it
+template <class T>
+void copy_out(void* dst, const std::vector<T>& v) {
+    if (dst && !v.empty()) std::memcpy(dst, v.data(), sizeof(T) * v.size());
+}
+
+// the accumulated records / the clips on the device, for the length of one stage call (a trim exists and there are reads when the
+// clips are asked for)
+int upload_records(bella_ctx* c, Buf& recs) {
+    const size_t bytes = sizeof(bella_overlap) * c->as.records.size();
+    ENSURE(c, recs, bytes);
+    if (bytes) HIPCHK(c, c->stager.h2d(recs.p, c->as.records.data(), bytes, c->stream));
+    return 0;
+}
+int upload_clips(bella_ctx* c, Buf& clips) {
+    const size_t bytes = sizeof(bella_read_clip) * c->as.trim.clips.size();
+    ENSURE(c, clips, bytes);
+    HIPCHK(c, c->stager.h2d(clips.p, c->as.trim.clips.data(), bytes, c->stream));
     return 0;
 }
 
@@ -1034,9 +1100,9 @@ static int set_reads_impl(bella_ctx* c, const uint64_t* offsets, uint32_t nreads
     c->have_matrix = c->have_pairs = c->have_alns = false;
     c->have_tuples = false;
     for (Buf* b : {&c->pile, &c->cons_out, &c->cons_offs, &c->cons_stats}) release(*b);      // (the pileup belongs to the reads it was sized for)
-    c->have_pile = c->have_cons = false;
-    c->g_recs.clear();                                                // (so do the overlap records, the clips and the graph)
-    c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;
+    drop(c, PILE);
+    c->as.records.clear();                                            // (so do the overlap records, the clips and the graph)
+    changed(c, RECORDS);
     return 0;
 }
 
@@ -3841,7 +3907,7 @@ void trace_release(bella_ctx* c) {      // the batch buffers go back (directions
 static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0, int passed_only, bool vote, bool keep_ops, uint64_t* ntraced, uint64_t* nops) {
     if (!c) return BELLA_ERR_BAD_ARG;
     if (!c->have_alns) return fail(c, BELLA_ERR_STATE, "align_pairs first");
-    if (vote && !c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
+    if (vote) if (int r = need(c, PILE)) return r;
     int rc = check_params(c, p);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -3861,7 +3927,7 @@ static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0,
     std::vector<bella_trace> tr(jobs.size());
     c->trace_ops.clear();
     if (!keep_ops) std::vector<uint32_t>().swap(c->trace_ops);
-    if (vote) c->have_cons = c->have_polish = false;
+    if (vote) changed(c, PILE);
     rc = run_trace(c, p, jobs, band0, tr.data(), c->trace_ops, c->trace_stats, vote, keep_ops);
     trace_release(c);
     if (vote) release(c->pile_pairs);
@@ -3949,25 +4015,25 @@ int bella_hip_pileup_reset(bella_ctx* c) {
     if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->total_bases * kPileCounters * 4;
-    c->have_pile = c->have_cons = c->have_polish = false;
+    drop(c, PILE);
     if (ensure_bytes(c, c->pile, bytes))
         return fail(c, BELLA_ERR_NOMEM, "the pileup table needs %zu bytes of device memory (36 per base of %llu bases) and they do not fit", bytes,
                     (unsigned long long)c->total_bases);
     HIPCHK(c, hipMemsetAsync(c->pile.p, 0, bytes ? bytes : 16, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_pile = true;
+    made(c, PILE);
     return 0;
 }
 
 int bella_hip_get_pileup_bytes(bella_ctx* c, uint64_t* bytes) {
     if (!c || !bytes) return BELLA_ERR_BAD_ARG;
-    *bytes = c->have_pile ? (uint64_t)c->total_bases * kPileCounters * 4 : 0;
+    *bytes = has(c, PILE) ? (uint64_t)c->total_bases * kPileCounters * 4 : 0;
     return 0;
 }
 
 // counters [*first, *first + *count) of the table = the reads [first_read, first_read + nreads)
 static int pileup_range(bella_ctx* c, uint32_t first_read, uint32_t nreads, uint64_t* first, uint64_t* count) {
-    if (!c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
+    if (int r = need(c, PILE)) return r;
     if ((uint64_t)first_read + nreads > c->nreads) return fail(c, BELLA_ERR_BAD_ARG, "reads [%u, %u + %u) out of range", first_read, first_read, nreads);
     uint64_t a = 0, b = 0;
     for (uint32_t r = 0; r < first_read + nreads; ++r) { if (r < first_read) a += c->host_lens[r]; b += c->host_lens[r]; }
@@ -3997,7 +4063,7 @@ int bella_hip_add_pileup(bella_ctx* c, uint32_t first_read, uint32_t nreads, con
     if (!count) return 0;
     if (!in) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_cons = c->have_polish = false;
+    changed(c, PILE);
     constexpr uint64_t kChunk = 16ull << 20;                          // counters per step: 64 MB of device scratch whatever the range
     ENSURE(c, c->pile_tmp, 4 * (size_t)std::min(kChunk, count));
     for (uint64_t o = 0; o < count; o += kChunk) {
@@ -4016,9 +4082,9 @@ int bella_hip_consensus(bella_ctx* c, const bella_consensus_params* params, uint
     bella_consensus_params cp{};                                      // (no defaults: NULL was refused)
     if (int r = take_params(c, cp, params, "bella_consensus_params")) return r;
     if (cp.min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
-    if (!c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
+    if (int r = need(c, PILE)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_cons = false;
+    drop(c, CONS);
     const uint64_t total = c->total_bases;
     const uint32_t nr = c->nreads;
     if (total >= 0x7FFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "consensus: the read set must have fewer than 2^31 bases");
@@ -4052,14 +4118,14 @@ int bella_hip_consensus(bella_ctx* c, const bella_consensus_params* params, uint
     release(c->cons_emit);
     release(c->cons_scan);
     c->cons_total = nout;
-    c->have_cons = true;
+    made(c, CONS);
     if (total_bases) *total_bases = nout;
     return 0;
 }
 
 int bella_hip_get_consensus(bella_ctx* c, uint64_t* offsets, uint8_t* bases, bella_consensus_read* stats) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_cons) return fail(c, BELLA_ERR_STATE, "bella_hip_consensus first");
+    if (int r = need(c, CONS)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if (offsets) HIPCHK(c, c->stager.d2h(offsets, c->cons_offs.p, 8 * ((size_t)c->nreads + 1), c->stream));
     if (bases && c->cons_total) HIPCHK(c, c->stager.d2h(bases, c->cons_out.p, (size_t)c->cons_total, c->stream));
@@ -4089,15 +4155,15 @@ int bella_hip_write_fasta(const char* path, uint32_t nreads, const char* const* 
 // ---- string graph (graph.hpp) ----------------------------------------------------------------------------------
 int bella_hip_graph_reset(bella_ctx* c) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    std::vector<bella_overlap>().swap(c->g_recs);
-    c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;
+    std::vector<bella_overlap>().swap(c->as.records);
+    changed(c, RECORDS);
     return 0;
 }
 
 int bella_hip_graph_add_overlaps(bella_ctx* c, const bella_overlap* recs, uint64_t n) {
     if (!c || (n && !recs)) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
     if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
-    if (c->g_recs.size() + n >= (1ull << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 overlap records");
+    if (c->as.records.size() + n >= (1ull << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 overlap records");
     for (uint64_t i = 0; i < n; ++i) {
         const bella_overlap& r = recs[i];
         if (r.cid == r.rid || r.cid >= c->nreads || r.rid >= c->nreads || r.strand > 1)
@@ -4107,8 +4173,8 @@ int bella_hip_graph_add_overlaps(bella_ctx* c, const bella_overlap* recs, uint64
             return fail(c, BELLA_ERR_BAD_ARG, "overlap record %llu: [%d, %d) of %lld bases and [%d, %d) of %lld", (unsigned long long)i, r.begV, r.endV, (long long)l1, r.begH,
                         r.endH, (long long)l2);
     }
-    c->g_recs.insert(c->g_recs.end(), recs, recs + n);
-    c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;      // (the clips were those of the records before)
+    c->as.records.insert(c->as.records.end(), recs, recs + n);
+    changed(c, RECORDS);                                              // (the clips were those of the records before)
     return 0;
 }
 
@@ -4144,8 +4210,8 @@ int bella_hip_graph_add_traced(bella_ctx* c, uint64_t* added) {
 
 int bella_hip_graph_get_overlaps(bella_ctx* c, bella_overlap* out, uint64_t* n) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (n) *n = c->g_recs.size();
-    if (out && !c->g_recs.empty()) std::memcpy(out, c->g_recs.data(), sizeof(bella_overlap) * c->g_recs.size());
+    if (n) *n = c->as.records.size();
+    copy_out(out, c->as.records);
     return 0;
 }
 
@@ -4157,14 +4223,14 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
     HIPCHK(c, hipSetDevice(c->device));
     const auto t_begin = clk::now();
-    c->have_graph = c->have_unitigs = c->have_polish = false;
+    drop(c, GRAPH);
+    StageState::Graph& g = c->as.graph;
     const uint32_t nr = c->nreads, nv = 2 * nr;
-    const uint32_t n = (uint32_t)c->g_recs.size(), nc = 2 * n;
+    const uint32_t n = (uint32_t)c->as.records.size(), nc = 2 * n;
     if (nr >= (1u << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 reads");
     bella_graph_stats st{};
     st.records = n;
     TmpBuf recs, cand, cont, cnt, ok, deg, off, key1, key1b, idx, idxb, key2, key2b, edges, pos, bykey, bykeyb, gmark, red, keep, scan, fin, foff;
-    ENSURE(c, recs, sizeof(bella_overlap) * (size_t)n);
     ENSURE(c, cand, sizeof(bella_graph_edge) * (size_t)nc);
     ENSURE(c, cont, 4 * (size_t)nr);
     ENSURE(c, cnt, 4 * kGcCount);
@@ -4178,13 +4244,12 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     uint32_t* const d_cnt = ptr<uint32_t>(cnt);
     EventSet ev;
     if (int r = ev.create(c, 4)) return r;
-    if (n) HIPCHK(c, c->stager.h2d(recs.p, c->g_recs.data(), sizeof(bella_overlap) * (size_t)n, c->stream));
+    if (int r = upload_records(c, recs)) return r;
     HIPCHK(c, hipMemsetAsync(cont.p, 0, std::max<size_t>(4 * (size_t)nr, 16), c->stream));
     TmpBuf clipb;
     const bella_read_clip* d_clip = nullptr;                              // the clips of bella_hip_graph_trim, while they exist
-    if (c->have_trim && nr) {
-        ENSURE(c, clipb, sizeof(bella_read_clip) * (size_t)nr);
-        HIPCHK(c, c->stager.h2d(clipb.p, c->t_clips.data(), sizeof(bella_read_clip) * (size_t)nr, c->stream));
+    if (has(c, TRIM) && nr) {
+        if (int r = upload_clips(c, clipb)) return r;
         d_clip = ptr<bella_read_clip>(clipb);
         k_trim_flags<<<nblk(nr), 256, 0, c->stream>>>(d_clip, nr, ptr<uint32_t>(cont));
         KCHK(c);
@@ -4240,7 +4305,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     ENSURE(c, red, (size_t)m + 1);
     ENSURE(c, keep, (size_t)m + 1);
     ENSURE(c, scan, 4 * ((size_t)m + 1));
-    ENSURE(c, foff, 8 * ((size_t)nv + 1));
+    ENSURE(c, foff, 4 * ((size_t)nv + 1));
     HIPCHK(c, hipMemsetAsync(red.p, 0, (size_t)m + 1, c->stream));
     if (m) {
         k_graph_reduce<<<nblk(nv, kGraphBlock / 64), kGraphBlock, 0, c->stream>>>(ptr<uint32_t>(off), ptr<bella_graph_edge>(edges), nv, gp.fuzz, force_global ? 1u : 0u, d_bykey,
@@ -4261,47 +4326,47 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
         k_graph_compact<<<nblk(m), 256, 0, c->stream>>>(ptr<bella_graph_edge>(edges), ptr<uint8_t>(keep), ptr<uint32_t>(scan), m, ptr<bella_graph_edge>(fin));
         KCHK(c);
     }
-    k_graph_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint64_t>(foff));
+    k_graph_new_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint32_t>(foff));
     KCHK(c);
     HIPCHK(c, hipEventRecord(ev.e, c->stream));
-    c->g_off.assign((size_t)nv + 1, 0);
-    c->g_edges.assign(nfinal, bella_graph_edge{});
+    g.off.assign((size_t)nv + 1, 0);
+    g.edges.assign(nfinal, bella_graph_edge{});
     std::vector<uint32_t> cont32(nr);
-    HIPCHK(c, hipMemcpyAsync(c->g_off.data(), foff.p, 8 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
-    if (nfinal) HIPCHK(c, c->stager.d2h(c->g_edges.data(), fin.p, sizeof(bella_graph_edge) * (size_t)nfinal, c->stream));
+    HIPCHK(c, hipMemcpyAsync(g.off.data(), foff.p, 4 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
+    if (nfinal) HIPCHK(c, c->stager.d2h(g.edges.data(), fin.p, sizeof(bella_graph_edge) * (size_t)nfinal, c->stream));
     if (nr) HIPCHK(c, hipMemcpyAsync(cont32.data(), cont.p, 4 * (size_t)nr, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->g_cont.resize(nr);
-    for (uint32_t r = 0; r < nr; ++r) c->g_cont[r] = (uint8_t)cont32[r];      // 1 contained; 2 uncovered (only with clips)
-    if (c->have_trim) c->t_stats.records_outside = hc[kGcOutside];
+    g.contained.resize(nr);
+    for (uint32_t r = 0; r < nr; ++r) g.contained[r] = (uint8_t)cont32[r];    // 1 contained; 2 uncovered (only with clips)
+    if (has(c, TRIM)) c->as.trim.stats.records_outside = hc[kGcOutside];
     st.n_short = hc[kGcShort]; st.n_internal = hc[kGcInternal]; st.contained_reads = hc[kGcContained];
     st.edges_all = hc[kGcEdgesAll]; st.edges_kept = m; st.edges_reduced = hc[kGcReduced]; st.edges_final = nfinal;
     st.max_degree = hc[kGcMaxDegree]; st.overcap_vertices = hc[kGcOvercap];
     st.classify_ms = ev_ms(ev.a, ev.b); st.sort_ms = ev_ms(ev.b, ev.d); st.reduce_ms = ev_ms(ev.d, ev.e);
     st.host_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
-    c->g_stats = st;
-    c->g_removed.assign(nr, 0);
-    c->u_stats = bella_unitig_stats{};
-    c->b_stats = bella_bubble_stats{};
-    c->have_graph = true;
+    g.stats = st;
+    g.removed.assign(nr, 0);
+    g.clean = bella_unitig_stats{};
+    g.bubbles = bella_bubble_stats{};
+    c->as.unitigs.stats = bella_unitig_stats{};
+    made(c, GRAPH);
     return 0;
 }
 
 int bella_hip_graph_get(bella_ctx* c, uint32_t* nvertices, uint64_t* nedges, uint64_t* offsets, bella_graph_edge* edges, uint8_t* contained) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
-    if (nvertices) *nvertices = (uint32_t)(c->g_off.size() - 1);
-    if (nedges) *nedges = c->g_edges.size();
-    if (offsets) std::memcpy(offsets, c->g_off.data(), 8 * c->g_off.size());
-    if (edges && !c->g_edges.empty()) std::memcpy(edges, c->g_edges.data(), sizeof(bella_graph_edge) * c->g_edges.size());
-    if (contained && !c->g_cont.empty()) std::memcpy(contained, c->g_cont.data(), c->g_cont.size());
+    if (int r = need(c, GRAPH)) return r;
+    const StageState::Graph& g = c->as.graph;
+    if (nvertices) *nvertices = (uint32_t)(g.off.size() - 1);
+    if (nedges) *nedges = g.edges.size();
+    if (offsets) std::copy(g.off.begin(), g.off.end(), offsets);      // (the ABI's offsets are 64 bits wide)
+    copy_out(edges, g.edges);
+    copy_out(contained, g.contained);
     return 0;
 }
 
 int bella_hip_graph_get_stats(bella_ctx* c, void* out, uint64_t struct_size) {
-    if (!c || !out) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
-    return put_sized(out, struct_size, c->g_stats);
+    return get_stats(c, GRAPH, out, struct_size, [](const StageState& a) { return a.graph.stats; });
 }
 
 // ---- coverage trimming (trim.hpp) ------------------------------------------------------------------------------
@@ -4315,24 +4380,24 @@ int bella_hip_graph_trim(bella_ctx* c, const bella_graph_trim_params* params) {
     if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
     HIPCHK(c, hipSetDevice(c->device));
     const auto t_begin = clk::now();
-    c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;
-    const uint32_t nr = c->nreads, n = (uint32_t)c->g_recs.size();
+    drop(c, TRIM);
+    StageState::Trim& t = c->as.trim;
+    const uint32_t nr = c->nreads, n = (uint32_t)c->as.records.size();
     if (nr >= (1u << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 reads");
     if (n >= (1u << 29)) return fail(c, BELLA_ERR_BAD_ARG, "trim: fewer than 2^29 overlap records (four sort keys each)");
     const uint64_t nkeys = 4 * (uint64_t)n;
     bella_trim_stats st{};
-    c->t_clips.assign(nr, bella_read_clip{0, 0, 0, 0});
+    t.clips.assign(nr, bella_read_clip{0, 0, 0, 0});
     uint32_t nint = 0;
     if (n && nr) {
         TmpBuf recs, keys, keysb, evoff, clip, cnt;
-        ENSURE(c, recs, sizeof(bella_overlap) * (size_t)n);
         ENSURE(c, keys, 8 * (size_t)nkeys); ENSURE(c, keysb, 8 * (size_t)nkeys);
         ENSURE(c, evoff, 4 * ((size_t)nr + 1));
         ENSURE(c, clip, sizeof(bella_read_clip) * (size_t)nr);
         ENSURE(c, cnt, 4);
         EventSet ev;
         if (int r = ev.create(c, 4)) return r;
-        HIPCHK(c, c->stager.h2d(recs.p, c->g_recs.data(), sizeof(bella_overlap) * (size_t)n, c->stream));
+        if (int r = upload_records(c, recs)) return r;
         HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4, c->stream));
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
         k_trim_events<<<nblk(n), 256, 0, c->stream>>>(ptr<bella_overlap>(recs), n, ptr<uint64_t>(c->roff), tp.end_clip, tp.min_span, ptr<uint64_t>(keys), ptr<uint32_t>(cnt));
@@ -4348,14 +4413,14 @@ int bella_hip_graph_trim(bella_ctx* c, const bella_graph_trim_params* params) {
                                                                              ptr<bella_read_clip>(clip));
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.e, c->stream));
-        HIPCHK(c, c->stager.d2h(c->t_clips.data(), clip.p, sizeof(bella_read_clip) * (size_t)nr, c->stream));
+        HIPCHK(c, c->stager.d2h(t.clips.data(), clip.p, sizeof(bella_read_clip) * (size_t)nr, c->stream));
         HIPCHK(c, hipMemcpyAsync(&nint, cnt.p, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         st.events_ms = ev_ms(ev.a, ev.b); st.sort_ms = ev_ms(ev.b, ev.d); st.sweep_ms = ev_ms(ev.d, ev.e);
     }
     st.intervals = nint;
     for (uint32_t r = 0; r < nr; ++r) {
-        const bella_read_clip& k = c->t_clips[r];
+        const bella_read_clip& k = t.clips[r];
         st.bases_before += c->host_lens[r];
         st.bases_after += k.end - k.beg;
         if (k.end == k.beg) ++st.reads_uncovered;
@@ -4363,27 +4428,25 @@ int bella_hip_graph_trim(bella_ctx* c, const bella_graph_trim_params* params) {
         if (k.nregions >= 2) ++st.reads_multi;
     }
     st.host_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
-    c->t_stats = st;
-    c->have_trim = true;
+    t.stats = st;
+    made(c, TRIM);
     return 0;
 }
 
 int bella_hip_graph_get_trim(bella_ctx* c, bella_read_clip* out) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_trim) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_trim first");
-    if (out && !c->t_clips.empty()) std::memcpy(out, c->t_clips.data(), sizeof(bella_read_clip) * c->t_clips.size());
+    if (int r = need(c, TRIM)) return r;
+    copy_out(out, c->as.trim.clips);
     return 0;
 }
 
 int bella_hip_graph_get_trim_stats(bella_ctx* c, void* out, uint64_t struct_size) {
-    if (!c || !out) return BELLA_ERR_BAD_ARG;
-    if (!c->have_trim) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_trim first");
-    return put_sized(out, struct_size, c->t_stats);
+    return get_stats(c, TRIM, out, struct_size, [](const StageState& a) { return a.trim.stats; });
 }
 
 int bella_hip_graph_untrim(bella_ctx* c) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (c->have_trim) c->have_graph = c->have_unitigs = c->have_polish = c->have_trim = false;
+    if (has(c, TRIM)) drop(c, TRIM);                                  // (no trim: the graph was built without one and stays)
     return 0;
 }
 
@@ -4393,14 +4456,12 @@ int bella_hip_graph_untrim(bella_ctx* c) {
 namespace {
 // the context's current graph on the device: 32-bit offsets, the edges
 int graph_upload(bella_ctx* c, Buf& off, Buf& edges) {
-    const size_t nv1 = c->g_off.size(), m = c->g_edges.size();
-    std::vector<uint32_t> off32(nv1);
-    for (size_t i = 0; i < nv1; ++i) off32[i] = (uint32_t)c->g_off[i];
+    const StageState::Graph& g = c->as.graph;
+    const size_t nv1 = g.off.size(), m = g.edges.size();
     ENSURE(c, off, 4 * nv1);
     ENSURE(c, edges, sizeof(bella_graph_edge) * m);
-    HIPCHK(c, c->stager.h2d(off.p, off32.data(), 4 * nv1, c->stream));
-    if (m) HIPCHK(c, c->stager.h2d(edges.p, c->g_edges.data(), sizeof(bella_graph_edge) * m, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                       // (off32 leaves scope)
+    HIPCHK(c, c->stager.h2d(off.p, g.off.data(), 4 * nv1, c->stream));
+    if (m) HIPCHK(c, c->stager.h2d(edges.p, g.edges.data(), sizeof(bella_graph_edge) * m, c->stream));
     return 0;
 }
 
@@ -4412,10 +4473,9 @@ struct ReadSpans {
     int make(bella_ctx* c) {
         const uint32_t nr = c->nreads;
         beg = ptr<uint64_t>(c->roff); end = ptr<uint64_t>(c->roff) + 1;
-        if (!c->have_trim || !nr) return 0;
-        ENSURE(c, clipb, sizeof(bella_read_clip) * (size_t)nr);
+        if (!has(c, TRIM) || !nr) return 0;
+        if (int r = upload_clips(c, clipb)) return r;
         ENSURE(c, begs, 8 * (size_t)nr); ENSURE(c, ends, 8 * (size_t)nr);
-        HIPCHK(c, c->stager.h2d(clipb.p, c->t_clips.data(), sizeof(bella_read_clip) * (size_t)nr, c->stream));
         k_trim_spans<<<nblk(nr), 256, 0, c->stream>>>(ptr<bella_read_clip>(clipb), ptr<uint64_t>(c->roff), nr, ptr<uint64_t>(begs), ptr<uint64_t>(ends));
         KCHK(c);
         beg = ptr<uint64_t>(begs); end = ptr<uint64_t>(ends);
@@ -4424,8 +4484,8 @@ struct ReadSpans {
 };
 
 // What tip clipping and bubble popping share: the graph and the removed-read marks on the device, the buffers a round filters and
-// compacts with, the stage's two events.  A stage marks the reads of a round in `hit`, the edges that stay in `keep`, scans `keep`
-// into `scan`, and owns everything else: its kernels, its counters, its read-backs and synchronisations.
+// compacts with, the stage's two events.  A stage marks the reads of a round in `hit` and owns everything else: its kernels, its
+// counters, its read-backs and synchronisations.  Nothing here waits for the device but finish().
 struct GraphRound {
     TmpBuf off, off2, E, E2, rem, hit, keep, scan;
     EventSet ev;
@@ -4433,7 +4493,7 @@ struct GraphRound {
     // upload, allocate, start the clock
     int begin(bella_ctx* c) {
         nr = c->nreads; nv = 2 * nr;
-        m = m0 = (uint32_t)c->g_edges.size();
+        m = m0 = (uint32_t)c->as.graph.edges.size();
         int rc = graph_upload(c, off, E);
         if (rc) return rc;
         ENSURE(c, off2, 4 * ((size_t)nv + 1));
@@ -4441,16 +4501,25 @@ struct GraphRound {
         ENSURE(c, hit, nr); ENSURE(c, rem, nr);
         ENSURE(c, keep, (size_t)m + 1);
         ENSURE(c, scan, 4 * ((size_t)m + 1));
-        HIPCHK(c, hipMemcpyAsync(rem.p, c->g_removed.data(), nr, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(rem.p, c->as.graph.removed.data(), nr, hipMemcpyHostToDevice, c->stream));
         if ((rc = ev.create(c, 2))) return rc;
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
         return 0;
     }
-    // the kept edges become the graph (enqueued, not waited for); the caller sets m to the count it read back from scan[m]
+    // the edges that stay (no end of theirs in `hit`, not named by `ekill` when there is one) into `keep`, its scan, and how many they
+    // are on the way into *kept
+    int filter(bella_ctx* c, const uint8_t* ekill, uint32_t* kept) {
+        k_graph_keep_filter<<<nblk((uint64_t)m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), m, ptr<uint8_t>(hit), ekill, ptr<uint8_t>(keep));
+        KCHK(c);
+        if (int rc = scan_u8_to_u32(c, ptr<uint8_t>(keep), ptr<uint32_t>(scan), (uint64_t)m + 1)) return rc;
+        HIPCHK(c, hipMemcpyAsync(kept, ptr<uint32_t>(scan) + m, 4, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }
+    // the kept edges become the graph; the caller sets m to the count it read back
     int apply_keep(bella_ctx* c) {
         k_graph_compact<<<nblk(m), 256, 0, c->stream>>>(ptr<bella_graph_edge>(E), ptr<uint8_t>(keep), ptr<uint32_t>(scan), m, ptr<bella_graph_edge>(E2));
         KCHK(c);
-        k_utg_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint32_t>(off2));
+        k_graph_new_offsets<<<nblk((uint64_t)nv + 1), 256, 0, c->stream>>>(ptr<uint32_t>(off), ptr<uint32_t>(scan), nv, ptr<uint32_t>(off2));
         KCHK(c);
         E.swap(E2);
         off.swap(off2);
@@ -4459,16 +4528,16 @@ struct GraphRound {
     // stop the clock; the graph and the marks back into the context
     int finish(bella_ctx* c, uint64_t* edges_removed, double* ms) {
         HIPCHK(c, hipEventRecord(ev.b, c->stream));
-        std::vector<uint32_t> off32((size_t)nv + 1);
+        std::vector<uint32_t> offs((size_t)nv + 1);
         std::vector<bella_graph_edge> edges(m);
         std::vector<uint8_t> removed(nr);
-        HIPCHK(c, hipMemcpyAsync(off32.data(), off.p, 4 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(offs.data(), off.p, 4 * ((size_t)nv + 1), hipMemcpyDeviceToHost, c->stream));
         if (m) HIPCHK(c, c->stager.d2h(edges.data(), E.p, sizeof(bella_graph_edge) * (size_t)m, c->stream));
         HIPCHK(c, hipMemcpyAsync(removed.data(), rem.p, nr, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (size_t i = 0; i <= nv; ++i) c->g_off[i] = off32[i];
-        c->g_edges.swap(edges);
-        c->g_removed.swap(removed);
+        c->as.graph.off.swap(offs);
+        c->as.graph.edges.swap(edges);
+        c->as.graph.removed.swap(removed);
         *edges_removed = m0 - m;
         *ms = ev_ms(ev.a, ev.b);
         return 0;
@@ -4483,14 +4552,15 @@ int bella_hip_graph_clean(bella_ctx* c, const bella_graph_clean_params* params) 
     bella_graph_clean_params cp{(uint32_t)sizeof(bella_graph_clean_params), 4, 3};
     if (int r = take_params(c, cp, params, "bella_graph_clean_params")) return r;
     if (cp.tip_rounds > BELLA_MAX_TIP_ROUNDS) return fail(c, BELLA_ERR_BAD_ARG, "tip_rounds %u: at most %d", cp.tip_rounds, BELLA_MAX_TIP_ROUNDS);
-    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    if (int r = need(c, GRAPH)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_unitigs = c->have_polish = false;
-    bella_unitig_stats st{};
+    changed(c, GRAPH);
+    c->as.unitigs.stats = bella_unitig_stats{};
+    bella_unitig_stats& st = c->as.graph.clean;
+    st = bella_unitig_stats{};
     const uint32_t nr = c->nreads, nv = 2 * nr;
-    const uint32_t m = (uint32_t)c->g_edges.size();
-    if (!cp.max_tip_reads || !cp.tip_rounds) { c->u_stats = st; return 0; }
-    if (!m) { st.rounds = 1; c->u_stats = st; return 0; }             // (a round over no edges finds nothing)
+    if (!cp.max_tip_reads || !cp.tip_rounds) return 0;
+    if (c->as.graph.edges.empty()) { st.rounds = 1; return 0; }       // (a round over no edges finds nothing)
     TmpBuf cnt;
     ENSURE(c, cnt, 4 * kUcCount);
     GraphRound g;
@@ -4502,7 +4572,7 @@ int bella_hip_graph_clean(bella_ctx* c, const bella_graph_clean_params* params) 
         HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kUcCount, c->stream));
         k_tip_walk<<<nblk(nv), 256, 0, c->stream>>>(ptr<uint32_t>(g.off), ptr<bella_graph_edge>(g.E), nv, cp.max_tip_reads, ptr<uint8_t>(g.hit), ptr<uint32_t>(cnt));
         KCHK(c);
-        k_tip_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(g.hit), nr, ptr<uint8_t>(g.rem), ptr<uint32_t>(cnt));
+        k_graph_mark_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(g.hit), nr, ptr<uint8_t>(g.rem), ptr<uint32_t>(cnt) + kUcReads);
         KCHK(c);
         HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kUcCount, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4511,25 +4581,19 @@ int bella_hip_graph_clean(bella_ctx* c, const bella_graph_clean_params* params) 
         st.rounds = round + 1;
         st.reads_removed += hc[kUcReads];
         if (!hc[kUcReads]) break;
-        k_tip_filter<<<nblk((uint64_t)g.m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(g.E), g.m, ptr<uint8_t>(g.hit), ptr<uint8_t>(g.keep));
-        KCHK(c);
-        rc = scan_u8_to_u32(c, ptr<uint8_t>(g.keep), ptr<uint32_t>(g.scan), (uint64_t)g.m + 1);
-        if (rc) return rc;
         uint32_t nm = 0;
-        HIPCHK(c, hipMemcpyAsync(&nm, ptr<uint32_t>(g.scan) + g.m, 4, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = g.filter(c, nullptr, &nm))) return rc;
         if ((rc = g.apply_keep(c))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         g.m = nm;
     }
-    if ((rc = g.finish(c, &st.edges_removed, &st.clean_ms))) return rc;
-    c->u_stats = st;
-    return 0;
+    return g.finish(c, &st.edges_removed, &st.clean_ms);
 }
 
 int bella_hip_graph_get_removed(bella_ctx* c, uint8_t* removed) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
-    if (removed && !c->g_removed.empty()) std::memcpy(removed, c->g_removed.data(), c->g_removed.size());
+    if (int r = need(c, GRAPH)) return r;
+    copy_out(removed, c->as.graph.removed);
     return 0;
 }
 
@@ -4540,14 +4604,15 @@ int bella_hip_graph_pop_bubbles(bella_ctx* c, const bella_graph_bubble_params* p
     if (int r = take_params(c, bp, params, "bella_graph_bubble_params")) return r;
     if (bp.bubble_rounds > BELLA_MAX_BUBBLE_ROUNDS) return fail(c, BELLA_ERR_BAD_ARG, "bubble_rounds %u: at most %d", bp.bubble_rounds, BELLA_MAX_BUBBLE_ROUNDS);
     if (bp.max_bubble_reads > BELLA_MAX_BUBBLE_READS) return fail(c, BELLA_ERR_BAD_ARG, "max_bubble_reads %u: at most %d", bp.max_bubble_reads, BELLA_MAX_BUBBLE_READS);
-    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    if (int r = need(c, GRAPH)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_unitigs = c->have_polish = false;
-    bella_bubble_stats st{};
+    changed(c, GRAPH);
+    bella_bubble_stats& st = c->as.graph.bubbles;
+    st = bella_bubble_stats{};
     const uint32_t nr = c->nreads, nv = 2 * nr;
-    const uint32_t m = (uint32_t)c->g_edges.size();
-    if (!bp.max_bubble_reads || !bp.bubble_rounds) { c->b_stats = st; return 0; }
-    if (!m) { st.rounds = 1; c->b_stats = st; return 0; }             // (a round over no edges finds nothing)
+    const uint32_t m = (uint32_t)c->as.graph.edges.size();
+    if (!bp.max_bubble_reads || !bp.bubble_rounds) return 0;
+    if (!m) { st.rounds = 1; return 0; }                              // (a round over no edges finds nothing)
     TmpBuf list, claim, ekill, cnt;
     ENSURE(c, list, 4 * (size_t)nv);
     ENSURE(c, claim, 4 * (size_t)nr);
@@ -4571,13 +4636,9 @@ int bella_hip_graph_pop_bubbles(bella_ctx* c, const bella_graph_bubble_params* p
         k_bub_apply<<<nblk(nv, kBubBlock / 64), kBubBlock, 0, c->stream>>>(ptr<uint32_t>(g.off), ptr<bella_graph_edge>(g.E), ptr<uint32_t>(list), bp.max_bubble_reads,
                                                                            bp.max_bubble_dist, ptr<uint32_t>(claim), ptr<uint8_t>(g.hit), ptr<uint8_t>(ekill), ptr<uint32_t>(cnt));
         KCHK(c);
-        k_bub_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(g.hit), nr, ptr<uint8_t>(g.rem), ptr<uint32_t>(cnt));
+        k_graph_mark_reads<<<nblk(nr), 256, 0, c->stream>>>(ptr<uint8_t>(g.hit), nr, ptr<uint8_t>(g.rem), ptr<uint32_t>(cnt) + kBcReads);
         KCHK(c);
-        k_bub_filter<<<nblk((uint64_t)g.m + 1), 256, 0, c->stream>>>(ptr<bella_graph_edge>(g.E), g.m, ptr<uint8_t>(g.hit), ptr<uint8_t>(ekill), ptr<uint8_t>(g.keep));
-        KCHK(c);
-        rc = scan_u8_to_u32(c, ptr<uint8_t>(g.keep), ptr<uint32_t>(g.scan), (uint64_t)g.m + 1);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(&nm, ptr<uint32_t>(g.scan) + g.m, 4, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = g.filter(c, ptr<uint8_t>(ekill), &nm))) return rc;
         HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kBcCount, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));                   // the round's one read-back
         st.sources[round] = hc[kBcSources]; st.found[round] = hc[kBcFound]; st.popped[round] = hc[kBcPopped];
@@ -4588,32 +4649,28 @@ int bella_hip_graph_pop_bubbles(bella_ctx* c, const bella_graph_bubble_params* p
         if ((rc = g.apply_keep(c))) return rc;
         g.m = nm;
     }
-    if ((rc = g.finish(c, &st.edges_removed, &st.pop_ms))) return rc;
-    c->b_stats = st;
-    return 0;
+    return g.finish(c, &st.edges_removed, &st.pop_ms);
 }
 
 int bella_hip_graph_get_bubble_stats(bella_ctx* c, void* out, uint64_t struct_size) {
-    if (!c || !out) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
-    return put_sized(out, struct_size, c->b_stats);
+    return get_stats(c, GRAPH, out, struct_size, [](const StageState& a) { return a.graph.bubbles; });
 }
 
 int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertices, uint64_t* nlinks, uint64_t* total_bases) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
+    if (int r = need(c, GRAPH)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_unitigs = c->have_polish = false;
-    const uint32_t nr = c->nreads, nv = 2 * nr, m = (uint32_t)c->g_edges.size();
-    bella_unitig_stats& st = c->u_stats;                              // (the clean's figures stay)
-    st.unitigs = st.vertices = st.links = st.total_bases = st.circular = st.largest = st.n50 = st.cycle_vertices = st.gather_bytes = 0;
-    st.rank_rounds = 0;
-    st.rank_ms = st.gather_ms = 0;
+    drop(c, UNITIGS);
+    const StageState::Graph& g = c->as.graph;
+    StageState::Unitigs& u = c->as.unitigs;
+    const uint32_t nr = c->nreads, nv = 2 * nr, m = (uint32_t)g.edges.size();
+    bella_unitig_stats& st = u.stats;                                 // (the clean's figures are the graph's)
+    st = bella_unitig_stats{};
     std::vector<uint8_t> dead(nr);
     uint32_t nlive = 0;
-    for (uint32_t r = 0; r < nr; ++r) { dead[r] = (c->g_cont[r] | c->g_removed[r]) ? 1 : 0; nlive += dead[r] ? 0u : 1u; }
-    c->u_voff.assign(1, 0); c->u_boff.assign(1, 0);
-    c->u_pos.clear(); c->u_len.clear(); c->u_verts.clear(); c->u_nb.clear(); c->u_circ.clear(); c->u_bases.clear(); c->u_links.clear();
+    for (uint32_t r = 0; r < nr; ++r) { dead[r] = (g.contained[r] | g.removed[r]) ? 1 : 0; nlive += dead[r] ? 0u : 1u; }
+    u.voff.assign(1, 0); u.boff.assign(1, 0);
+    u.pos.clear(); u.len.clear(); u.verts.clear(); u.nb.clear(); u.circ.clear(); u.bases.clear(); u.links.clear();
     uint32_t nutg = 0, nverts = 0, nlk = 0;
     uint64_t total = 0;
     if (nlive) {
@@ -4730,40 +4787,40 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
             KCHK(c);
         }
         HIPCHK(c, hipEventRecord(ev.e, c->stream));
-        c->u_voff.assign((size_t)nutg + 1, 0); c->u_boff.assign((size_t)nutg + 1, 0);
-        c->u_len.assign(nutg, 0); c->u_circ.assign(nutg, 0);
-        c->u_verts.assign(nverts, 0); c->u_nb.assign(nverts, 0); c->u_pos.assign(nverts, 0);
-        c->u_links.assign(nlk, bella_unitig_link{});
-        c->u_bases.assign((size_t)total, 0);
+        u.voff.assign((size_t)nutg + 1, 0); u.boff.assign((size_t)nutg + 1, 0);
+        u.len.assign(nutg, 0); u.circ.assign(nutg, 0);
+        u.verts.assign(nverts, 0); u.nb.assign(nverts, 0); u.pos.assign(nverts, 0);
+        u.links.assign(nlk, bella_unitig_link{});
+        u.bases.assign((size_t)total, 0);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         st.rank_ms = ev_ms(ev.a, ev.b);
         st.gather_ms = ev_ms(ev.d, ev.e);
         if (nutg) {
-            HIPCHK(c, hipMemcpy(c->u_voff.data(), uvoff.p, 8 * (size_t)nutg, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(c->u_boff.data(), uboff.p, 8 * ((size_t)nutg + 1), hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(c->u_len.data(), ulen.p, 8 * (size_t)nutg, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(c->u_circ.data(), ucirc.p, nutg, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(u.voff.data(), uvoff.p, 8 * (size_t)nutg, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(u.boff.data(), uboff.p, 8 * ((size_t)nutg + 1), hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(u.len.data(), ulen.p, 8 * (size_t)nutg, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(u.circ.data(), ucirc.p, nutg, hipMemcpyDeviceToHost));
         }
-        c->u_voff[nutg] = nverts;
+        u.voff[nutg] = nverts;
         if (nverts) {
-            HIPCHK(c, c->stager.d2h(c->u_verts.data(), verts.p, 4 * (size_t)nverts, c->stream));
-            HIPCHK(c, c->stager.d2h(c->u_nb.data(), nb.p, 4 * (size_t)nverts, c->stream));
-            HIPCHK(c, c->stager.d2h(c->u_pos.data(), pos.p, 8 * (size_t)nverts, c->stream));
+            HIPCHK(c, c->stager.d2h(u.verts.data(), verts.p, 4 * (size_t)nverts, c->stream));
+            HIPCHK(c, c->stager.d2h(u.nb.data(), nb.p, 4 * (size_t)nverts, c->stream));
+            HIPCHK(c, c->stager.d2h(u.pos.data(), pos.p, 8 * (size_t)nverts, c->stream));
         }
-        if (nlk) HIPCHK(c, c->stager.d2h(c->u_links.data(), links.p, sizeof(bella_unitig_link) * (size_t)nlk, c->stream));
-        if (total) HIPCHK(c, c->stager.d2h(c->u_bases.data(), out.p, (size_t)total, c->stream));
+        if (nlk) HIPCHK(c, c->stager.d2h(u.links.data(), links.p, sizeof(bella_unitig_link) * (size_t)nlk, c->stream));
+        if (total) HIPCHK(c, c->stager.d2h(u.bases.data(), out.p, (size_t)total, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     st.unitigs = nutg; st.vertices = nverts; st.links = nlk; st.total_bases = total; st.gather_bytes = total;
     {
-        std::vector<uint64_t> sorted(c->u_len);
+        std::vector<uint64_t> sorted(u.len);
         std::sort(sorted.begin(), sorted.end(), std::greater<uint64_t>());
         uint64_t acc = 0;
         for (uint64_t l : sorted) { acc += l; if (2 * acc >= total) { st.n50 = l; break; } }
         st.largest = sorted.empty() ? 0 : sorted[0];
-        for (uint8_t f : c->u_circ) st.circular += f;
+        for (uint8_t f : u.circ) st.circular += f;
     }
-    c->have_unitigs = true;
+    made(c, UNITIGS);
     if (nunitigs) *nunitigs = nutg;
     if (nvertices) *nvertices = nverts;
     if (nlinks) *nlinks = nlk;
@@ -4774,30 +4831,36 @@ int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertice
 int bella_hip_graph_get_unitigs(bella_ctx* c, uint64_t* vertex_offsets, uint32_t* vertices, uint64_t* pos, uint32_t* nbases, uint64_t* len, uint8_t* circular,
                                 bella_unitig_link* links) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph || !c->have_unitigs) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_unitigs first");
-    auto copy = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) std::memcpy(dst, src, bytes); };
-    copy(vertex_offsets, c->u_voff.data(), 8 * c->u_voff.size());
-    copy(vertices, c->u_verts.data(), 4 * c->u_verts.size());
-    copy(pos, c->u_pos.data(), 8 * c->u_pos.size());
-    copy(nbases, c->u_nb.data(), 4 * c->u_nb.size());
-    copy(len, c->u_len.data(), 8 * c->u_len.size());
-    copy(circular, c->u_circ.data(), c->u_circ.size());
-    copy(links, c->u_links.data(), sizeof(bella_unitig_link) * c->u_links.size());
+    if (int r = need(c, UNITIGS)) return r;
+    const StageState::Unitigs& u = c->as.unitigs;
+    copy_out(vertex_offsets, u.voff);
+    copy_out(vertices, u.verts);
+    copy_out(pos, u.pos);
+    copy_out(nbases, u.nb);
+    copy_out(len, u.len);
+    copy_out(circular, u.circ);
+    copy_out(links, u.links);
     return 0;
 }
 
 int bella_hip_graph_get_unitig_bases(bella_ctx* c, uint64_t* offsets, uint8_t* bases) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph || !c->have_unitigs) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_unitigs first");
-    if (offsets) std::memcpy(offsets, c->u_boff.data(), 8 * c->u_boff.size());
-    if (bases && !c->u_bases.empty()) std::memcpy(bases, c->u_bases.data(), c->u_bases.size());
+    if (int r = need(c, UNITIGS)) return r;
+    copy_out(offsets, c->as.unitigs.boff);
+    copy_out(bases, c->as.unitigs.bases);
     return 0;
 }
 
+// the unitigs' figures (zero while there are none) with the clean's, which belong to the graph
 int bella_hip_graph_get_unitig_stats(bella_ctx* c, void* out, uint64_t struct_size) {
-    if (!c || !out) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_build first");
-    return put_sized(out, struct_size, c->u_stats);
+    return get_stats(c, GRAPH, out, struct_size, [](const StageState& a) {
+        bella_unitig_stats s = a.unitigs.stats;
+        const bella_unitig_stats& k = a.graph.clean;
+        s.reads_removed = k.reads_removed; s.edges_removed = k.edges_removed; s.rounds = k.rounds; s.clean_ms = k.clean_ms;
+        std::memcpy(s.tips_per_round, k.tips_per_round, sizeof(s.tips_per_round));
+        std::memcpy(s.reads_per_round, k.reads_per_round, sizeof(s.reads_per_round));
+        return s;
+    });
 }
 
 // ---- unitig consensus (polish.hpp) ---------------------------------------------------------------------------------
@@ -4806,18 +4869,20 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
     bella_polish_params pp{};                                         // (no defaults: NULL was refused)
     if (int r = take_params(c, pp, params, "bella_polish_params")) return r;
     if (pp.min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
-    if (!c->have_graph || !c->have_unitigs) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_unitigs first");
-    if (!c->have_pile) return fail(c, BELLA_ERR_STATE, "bella_hip_pileup_reset first");
+    if (int r = need(c, UNITIGS)) return r;
+    if (int r = need(c, PILE)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_polish = false;
-    const uint32_t nutg = (uint32_t)c->u_len.size(), nseg = (uint32_t)c->u_verts.size();
-    const uint64_t total = c->u_boff[nutg];
+    drop(c, POLISH);
+    const StageState::Unitigs& u = c->as.unitigs;
+    StageState::Polish& p = c->as.polish;
+    const uint32_t nutg = (uint32_t)u.len.size(), nseg = (uint32_t)u.verts.size();
+    const uint64_t total = u.boff[nutg];
     bella_polish_stats st{};
     st.unitigs = nutg; st.vertices = nseg; st.bases_before = total; st.min_depth = pp.min_depth;
-    c->p_offs.assign((size_t)nutg + 1, 0);
-    c->p_pos.assign(nseg, 0); c->p_nb.assign(nseg, 0);
-    c->p_recs.assign(nutg, bella_polish_unitig{});
-    c->p_bases.clear();
+    p.offs.assign((size_t)nutg + 1, 0);
+    p.pos.assign(nseg, 0); p.nb.assign(nseg, 0);
+    p.recs.assign(nutg, bella_polish_unitig{});
+    p.bases.clear();
     uint64_t nout = 0;
     if (total) {                                                      // (no unitig position: nothing is launched)
         const uint64_t ntiles = (total + kPolTile - 1) / kPolTile;
@@ -4825,8 +4890,8 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
         st.tiles = (uint32_t)ntiles;
         st.table_bytes = total * kPileCounters * 4;
         std::vector<uint32_t> slot(nseg);
-        for (uint32_t u = 0; u < nutg; ++u)
-            for (uint64_t i = c->u_voff[u]; i < c->u_voff[u + 1]; ++i) slot[(size_t)i] = u;
+        for (uint32_t j = 0; j < nutg; ++j)
+            for (uint64_t i = u.voff[j]; i < u.voff[j + 1]; ++i) slot[(size_t)i] = j;
         TmpBuf verts, slot_utg, pos, uvoff, uboff, gseg, emit, tcnt, tpref, gp, ppos, pnb, poffs, recs, out;
         ENSURE(c, verts, 4 * (size_t)nseg); ENSURE(c, slot_utg, 4 * (size_t)nseg); ENSURE(c, pnb, 4 * (size_t)nseg);
         ENSURE(c, pos, 8 * (size_t)nseg); ENSURE(c, ppos, 8 * (size_t)nseg);
@@ -4835,11 +4900,11 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
         ENSURE(c, recs, sizeof(bella_polish_unitig) * (size_t)nutg);
         ENSURE(c, emit, (size_t)(ntiles * kPolTile));
         ENSURE(c, tcnt, 4 * ((size_t)ntiles + 1)); ENSURE(c, tpref, 8 * ((size_t)ntiles + 1));
-        HIPCHK(c, c->stager.h2d(verts.p, c->u_verts.data(), 4 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(verts.p, u.verts.data(), 4 * (size_t)nseg, c->stream));
         HIPCHK(c, c->stager.h2d(slot_utg.p, slot.data(), 4 * (size_t)nseg, c->stream));
-        HIPCHK(c, c->stager.h2d(pos.p, c->u_pos.data(), 8 * (size_t)nseg, c->stream));
-        HIPCHK(c, c->stager.h2d(uvoff.p, c->u_voff.data(), 8 * ((size_t)nutg + 1), c->stream));
-        HIPCHK(c, c->stager.h2d(uboff.p, c->u_boff.data(), 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, c->stager.h2d(pos.p, u.pos.data(), 8 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(uvoff.p, u.voff.data(), 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, c->stager.h2d(uboff.p, u.boff.data(), 8 * ((size_t)nutg + 1), c->stream));
         HIPCHK(c, hipMemsetAsync(recs.p, 0, sizeof(bella_polish_unitig) * (size_t)nutg, c->stream));
         HIPCHK(c, hipMemsetAsync(ptr<uint32_t>(tcnt) + ntiles, 0, 4, c->stream));
         k_utg_segoff<<<nblk((uint64_t)nseg + 1), 256, 0, c->stream>>>(ptr<uint32_t>(slot_utg), ptr<uint64_t>(pos), ptr<uint64_t>(uboff), nseg, nutg, ptr<uint64_t>(gseg));
@@ -4870,42 +4935,40 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
         k_pol_write<<<(uint32_t)ntiles, kPolBlock, 0, c->stream>>>(ptr<uint8_t>(emit), ptr<uint64_t>(tpref), ptr<uint8_t>(out));
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.e, c->stream));
-        c->p_bases.assign((size_t)nout, 0);
-        HIPCHK(c, c->stager.d2h(c->p_offs.data(), poffs.p, 8 * ((size_t)nutg + 1), c->stream));
-        HIPCHK(c, c->stager.d2h(c->p_recs.data(), recs.p, sizeof(bella_polish_unitig) * (size_t)nutg, c->stream));
-        HIPCHK(c, c->stager.d2h(c->p_pos.data(), ppos.p, 8 * (size_t)nseg, c->stream));
-        HIPCHK(c, c->stager.d2h(c->p_nb.data(), pnb.p, 4 * (size_t)nseg, c->stream));
-        if (nout) HIPCHK(c, c->stager.d2h(c->p_bases.data(), out.p, (size_t)nout, c->stream));
+        p.bases.assign((size_t)nout, 0);
+        HIPCHK(c, c->stager.d2h(p.offs.data(), poffs.p, 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, c->stager.d2h(p.recs.data(), recs.p, sizeof(bella_polish_unitig) * (size_t)nutg, c->stream));
+        HIPCHK(c, c->stager.d2h(p.pos.data(), ppos.p, 8 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.d2h(p.nb.data(), pnb.p, 4 * (size_t)nseg, c->stream));
+        if (nout) HIPCHK(c, c->stager.d2h(p.bases.data(), out.p, (size_t)nout, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         st.decide_ms = ev_ms(ev.a, ev.b);
         st.write_ms = ev_ms(ev.d, ev.e);
     }
     st.bases_after = nout;
-    for (const bella_polish_unitig& r : c->p_recs) {
+    for (const bella_polish_unitig& r : p.recs) {
         st.substituted += r.substituted; st.deleted += r.deleted; st.inserted += r.inserted; st.covered += r.covered; st.depth_sum += r.depth_sum;
     }
-    c->p_stats = st;
-    c->have_polish = true;
+    p.stats = st;
+    made(c, POLISH);
     if (total_bases) *total_bases = nout;
     return 0;
 }
 
 int bella_hip_graph_get_polished(bella_ctx* c, uint64_t* offsets, uint8_t* bases, uint64_t* ppos, uint32_t* pnbases, bella_polish_unitig* per_unitig) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph || !c->have_unitigs || !c->have_polish) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_polish_unitigs first");
-    auto copy = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) std::memcpy(dst, src, bytes); };
-    copy(offsets, c->p_offs.data(), 8 * c->p_offs.size());
-    copy(bases, c->p_bases.data(), c->p_bases.size());
-    copy(ppos, c->p_pos.data(), 8 * c->p_pos.size());
-    copy(pnbases, c->p_nb.data(), 4 * c->p_nb.size());
-    copy(per_unitig, c->p_recs.data(), sizeof(bella_polish_unitig) * c->p_recs.size());
+    if (int r = need(c, POLISH)) return r;
+    const StageState::Polish& p = c->as.polish;
+    copy_out(offsets, p.offs);
+    copy_out(bases, p.bases);
+    copy_out(ppos, p.pos);
+    copy_out(pnbases, p.nb);
+    copy_out(per_unitig, p.recs);
     return 0;
 }
 
 int bella_hip_graph_get_polish_stats(bella_ctx* c, void* out, uint64_t struct_size) {
-    if (!c || !out) return BELLA_ERR_BAD_ARG;
-    if (!c->have_graph || !c->have_unitigs || !c->have_polish) return fail(c, BELLA_ERR_STATE, "bella_hip_graph_polish_unitigs first");
-    return put_sized(out, struct_size, c->p_stats);
+    return get_stats(c, POLISH, out, struct_size, [](const StageState& a) { return a.polish.stats; });
 }
 
 int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,

@@ -196,21 +196,6 @@ __global__ __launch_bounds__(kBubBlock) void k_bub_apply(const uint32_t* off, co
     }
     if (lane == 0) atomicAdd(counters + kBcPopped, 1u);
 }
-
-// removed |= hit; the round's reads
-__global__ __launch_bounds__(256) void k_bub_reads(const uint8_t* hit, uint32_t nr, uint8_t* removed, uint32_t* counters) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool h = r < nr && hit[r];
-    if (h) removed[r] = 1;
-    graph_count(counters + kBcReads, h);
-}
-
-// keep[i] = edge i was not killed and neither end of it was hit; keep[m] = 0 (the scan's last element)
-__global__ void k_bub_filter(const bella_graph_edge* E, uint32_t m, const uint8_t* hit, const uint8_t* ekill, uint8_t* keep) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > m) return;
-    keep[i] = (i < m && !(hit[E[i].src >> 1] | hit[E[i].dst >> 1] | ekill[i])) ? 1 : 0;
-}
 #endif
 
 }  // namespace bella

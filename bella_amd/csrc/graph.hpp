@@ -275,9 +275,25 @@ __global__ void k_graph_compact(const bella_graph_edge* E, const uint8_t* keep, 
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < m && keep[i]) out[scan[i]] = E[i];
 }
-__global__ void k_graph_offsets(const uint32_t* off, const uint32_t* scan, uint32_t nv, uint64_t* out) {
+__global__ void k_graph_new_offsets(const uint32_t* off, const uint32_t* scan, uint32_t nv, uint32_t* out) {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v <= nv) out[v] = scan[off[v]];
+}
+
+// What a round of tip clipping (unitig.hpp) and of bubble popping (bubble.hpp) share once it has marked its reads in `hit`:
+// removed |= hit, and the round's reads into the stage's counter
+__global__ __launch_bounds__(256) void k_graph_mark_reads(const uint8_t* hit, uint32_t nr, uint8_t* removed, uint32_t* counter) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool h = r < nr && hit[r];
+    if (h) removed[r] = 1;
+    graph_count(counter, h);
+}
+
+// keep[i] = neither end of edge i was hit and (ekill != NULL) the edge was not killed itself; keep[m] = 0 (the scan's last element)
+__global__ void k_graph_keep_filter(const bella_graph_edge* E, uint32_t m, const uint8_t* hit, const uint8_t* ekill, uint8_t* keep) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > m) return;
+    keep[i] = (i < m && !(hit[E[i].src >> 1] | hit[E[i].dst >> 1] | (ekill ? ekill[i] : 0))) ? 1 : 0;
 }
 #endif
 

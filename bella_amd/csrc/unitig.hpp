@@ -67,25 +67,6 @@ __global__ __launch_bounds__(256) void k_tip_walk(const uint32_t* off, const bel
     graph_count(counters + kUcTips, tip);
 }
 
-// keep[i] = neither end of edge i was hit; keep[m] = 0 (the scan's last element)
-__global__ void k_tip_filter(const bella_graph_edge* E, uint32_t m, const uint8_t* hit, uint8_t* keep) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > m) return;
-    keep[i] = (i < m && !(hit[E[i].src >> 1] | hit[E[i].dst >> 1])) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void k_tip_reads(const uint8_t* hit, uint32_t nr, uint8_t* removed, uint32_t* counters) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool h = r < nr && hit[r];
-    if (h) removed[r] = 1;
-    graph_count(counters + kUcReads, h);
-}
-
-__global__ void k_utg_offsets(const uint32_t* off, const uint32_t* scan, uint32_t nv, uint32_t* out) {
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v <= nv) out[v] = scan[off[v]];
-}
-
 // ---- compaction ------------------------------------------------------------------------------------------------------------------------
 // pred is all ones on entry; an in-degree-1 vertex has one writer
 __global__ void k_utg_succ(const uint32_t* off, const bella_graph_edge* E, uint32_t nv, uint32_t* succ, uint32_t* pred, uint32_t* outlen, uint32_t* inlen) {

@@ -1,0 +1,68 @@
+"""What the GPU tests of the stages after the alignment share: the way to aligned pairs, the overlap records of traced pairs, a stress
+input for the graph, an error check, and the runner of the command line."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from bella_amd import BellaPars, api
+from bella_testkit import graph_mirror as G
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def aligned(eng, g):
+    """a golden set's reads and tuples -> overlap -> alignment: (pars, pairs, alignments)"""
+    eng.set_reads(g.rs)
+    eng.assemble_tuples(g.k, g.nkmers, g.tk, g.tr, g.tp)
+    pars = BellaPars(kmerSize=g.k, errorRate=g.err)
+    eng.overlap(pars)
+    pairs, _, _ = eng.get_pairs()
+    eng.align_pairs(pars)
+    return pars, pairs, eng.get_alignments()
+
+
+def records(pairs, alns, tr):
+    """the overlap records graph_add_traced makes of the passed, traced pairs"""
+    m = (alns["passed"] == 1) & (tr["nops"] > 0)
+    recs = np.zeros(int(m.sum()), G.OVL_DT)
+    recs["cid"], recs["rid"] = pairs["cid"][m], pairs["rid"][m]
+    for f, t in (("begV", "tbegV"), ("endV", "tendV"), ("begH", "tbegH"), ("endH", "tendH")):
+        recs[f] = tr[t][m]
+    recs["score"], recs["strand"] = alns["score"][m], alns["strand"][m]
+    return recs
+
+
+def hub_and_band(nreads=3000, hub=700, band=8, L=20000):
+    """a 700-way fork at read 0 and an eight-wide band over the other reads: (records, lengths)"""
+    out = []
+    for j in range(1, hub + 1):
+        out.append((0, j, L // 2 + j, L, 0, L // 2 - j, 0, j & 1, (0, 0, 0)))
+    for i in range(1, nreads - band):
+        for d in range(1, band + 1):
+            out.append((i, i + d, 1000 * d, L, 0, L - 1000 * d, 0, (i + d) % 3 == 0, (0, 0, 0)))
+    out.append((nreads - 2, nreads - 1, 0, L, 0, L, 0, 0, (0, 0, 0)))
+    return np.array(out, G.OVL_DT), np.full(nreads, L, np.int64)
+
+
+def raises(code, fn, *a, **kw):
+    with pytest.raises(api.BellaHipError) as ex:
+        fn(*a, **kw)
+    assert ex.value.code == code, (fn, ex.value.code)
+
+
+def run_cli(fastqs, flags, cwd, env_extra=None):
+    """bella-hip -f <list of fastqs> -o out <flags> in `cwd`, which must succeed: {file name: bytes} of every file it left there (the
+    -o file is "out.out"), and its log under "stderr" (bytes)"""
+    exe = os.path.join(ROOT, "bella_amd", "bin", "bella-hip")
+    os.makedirs(cwd, exist_ok=True)
+    with open(os.path.join(cwd, "in.txt"), "w") as f:
+        f.write("".join(p + "\n" for p in fastqs))
+    env = dict(os.environ)
+    env.update(env_extra or {})
+    p = subprocess.run([exe, "-f", "in.txt", "-o", "out"] + list(flags), cwd=cwd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
+    out = {n: open(os.path.join(cwd, n), "rb").read() for n in os.listdir(cwd) if n != "in.txt" and os.path.isfile(os.path.join(cwd, n))}
+    out["stderr"] = p.stderr
+    return out

@@ -2,8 +2,6 @@
 -- popped CSR, removed flags, every per-round count, and the unitigs and bases that follow -- on every input of the CPU tests; state and
 errors; the composition with graph_clean; bella-hip --pop-bubbles end to end on a diploid read set."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +11,7 @@ from bella_testkit import bubble_mirror as B
 from bella_testkit import graph_mirror as G
 from bella_testkit import synth
 from bella_testkit import unitig_mirror as U
-from conftest import ROOT
+from bella_testkit.pipeline import run_cli
 
 pytestmark = pytest.mark.gpu
 
@@ -201,17 +199,9 @@ def test_state_and_errors(eng, inputs):
 
 
 # ---- command line ----------------------------------------------------------------------------------------------------------------
-def _run(fastqs, flags, cwd, env_extra=None):
-    exe = os.path.join(ROOT, "bella_amd", "bin", "bella-hip")
-    os.makedirs(cwd, exist_ok=True)
-    with open(os.path.join(cwd, "in.txt"), "w") as f:
-        f.write("".join(p + "\n" for p in fastqs))
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    p = subprocess.run([exe, "-f", "in.txt", "-o", "out"] + list(flags), cwd=cwd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
-    rd = lambda n: open(os.path.join(cwd, n), "rb").read() if os.path.exists(os.path.join(cwd, n)) else None
-    return (rd("g.gfa"), rd("u.gfa"), rd("u.fa")), p.stderr.decode()             # (the log lines go to stderr)
+def _run(*args):
+    files = run_cli(*args)
+    return tuple(files.get(n) for n in ("g.gfa", "u.gfa", "u.fa")), files["stderr"].decode()      # (the log lines go to stderr)
 
 
 def test_cli_pop_bubbles_end_to_end(eng, tmp_path):

@@ -4,7 +4,6 @@ tests/test_trace_gpu.py pins to the trace mirror -- and bella-hip --correct end 
 import gzip
 import multiprocessing as mp
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +12,8 @@ from bella_amd import BellaPars, Engine, _lib, api
 from bella_testkit import pileup_mirror as P
 from bella_testkit import synth
 from bella_testkit import trace_mirror as M
-from conftest import GOLD, ROOT, load_golden
+from bella_testkit.pipeline import aligned as _aligned, run_cli
+from conftest import GOLD, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -23,16 +23,6 @@ def eng():
     e = Engine(0)
     yield e
     e.close()
-
-
-def _aligned(eng, g):
-    eng.set_reads(g.rs)
-    eng.assemble_tuples(g.k, g.nkmers, g.tk, g.tr, g.tp)
-    pars = BellaPars(kmerSize=g.k, errorRate=g.err)
-    eng.overlap(pars)
-    pairs, _, _ = eng.get_pairs()
-    eng.align_pairs(pars)
-    return pars, pairs, eng.get_alignments()
 
 
 def _offsets(seqs):
@@ -169,17 +159,9 @@ def test_every_column_votes_twice_every_gap_base_once_every_gap_run_once(eng):
 
 
 # ---- command line ----------------------------------------------------------------------------------------------------------------
-def _run(fastqs, flags, cwd, env_extra=None):
-    exe = os.path.join(ROOT, "bella_amd", "bin", "bella-hip")
-    os.makedirs(cwd, exist_ok=True)
-    with open(os.path.join(cwd, "in.txt"), "w") as f:
-        f.write("".join(p + "\n" for p in fastqs))
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    p = subprocess.run([exe, "-f", "in.txt", "-o", "out"] + list(flags), cwd=cwd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
-    fa = os.path.join(cwd, "c.fasta")
-    return open(os.path.join(cwd, "out.out"), "rb").read(), open(fa, "rb").read() if os.path.exists(fa) else None
+def _run(*args):
+    files = run_cli(*args)
+    return files["out.out"], files.get("c.fasta")
 
 
 def _fasta(names, seqs):

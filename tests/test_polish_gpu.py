@@ -5,7 +5,6 @@ measured effect on 2,000 reads of 10 kb at 15 % error."""
 import ctypes as C
 import gzip
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,7 +14,8 @@ from bella_testkit import graph_mirror as G
 from bella_testkit import pileup_mirror as P
 from bella_testkit import synth
 from bella_testkit import unitig_mirror as U
-from conftest import GOLD, ROOT, load_golden
+from bella_testkit.pipeline import aligned as _aligned, raises, run_cli
+from conftest import GOLD, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -174,16 +174,6 @@ def test_one_vertex_unitigs_are_the_reads_consensus(eng):
     assert raw[:int(p["pos"][1])] == P.consensus(seqs[0][:4000], t[:4000], 3)[0]
 
 
-def _aligned(eng, g):
-    eng.set_reads(g.rs)
-    eng.assemble_tuples(g.k, g.nkmers, g.tk, g.tr, g.tp)
-    pars = BellaPars(kmerSize=g.k, errorRate=g.err)
-    eng.overlap(pars)
-    pairs, _, _ = eng.get_pairs()
-    eng.align_pairs(pars)
-    return pars, pairs, eng.get_alignments()
-
-
 @pytest.mark.parametrize("name", ["toy120", "toylen80", "sanity3"])
 def test_real_traces_equal_the_mirror(eng, name):
     """align -> trace with votes, runs kept -> graph_add_traced -> graph_build (loose and default) -> clean -> unitigs -> polish, against
@@ -225,11 +215,6 @@ def test_state_and_errors():
     try:
         _, seqs, recs, graph, clean = CASES["two_round"]
         STATE, BAD = -7, -3
-
-        def raises(code, call, *a):
-            with pytest.raises(api.BellaHipError) as ex:
-                call(*a)
-            assert ex.value.code == code, (call, ex.value.code)
         e.set_reads(synth.ReadSet.from_strings(seqs))
         e.pileup_reset()
         raises(STATE, e.graph_polish_unitigs)                           # no graph, no unitigs
@@ -268,17 +253,9 @@ def test_state_and_errors():
 
 
 # ---- command line ----------------------------------------------------------------------------------------------------------------
-def _run(fastqs, flags, cwd, env_extra=None):
-    exe = os.path.join(ROOT, "bella_amd", "bin", "bella-hip")
-    os.makedirs(cwd, exist_ok=True)
-    with open(os.path.join(cwd, "in.txt"), "w") as f:
-        f.write("".join(p + "\n" for p in fastqs))
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    p = subprocess.run([exe, "-f", "in.txt", "-o", "out"] + list(flags), cwd=cwd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
-    rd = lambda n: open(os.path.join(cwd, n), "rb").read() if os.path.exists(os.path.join(cwd, n)) else None
-    return (rd("out.out"), rd("u.gfa"), rd("u.fa"), rd("c.fasta")), p.stderr
+def _run(*args):
+    files = run_cli(*args)
+    return tuple(files.get(n) for n in ("out.out", "u.gfa", "u.fa", "c.fasta")), files["stderr"]
 
 
 def test_cli_polish_end_to_end(eng, tmp_path):

@@ -3,7 +3,6 @@ definition (bella_testkit/trace_mirror.py), the replay checker on every traced p
 import gzip
 import multiprocessing as mp
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,7 +10,8 @@ import pytest
 from bella_amd import BellaPars, Engine, _lib, api
 from bella_testkit import synth
 from bella_testkit import trace_mirror as M
-from conftest import GOLD, ROOT, load_golden
+from bella_testkit.pipeline import aligned as _aligned, run_cli
+from conftest import GOLD, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -40,16 +40,6 @@ def _mirror(seqs, jobs):
     # (forked workers inherit the parent's device file descriptors: 12 of them + the parent stay clear of a limit of 16 such processes)
     with mp.get_context("fork").Pool(min(12, os.cpu_count() or 1)) as pool:
         return pool.map(_mirror_job, jobs, chunksize=4)
-
-
-def _aligned(eng, g):
-    eng.set_reads(g.rs)
-    eng.assemble_tuples(g.k, g.nkmers, g.tk, g.tr, g.tp)
-    pars = BellaPars(kmerSize=g.k, errorRate=g.err)
-    eng.overlap(pars)
-    pairs, _, _ = eng.get_pairs()
-    eng.align_pairs(pars)
-    return pars, pairs, eng.get_alignments()
 
 
 def _check_all(seqs, pairs, alns, tr, ops, idx, k_of=17):
@@ -192,16 +182,8 @@ def _parse_paf_cigar(data, seqs_by_name):
     return lines
 
 
-def _run(fastqs, flags, cwd, env_extra=None):
-    exe = os.path.join(ROOT, "bella_amd", "bin", "bella-hip")
-    os.makedirs(cwd, exist_ok=True)
-    with open(os.path.join(cwd, "in.txt"), "w") as f:
-        f.write("".join(p + "\n" for p in fastqs))
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    p = subprocess.run([exe, "-f", "in.txt", "-o", "out"] + list(flags), cwd=cwd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
-    return open(os.path.join(cwd, "out.out"), "rb").read()
+def _run(*args):
+    return run_cli(*args)["out.out"]
 
 
 @pytest.mark.parametrize("name", ["toy120", "toylen80"])

@@ -5,7 +5,6 @@ state and errors; bella-hip --trim end to end."""
 import ctypes as C
 import gzip
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,7 +15,8 @@ from bella_testkit import graph_mirror as G
 from bella_testkit import synth
 from bella_testkit import trim_mirror as T
 from bella_testkit import unitig_mirror as U
-from conftest import GOLD, ROOT, load_golden
+from bella_testkit.pipeline import aligned as _aligned, raises, records as _records, run_cli
+from conftest import GOLD, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -235,11 +235,7 @@ def test_state_and_errors():
     jl, jr, _, _ = T.junk_ends(starts, lens, strands, recs, 0.3, 1200, 3000)
     e = Engine(0)
     try:
-        def raises(code, fn, *a, **kw):
-            with pytest.raises(api.BellaHipError) as ei:
-                fn(*a, **kw)
-            assert ei.value.code == code
-        raises(STATE, e.graph_trim)                                     # no reads
+        raises(STATE, e.graph_trim)                                   # no reads
         _load(e, jl)
         raises(STATE, e.graph_clips)                                    # no trim
         raises(STATE, e.trim_stats)
@@ -288,37 +284,9 @@ def test_state_and_errors():
         e.close()
 
 
-def _aligned(eng, g):
-    eng.set_reads(g.rs)
-    eng.assemble_tuples(g.k, g.nkmers, g.tk, g.tr, g.tp)
-    pars = BellaPars(kmerSize=g.k, errorRate=g.err)
-    eng.overlap(pars)
-    pairs, _, _ = eng.get_pairs()
-    eng.align_pairs(pars)
-    return pars, pairs, eng.get_alignments()
-
-
-def _records(pairs, alns, tr):
-    m = (alns["passed"] == 1) & (tr["nops"] > 0)
-    recs = np.zeros(int(m.sum()), G.OVL_DT)
-    recs["cid"], recs["rid"] = pairs["cid"][m], pairs["rid"][m]
-    for f, t in (("begV", "tbegV"), ("endV", "tendV"), ("begH", "tbegH"), ("endH", "tendH")):
-        recs[f] = tr[t][m]
-    recs["score"], recs["strand"] = alns["score"][m], alns["strand"][m]
-    return recs
-
-
-def _run(fastqs, flags, cwd, env_extra=None):
-    exe = os.path.join(ROOT, "bella_amd", "bin", "bella-hip")
-    os.makedirs(cwd, exist_ok=True)
-    with open(os.path.join(cwd, "in.txt"), "w") as f:
-        f.write("".join(p + "\n" for p in fastqs))
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    p = subprocess.run([exe, "-f", "in.txt", "-o", "out"] + list(flags), cwd=cwd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
-    rd = lambda n: open(os.path.join(cwd, n), "rb").read() if os.path.exists(os.path.join(cwd, n)) else None
-    return (rd("out.out"), rd("g.gfa"), rd("u.gfa"), rd("u.fa"), rd("t.fa")), p.stderr
+def _run(*args):
+    files = run_cli(*args)
+    return tuple(files.get(n) for n in ("out.out", "g.gfa", "u.gfa", "u.fa", "t.fa")), files["stderr"]
 
 
 @pytest.mark.parametrize("name", ["toy120", "toyjunk220"])

@@ -5,16 +5,16 @@ golden sets, on reads cut from a known genome (the unitig is the genome), on a t
 import ctypes as C
 import gzip
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from bella_amd import BellaPars, Engine, _lib, api
+from bella_amd import Engine, _lib, api
 from bella_testkit import graph_mirror as G
 from bella_testkit import synth
 from bella_testkit import unitig_mirror as U
-from conftest import GOLD, ROOT, load_golden
+from bella_testkit.pipeline import aligned as _aligned, hub_and_band as _hub_and_band, records as _records, run_cli
+from conftest import GOLD, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -27,26 +27,6 @@ def eng():
     e = Engine(0)
     yield e
     e.close()
-
-
-def _aligned(eng, g):
-    eng.set_reads(g.rs)
-    eng.assemble_tuples(g.k, g.nkmers, g.tk, g.tr, g.tp)
-    pars = BellaPars(kmerSize=g.k, errorRate=g.err)
-    eng.overlap(pars)
-    pairs, _, _ = eng.get_pairs()
-    eng.align_pairs(pars)
-    return pars, pairs, eng.get_alignments()
-
-
-def _records(pairs, alns, tr):
-    m = (alns["passed"] == 1) & (tr["nops"] > 0)
-    recs = np.zeros(int(m.sum()), G.OVL_DT)
-    recs["cid"], recs["rid"] = pairs["cid"][m], pairs["rid"][m]
-    for f, t in (("begV", "tbegV"), ("endV", "tendV"), ("begH", "tbegH"), ("endH", "tendH")):
-        recs[f] = tr[t][m]
-    recs["score"], recs["strand"] = alns["score"][m], alns["strand"][m]
-    return recs
 
 
 def _same(eng, m, lens, seqs, clean=None):
@@ -206,17 +186,6 @@ def test_segments_shorter_than_the_gathers_groups(eng):
     assert len(mu["len"]) == 1 and mu["nbases"].min() == 1 and np.median(mu["nbases"]) < 16 and _is_substring(bases, genome, lo, hi)
 
 
-def _hub_and_band(nreads=3000, hub=700, band=8, L=20000):
-    out = []
-    for j in range(1, hub + 1):
-        out.append((0, j, L // 2 + j, L, 0, L // 2 - j, 0, j & 1, (0, 0, 0)))
-    for i in range(1, nreads - band):
-        for d in range(1, band + 1):
-            out.append((i, i + d, 1000 * d, L, 0, L - 1000 * d, 0, (i + d) % 3 == 0, (0, 0, 0)))
-    out.append((nreads - 2, nreads - 1, 0, L, 0, L, 0, 0, (0, 0, 0)))
-    return np.array(out, G.OVL_DT), np.full(nreads, L, np.int64)
-
-
 @pytest.fixture(scope="module")
 def hub():
     recs, lens = _hub_and_band()
@@ -284,17 +253,9 @@ def test_state_and_errors(eng):
 
 
 # ---- command line ----------------------------------------------------------------------------------------------------------------
-def _run(fastqs, flags, cwd, env_extra=None):
-    exe = os.path.join(ROOT, "bella_amd", "bin", "bella-hip")
-    os.makedirs(cwd, exist_ok=True)
-    with open(os.path.join(cwd, "in.txt"), "w") as f:
-        f.write("".join(p + "\n" for p in fastqs))
-    env = dict(os.environ)
-    env.update(env_extra or {})
-    p = subprocess.run([exe, "-f", "in.txt", "-o", "out"] + list(flags), cwd=cwd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
-    rd = lambda n: open(os.path.join(cwd, n), "rb").read() if os.path.exists(os.path.join(cwd, n)) else None
-    return rd("out.out"), rd("g.gfa"), rd("u.gfa"), rd("u.fa")
+def _run(*args):
+    files = run_cli(*args)
+    return tuple(files.get(n) for n in ("out.out", "g.gfa", "u.gfa", "u.fa"))
 
 
 def test_cli_unitigs_end_to_end(eng, tmp_path):

@@ -135,10 +135,11 @@ struct CountU64 {                                        // pair counts: without
     __host__ __device__ uint64_t operator()(const uint32_t& v) const { return (uint64_t)(v & ~kOrderedBit); }
 };
 
-// The results of the stages that follow the alignment, one member per stage, and which of them are valid.  All of
-// it lives on the host: the graph is small next to what it was made from, and a stage uploads what it reads.  drop / changed / need
-// (below) are the only code that touches `valid`.
-enum Stage : uint32_t { RECORDS, TRIM, GRAPH, UNITIGS, POLISH, PILE, CONS, kStages };
+// Which results of the pipeline's stages a context holds: one bit per stage, from the reads to the polished unitigs.
+// drop / changed / made / has / need (below) are the only code that touches `valid`.  The stages up to the traces keep their results in
+// members of the context (device buffers, mostly), PILE and CONS too; those of the stages that follow the alignment are here, one member
+// per stage, on the host: the graph is small next to what it was made from, and a stage uploads what it reads.
+enum Stage : uint32_t { READS, TUPLES, PANEL, MATRIX, PAIRS, ALNS, TRACES, BATCH_OPS, RECORDS, TRIM, GRAPH, UNITIGS, POLISH, PILE, CONS, kStages };
 struct StageState {
     uint32_t valid = 1u << RECORDS;          // one bit per Stage (the records are always there: possibly none)
     std::vector<bella_overlap> records;      // accumulated by bella_hip_graph_add_overlaps (graph.hpp)
@@ -168,7 +169,7 @@ struct StageState {
         std::vector<bella_polish_unitig> recs;
         bella_polish_stats stats{};
     } polish;
-    // PILE and CONS (pileup.hpp; section 10) are device buffers of the context: only their bits are here
+    // READS .. BATCH_OPS, PILE and CONS (pileup.hpp; section 10) are members of the context: only their bits are here
 };
 
 }  // namespace
@@ -186,11 +187,9 @@ struct bella_ctx {
     // B (reference layout) and device layout
     uint32_t nkmers = 0, kmer_size = 0;
     uint64_t nnz = 0;
-    bool have_reads = false, have_matrix = false, have_pairs = false, have_alns = false;
     std::vector<std::string> names;      // read names when the reads came through bella_hip_load_fastq
     std::vector<uint32_t> host_lens;
-    bool have_tuples = false;            // device-resident tuples + dictionary of bella_hip_count_kmers
-    uint64_t kc_ntuples = 0;
+    uint64_t kc_ntuples = 0;             // TUPLES: the device-resident tuples + dictionary of bella_hip_count_kmers
     uint32_t kc_nkmers = 0, kc_k = 0;
     uint32_t kc_bfirst = 0, kc_brows = 0; // the read block the device-resident tuples cover (all reads unless counted distributed)
     Buf kc_nk, kc_koff, kc_hist, kc_keys, kc_alt, kc_runlen, kc_flag, kc_slot, kc_nruns, kc_dcode, kc_dcount, kc_hkey, kc_hval, kc_found,
@@ -205,7 +204,6 @@ struct bella_ctx {
     uint64_t sym_sig[6] = {};            // what flops / nnzC were last cleared for
     uint64_t layout_gen = 0;             // bumped by every build of the device layout
     uint32_t range_lo = 0, range_hi = 0xFFFFFFFFu;   // stage: the contiguous column range computed by the next passes
-    bool have_panel = false;
     uint32_t panel_first = 0, panel_rows = 0;
     uint64_t panel_nnz = 0;
     // assembly temporaries
@@ -230,18 +228,16 @@ struct bella_ctx {
     uint64_t nalns = 0;
     Buf alns, seeds, xest, xest2, xids, xorder, xres, xstate, xlive, lg_res, lg_redo, lg_scratch;
     // traced alignments of the last bella_hip_trace_pairs (records index-aligned with the pairs; the ops stay on the host)
-    bool have_traces = false;
     std::vector<bella_trace> traces;
     std::vector<uint32_t> trace_ops;
     std::vector<uint32_t> batch_ops;     // runs of the last bella_hip_trace_batch
-    bool have_batch_ops = false;
     bella_trace_stats trace_stats{};
     Buf tr_exts, tr_lists, tr_res, tr_pres, tr_opoff, tr_dirs, tr_scr, tr_ops;
     bool trace_ops_kept = true;          // false: the last call piled its runs up on the device and did not stage them (keep_ops == 0)
     // read correction (pileup.hpp): the table of the loaded reads, and the last consensus
     uint64_t cons_total = 0;
     Buf pile, pile_pairs, pile_cnt, pile_tmp, cons_emit, cons_scan, cons_out, cons_offs, cons_stats;
-    StageState as;                       // overlap records, clips, graph, unitigs, polish; what of them and of the two above is valid
+    StageState as;                       // overlap records, clips, graph, unitigs, polish; which of all the stages' results are valid
     bella_timings tm{};
     hipEvent_t ev[12]{};
     uint32_t* pinned = nullptr;          // 128 host words the per-pass read backs land in
@@ -480,6 +476,14 @@ int put_sized(void* out, uint64_t struct_size, const S& s) {
 // from that; drop(s): s goes too (a stage drops itself when it starts and comes back with made(s) when it has succeeded).
 constexpr uint32_t stage_bit(Stage s) { return 1u << s; }
 constexpr uint32_t kBuiltFrom[kStages] = {
+    /* READS   */ stage_bit(TUPLES) | stage_bit(PANEL) | stage_bit(MATRIX) | stage_bit(TRIM) | stage_bit(GRAPH) | stage_bit(PILE),
+    /* TUPLES  */ 0,                         // (a recount keeps the matrix: its B was copied out of the tuples)
+    /* PANEL   */ 0,
+    /* MATRIX  */ stage_bit(PAIRS),
+    /* PAIRS   */ stage_bit(ALNS),
+    /* ALNS    */ stage_bit(TRACES),
+    /* TRACES  */ 0,                         // (bella_hip_graph_add_traced copies records out)
+    /* BATCH_OPS */ 0,                       // (the runs of a bella_hip_trace_batch, whose pairs were the caller's)
     /* RECORDS */ stage_bit(TRIM) | stage_bit(GRAPH),
     /* TRIM    */ stage_bit(GRAPH),
     /* GRAPH   */ stage_bit(UNITIGS),
@@ -501,7 +505,9 @@ void made(bella_ctx* c, Stage s) { c->as.valid |= stage_bit(s); }
 bool has(const bella_ctx* c, Stage s) { return (c->as.valid & stage_bit(s)) != 0; }
 // the precondition of a call that reads stage s
 int need(bella_ctx* c, Stage s) {
-    static const char* const first[kStages] = {"", "bella_hip_graph_trim first", "bella_hip_graph_build first", "bella_hip_graph_unitigs first",
+    static const char* const first[kStages] = {"set_reads first", "count_kmers first", "assemble_panel first", "set_B / assemble_tuples first",
+                                               "overlap first", "align_pairs first", "trace_pairs first", "trace_batch first",
+                                               "", "bella_hip_graph_trim first", "bella_hip_graph_build first", "bella_hip_graph_unitigs first",
                                                "bella_hip_graph_polish_unitigs first", "bella_hip_pileup_reset first", "bella_hip_consensus first"};
     return has(c, s) ? 0 : fail(c, BELLA_ERR_STATE, "%s", first[s]);
 }
@@ -582,7 +588,7 @@ int build_layout(bella_ctx* c, bool collective = false) {
     const uint32_t nk = c->nkmers;
     const uint32_t pf = c->part_first, ps = c->part_stride;
     if (nnz >= 0xFFFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "nnz(A) must be < 2^32 (KMERINDEX uint32, main.cpp:60)");
-    c->have_matrix = false;
+    drop(c, MATRIX);
     c->have_rowlists = false;
     c->layout_inline = 0;
     c->tm.expand_ms = 0.f;
@@ -813,9 +819,8 @@ int build_layout(bella_ctx* c, bool collective = false) {
     // assembly temporaries are large (tens of bytes per nonzero): give them back
     release(c->lk_key); release(c->lk_key2); release(c->lk_val); release(c->lk_val2); release(c->w); release(c->wscan); release(c->lk_rinfo);
     c->tm.layout_ms = ev_ms(c->ev[4], c->ev[5]);
-    c->have_matrix = true;
+    made(c, MATRIX);
     c->layout_gen++;
-    c->have_pairs = c->have_alns = false;
     return 0;
 }
 
@@ -1047,7 +1052,7 @@ int bella_hip_set_column_range(bella_ctx* c, uint32_t first, uint32_t count) {
     if (!c) return BELLA_ERR_BAD_ARG;
     c->range_lo = first;
     c->range_hi = (uint64_t)first + count > 0xFFFFFFFFull ? 0xFFFFFFFFu : first + count;
-    c->have_pairs = c->have_alns = false;
+    changed(c, MATRIX);
     return 0;
 }
 
@@ -1055,7 +1060,7 @@ int bella_hip_set_partition(bella_ctx* c, uint32_t first, uint32_t stride) {
     if (!c || stride == 0 || first >= stride) return fail(c, BELLA_ERR_BAD_ARG, "partition needs 0 <= first < stride");
     c->part_first = first;
     c->part_stride = stride;
-    c->have_pairs = c->have_alns = false;
+    changed(c, MATRIX);
     return 0;
 }
 
@@ -1096,13 +1101,10 @@ static int set_reads_impl(bella_ctx* c, const uint64_t* offsets, uint32_t nreads
     c->names.clear();
     c->host_lens.resize(nreads);
     for (uint32_t r = 0; r < nreads; ++r) c->host_lens[r] = (uint32_t)(offsets[r + 1] - offsets[r]);
-    c->have_reads = true;
-    c->have_matrix = c->have_pairs = c->have_alns = false;
-    c->have_tuples = false;
     for (Buf* b : {&c->pile, &c->cons_out, &c->cons_offs, &c->cons_stats}) release(*b);      // (the pileup belongs to the reads it was sized for)
-    drop(c, PILE);
-    c->as.records.clear();                                            // (so do the overlap records, the clips and the graph)
-    changed(c, RECORDS);
+    c->as.records.clear();                                            // (so do the overlap records)
+    changed(c, READS);                                                // (... and everything else but the runs of a trace_batch)
+    made(c, READS);
     return 0;
 }
 
@@ -1175,7 +1177,7 @@ int bella_hip_get_ingest_stats(bella_ctx* c, bella_ingest_stats* out) {
 
 int bella_hip_get_read_names(bella_ctx* c, char* buf, uint64_t buflen, uint64_t* offsets, uint64_t* needed) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_reads || c->names.size() != c->nreads) return fail(c, BELLA_ERR_STATE, "the reads were not loaded with bella_hip_load_fastq");
+    if (!has(c, READS) || c->names.size() != c->nreads) return fail(c, BELLA_ERR_STATE, "the reads were not loaded with bella_hip_load_fastq");
     uint64_t tot = 0;
     for (const auto& n : c->names) tot += n.size() + 1;
     if (needed) *needed = tot;
@@ -1193,20 +1195,30 @@ int bella_hip_get_read_names(bella_ctx* c, char* buf, uint64_t buflen, uint64_t*
 
 int bella_hip_get_read_lengths(bella_ctx* c, uint32_t* lens) {
     if (!c || !lens) return BELLA_ERR_BAD_ARG;
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "no reads");
+    if (int r = need(c, READS)) return r;
     std::memcpy(lens, c->host_lens.data(), 4 * (size_t)c->nreads);
+    return 0;
+}
+
+// The end of an assembly entry point: its times; the temporaries of assemble_rows_device go back where rows were assembled, and the tuple
+// buffers where the tuples were the caller's (those of a count stay: bella_hip_get_tuples, the next panel)
+static int assembly_done(bella_ctx* c, bool rows, bool host_tuples) {
+    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev[1]));
+    c->tm.assemble_ms = ev_ms(c->ev[0], c->ev[1]);
+    if (rows) c->tm.rows_ms = ev_ms(c->ev[0], c->ev[6]);
+    if (host_tuples) { release(c->t_kmer); release(c->t_read); release(c->t_pos); }
+    if (rows) { release(c->Bk_tmp); release(c->Bpos_tmp); release(c->asm_ws); }
     return 0;
 }
 
 int bella_hip_set_B(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, const uint32_t* colptr, const uint32_t* rowids,
                     const uint16_t* values) {
     if (!c || !colptr) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     if (kmer_size < 1 || kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32] (MAX_KMER_SIZEK, kmercode/common.h:13)");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_matrix = c->have_pairs = c->have_alns = false;
-    c->have_panel = false;
-    c->have_tuples = false;
+    drop(c, TUPLES); drop(c, PANEL); drop(c, MATRIX);
     if (colptr[0] != 0) return fail(c, BELLA_ERR_BAD_ARG, "colptr[0] must be 0");
     for (uint32_t r = 0; r < c->nreads; ++r) {
         if (colptr[r + 1] < colptr[r]) return fail(c, BELLA_ERR_BAD_ARG, "colptr must be non-decreasing (column %u)", r);
@@ -1228,10 +1240,7 @@ int bella_hip_set_B(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, const uin
     c->kmer_size = kmer_size;
     int rc = build_layout(c);
     if (rc) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    c->tm.assemble_ms = ev_ms(c->ev[0], c->ev[1]);
-    return 0;
+    return assembly_done(c, false, false);
 }
 
 // tuples of the reads first .. first+nr-1 -> their rows of B (CSR: c->Bptr local offsets, c->Bk, c->Bpos), on device
@@ -1357,13 +1366,11 @@ static int assemble_rows_device(bella_ctx* c, uint32_t first, uint32_t nr, uint6
 int bella_hip_assemble_tuples(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, uint64_t ntuples, const uint32_t* t_kmer,
                               const uint32_t* t_read, const uint16_t* t_pos) {
     if (!c || (ntuples && (!t_kmer || !t_read || !t_pos))) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     if (kmer_size < 1 || kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
     if (ntuples >= 0xFFFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "tuple count must be < 2^32");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_matrix = c->have_pairs = c->have_alns = false;
-    c->have_panel = false;
-    c->have_tuples = false;
+    drop(c, TUPLES); drop(c, PANEL); drop(c, MATRIX);
     uint64_t nnz = 0;
     int rc = assemble_rows_device(c, 0, c->nreads, ntuples, t_kmer, t_read, t_pos, &nnz);
     if (rc) return rc;
@@ -1372,12 +1379,7 @@ int bella_hip_assemble_tuples(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers,
     c->kmer_size = kmer_size;
     rc = build_layout(c);
     if (rc) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    c->tm.assemble_ms = ev_ms(c->ev[0], c->ev[1]);
-    c->tm.rows_ms = ev_ms(c->ev[0], c->ev[6]);
-    release(c->t_kmer); release(c->t_read); release(c->t_pos); release(c->Bk_tmp); release(c->Bpos_tmp); release(c->asm_ws);
-    return 0;
+    return assembly_done(c, true, true);
 }
 
 // ---- k-mer counting, dictionary, tuples (kcount.hpp) ----------------------------------------------------------------------
@@ -1397,17 +1399,28 @@ static int grow_keep(bella_ctx* c, Buf& b, size_t need, size_t used) {
 static int comm_agree(bella_ctx* c, int local_rc);
 static int comm_sync(bella_ctx* c, const char* what);
 
-static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, uint32_t upper, uint32_t mode, uint32_t window,
-                            uint32_t* nkmers_out, uint64_t* ntuples_out, uint64_t* ndistinct_out, bool dist = false, uint32_t bfirst = 0,
-                            uint32_t brows = 0xFFFFFFFFu) {
-    if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+// what a count asks of the reads and of its arguments (mode: 0 all k-mers, 1 syncmers, 2 minimizers; the read block the tuples are for)
+static int count_args(bella_ctx* c, uint16_t kmer_size, uint32_t lower, uint32_t upper, uint32_t mode, uint32_t window, uint32_t bfirst,
+                      uint32_t brows) {
+    if (int r = need(c, READS)) return r;
     if (kmer_size < 1 || kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
     if (lower < 2 || upper < lower || upper > 65535) return fail(c, BELLA_ERR_BAD_ARG, "need 2 <= lower <= upper <= 65535");
     if (mode == 2 && (window < 1 || window > 65535)) return fail(c, BELLA_ERR_BAD_ARG, "minimizer window must be in [1,65535]");
     if (mode == 1 && kmer_size <= kSmerLen) return fail(c, BELLA_ERR_BAD_ARG, "syncmer selection needs k > 5 (smerlen, syncmer.hpp:45)");
+    if ((uint64_t)bfirst + brows > c->nreads) return fail(c, BELLA_ERR_BAD_ARG, "read block exceeds the read set");
+    return 0;
+}
+
+static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, uint32_t upper, uint32_t mode, uint32_t window,
+                            uint32_t* nkmers_out, uint64_t* ntuples_out, uint64_t* ndistinct_out, bool dist = false, uint32_t bfirst = 0,
+                            uint32_t brows = 0) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (!dist) {                                                   // the tuples are for all reads (dist: the entry point has made the checks)
+        bfirst = 0; brows = c->nreads;
+        if (int r = count_args(c, kmer_size, lower, upper, mode, window, bfirst, brows)) return r;
+    }
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_tuples = false;
+    drop(c, TUPLES);
     const uint32_t nr = c->nreads, k = kmer_size;
     static const int dev_marks = getenv("BELLA_DEV_KCMARKS") ? atoi(getenv("BELLA_DEV_KCMARKS")) : 0;   // 1: stage times (synchronising), 2: host time only
     auto tmark0 = std::chrono::steady_clock::now();
@@ -1420,8 +1433,6 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
     };
     const int NR = dist ? c->comm_ranks : 1, me = dist ? c->comm_rank : 0;
     if (dist && !c->comm) return fail(c, BELLA_ERR_STATE, "bella_hip_comm_init first");
-    if (brows == 0xFFFFFFFFu) { bfirst = 0; brows = nr; }
-    if ((uint64_t)bfirst + brows > nr) return fail(c, BELLA_ERR_BAD_ARG, "read block exceeds the read set");
     // Local phase (histogram, sort passes, partial dictionary): a rank that fails here still takes part in the status exchange below,
     // so that all ranks leave the call together instead of waiting for it in the dictionary exchange.
     const uint8_t* d_sel = nullptr;
@@ -1758,7 +1769,7 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
     c->kc_k = k;
     c->kc_bfirst = bfirst;
     c->kc_brows = brows;
-    c->have_tuples = true;
+    made(c, TUPLES);
     if (nkmers_out) *nkmers_out = (uint32_t)nk_total;
     if (ntuples_out) *ntuples_out = nt;
     if (ndistinct_out) *ndistinct_out = ndistinct;
@@ -1778,12 +1789,7 @@ int bella_hip_count_kmers_dist(bella_ctx* c, uint16_t kmer_size, uint32_t lower,
     // instead of waiting for it in the dictionary exchange
     int rc = 0;
     if (selector > 2) rc = fail(c, BELLA_ERR_BAD_ARG, "selector: 0 = all k-mers, 1 = syncmers, 2 = minimizers");
-    else if (!c->have_reads) rc = fail(c, BELLA_ERR_STATE, "set_reads first");
-    else if (kmer_size < 1 || kmer_size > 32) rc = fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
-    else if (lower < 2 || upper < lower || upper > 65535) rc = fail(c, BELLA_ERR_BAD_ARG, "need 2 <= lower <= upper <= 65535");
-    else if (selector == 2 && (window < 1 || window > 65535)) rc = fail(c, BELLA_ERR_BAD_ARG, "minimizer window must be in [1,65535]");
-    else if (selector == 1 && kmer_size <= kSmerLen) rc = fail(c, BELLA_ERR_BAD_ARG, "syncmer selection needs k > 5 (smerlen, syncmer.hpp:45)");
-    else if ((uint64_t)first_read + nreads_block > c->nreads) rc = fail(c, BELLA_ERR_BAD_ARG, "read block exceeds the read set");
+    else rc = count_args(c, kmer_size, lower, upper, selector, window, first_read, nreads_block);
     if (hipSetDevice(c->device) != hipSuccess && !rc) rc = fail(c, BELLA_ERR_HIP, "hipSetDevice failed");
     const std::string local_err = c->err;
     rc = comm_agree(c, rc);
@@ -1803,7 +1809,7 @@ int bella_hip_count_minimizers(bella_ctx* c, uint16_t kmer_size, uint32_t window
 
 int bella_hip_get_dictionary(bella_ctx* c, uint64_t* codes, uint16_t* counts) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_tuples) return fail(c, BELLA_ERR_STATE, "count_kmers first");
+    if (int r = need(c, TUPLES)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if (codes && c->kc_nkmers) HIPCHK(c, hipMemcpyAsync(codes, c->kc_dcode.p, 8 * (size_t)c->kc_nkmers, hipMemcpyDeviceToHost, c->stream));
     if (counts && c->kc_nkmers) HIPCHK(c, hipMemcpyAsync(counts, c->kc_dcount.p, 2 * (size_t)c->kc_nkmers, hipMemcpyDeviceToHost, c->stream));
@@ -1813,7 +1819,7 @@ int bella_hip_get_dictionary(bella_ctx* c, uint64_t* codes, uint16_t* counts) {
 
 int bella_hip_get_tuples(bella_ctx* c, uint32_t* t_kmer, uint32_t* t_read, uint16_t* t_pos) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_tuples) return fail(c, BELLA_ERR_STATE, "count_kmers first");
+    if (int r = need(c, TUPLES)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = c->kc_ntuples;
     if (t_kmer && n) HIPCHK(c, hipMemcpyAsync(t_kmer, c->t_kmer.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
@@ -1825,11 +1831,10 @@ int bella_hip_get_tuples(bella_ctx* c, uint32_t* t_kmer, uint32_t* t_read, uint1
 
 int bella_hip_assemble_counted(bella_ctx* c) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_tuples) return fail(c, BELLA_ERR_STATE, "count_kmers first");
+    if (int r = need(c, TUPLES)) return r;
     if (c->kc_bfirst != 0 || c->kc_brows != c->nreads) return fail(c, BELLA_ERR_STATE, "the tuples cover a read block only: assemble_counted_panel + allgather_panels");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_matrix = c->have_pairs = c->have_alns = false;
-    c->have_panel = false;
+    drop(c, PANEL); drop(c, MATRIX);
     uint64_t nnz = 0;
     int rc = assemble_rows_device(c, 0, c->nreads, c->kc_ntuples, nullptr, nullptr, nullptr, &nnz);
     if (rc) return rc;
@@ -1838,39 +1843,28 @@ int bella_hip_assemble_counted(bella_ctx* c) {
     c->kmer_size = (uint16_t)c->kc_k;
     rc = build_layout(c);
     if (rc) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    c->tm.assemble_ms = ev_ms(c->ev[0], c->ev[1]);
-    c->tm.rows_ms = ev_ms(c->ev[0], c->ev[6]);
-    release(c->Bk_tmp); release(c->Bpos_tmp); release(c->asm_ws);
-    return 0;
+    return assembly_done(c, true, false);
 }
 
 int bella_hip_assemble_panel(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, uint32_t first_read, uint32_t nreads_panel,
                              uint64_t ntuples, const uint32_t* t_kmer, const uint32_t* t_read, const uint16_t* t_pos) {
     if (!c || (ntuples && (!t_kmer || !t_read || !t_pos))) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     if (kmer_size < 1 || kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
     if ((uint64_t)first_read + nreads_panel > c->nreads) return fail(c, BELLA_ERR_BAD_ARG, "panel exceeds the read set");
     if (ntuples >= 0xFFFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "tuple count must be < 2^32");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_matrix = c->have_pairs = c->have_alns = false;
-    c->have_panel = false;
-    c->have_tuples = false;
+    drop(c, TUPLES); drop(c, PANEL); drop(c, MATRIX);
     uint64_t nnz = 0;
     int rc = assemble_rows_device(c, first_read, nreads_panel, ntuples, t_kmer, t_read, t_pos, &nnz);
     if (rc) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    c->tm.assemble_ms = ev_ms(c->ev[0], c->ev[1]);
-    c->tm.rows_ms = ev_ms(c->ev[0], c->ev[6]);
-    release(c->t_kmer); release(c->t_read); release(c->t_pos); release(c->Bk_tmp); release(c->Bpos_tmp); release(c->asm_ws);
+    if (int r = assembly_done(c, true, true)) return r;
     c->nkmers = nkmers;
     c->kmer_size = kmer_size;
     c->panel_first = first_read;
     c->panel_rows = nreads_panel;
     c->panel_nnz = nnz;
-    c->have_panel = true;
+    made(c, PANEL);
     return 0;
 }
 
@@ -1879,13 +1873,11 @@ int bella_hip_assemble_panel(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, 
 int bella_hip_set_B_panel(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, uint32_t first_read, uint32_t nreads_panel, const uint32_t* colptr,
                           const uint32_t* rowids, const uint16_t* values) {
     if (!c || !colptr) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     if (kmer_size < 1 || kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
     if ((uint64_t)first_read + nreads_panel > c->nreads) return fail(c, BELLA_ERR_BAD_ARG, "panel exceeds the read set");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_matrix = c->have_pairs = c->have_alns = false;
-    c->have_panel = false;
-    c->have_tuples = false;
+    drop(c, TUPLES); drop(c, PANEL); drop(c, MATRIX);
     const uint32_t* cp = colptr + first_read;                      // colptr: the whole matrix's [nreads + 1]
     std::vector<uint32_t> cnt((size_t)nreads_panel + 2, 0);
     for (uint32_t r = 0; r < nreads_panel; ++r) {
@@ -1909,19 +1901,18 @@ int bella_hip_set_B_panel(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, uin
     c->panel_first = first_read;
     c->panel_rows = nreads_panel;
     c->panel_nnz = nnz;
-    c->have_panel = true;
+    made(c, PANEL);
     return 0;
 }
 
 int bella_hip_assemble_counted_panel(bella_ctx* c, uint32_t first_read, uint32_t nreads_panel) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_tuples) return fail(c, BELLA_ERR_STATE, "count_kmers first");
+    if (int r = need(c, TUPLES)) return r;
     if ((uint64_t)first_read + nreads_panel > c->nreads) return fail(c, BELLA_ERR_BAD_ARG, "panel exceeds the read set");
     if (first_read < c->kc_bfirst || (uint64_t)first_read + nreads_panel > (uint64_t)c->kc_bfirst + c->kc_brows)
         return fail(c, BELLA_ERR_BAD_ARG, "the device-resident tuples cover the reads %u .. %u only", c->kc_bfirst, c->kc_bfirst + c->kc_brows);
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_matrix = c->have_pairs = c->have_alns = false;
-    c->have_panel = false;
+    drop(c, PANEL); drop(c, MATRIX);
     uint64_t t0 = 0, t1 = 0;                                       // the panel's tuples are contiguous: tstart of its first / last read
     const uint32_t rel = first_read - c->kc_bfirst;
     HIPCHK(c, hipMemcpyAsync(&t0, ptr<uint64_t>(c->kc_tstart) + rel, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1930,24 +1921,20 @@ int bella_hip_assemble_counted_panel(bella_ctx* c, uint32_t first_read, uint32_t
     uint64_t nnz = 0;
     int rc = assemble_rows_device(c, first_read, nreads_panel, t1 - t0, nullptr, nullptr, nullptr, &nnz, t0);
     if (rc) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    c->tm.assemble_ms = ev_ms(c->ev[0], c->ev[1]);
-    c->tm.rows_ms = ev_ms(c->ev[0], c->ev[6]);
-    release(c->Bk_tmp); release(c->Bpos_tmp); release(c->asm_ws);
+    if (int r = assembly_done(c, true, false)) return r;
     c->nkmers = c->kc_nkmers;
     c->kmer_size = (uint16_t)c->kc_k;
     c->panel_first = first_read;
     c->panel_rows = nreads_panel;
     c->panel_nnz = nnz;
-    c->have_panel = true;
+    made(c, PANEL);
     return 0;
 }
 
 int bella_hip_panel_device_ptrs(bella_ctx* c, uint32_t* first_read, uint32_t* nreads_panel, uint64_t* nnz, const void** d_rowcnt,
                                 const void** d_rowids, const void** d_values) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_panel) return fail(c, BELLA_ERR_STATE, "assemble_panel first");
+    if (int r = need(c, PANEL)) return r;
     if (first_read) *first_read = c->panel_first;
     if (nreads_panel) *nreads_panel = c->panel_rows;
     if (nnz) *nnz = c->panel_nnz;
@@ -1960,10 +1947,10 @@ int bella_hip_panel_device_ptrs(bella_ctx* c, uint32_t* first_read, uint32_t* nr
 int bella_hip_set_B_device(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, const uint32_t* d_colptr, const uint32_t* d_rowids,
                            const uint16_t* d_values, uint64_t nnz) {
     if (!c || !d_colptr || (nnz && (!d_rowids || !d_values))) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     if (kmer_size < 1 || kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_matrix = c->have_pairs = c->have_alns = false;
+    drop(c, MATRIX);
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     // the sources may alias our own panel buffers: stage through fresh allocations
     TmpBuf nBptr, nBk, nBpos;
@@ -1975,16 +1962,13 @@ int bella_hip_set_B_device(bella_ctx* c, uint16_t kmer_size, uint32_t nkmers, co
     if (nnz) HIPCHK(c, hipMemcpyAsync(nBpos.p, d_values, 2 * nnz, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     nBptr.give_to(c->Bptr); nBk.give_to(c->Bk); nBpos.give_to(c->Bpos);
-    c->have_panel = false;
+    drop(c, PANEL);
     c->nkmers = nkmers;
     c->nnz = nnz;
     c->kmer_size = kmer_size;
     int rc = build_layout(c);
     if (rc) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    c->tm.assemble_ms = ev_ms(c->ev[0], c->ev[1]);
-    return 0;
+    return assembly_done(c, false, false);
 }
 
 // ---- multi-GPU: RCCL communicator + panel all-gather -------------------------------------------------------------------------
@@ -2302,7 +2286,7 @@ int bella_hip_allgather_panels(bella_ctx* c) {
     const int N = c->comm_ranks, me = c->comm_rank;
     c->dist_agreed = false;
     // a rank without a panel still takes part in the status exchange: all ranks leave the call together
-    int rc = comm_agree(c, c->have_panel ? 0 : fail(c, BELLA_ERR_STATE, "assemble_panel first"));
+    int rc = comm_agree(c, need(c, PANEL));
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     // who holds what: {first read, rows, nnz} of every rank
@@ -2375,20 +2359,16 @@ int bella_hip_allgather_panels(bella_ctx* c) {
     nCnt.reset();
     if (rc) return rc;
     nBptr.give_to(c->Bptr); nBk.give_to(c->Bk); nBpos.give_to(c->Bpos);
-    c->have_panel = false;
-    c->have_matrix = c->have_pairs = c->have_alns = false;
+    drop(c, PANEL); drop(c, MATRIX);
     c->nnz = nnz;
     rc = build_layout(c, true);
     if (rc) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    c->tm.assemble_ms = ev_ms(c->ev[0], c->ev[1]);     // exchange + layout
-    return 0;
+    return assembly_done(c, false, false);                        // (assemble_ms: exchange + layout)
 }
 
 int bella_hip_get_B(bella_ctx* c, uint64_t* nnz, uint32_t* colptr, uint32_t* rowids, uint16_t* values) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_matrix) return fail(c, BELLA_ERR_STATE, "no matrix");
+    if (int r = need(c, MATRIX)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if (nnz) *nnz = c->nnz;
     if (colptr) HIPCHK(c, hipMemcpyAsync(colptr, c->Bptr.p, 4 * ((size_t)c->nreads + 1), hipMemcpyDeviceToHost, c->stream));
@@ -3165,10 +3145,11 @@ static uint32_t owned_columns(const bella_ctx* c, uint32_t* i0_out) {
 
 int bella_hip_overlap(bella_ctx* c, const bella_params* p, uint64_t* npairs, uint64_t* flops) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_matrix) return fail(c, BELLA_ERR_STATE, "set_B / assemble_tuples first");
+    if (int r = need(c, MATRIX)) return r;
     int rc = check_params(c, p);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
+    drop(c, PAIRS);
     rc = layout_for_partition(c);
     if (rc) return rc;
     uint32_t st = 0;
@@ -3184,8 +3165,7 @@ int bella_hip_overlap(bella_ctx* c, const bella_params* p, uint64_t* npairs, uin
     }
     if (rc) { (void)hipDeviceSynchronize(); return rc; }     // side-stream kernels of the pass may still be in flight
     if (st & 1u) return fail(c, BELLA_ERR_BINS, "internal: > 16 bins without sort scratch");
-    c->have_pairs = true;
-    c->have_alns = false;
+    made(c, PAIRS);
     c->tm.numeric_passes++;
     c->tm.numeric_columns += owned_columns(c, nullptr);
     if (npairs) *npairs = c->npairs;
@@ -3196,7 +3176,7 @@ int bella_hip_overlap(bella_ctx* c, const bella_params* p, uint64_t* npairs, uin
 // the symbolic phase alone (spgemm.hpp: k_count_pairs)
 int bella_hip_count_pairs(bella_ctx* c, const bella_params* p, uint64_t* colptrC, uint64_t* npairs, uint64_t* flops) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_matrix) return fail(c, BELLA_ERR_STATE, "set_B / assemble_tuples first");
+    if (int r = need(c, MATRIX)) return r;
     int rc = check_params(c, p);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -3208,7 +3188,7 @@ int bella_hip_count_pairs(bella_ctx* c, const bella_params* p, uint64_t* colptrC
     ENSURE(c, c->colptrC, 8 * ((size_t)nr + 2));
     ENSURE(c, c->ctl, 4 * kCtlWords);
     std::memset(c->sym_sig, 0, sizeof(c->sym_sig));          // (the next numeric pass clears flops / nnzC for itself)
-    c->have_pairs = c->have_alns = false;
+    changed(c, MATRIX);
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     HIPCHK(c, hipMemsetAsync(c->flopsr.p, 0, 4 * ((size_t)nr + 2), c->stream));
     HIPCHK(c, hipMemsetAsync(c->nnzC.p, 0, 4 * ((size_t)nr + 2), c->stream));
@@ -3304,15 +3284,16 @@ static int get_memory_impl(bella_ctx* c, bella_memory* m) {
                           &c->kc_dcode, &c->kc_dcount, &c->kc_hkey, &c->kc_hval, &c->kc_found, &c->kc_tstart, &c->kc_cursor, &c->kc_sel, &c->kc_ringo, &c->kc_ringp, &c->kc_opos, &c->kc_oid, &c->kc_opos2, &c->kc_oid2, &c->alns,
                           &c->seeds, &c->xest, &c->xest2, &c->xids, &c->xorder, &c->xres, &c->xstate, &c->xlive, &c->lg_res, &c->lg_redo, &c->lg_scratch, &c->status, &c->comm_meta});
     m->other_bytes += c->pool.bytes;                               // (released buffers waiting for the next request they fit)
-    m->owned_nnz = c->have_matrix ? c->owned_nnz : 0;
-    m->layout_shared = c->have_matrix && c->layout_dist ? 1 : 0;
-    m->live_nnz = c->have_matrix ? c->live_nnz : 0;
+    const bool layout = has(c, MATRIX);
+    m->owned_nnz = layout ? c->owned_nnz : 0;
+    m->layout_shared = layout && c->layout_dist;
+    m->live_nnz = layout ? c->live_nnz : 0;
     return 0;
 }
 
 int bella_hip_get_pairs(bella_ctx* c, bella_pair* pairs, bella_pair_ext* ext, uint64_t* colptrC) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_pairs) return fail(c, BELLA_ERR_STATE, "overlap first");
+    if (int r = need(c, PAIRS)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if (pairs && c->npairs)
         HIPCHK(c, c->stager.d2h(pairs, c->pairs.p, sizeof(bella_pair) * c->npairs, c->stream));
@@ -3586,17 +3567,17 @@ int bella_hip_align_pairs_exact(bella_ctx* c, const bella_params* p, uint64_t* n
 
 static int align_pairs_impl(bella_ctx* c, const bella_params* p, uint64_t* npassed, bool exact) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_pairs) return fail(c, BELLA_ERR_STATE, "overlap first");
+    if (int r = need(c, PAIRS)) return r;
     int rc = check_params(c, p);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
+    drop(c, ALNS);
     ENSURE(c, c->alns, sizeof(bella_aln) * c->npairs);
     rc = exact ? run_logan(c, p, nullptr, ptr<bella_pair>(c->pairs), c->npairs, ptr<bella_aln>(c->alns))
                : run_xdrop(c, p, nullptr, ptr<bella_pair>(c->pairs), c->npairs, ptr<bella_aln>(c->alns));
     if (rc) { (void)hipDeviceSynchronize(); return rc; }      // (an error may leave class slices in flight on the side streams)
     c->nalns = c->npairs;
-    c->have_alns = true;
-    c->have_traces = false;
+    made(c, ALNS);
     if (npassed) {
         // small reduction on the host side of the ABI would need a copy; count on device instead
         ENSURE(c, c->cubtmp, 64);
@@ -3616,7 +3597,7 @@ static int align_pairs_impl(bella_ctx* c, const bella_params* p, uint64_t* npass
 
 int bella_hip_get_alignments(bella_ctx* c, bella_aln* out) {
     if (!c || !out) return BELLA_ERR_BAD_ARG;
-    if (!c->have_alns) return fail(c, BELLA_ERR_STATE, "align_pairs first");
+    if (int r = need(c, ALNS)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->nalns) HIPCHK(c, c->stager.d2h(out, c->alns.p, sizeof(bella_aln) * c->nalns, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3633,7 +3614,7 @@ int bella_hip_xdrop_batch_exact(bella_ctx* c, const bella_seed* seeds, uint64_t 
 
 static int xdrop_batch_impl(bella_ctx* c, const bella_seed* seeds, uint64_t n, const bella_params* p, bella_aln* out, bool exact) {
     if (!c || !p || (n && (!seeds || !out))) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     if (p->kmer_size < 1 || p->kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
     HIPCHK(c, hipSetDevice(c->device));
     // validate on the host: the kernel trusts seeds
@@ -3906,12 +3887,12 @@ void trace_release(bella_ctx* c) {      // the batch buffers go back (directions
 
 static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0, int passed_only, bool vote, bool keep_ops, uint64_t* ntraced, uint64_t* nops) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_alns) return fail(c, BELLA_ERR_STATE, "align_pairs first");
+    if (int r = need(c, ALNS)) return r;
     if (vote) if (int r = need(c, PILE)) return r;
     int rc = check_params(c, p);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    c->have_traces = false;
+    drop(c, TRACES);
     const size_t n = (size_t)c->nalns;
     std::vector<bella_pair> pairs(n);
     std::vector<bella_aln> alns(n);
@@ -3934,7 +3915,7 @@ static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0,
     if (rc) { (void)hipDeviceSynchronize(); return rc; }
     c->traces.assign(n, bella_trace{});
     for (size_t i = 0; i < which.size(); ++i) c->traces[which[i]] = tr[i];
-    c->have_traces = true;
+    made(c, TRACES);
     c->trace_ops_kept = keep_ops;
     if (ntraced) *ntraced = jobs.size();
     if (nops) *nops = c->trace_stats.ops;
@@ -3961,7 +3942,7 @@ int bella_hip_trace_pairs_flags(bella_ctx* c, const bella_params* p, uint32_t ba
 
 int bella_hip_get_traces(bella_ctx* c, bella_trace* out, uint32_t* ops) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_traces || !c->have_alns) return fail(c, BELLA_ERR_STATE, "trace_pairs first");
+    if (int r = need(c, TRACES)) return r;
     if (ops && !c->trace_ops_kept) return fail(c, BELLA_ERR_STATE, "the last trace ran with keep_ops = 0 / BELLA_TRACE_DROP_OPS: the runs were not kept (pass ops = NULL)");
     if (out && !c->traces.empty()) std::memcpy(out, c->traces.data(), sizeof(bella_trace) * c->traces.size());
     if (ops && !c->trace_ops.empty()) std::memcpy(ops, c->trace_ops.data(), 4 * c->trace_ops.size());
@@ -3971,20 +3952,20 @@ int bella_hip_get_traces(bella_ctx* c, bella_trace* out, uint32_t* ops) {
 int bella_hip_trace_batch(bella_ctx* c, const bella_seed* seeds, const bella_aln* alns, uint64_t n, const bella_params* p, uint32_t band0, bella_trace* out,
                           uint32_t* ops, uint64_t ops_cap, uint64_t* nops) {
     if (!c || !p || (n && (!seeds || !alns || !out))) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     if (p->kmer_size < 1 || p->kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<TraceJob> jobs((size_t)n);
     for (uint64_t i = 0; i < n; ++i) jobs[(size_t)i] = TraceJob{seeds[i].rid, seeds[i].cid, seeds[i].seedH, seeds[i].seedV, alns[i]};
     std::vector<uint32_t>& v = c->batch_ops;       // the runs stay with the context: a caller that could not know their number fetches them
     v.clear();
-    c->have_batch_ops = false;
+    drop(c, BATCH_OPS);
     bella_trace_stats st;
     const int rc = run_trace(c, p, jobs, band0, out, v, st);
     trace_release(c);
     if (rc) { (void)hipDeviceSynchronize(); return rc; }
     c->trace_stats = st;
-    c->have_batch_ops = true;
+    made(c, BATCH_OPS);
     if (nops) *nops = v.size();
     if (!ops) return 0;
     if (v.size() > ops_cap) return fail(c, BELLA_ERR_NOMEM, "trace_batch: %zu ops, room for %llu (bella_hip_get_batch_ops hands them out)", v.size(), (unsigned long long)ops_cap);
@@ -3994,7 +3975,7 @@ int bella_hip_trace_batch(bella_ctx* c, const bella_seed* seeds, const bella_aln
 
 int bella_hip_get_batch_ops(bella_ctx* c, uint32_t* ops, uint64_t ops_cap) {
     if (!c || (!ops && ops_cap)) return BELLA_ERR_BAD_ARG;
-    if (!c->have_batch_ops) return fail(c, BELLA_ERR_STATE, "trace_batch first");
+    if (int r = need(c, BATCH_OPS)) return r;
     if (c->batch_ops.size() > ops_cap) return fail(c, BELLA_ERR_BAD_ARG, "get_batch_ops: %zu ops, room for %llu", c->batch_ops.size(), (unsigned long long)ops_cap);
     if (!c->batch_ops.empty()) std::memcpy(ops, c->batch_ops.data(), 4 * c->batch_ops.size());
     return 0;
@@ -4012,7 +3993,7 @@ struct EmitCount {
 
 int bella_hip_pileup_reset(bella_ctx* c) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->total_bases * kPileCounters * 4;
     drop(c, PILE);
@@ -4162,7 +4143,7 @@ int bella_hip_graph_reset(bella_ctx* c) {
 
 int bella_hip_graph_add_overlaps(bella_ctx* c, const bella_overlap* recs, uint64_t n) {
     if (!c || (n && !recs)) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     if (c->as.records.size() + n >= (1ull << 30)) return fail(c, BELLA_ERR_BAD_ARG, "graph: fewer than 2^30 overlap records");
     for (uint64_t i = 0; i < n; ++i) {
         const bella_overlap& r = recs[i];
@@ -4180,7 +4161,7 @@ int bella_hip_graph_add_overlaps(bella_ctx* c, const bella_overlap* recs, uint64
 
 int bella_hip_graph_add_traced(bella_ctx* c, uint64_t* added) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_traces || !c->have_alns) return fail(c, BELLA_ERR_STATE, "trace_pairs first");
+    if (int r = need(c, TRACES)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->nalns;
     if (c->traces.size() != n) return fail(c, BELLA_ERR_STATE, "the traces are not those of the last alignment");
@@ -4220,7 +4201,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     if (!c) return BELLA_ERR_BAD_ARG;
     bella_graph_params gp{(uint32_t)sizeof(bella_graph_params), 1000, 1000, 800, 1000};
     if (int r = take_params(c, gp, params, "bella_graph_params")) return r;
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const auto t_begin = clk::now();
     drop(c, GRAPH);
@@ -4377,7 +4358,7 @@ int bella_hip_graph_trim(bella_ctx* c, const bella_graph_trim_params* params) {
     if (int r = take_params(c, tp, params, "bella_graph_trim_params")) return r;
     if (tp.min_depth < 1 || tp.min_depth > 0x7FFFFFFFu) return fail(c, BELLA_ERR_BAD_ARG, "trim: min_depth must be in [1, 2^31)");
     if (tp.end_clip >= (1u << 16)) tp.end_clip = 1u << 16;            // (no read is that long: the same result, and the sums stay small)
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const auto t_begin = clk::now();
     drop(c, TRIM);
@@ -5009,7 +4990,7 @@ int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* co
 
 int bella_hip_get_read_bases(bella_ctx* c, uint64_t* offsets, uint8_t* bases) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (!c->have_reads) return fail(c, BELLA_ERR_STATE, "set_reads first");
+    if (int r = need(c, READS)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if (offsets) {
         offsets[0] = 0;

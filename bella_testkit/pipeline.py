@@ -1,7 +1,8 @@
 """What the GPU tests of the stages after the alignment share: the way to aligned pairs, the overlap records of traced pairs, a stress
-input for the graph, an error check, and the runner of the command line."""
+input for the graph, an error check, the runner of the command line, and the one of the ranks of a collective call."""
 import os
 import subprocess
+import threading
 
 import numpy as np
 import pytest
@@ -50,6 +51,24 @@ def raises(code, fn, *a, **kw):
     with pytest.raises(api.BellaHipError) as ex:
         fn(*a, **kw)
     assert ex.value.code == code, (fn, ex.value.code)
+
+
+def run_ranks(nranks, body, timeout=300):
+    """one host thread per context (ctypes releases the GIL): the collective entry points rendezvous inside the library"""
+    out, err = [None] * nranks, []
+
+    def work(r):
+        try:
+            out[r] = body(r)
+        except Exception as e:  # noqa: BLE001
+            err.append((r, e))
+    th = [threading.Thread(target=work, args=(r,), daemon=True) for r in range(nranks)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout)
+    assert not any(t.is_alive() for t in th), "a rank is still inside a collective call: the ranks did not leave it together"
+    return out, err
 
 
 def run_cli(fastqs, flags, cwd, env_extra=None):

@@ -10,6 +10,7 @@ import pytest
 import _oracle as O
 from bella_amd import BellaPars, Engine, api
 from bella_testkit import synth
+from bella_testkit.pipeline import run_ranks as _run_ranks
 from bella_amd.api import BellaHipError
 from conftest import GOLD, ROOT, load_golden, set_mode
 
@@ -1764,25 +1765,6 @@ def test_staged_output_equals_single_stage(eng, golden, tmp_path):
     api.hash_spgemm(eng, BellaPars(errorRate=g.err, kmerSize=g.k), f, stdout=so, stages=3)
     assert open(f, "rb").read() == open(one, "rb").read()
     assert int(so.getvalue().split()[0]) == int(g.stdout["align"][2])
-
-
-def _run_ranks(nranks, body, timeout=300):
-    """one host thread per context (ctypes releases the GIL): the collective entry points rendezvous inside the library"""
-    import threading
-    out, err = [None] * nranks, []
-
-    def work(r):
-        try:
-            out[r] = body(r)
-        except Exception as e:  # noqa: BLE001
-            err.append((r, e))
-    th = [threading.Thread(target=work, args=(r,), daemon=True) for r in range(nranks)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(timeout)
-    assert not any(t.is_alive() for t in th), "a rank is still inside a collective call: the ranks did not leave it together"
-    return out, err
 
 
 def test_in_process_transport_waits_have_a_deadline(monkeypatch):

@@ -115,6 +115,14 @@ class BubbleStats(C.Structure):
                 ("reads_per_round", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("edges_per_round", C.c_uint32 * MAX_BUBBLE_ROUNDS), ("pop_ms", C.c_double)]
 
 
+class GraphWeakParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("ratio_permille", C.c_uint32)]
+
+
+class WeakStats(C.Structure):
+    _fields_ = [("forks", C.c_uint64), ("weak", C.c_uint64), ("edges_removed", C.c_uint64), ("ratio_permille", C.c_uint32), ("cut_ms", C.c_double)]
+
+
 class PolishParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_depth", C.c_uint32)]
 
@@ -230,6 +238,8 @@ SIGNATURES = [
     ("bella_hip_graph_get_unitig_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_graph_pop_bubbles", C.c_int, [vp, C.POINTER(GraphBubbleParams)]),
     ("bella_hip_graph_get_bubble_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_graph_cut_weak", C.c_int, [vp, C.POINTER(GraphWeakParams)]),
+    ("bella_hip_graph_get_weak_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_graph_polish_unitigs", C.c_int, [vp, C.POINTER(PolishParams), C.POINTER(C.c_uint64)]),
     ("bella_hip_graph_get_polished", C.c_int, [vp, vp, vp, vp, vp, vp]),
     ("bella_hip_graph_get_polish_stats", C.c_int, [vp, vp, C.c_uint64]),

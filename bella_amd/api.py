@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CLIP_DT, GraphTrimParams, TrimStats
-from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, POLISH_DT, PolishParams, PolishStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
+from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, POLISH_DT, PolishParams, PolishStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphWeakParams, WeakStats, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
 class BellaHipError(RuntimeError):
@@ -481,6 +481,21 @@ class Engine:
         for k in ("sources", "found", "popped", "reads_per_round", "edges_per_round"):
             out[k] = list(st[k])[:st["rounds"]]
         return out
+
+    # ---- weak-overlap removal ----
+    WEAK_DEFAULTS = dict(ratio_permille=500)
+
+    def graph_cut_weak(self, **params):
+        """removes the weak edges of the current graph (on the device) and replaces it, as graph_clean does: an edge goes when its overlap,
+        or its twin's, is below ratio_permille (default 500; 0 = off, at most 1000) thousandths of the best overlap of its source vertex.
+        No read is removed"""
+        p = _over(self.WEAK_DEFAULTS, params, "weak")
+        wp = GraphWeakParams(C.sizeof(GraphWeakParams), p["ratio_permille"])
+        self._chk(self.lib.bella_hip_graph_cut_weak(self.h, C.byref(wp)))
+
+    def weak_stats(self) -> dict:
+        """of the last graph_cut_weak: forks, weak, edges_removed, ratio_permille, cut_ms"""
+        return self._stats(self.lib.bella_hip_graph_get_weak_stats, WeakStats)
 
     def graph_unitigs(self) -> dict:
         """unitigs of the current graph (on the device): voff uint64[n + 1] into verts uint32 / pos uint64 / nbases uint32, len uint64[n],

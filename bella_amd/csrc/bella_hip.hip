@@ -147,13 +147,14 @@ struct StageState {
         std::vector<bella_read_clip> clips;  // in the context was always built in the trim state the context is in now
         bella_trim_stats stats{};
     } trim;
-    struct Graph {                           // the last build's result, as bella_hip_graph_clean and _pop_bubbles left it (sections 11 to 13)
+    struct Graph {                           // the last build's result, as bella_hip_graph_clean, _pop_bubbles and _cut_weak left it (sections 11 to 13, 17)
         std::vector<uint32_t> off;
         std::vector<bella_graph_edge> edges;
         std::vector<uint8_t> contained, removed;
         bella_graph_stats stats{};
         bella_unitig_stats clean{};          // the clean's part of bella_unitig_stats (rounds .. edges_removed, clean_ms)
         bella_bubble_stats bubbles{};
+        bella_weak_stats weak{};
     } graph;
     struct Unitigs {                         // the last bella_hip_graph_unitigs (unitig.hpp; section 12)
         std::vector<uint64_t> voff, pos, len, boff;
@@ -4329,6 +4330,7 @@ int bella_hip_graph_build(bella_ctx* c, const bella_graph_params* params) {
     g.removed.assign(nr, 0);
     g.clean = bella_unitig_stats{};
     g.bubbles = bella_bubble_stats{};
+    g.weak = bella_weak_stats{};
     c->as.unitigs.stats = bella_unitig_stats{};
     made(c, GRAPH);
     return 0;
@@ -4635,6 +4637,47 @@ int bella_hip_graph_pop_bubbles(bella_ctx* c, const bella_graph_bubble_params* p
 
 int bella_hip_graph_get_bubble_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     return get_stats(c, GRAPH, out, struct_size, [](const StageState& a) { return a.graph.bubbles; });
+}
+
+// ---- weak-overlap removal (graph.hpp) ----
+int bella_hip_graph_cut_weak(bella_ctx* c, const bella_graph_weak_params* params) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    bella_graph_weak_params wp{(uint32_t)sizeof(bella_graph_weak_params), 500};
+    if (int r = take_params(c, wp, params, "bella_graph_weak_params")) return r;
+    if (wp.ratio_permille > 1000) return fail(c, BELLA_ERR_BAD_ARG, "ratio_permille %u: at most 1000", wp.ratio_permille);
+    if (int r = need(c, GRAPH)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    changed(c, GRAPH);
+    bella_weak_stats& st = c->as.graph.weak;
+    st = bella_weak_stats{};
+    st.ratio_permille = wp.ratio_permille;
+    const uint32_t nr = c->nreads, nv = 2 * nr;
+    const uint32_t m = (uint32_t)c->as.graph.edges.size();
+    if (!wp.ratio_permille || !m) return 0;
+    TmpBuf ekill, cnt;
+    ENSURE(c, ekill, m);
+    ENSURE(c, cnt, 4 * kWcCount);
+    GraphRound g;
+    int rc = g.begin(c);
+    if (rc) return rc;
+    uint32_t hc[kWcCount] = {}, nm = 0;
+    HIPCHK(c, hipMemsetAsync(g.hit.p, 0, nr, c->stream));             // (no read is removed: the filter sees the killed edges alone)
+    HIPCHK(c, hipMemsetAsync(cnt.p, 0, 4 * kWcCount, c->stream));
+    k_graph_weak<<<nblk(std::max(m, nv)), 256, 0, c->stream>>>(ptr<uint32_t>(g.off), ptr<bella_graph_edge>(g.E), m, nv, wp.ratio_permille, ptr<uint8_t>(ekill), ptr<uint32_t>(cnt));
+    KCHK(c);
+    if ((rc = g.filter(c, ptr<uint8_t>(ekill), &nm))) return rc;
+    HIPCHK(c, hipMemcpyAsync(hc, cnt.p, 4 * kWcCount, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                       // the call's one read-back
+    st.forks = hc[kWcForks]; st.weak = hc[kWcWeak];
+    if (hc[kWcRemoved]) {                                             // (kept = m - removed)
+        if ((rc = g.apply_keep(c))) return rc;
+        g.m = nm;
+    }
+    return g.finish(c, &st.edges_removed, &st.cut_ms);
+}
+
+int bella_hip_graph_get_weak_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    return get_stats(c, GRAPH, out, struct_size, [](const StageState& a) { return a.graph.weak; });
 }
 
 int bella_hip_graph_unitigs(bella_ctx* c, uint64_t* nunitigs, uint64_t* nvertices, uint64_t* nlinks, uint64_t* total_bases) {

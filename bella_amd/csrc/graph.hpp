@@ -295,6 +295,31 @@ __global__ void k_graph_keep_filter(const bella_graph_edge* E, uint32_t m, const
     if (i > m) return;
     keep[i] = (i < m && !(hit[E[i].src >> 1] | hit[E[i].dst >> 1] | (ekill ? ekill[i] : 0))) ? 1 : 0;
 }
+
+// Weak-overlap removal: edge v -> w is weak iff 1000 ovl < permille best(v), best(v) = the ovl of the first edge of
+// v's list (the list is ordered by len and its edges share the source read's length).  One thread per edge: its own weakness, then its
+// twin's, found by a serial scan of the list of dst ^ 1 as k_bub_apply finds it (a handful of edges after the reduction; at most the
+// degree of a hub); ekill[j] = either.  Every byte has one writer.  Thread j < nv also counts vertex j when it is a fork.
+enum { kWcForks = 0, kWcWeak, kWcRemoved, kWcCount };                  // device counters (uint32 each)
+__device__ __forceinline__ bool graph_is_weak(uint32_t ovl, uint32_t best, uint32_t permille) { return 1000ull * ovl < (uint64_t)permille * best; }
+__global__ __launch_bounds__(256) void k_graph_weak(const uint32_t* off, const bella_graph_edge* E, uint32_t m, uint32_t nv, uint32_t permille, uint8_t* ekill,
+                                                    uint32_t* counters) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    bool weak = false, gone = false;
+    if (j < m) {
+        const uint32_t s = E[j].src, d = E[j].dst;
+        weak = graph_is_weak(E[j].ovl, E[off[s]].ovl, permille);
+        bool twin_weak = false;
+        const uint32_t ta = off[d ^ 1u], tb = off[(d ^ 1u) + 1];
+        for (uint32_t q = ta; q < tb; ++q)
+            if (E[q].dst == (s ^ 1u)) { twin_weak = graph_is_weak(E[q].ovl, E[ta].ovl, permille); break; }
+        gone = weak | twin_weak;
+        ekill[j] = gone ? 1 : 0;
+    }
+    graph_count(counters + kWcForks, j < nv && off[j + 1] - off[j] >= 2);
+    graph_count(counters + kWcWeak, weak);
+    graph_count(counters + kWcRemoved, gone);
+}
 #endif
 
 }  // namespace bella

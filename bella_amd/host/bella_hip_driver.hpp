@@ -125,6 +125,8 @@ struct StageOpts {
     int trim = 0;                    // coverage trimming: the reads are clipped to their longest well-covered stretch before the graph
     uint32_t trim_depth = 3, trim_end_clip = 500;     // is built (min_span = gfa_min_overlap); every graph file is in clipped coordinates
     const char* trimmed_reads = nullptr;              // the clipped reads as FASTA, in input order, without the uncovered ones
+    int cut_weak = 0;                // weak-overlap removal after the tip clipping and the bubble popping: weak_steps + 1 cuts with the
+    uint32_t weak_min = 500, weak_max = 700, weak_steps = 2;   // ratio rising from weak_min to weak_max permille, tips and bubbles again after each that cut
     bool graph() const { return gfa || unitigs || unitigs_fasta; }
     bool pileup() const { return correct || polish; }
 };
@@ -229,12 +231,46 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
     cp.max_tip_reads = o.tip_reads; cp.tip_rounds = o.tip_rounds;
     check(c0, bella_hip_graph_clean(c0, &cp), "bella_hip_graph_clean");
     bella_bubble_stats bs{};
+    bella_graph_bubble_params bp;
+    bp.struct_size = (uint32_t)sizeof(bp);
+    bp.max_bubble_reads = o.bubble_reads; bp.max_bubble_dist = o.bubble_dist; bp.bubble_rounds = o.bubble_rounds;
     if (o.pop_bubbles) {                                              // (popping cannot create a tip: a bubble is closed)
-        bella_graph_bubble_params bp;
-        bp.struct_size = (uint32_t)sizeof(bp);
-        bp.max_bubble_reads = o.bubble_reads; bp.max_bubble_dist = o.bubble_dist; bp.bubble_rounds = o.bubble_rounds;
         check(c0, bella_hip_graph_pop_bubbles(c0, &bp), "bella_hip_graph_pop_bubbles");
         check(c0, bella_hip_graph_get_bubble_stats(c0, &bs, sizeof(bs)), "bella_hip_graph_get_bubble_stats");
+    }
+    // --cut-weak: miniasm's order -- del_short with a rising ratio, and after every cut that took an edge cut_tip and pop_bubble again.  The
+    // stats calls report their last invocation, so the sums of the log line are kept here, and so are the first clean's figures for the
+    // Unitigs line.
+    bella_unitig_stats first_clean{};
+    if (o.cut_weak) {
+        check(c0, bella_hip_graph_get_unitig_stats(c0, &first_clean, sizeof(first_clean)), "bella_hip_graph_get_unitig_stats");
+        uint64_t cut_edges = 0, clipped_after = 0, popped_after = 0;
+        uint32_t r_first = 0, r_last = 0;
+        for (uint32_t i = 0; i <= o.weak_steps; ++i) {
+            bella_graph_weak_params wp;
+            wp.struct_size = (uint32_t)sizeof(wp);
+            wp.ratio_permille = o.weak_steps ? o.weak_min + (o.weak_max - o.weak_min) * i / o.weak_steps : o.weak_min;
+            if (!i) r_first = wp.ratio_permille;
+            r_last = wp.ratio_permille;
+            check(c0, bella_hip_graph_cut_weak(c0, &wp), "bella_hip_graph_cut_weak");
+            bella_weak_stats ws;
+            check(c0, bella_hip_graph_get_weak_stats(c0, &ws, sizeof(ws)), "bella_hip_graph_get_weak_stats");
+            cut_edges += ws.edges_removed;
+            if (!ws.edges_removed) continue;
+            check(c0, bella_hip_graph_clean(c0, &cp), "bella_hip_graph_clean");
+            bella_unitig_stats cs;
+            check(c0, bella_hip_graph_get_unitig_stats(c0, &cs, sizeof(cs)), "bella_hip_graph_get_unitig_stats");
+            clipped_after += cs.reads_removed;
+            if (!o.pop_bubbles) continue;
+            check(c0, bella_hip_graph_pop_bubbles(c0, &bp), "bella_hip_graph_pop_bubbles");
+            bella_bubble_stats ps;
+            check(c0, bella_hip_graph_get_bubble_stats(c0, &ps, sizeof(ps)), "bella_hip_graph_get_bubble_stats");
+            for (uint32_t r = 0; r < ps.rounds; ++r) popped_after += ps.popped[r];
+        }
+        const std::string WeakOverlaps = std::to_string(cut_edges) + " edges cut in " + std::to_string(o.weak_steps + 1) + " rounds at " + std::to_string(r_first) + ".." +
+                                         std::to_string(r_last) + " permille, " + std::to_string(clipped_after) + " reads clipped after, " + std::to_string(popped_after) +
+                                         " bubbles popped after";
+        BELLA_HIP_LOGT(o.tag, WeakOverlaps);
     }
     if (o.gfa && o.gfa_clean) write_gfa();
     if (!o.unitigs && !o.unitigs_fasta) return;
@@ -280,6 +316,7 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
     }
     bella_unitig_stats us;
     check(c0, bella_hip_graph_get_unitig_stats(c0, &us, sizeof(us)), "bella_hip_graph_get_unitig_stats");
+    if (o.cut_weak) { us.reads_removed = first_clean.reads_removed; us.rounds = first_clean.rounds; }   // (the schedule's cleans are in its own line)
     uint64_t npopped = 0;
     for (uint32_t r = 0; r < bs.rounds; ++r) npopped += bs.popped[r];
     const std::string Popped = o.pop_bubbles ? std::to_string(npopped) + " bubbles popped, " + std::to_string(bs.reads_removed) + " reads, " : std::string();

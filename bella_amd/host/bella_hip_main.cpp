@@ -61,6 +61,8 @@ struct Options {
     int trim_depth = 3, trim_end_clip = 500;
     std::string trimmed_reads;
     bool trim = false, trim_param_given = false;
+    int weak_min = 500, weak_max = 700, weak_steps = 2;
+    bool cut_weak = false, weak_param_given = false;
     bool graph() const { return !gfa.empty() || !unitigs.empty() || !unitigs_fasta.empty(); }
 };
 
@@ -106,6 +108,11 @@ const char* kHelp =
     "      --bubble-reads arg     with --pop-bubbles: largest bubble that is popped, in reads (default: 64; at most 255; 0: no popping)\n"
     "      --bubble-dist arg      ... its largest distance from the source, in bases (default: 50000)\n"
     "      --bubble-rounds arg    ... and the number of popping rounds (default: 3)\n"
+    "      --cut-weak             with --unitigs / --unitigs-fasta / --gfa-clean: remove weak overlaps after the tip clipping and the bubble popping, on the device:\n"
+    "                             an edge goes when its overlap is below a fraction of the best overlap of its vertex; tips and bubbles again after every cut\n"
+    "      --weak-min arg         with --cut-weak: the fraction of the first cut, in permille (default: 500)\n"
+    "      --weak-max arg         ... the fraction of the last cut (default: 700)\n"
+    "      --weak-steps arg       ... and the steps from the first to the last: steps + 1 cuts (default: 2; at most 16)\n"
     "      --polish               with --unitigs / --unitigs-fasta: unitig consensus from the pileup of the base-level alignments, on the device\n"
     "      --polish-min-depth arg with --polish: votes a position needs before it is changed (default: 3)\n"
     "      --trim                 with --gfa / --unitigs / --unitigs-fasta: clip every read to its longest stretch that --trim-depth overlaps cover, on the\n"
@@ -135,6 +142,7 @@ Options parse(int argc, char** argv) {
         {"gfa-no-seq", 0, 0, &o.gfa_no_seq},
         {"unitigs", 0, 3, &o.unitigs}, {"unitigs-fasta", 0, 3, &o.unitigs_fasta}, {"tip-reads", 0, 1, &o.tip_reads}, {"tip-rounds", 0, 1, &o.tip_rounds}, {"gfa-clean", 0, 0, &o.gfa_clean},
         {"pop-bubbles", 0, 0, &o.pop_bubbles}, {"bubble-reads", 0, 1, &o.bubble_reads}, {"bubble-dist", 0, 1, &o.bubble_dist}, {"bubble-rounds", 0, 1, &o.bubble_rounds},
+        {"cut-weak", 0, 0, &o.cut_weak}, {"weak-min", 0, 1, &o.weak_min}, {"weak-max", 0, 1, &o.weak_max}, {"weak-steps", 0, 1, &o.weak_steps},
         {"polish", 0, 0, &o.polish}, {"polish-min-depth", 0, 1, &o.polish_min_depth},
         {"trim", 0, 0, &o.trim}, {"trim-depth", 0, 1, &o.trim_depth}, {"trim-end-clip", 0, 1, &o.trim_end_clip}, {"trimmed-reads", 0, 3, &o.trimmed_reads},
         {"help", 'h', 0, &o.help}};
@@ -175,6 +183,7 @@ Options parse(int argc, char** argv) {
         if (sp->dst == &o.gfa_fuzz || sp->dst == &o.gfa_max_overhang || sp->dst == &o.gfa_min_overlap) o.gfa_param_given = true;
         if (sp->dst == &o.tip_reads || sp->dst == &o.tip_rounds) o.tip_param_given = true;
         if (sp->dst == &o.bubble_reads || sp->dst == &o.bubble_dist || sp->dst == &o.bubble_rounds) o.bubble_param_given = true;
+        if (sp->dst == &o.weak_min || sp->dst == &o.weak_max || sp->dst == &o.weak_steps) o.weak_param_given = true;
         if (sp->dst == &o.polish_min_depth) o.polish_param_given = true;
         if (sp->dst == &o.trim_depth || sp->dst == &o.trim_end_clip || sp->dst == &o.trimmed_reads) o.trim_param_given = true;
     }
@@ -241,6 +250,10 @@ int main(int argc, char** argv) {
     if (o.bubble_reads < 0 || o.bubble_reads > BELLA_MAX_BUBBLE_READS || o.bubble_dist < 0 || o.bubble_rounds < 0 || o.bubble_rounds > BELLA_MAX_BUBBLE_ROUNDS)
         die("--bubble-reads must be in [0, " + std::to_string(BELLA_MAX_BUBBLE_READS) + "], --bubble-dist must not be negative and --bubble-rounds must be in [0, " +
             std::to_string(BELLA_MAX_BUBBLE_ROUNDS) + "]");
+    if (o.weak_param_given && !o.cut_weak) die("--weak-min, --weak-max and --weak-steps need --cut-weak");
+    if (o.cut_weak && o.unitigs.empty() && o.unitigs_fasta.empty() && !o.gfa_clean) die("--cut-weak needs --unitigs, --unitigs-fasta or --gfa-clean");
+    if (o.weak_min <= 0 || o.weak_min > o.weak_max || o.weak_max > 1000 || o.weak_steps < 0 || o.weak_steps > 16)
+        die("--weak-min and --weak-max must be in [1, 1000] with --weak-min not above --weak-max, and --weak-steps must be in [0, 16]");
     if (o.polish_param_given && !o.polish) die("--polish-min-depth needs --polish");
     if (o.polish && o.unitigs.empty() && o.unitigs_fasta.empty()) die("--polish needs --unitigs or --unitigs-fasta");
     if (o.polish && o.gfa_no_seq && o.unitigs_fasta.empty()) die("--polish with --gfa-no-seq needs --unitigs-fasta (there is no sequence to polish into)");
@@ -399,6 +412,8 @@ int main(int argc, char** argv) {
     so.gfa_clean = o.gfa_clean ? 1 : 0;
     so.pop_bubbles = o.pop_bubbles ? 1 : 0;
     so.bubble_reads = (uint32_t)o.bubble_reads; so.bubble_dist = (uint32_t)o.bubble_dist; so.bubble_rounds = (uint32_t)o.bubble_rounds;
+    so.cut_weak = o.cut_weak ? 1 : 0;
+    so.weak_min = (uint32_t)o.weak_min; so.weak_max = (uint32_t)o.weak_max; so.weak_steps = (uint32_t)o.weak_steps;
     so.polish = o.polish ? 1 : 0;
     so.polish_min_depth = (uint32_t)o.polish_min_depth;
     so.trim = o.trim ? 1 : 0;

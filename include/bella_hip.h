@@ -613,6 +613,34 @@ typedef struct {
 int bella_hip_graph_pop_bubbles(bella_ctx* ctx, const bella_graph_bubble_params* params);
 int bella_hip_graph_get_bubble_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 
+/* ---- weak-overlap removal (no counterpart in the reference; the pass is miniasm's asg_arc_del_short) -------------
+ * On the context's current graph, in the notation of the string graph section; integers only.  best(v) = the largest ovl among v's
+ * out-edges: they share the source read's length and the list is ordered by len, so it is the ovl of the list's first edge.  Edge
+ * e = v -> w is WEAK iff 1000 ovl(e) < ratio_permille best(v); with ratio_permille <= 1000 the best edge of a vertex is never weak, and a
+ * vertex with one out-edge loses nothing by its own rule.  All decisions are taken on one snapshot, and an edge leaves when it OR ITS TWIN
+ * (w ^ 1 -> v ^ 1) is weak: the graph stays twin-symmetric and the result does not depend on the order the device works in.  No read is
+ * removed (bella_hip_graph_get_removed is unchanged); a read left without edges becomes a one-vertex unitig.  ovl is the edge's own field,
+ * in clipped coordinates while a trim exists.  The result is the CSR in the old order with the deleted edges compacted out. */
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_graph_weak_params) of the caller's header (the struct may grow)           */
+    uint32_t ratio_permille;      /* documented default 500; at most 1000; 0 = off                                         */
+} bella_graph_weak_params;
+/* What the last bella_hip_graph_cut_weak did (zero without one since the build).  A sized struct: bella_hip_graph_get_weak_stats writes
+ * at most struct_size bytes. */
+typedef struct {
+    uint64_t forks;               /* vertices with out-degree >= 2                                                         */
+    uint64_t weak;                /* edges below their own vertex's threshold                                              */
+    uint64_t edges_removed;       /* edges that are weak or whose twin is                                                  */
+    uint32_t ratio_permille;      /* the call's                                                                            */
+    double cut_ms;                /* between two events on the stream: the kernel, filter, scan, compaction, one read-back */
+} bella_weak_stats;
+/* Removes the weak edges of the context's current graph (on the device) and REPLACES it, as bella_hip_graph_clean and
+ * bella_hip_graph_pop_bubbles do.  params == NULL: the defaults.  BELLA_ERR_STATE without a built graph; BELLA_ERR_BAD_ARG for a
+ * struct_size too small or ratio_permille > 1000.  Drops the unitigs; keeps the clips, the contained and the removed marks.  A graph
+ * without edges or ratio_permille == 0 launch nothing. */
+int bella_hip_graph_cut_weak(bella_ctx* ctx, const bella_graph_weak_params* params);
+int bella_hip_graph_get_weak_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+
 /* ---- unitig consensus: the pileup's majority vote per position of the backbone reads (no counterpart in the
  * reference) -----------------------------------------------------------------------------------------------------------------------
  * Needs the unitigs of bella_hip_graph_unitigs and the pileup table of the read-correction section, both on this context.  The DECISION

@@ -8,7 +8,10 @@ span the host's read-backs: bella_unitig_stats in include/bella_hip.h) next to t
 and the gather's bytes over its time (one byte written per base, a quarter byte read).  Then the same with graph_pop_bubbles between the
 clean and the unitigs: sources / found / popped / reads removed per round, pop_ms, and unitigs, largest and N50
 with the stage next to those without it.  Last, the unitig consensus of those unitigs: decide_ms and write_ms (one
-launch each), the table bytes the decision read over its time, and the unitigs' total length raw and polished against the genome span."""
+launch each), the table bytes the decision read over its time, and the unitigs' total length raw and polished against the genome span.
+--cut-weak: one more pass per repeat -- build, clean, pop, then the command line's weak-overlap schedule (cuts at 500,
+600 and 700 permille, tips and bubbles again after a cut that took an edge), unitigs -- and per set the edges cut, forks and weak edges per
+step, cut_ms per step next to clean_ms and pop_ms of the same run, and unitigs, largest and N50 with the schedule next to those without."""
 import argparse
 import json
 import os
@@ -21,7 +24,34 @@ from bella_amd import BellaPars, Engine  # noqa: E402
 from bella_testkit import synth  # noqa: E402
 
 
-def probe(nreads, seed, repeats, fast):
+WEAK_RATIOS = (500, 600, 700)                                         # bella-hip --cut-weak's defaults: --weak-min 500 --weak-max 700 --weak-steps 2
+
+
+def weak_pass(eng):
+    """build, clean, pop, the schedule, unitigs: -> dict of the pass's figures"""
+    eng.graph_build()
+    eng.graph_clean()
+    clean_ms = eng.unitig_stats()["clean_ms"]
+    eng.graph_pop_bubbles()
+    pop_ms = eng.bubble_stats()["pop_ms"]
+    steps = []
+    for r in WEAK_RATIOS:
+        eng.graph_cut_weak(ratio_permille=r)
+        ws = eng.weak_stats()
+        step = dict(ratio_permille=r, forks=int(ws["forks"]), weak=int(ws["weak"]), edges_cut=int(ws["edges_removed"]), cut_ms=ws["cut_ms"], reads_clipped_after=0, bubbles_popped_after=0)
+        if ws["edges_removed"]:
+            eng.graph_clean()
+            step["reads_clipped_after"] = int(eng.unitig_stats()["reads_removed"])
+            eng.graph_pop_bubbles()
+            step["bubbles_popped_after"] = int(sum(eng.bubble_stats()["popped"]))
+        steps.append(step)
+    eng.graph_unitigs()
+    us = eng.unitig_stats()
+    return dict(steps=steps, edges_cut=sum(x["edges_cut"] for x in steps), cut_ms=sum(x["cut_ms"] for x in steps), clean_ms=clean_ms, pop_ms=pop_ms,
+                unitigs=int(us["unitigs"]), largest=int(us["largest"]), n50=int(us["n50"]), total_bases=int(us["total_bases"]))
+
+
+def probe(nreads, seed, repeats, fast, cut_weak=False):
     rs = (synth.make_reads_fast if fast else synth.make_reads)(nreads, read_len=10000, err=0.15, seed=seed)
     meta = [[int(x) for x in n.split("_")[1:]] for n in rs.names]     # (start, length, strand)
     span = max(m[0] + m[1] for m in meta) - min(m[0] for m in meta)
@@ -50,9 +80,9 @@ def probe(nreads, seed, repeats, fast):
         bs = eng.bubble_stats()
         eng.graph_unitigs()
         eng.graph_polish_unitigs()
-        runs.append((gs, us, bs, eng.unitig_stats(), eng.polish_stats()))
-    gs, us, _, _, _ = min(runs, key=lambda r: r[1]["rank_ms"] + r[1]["gather_ms"])
-    _, _, bs, ps, _ = min(runs, key=lambda r: r[2]["pop_ms"])
+        runs.append((gs, us, bs, eng.unitig_stats(), eng.polish_stats(), weak_pass(eng) if cut_weak else None))
+    gs, us = min(runs, key=lambda r: r[1]["rank_ms"] + r[1]["gather_ms"])[:2]
+    bs, ps = min(runs, key=lambda r: r[2]["pop_ms"])[2:4]
     pol = min((r[4] for r in runs), key=lambda q: q["decide_ms"] + q["write_ms"])
     build_ms = gs["classify_ms"] + gs["sort_ms"] + gs["reduce_ms"]
     out = dict(reads=nreads, bases=int(rs.offsets[-1]), genome_span=int(span), edges_final=int(gs["edges_final"]), contained_reads=int(gs["contained_reads"]),
@@ -73,6 +103,8 @@ def probe(nreads, seed, repeats, fast):
                          gather_ms=ps["gather_ms"], table_bytes=int(pol["table_bytes"]),
                          decide_gb_per_s=(pol["table_bytes"] + pol["bases_before"]) / max(1e-9, pol["decide_ms"] * 1e6),
                          write_gb_per_s=(pol["bases_before"] + pol["bases_after"]) / max(1e-9, pol["write_ms"] * 1e6))
+    if cut_weak:                                                      # (the unitigs "without" are the pop pass's: clean and pop, no schedule)
+        out["weak"] = dict(min((r[5] for r in runs), key=lambda w: w["cut_ms"]), unitigs_without=int(ps["unitigs"]), largest_without=int(ps["largest"]), n50_without=int(ps["n50"]))
     eng.close()
     return out
 
@@ -82,11 +114,12 @@ if __name__ == "__main__":
     ap.add_argument("--sets", nargs="+", default=["2000:21:exact", "10000:1:fast"], help="reads:seed:exact|fast (the generator: synth.make_reads / make_reads_fast)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "unitig_probe.json"))
+    ap.add_argument("--cut-weak", action="store_true", help="also run the weak-overlap schedule after the clean and the pop (DESIGN.md section 17)")
     a = ap.parse_args()
     res = []
     for s in a.sets:
         n, seed, gen = s.split(":")
-        res.append(probe(int(n), int(seed), a.repeats, gen == "fast"))
+        res.append(probe(int(n), int(seed), a.repeats, gen == "fast", a.cut_weak))
         print(json.dumps(res[-1]), flush=True)
     with open(a.out, "w") as f:
         json.dump(dict(sets=res), f, indent=1)

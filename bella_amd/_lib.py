@@ -32,6 +32,10 @@ LINK_A_MINUS, LINK_B_MINUS, MAX_TIP_ROUNDS = 1, 2, 16
 POLISH_DT = np.dtype([("len_before", "<u8"), ("len_after", "<u8"), ("substituted", "<u8"), ("deleted", "<u8"), ("inserted", "<u8"), ("covered", "<u8"),
                       ("depth_sum", "<u8")])
 assert POLISH_DT.itemsize == 56
+PLACE_DT = np.dtype([("unitig", "<u4"), ("orient", "<u4"), ("s", "<i8"), ("e", "<i8"), ("anchor", "<u4"), ("status", "<u4"), ("band", "<u4"), ("n_eq", "<u4"), ("n_x", "<u4"),
+                     ("n_ins", "<u4"), ("n_del", "<u4"), ("score", "<i4"), ("q_begin", "<i8"), ("q_end", "<i8"), ("op_off", "<u8"), ("nops", "<u4"), ("pad", "<u4")])
+assert PLACE_DT.itemsize == 88
+REALIGN_NONE, REALIGN_VOTED, REALIGN_UNPLACED, REALIGN_OUTSIDE, REALIGN_BAND_CAPPED, REALIGN_LOW_IDENTITY = range(6)
 TRACE_PASSED_ONLY, TRACE_DROP_OPS, TRACE_PILEUP = 1, 2, 4
 PILEUP_COUNTERS = 9      # per base: votes for A C G T, del, one inserted A C G T in the junction before the base
 assert PAIR_DT.itemsize == 16 and EXT_DT.itemsize == 8 and ALN_DT.itemsize == 32 and SEED_DT.itemsize == 12
@@ -125,6 +129,19 @@ class WeakStats(C.Structure):
 
 class PolishParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_depth", C.c_uint32)]
+
+
+class RealignParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("band0", C.c_uint32), ("band_max", C.c_uint32), ("min_identity", C.c_uint32), ("min_depth", C.c_uint32),
+                ("keep_ops", C.c_uint32)]
+
+
+class RealignStats(C.Structure):
+    _fields_ = [("round", C.c_uint32), ("batches", C.c_uint32), ("backbone", C.c_uint64), ("contained", C.c_uint64), ("unplaced", C.c_uint64), ("outside", C.c_uint64),
+                ("band_capped", C.c_uint64), ("low_identity", C.c_uint64), ("voted", C.c_uint64), ("repeated", C.c_uint64), ("dp_cells", C.c_uint64),
+                ("dir_bytes_peak", C.c_uint64), ("votes", C.c_uint64), ("bases_before", C.c_uint64), ("bases_after", C.c_uint64), ("substituted", C.c_uint64),
+                ("deleted", C.c_uint64), ("inserted", C.c_uint64), ("place_ms", C.c_double), ("dp_ms", C.c_double), ("walk_ms", C.c_double), ("vote_ms", C.c_double),
+                ("decide_ms", C.c_double)]
 
 
 class PolishStats(C.Structure):
@@ -243,6 +260,11 @@ SIGNATURES = [
     ("bella_hip_graph_polish_unitigs", C.c_int, [vp, C.POINTER(PolishParams), C.POINTER(C.c_uint64)]),
     ("bella_hip_graph_get_polished", C.c_int, [vp, vp, vp, vp, vp, vp]),
     ("bella_hip_graph_get_polish_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_graph_realign_unitigs", C.c_int, [vp, C.POINTER(RealignParams), C.POINTER(C.c_uint64)]),
+    ("bella_hip_graph_get_realigned", C.c_int, [vp, vp, vp, vp, vp, vp]),
+    ("bella_hip_graph_get_realign_placements", C.c_int, [vp, vp]),
+    ("bella_hip_graph_get_realign_ops", C.c_int, [vp, C.POINTER(C.c_uint64), vp, vp]),
+    ("bella_hip_graph_get_realign_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_graph_trim", C.c_int, [vp, C.POINTER(GraphTrimParams)]),
     ("bella_hip_graph_get_trim", C.c_int, [vp, vp]),
     ("bella_hip_graph_get_trim_stats", C.c_int, [vp, vp, C.c_uint64]),

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CLIP_DT, GraphTrimParams, TrimStats
-from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, POLISH_DT, PolishParams, PolishStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphWeakParams, WeakStats, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
+from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, PLACE_DT, POLISH_DT, PolishParams, PolishStats, RealignParams, RealignStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphWeakParams, WeakStats, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
 class BellaHipError(RuntimeError):
@@ -537,6 +537,42 @@ class Engine:
 
     def polish_stats(self) -> dict:
         return self._stats(self.lib.bella_hip_graph_get_polish_stats, PolishStats)
+
+    # ---- realignment ----
+    REALIGN_DEFAULTS = dict(band0=512, band_max=4096, min_identity=700, min_depth=3, keep_ops=0)
+
+    def graph_realign_unitigs(self, **params) -> dict:
+        """one realignment round against the newest sequence of the unitigs (the polish's, or the last round's), on the device: the
+        result in the shape of graph_polish_unitigs -- pos / nbases are where the polish's segments begin in the new sequence"""
+        rp = RealignParams(C.sizeof(RealignParams), *(_over(self.REALIGN_DEFAULTS, params, "graph_realign_unitigs")[k] for k in ("band0", "band_max", "min_identity", "min_depth", "keep_ops")))
+        tot = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_graph_realign_unitigs(self.h, C.byref(rp), C.byref(tot)))
+        return self.realigned()
+
+    def realigned(self) -> dict:
+        st, pst = self.realign_stats(), self.polish_stats()
+        out = dict(offsets=np.zeros(pst["unitigs"] + 1, np.uint64), bases=np.zeros(st["bases_after"], np.uint8), pos=np.zeros(pst["vertices"], np.uint64),
+                   nbases=np.zeros(pst["vertices"], np.uint32), stats=np.zeros(pst["unitigs"], POLISH_DT))
+        self._chk(self.lib.bella_hip_graph_get_realigned(self.h, *(_p(out[k]) for k in ("offsets", "bases", "pos", "nbases", "stats"))))
+        return out
+
+    def realign_placements(self) -> np.ndarray:
+        """one record of PLACE_DT per read"""
+        out = np.zeros(self.nreads, PLACE_DT)
+        self._chk(self.lib.bella_hip_graph_get_realign_placements(self.h, _p(out)))
+        return out
+
+    def realign_ops(self):
+        """tests: (runs, table) of a round that ran with keep_ops -- the voters' runs (a placement's op_off / nops index them) and the
+        round's counters, (bases_before, 9) uint32"""
+        n = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_graph_get_realign_ops(self.h, C.byref(n), None, None))
+        ops, table = np.zeros(n.value, np.uint32), np.zeros((self.realign_stats()["bases_before"], PILEUP_COUNTERS), np.uint32)
+        self._chk(self.lib.bella_hip_graph_get_realign_ops(self.h, C.byref(n), _p(ops), _p(table)))
+        return ops, table
+
+    def realign_stats(self) -> dict:
+        return self._stats(self.lib.bella_hip_graph_get_realign_stats, RealignStats)
 
     # ---- coverage trimming (DESIGN.md section 15) ----
     TRIM_DEFAULTS = dict(min_depth=3, end_clip=500, min_span=1000)

@@ -29,6 +29,7 @@
 #include "order.hpp"
 #include "pileup.hpp"
 #include "polish.hpp"
+#include "realign.hpp"
 #include "spgemm.hpp"
 #include "trace.hpp"
 #include "unitig.hpp"
@@ -139,7 +140,7 @@ struct CountU64 {                                        // pair counts: without
 // drop / changed / made / has / need (below) are the only code that touches `valid`.  The stages up to the traces keep their results in
 // members of the context (device buffers, mostly), PILE and CONS too; those of the stages that follow the alignment are here, one member
 // per stage, on the host: the graph is small next to what it was made from, and a stage uploads what it reads.
-enum Stage : uint32_t { READS, TUPLES, PANEL, MATRIX, PAIRS, ALNS, TRACES, BATCH_OPS, RECORDS, TRIM, GRAPH, UNITIGS, POLISH, PILE, CONS, kStages };
+enum Stage : uint32_t { READS, TUPLES, PANEL, MATRIX, PAIRS, ALNS, TRACES, BATCH_OPS, RECORDS, TRIM, GRAPH, UNITIGS, POLISH, REALIGN, PILE, CONS, kStages };
 struct StageState {
     uint32_t valid = 1u << RECORDS;          // one bit per Stage (the records are always there: possibly none)
     std::vector<bella_overlap> records;      // accumulated by bella_hip_graph_add_overlaps (graph.hpp)
@@ -170,6 +171,15 @@ struct StageState {
         std::vector<bella_polish_unitig> recs;
         bella_polish_stats stats{};
     } polish;
+    struct Realign {                         // the last round of bella_hip_graph_realign_unitigs (realign.hpp; section 18): a Polish in shape
+        std::vector<uint64_t> offs, pos;
+        std::vector<uint32_t> nb;
+        std::vector<uint8_t> bases;
+        std::vector<bella_polish_unitig> recs;
+        std::vector<bella_realign_placement> placements;
+        std::vector<uint32_t> ops, table;    // kept for the tests only (keep_ops)
+        bella_realign_stats stats{};
+    } realign;
     // READS .. BATCH_OPS, PILE and CONS (pileup.hpp; section 10) are members of the context: only their bits are here
 };
 
@@ -489,7 +499,8 @@ constexpr uint32_t kBuiltFrom[kStages] = {
     /* TRIM    */ stage_bit(GRAPH),
     /* GRAPH   */ stage_bit(UNITIGS),
     /* UNITIGS */ stage_bit(POLISH),
-    /* POLISH  */ 0,
+    /* POLISH  */ stage_bit(REALIGN),
+    /* REALIGN */ 0,                         // (a round reads the round before and replaces it)
     /* PILE    */ stage_bit(CONS) | stage_bit(POLISH),
     /* CONS    */ 0,
 };
@@ -509,7 +520,7 @@ int need(bella_ctx* c, Stage s) {
     static const char* const first[kStages] = {"set_reads first", "count_kmers first", "assemble_panel first", "set_B / assemble_tuples first",
                                                "overlap first", "align_pairs first", "trace_pairs first", "trace_batch first",
                                                "", "bella_hip_graph_trim first", "bella_hip_graph_build first", "bella_hip_graph_unitigs first",
-                                               "bella_hip_graph_polish_unitigs first", "bella_hip_pileup_reset first", "bella_hip_consensus first"};
+                                               "bella_hip_graph_polish_unitigs first", "bella_hip_graph_realign_unitigs first", "bella_hip_pileup_reset first", "bella_hip_consensus first"};
     return has(c, s) ? 0 : fail(c, BELLA_ERR_STATE, "%s", first[s]);
 }
 
@@ -4993,6 +5004,325 @@ int bella_hip_graph_get_polished(bella_ctx* c, uint64_t* offsets, uint8_t* bases
 
 int bella_hip_graph_get_polish_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     return get_stats(c, POLISH, out, struct_size, [](const StageState& a) { return a.polish.stats; });
+}
+
+// ---- realignment (realign.hpp) ------------------------------------------------------------------------------------
+int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* params, uint64_t* total_bases) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    bella_realign_params rp{};
+    rp.band0 = BELLA_REALIGN_DEFAULT_BAND; rp.band_max = BELLA_REALIGN_DEFAULT_BAND_MAX; rp.min_identity = BELLA_REALIGN_DEFAULT_MIN_IDENTITY; rp.min_depth = 3;
+    if (int r = take_params(c, rp, params, "bella_realign_params")) return r;
+    auto pow2 = [](uint32_t x) { return x && !(x & (x - 1)); };
+    if (!pow2(rp.band0) || !pow2(rp.band_max) || rp.band0 < kTrMinBand || rp.band_max > kTrMaxBand || rp.band0 > rp.band_max)
+        return fail(c, BELLA_ERR_BAD_ARG, "realign: band0 and band_max must be powers of two with 256 <= band0 <= band_max <= 262144");
+    if (rp.min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
+    if (rp.min_identity > 1000) return fail(c, BELLA_ERR_BAD_ARG, "min_identity is in permille: at most 1000");
+    if (int r = need(c, POLISH)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const StageState::Unitigs& u = c->as.unitigs;
+    const StageState::Graph& g = c->as.graph;
+    const bool again = has(c, REALIGN);                               // the sequence to align against: the last round's, or the polish's
+    const std::vector<uint64_t>& coffs = again ? c->as.realign.offs : c->as.polish.offs;
+    const std::vector<uint64_t>& cpos = again ? c->as.realign.pos : c->as.polish.pos;
+    const std::vector<uint32_t>& cnb = again ? c->as.realign.nb : c->as.polish.nb;
+    const std::vector<uint8_t>& cbases = again ? c->as.realign.bases : c->as.polish.bases;
+    const uint32_t nutg = (uint32_t)u.len.size(), nseg = (uint32_t)u.verts.size(), nr = c->nreads;
+    const uint64_t total = coffs[nutg];
+    StageState::Realign out;
+    bella_realign_stats st{};
+    st.round = again ? c->as.realign.stats.round + 1 : 1;
+    st.bases_before = total;
+    out.offs.assign((size_t)nutg + 1, 0);
+    out.pos.assign(nseg, 0); out.nb.assign(nseg, 0);
+    out.recs.assign(nutg, bella_polish_unitig{});
+    bella_realign_placement none{};
+    none.unitig = kReaNone; none.anchor = kReaNone;
+    out.placements.assign(nr, none);
+    uint64_t nout = 0;
+    if (nutg) {                                                       // (no unitig: nothing is launched)
+        if (total >= 0x7FFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "realign: the unitigs must have fewer than 2^31 bases");
+        for (uint32_t j = 0; j < nutg; ++j)
+            if (coffs[j + 1] - coffs[j] >= kReaMaxUnitig) return fail(c, BELLA_ERR_BAD_ARG, "realign: unitig %u has 2^30 bases or more", j);
+        std::vector<uint32_t> slot(nseg);
+        for (uint32_t j = 0; j < nutg; ++j)
+            for (uint64_t i = u.voff[j]; i < u.voff[j + 1]; ++i) slot[(size_t)i] = j;
+        const size_t nrec = c->as.records.size();
+        const size_t npw = (size_t)(total / 16 + 1);
+        TmpBuf recs, verts, slot_utg, pos, nb, dcpos, dcnb, uvoff, uboff, dcoffs, cont, rem, bvert, key, place, ascii, upk, table, votes;
+        int rc = upload_records(c, recs);
+        if (rc) return rc;
+        ENSURE(c, verts, 4 * (size_t)nseg); ENSURE(c, slot_utg, 4 * (size_t)nseg); ENSURE(c, nb, 4 * (size_t)nseg); ENSURE(c, dcnb, 4 * (size_t)nseg);
+        ENSURE(c, pos, 8 * (size_t)nseg); ENSURE(c, dcpos, 8 * (size_t)nseg);
+        ENSURE(c, uvoff, 8 * ((size_t)nutg + 1)); ENSURE(c, uboff, 8 * ((size_t)nutg + 1)); ENSURE(c, dcoffs, 8 * ((size_t)nutg + 1));
+        ENSURE(c, cont, nr); ENSURE(c, rem, nr);
+        ENSURE(c, bvert, 4 * (size_t)nr); ENSURE(c, key, 8 * (size_t)nr);
+        ENSURE(c, place, sizeof(bella_realign_placement) * (size_t)nr);
+        ENSURE(c, ascii, (size_t)total); ENSURE(c, upk, 4 * npw);
+        ENSURE(c, votes, 8);
+        const size_t tbytes = (size_t)total * kPileCounters * 4;
+        if (ensure_bytes(c, table, tbytes))
+            return fail(c, BELLA_ERR_NOMEM, "the realignment table needs %zu bytes of device memory (36 per base of %llu unitig bases) and they do not fit", tbytes,
+                        (unsigned long long)total);
+        HIPCHK(c, c->stager.h2d(verts.p, u.verts.data(), 4 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(slot_utg.p, slot.data(), 4 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(nb.p, u.nb.data(), 4 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(pos.p, u.pos.data(), 8 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(dcnb.p, cnb.data(), 4 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(dcpos.p, cpos.data(), 8 * (size_t)nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(uvoff.p, u.voff.data(), 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, c->stager.h2d(uboff.p, u.boff.data(), 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, c->stager.h2d(dcoffs.p, coffs.data(), 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, c->stager.h2d(cont.p, g.contained.data(), nr, c->stream));
+        HIPCHK(c, c->stager.h2d(rem.p, g.removed.data(), nr, c->stream));
+        if (total) HIPCHK(c, c->stager.h2d(ascii.p, cbases.data(), (size_t)total, c->stream));
+        HIPCHK(c, hipMemsetAsync(bvert.p, 0xFF, 4 * (size_t)nr, c->stream));
+        HIPCHK(c, hipMemsetAsync(key.p, 0, 8 * (size_t)nr, c->stream));
+        HIPCHK(c, hipMemsetAsync(table.p, 0, tbytes ? tbytes : 16, c->stream));
+        HIPCHK(c, hipMemsetAsync(votes.p, 0, 8, c->stream));
+        ReadSpans spans;
+        if ((rc = spans.make(c))) return rc;
+        EventSet ev;
+        if ((rc = ev.create(c, 3))) return rc;
+        const uint32_t* const rpacked = ptr<uint32_t>(c->packed);
+        const uint32_t* const upacked = ptr<uint32_t>(upk);
+        // ---- placement
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        k_rea_backbone<<<nblk(nseg), 256, 0, c->stream>>>(ptr<uint32_t>(verts), nseg, ptr<uint32_t>(bvert));
+        KCHK(c);
+        if (nrec) {
+            k_rea_anchor<<<nblk(nrec), 256, 0, c->stream>>>(ptr<bella_overlap>(recs), (uint32_t)nrec, ptr<uint32_t>(bvert), ptr<uint8_t>(cont), ptr<uint8_t>(rem),
+                                                            ptr<unsigned long long>(key));
+            KCHK(c);
+        }
+        k_rea_place<<<nblk(nr), 256, 0, c->stream>>>(nr, ptr<uint64_t>(c->roff), spans.beg, spans.end, ptr<uint32_t>(bvert), ptr<unsigned long long>(key), ptr<bella_overlap>(recs),
+                                                     ptr<uint8_t>(cont), ptr<uint8_t>(rem), ptr<uint32_t>(verts), ptr<uint32_t>(slot_utg), ptr<uint64_t>(pos), ptr<uint32_t>(nb),
+                                                     ptr<uint64_t>(dcpos), ptr<uint32_t>(dcnb), ptr<uint64_t>(uvoff), ptr<uint64_t>(uboff), ptr<uint64_t>(dcoffs), rp.band0,
+                                                     ptr<bella_realign_placement>(place));
+        KCHK(c);
+        if (total) {
+            k_rea_pack<<<nblk(npw), 256, 0, c->stream>>>(ptr<uint8_t>(ascii), total, ptr<uint32_t>(upk));
+            KCHK(c);
+        }
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        HIPCHK(c, c->stager.d2h(out.placements.data(), place.p, sizeof(bella_realign_placement) * (size_t)nr, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.place_ms = ev_ms(ev.a, ev.b);
+        ascii.reset();
+        // the reads' clips, as the kernels see them
+        std::vector<uint64_t> hroff((size_t)nr + 1, 0);
+        for (uint32_t r = 0; r < nr; ++r) hroff[r + 1] = hroff[r] + c->host_lens[r];
+        const bool clipped = has(c, TRIM);
+        std::vector<uint32_t> pending;
+        uint64_t nvert_reads = 0;
+        for (uint32_t r = 0; r < nr; ++r) {
+            bella_realign_placement& P = out.placements[r];
+            if (P.status == BELLA_REALIGN_NONE) continue;
+            if (P.anchor == kReaNone && P.status != BELLA_REALIGN_UNPLACED) { ++st.backbone; ++nvert_reads; }
+            else if (P.status != BELLA_REALIGN_UNPLACED) ++st.contained;
+            if (P.status == BELLA_REALIGN_UNPLACED) ++st.unplaced;
+            else if (P.status == BELLA_REALIGN_OUTSIDE) ++st.outside;
+            else pending.push_back(r);
+        }
+        st.repeated = nseg - nvert_reads;
+        // ---- DP, walks and votes: band by band, batch by batch
+        size_t mfree = 0, mtotal = 0;
+        HIPCHK(c, hipMemGetInfo(&mfree, &mtotal));
+        const uint64_t budget = std::max<uint64_t>(64ull << 20, std::min<uint64_t>((uint64_t)mfree / 2, 8ull << 30));       // direction bytes of a batch
+        TmpBuf jobs, res, cnt, dirs, scr, ops;
+        std::vector<ReaJob> hj;
+        std::vector<ReaRes> hres;
+        std::vector<ReaCnt> hcnt;
+        for (uint32_t B = rp.band0; !pending.empty(); B *= 2) {
+            std::vector<uint32_t> next;
+            for (size_t b0 = 0; b0 < pending.size();) {
+                hj.clear();
+                uint64_t dbytes = 0, sints = 0;
+                size_t b1 = b0;
+                for (; b1 < pending.size(); ++b1) {
+                    const uint32_t r = pending[b1];
+                    const bella_realign_placement& P = out.placements[r];
+                    const uint64_t beg = clipped ? c->as.trim.clips[r].beg : 0, end = clipped ? c->as.trim.clips[r].end : c->host_lens[r];
+                    const uint64_t n = end - beg, need_bytes = n * (B / 4);
+                    if (!hj.empty() && (dbytes + need_bytes > budget || hj.size() >= (1u << 20))) break;
+                    ReaJob j{};
+                    j.gH = (int64_t)coffs[P.unitig];
+                    j.gV = (int64_t)(hroff[r] + (P.orient ? end - 1 : beg));
+                    j.dir_off = dbytes; j.scr_off = sints; j.op_off = ~0ull;
+                    j.n = (uint32_t)n; j.m = (int32_t)(coffs[P.unitig + 1] - coffs[P.unitig]);
+                    const int64_t slack = (P.e - P.s) - (int64_t)n;
+                    j.c = (int32_t)(P.s + (slack >= 0 ? slack / 2 : -((-slack + 1) / 2)));      // floor
+                    j.band = B; j.dV = P.orient ? -1 : 1; j.comp = P.orient ? 3u : 0u;
+                    hj.push_back(j);
+                    dbytes += need_bytes; sints += 2ull * B;
+                    st.dp_cells += n * B;
+                }
+                const uint32_t nj = (uint32_t)hj.size();
+                ENSURE(c, jobs, sizeof(ReaJob) * (size_t)nj); ENSURE(c, res, sizeof(ReaRes) * (size_t)nj); ENSURE(c, cnt, sizeof(ReaCnt) * (size_t)nj);
+                if (ensure_bytes(c, dirs, (size_t)dbytes))
+                    return fail(c, BELLA_ERR_NOMEM, "realign: %llu direction bytes for a batch of %u reads do not fit", (unsigned long long)dbytes, nj);
+                if (B > kTrRegBand) ENSURE(c, scr, 4 * (size_t)sints);
+                st.dir_bytes_peak = std::max<uint64_t>(st.dir_bytes_peak, dbytes);
+                ++st.batches;
+                HIPCHK(c, c->stager.h2d(jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
+                HIPCHK(c, hipEventRecord(ev.a, c->stream));
+                const unsigned grid = nblk((uint64_t)nj * 64, kTraceBlock);
+                if (B == 256) k_rea_dp<4><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
+                else if (B == 512) k_rea_dp<8><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
+                else if (B == 1024) k_rea_dp<16><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
+                else k_rea_dp_wide<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<ReaRes>(res));
+                KCHK(c);
+                HIPCHK(c, hipEventRecord(ev.b, c->stream));
+                k_rea_count<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
+                KCHK(c);
+                HIPCHK(c, hipEventRecord(ev.d, c->stream));
+                hres.resize(nj); hcnt.resize(nj);
+                HIPCHK(c, c->stager.d2h(hres.data(), res.p, sizeof(ReaRes) * (size_t)nj, c->stream));
+                HIPCHK(c, c->stager.d2h(hcnt.data(), cnt.p, sizeof(ReaCnt) * (size_t)nj, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                st.dp_ms += ev_ms(ev.a, ev.b);
+                st.walk_ms += ev_ms(ev.b, ev.d);
+                uint64_t nops = 0;
+                for (uint32_t x = 0; x < nj; ++x) {
+                    const uint32_t r = pending[b0 + x];
+                    bella_realign_placement& P = out.placements[r];
+                    const ReaCnt& k = hcnt[x];
+                    P.band = B;
+                    P.n_eq = k.n_eq; P.n_x = k.n_x; P.n_ins = k.n_ins; P.n_del = k.n_del;
+                    const bool ended = k.nops > 0;
+                    P.score = ended ? hres[x].score : 0;
+                    P.q_begin = ended ? k.q_begin : 0; P.q_end = ended ? hres[x].q_end : 0;
+                    if (k.touch) {
+                        if (B < rp.band_max) next.push_back(r);
+                        else { P.status = BELLA_REALIGN_BAND_CAPPED; ++st.band_capped; }
+                    } else if (1000ull * k.n_eq < (uint64_t)rp.min_identity * ((uint64_t)k.n_eq + k.n_x + k.n_ins + k.n_del)) {
+                        P.status = BELLA_REALIGN_LOW_IDENTITY; ++st.low_identity;
+                    } else {
+                        P.status = BELLA_REALIGN_VOTED; ++st.voted;
+                        hj[x].op_off = nops;
+                        P.nops = k.nops;
+                        if (rp.keep_ops) P.op_off = out.ops.size() + nops;
+                        nops += k.nops;
+                    }
+                }
+                if (nops) {
+                    ENSURE(c, ops, 4 * (size_t)nops);
+                    HIPCHK(c, c->stager.h2d(jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
+                    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+                    k_rea_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
+                    KCHK(c);
+                    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+                    k_rea_vote<<<nblk((uint64_t)nj * 64, kPileBlock), kPileBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaCnt>(cnt), nj, ptr<uint32_t>(ops), rpacked,
+                                                                                                 ptr<uint32_t>(table), ptr<unsigned long long>(votes));
+                    KCHK(c);
+                    HIPCHK(c, hipEventRecord(ev.d, c->stream));
+                    if (rp.keep_ops) {
+                        const size_t at = out.ops.size();
+                        out.ops.resize(at + (size_t)nops);
+                        HIPCHK(c, c->stager.d2h(out.ops.data() + at, ops.p, 4 * (size_t)nops, c->stream));
+                    }
+                    HIPCHK(c, hipStreamSynchronize(c->stream));
+                    st.walk_ms += ev_ms(ev.a, ev.b);
+                    st.vote_ms += ev_ms(ev.b, ev.d);
+                }
+                b0 = b1;
+            }
+            pending.swap(next);
+            if (B >= rp.band_max) break;
+        }
+        dirs.reset(); scr.reset(); ops.reset();
+        HIPCHK(c, hipMemcpyAsync(&st.votes, votes.p, 8, hipMemcpyDeviceToHost, c->stream));
+        if (rp.keep_ops && total) {
+            out.table.resize((size_t)total * kPileCounters);
+            HIPCHK(c, c->stager.d2h(out.table.data(), table.p, tbytes, c->stream));
+        }
+        // ---- consensus: every unitig a read whose own bases are the sequence it was aligned against
+        TmpBuf emit, scan, outb, noffs, cstats, npos, nnb;
+        ENSURE(c, emit, (size_t)total + 1); ENSURE(c, scan, 8 * ((size_t)total + 1));
+        ENSURE(c, noffs, 8 * ((size_t)nutg + 1)); ENSURE(c, cstats, sizeof(bella_consensus_read) * (size_t)nutg);
+        ENSURE(c, npos, 8 * (size_t)nseg); ENSURE(c, nnb, 4 * (size_t)nseg);
+        HIPCHK(c, hipMemsetAsync(cstats.p, 0, sizeof(bella_consensus_read) * (size_t)nutg, c->stream));
+        HIPCHK(c, hipMemsetAsync(ptr<uint8_t>(emit) + total, 0, 1, c->stream));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        if (total) {
+            k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(table), upacked, ptr<uint64_t>(dcoffs), nutg, total, rp.min_depth, ptr<uint8_t>(emit),
+                                                              ptr<bella_consensus_read>(cstats));
+            KCHK(c);
+        }
+        {
+            hipcub::TransformInputIterator<uint64_t, EmitCount, const uint8_t*> it(ptr<uint8_t>(emit), EmitCount());
+            CUB(c, hipcub::DeviceScan::ExclusiveSum, it, ptr<uint64_t>(scan), (int)(total + 1), c->stream);
+        }
+        HIPCHK(c, hipMemcpyAsync(&nout, ptr<uint64_t>(scan) + total, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        ENSURE(c, outb, (size_t)nout);
+        if (total) {
+            k_cons_write<<<nblk(total), 256, 0, c->stream>>>(ptr<uint8_t>(emit), ptr<uint64_t>(scan), total, ptr<uint8_t>(outb));
+            KCHK(c);
+        }
+        k_cons_reads<<<nblk((uint64_t)nutg + 1), 256, 0, c->stream>>>(ptr<uint64_t>(dcoffs), ptr<uint64_t>(scan), nutg, ptr<uint64_t>(noffs), ptr<bella_consensus_read>(cstats));
+        KCHK(c);
+        if (nseg) {
+            k_rea_segpos<<<nblk(nseg), 256, 0, c->stream>>>(ptr<uint64_t>(scan), ptr<uint64_t>(dcpos), ptr<uint32_t>(slot_utg), ptr<uint64_t>(uvoff), ptr<uint64_t>(dcoffs), nseg,
+                                                            ptr<uint64_t>(npos), ptr<uint32_t>(nnb));
+            KCHK(c);
+        }
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        std::vector<bella_consensus_read> hs(nutg);
+        out.bases.assign((size_t)nout, 0);
+        HIPCHK(c, c->stager.d2h(out.offs.data(), noffs.p, 8 * ((size_t)nutg + 1), c->stream));
+        HIPCHK(c, c->stager.d2h(hs.data(), cstats.p, sizeof(bella_consensus_read) * (size_t)nutg, c->stream));
+        if (nseg) {
+            HIPCHK(c, c->stager.d2h(out.pos.data(), npos.p, 8 * (size_t)nseg, c->stream));
+            HIPCHK(c, c->stager.d2h(out.nb.data(), nnb.p, 4 * (size_t)nseg, c->stream));
+        }
+        if (nout) HIPCHK(c, c->stager.d2h(out.bases.data(), outb.p, (size_t)nout, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.decide_ms = ev_ms(ev.a, ev.b);
+        for (uint32_t j = 0; j < nutg; ++j) {
+            bella_polish_unitig& q = out.recs[j];
+            q.len_before = hs[j].len_before; q.len_after = hs[j].len_after;
+            q.substituted = hs[j].substituted; q.deleted = hs[j].deleted; q.inserted = hs[j].inserted; q.covered = hs[j].covered; q.depth_sum = hs[j].depth_sum;
+            st.substituted += q.substituted; st.deleted += q.deleted; st.inserted += q.inserted;
+        }
+    }
+    st.bases_after = nout;
+    out.stats = st;
+    c->as.realign = std::move(out);
+    made(c, REALIGN);
+    if (total_bases) *total_bases = nout;
+    return 0;
+}
+
+int bella_hip_graph_get_realigned(bella_ctx* c, uint64_t* offsets, uint8_t* bases, uint64_t* pos, uint32_t* nbases, bella_polish_unitig* per_unitig) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, REALIGN)) return r;
+    const StageState::Realign& p = c->as.realign;
+    copy_out(offsets, p.offs);
+    copy_out(bases, p.bases);
+    copy_out(pos, p.pos);
+    copy_out(nbases, p.nb);
+    copy_out(per_unitig, p.recs);
+    return 0;
+}
+
+int bella_hip_graph_get_realign_placements(bella_ctx* c, bella_realign_placement* out) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, REALIGN)) return r;
+    copy_out(out, c->as.realign.placements);
+    return 0;
+}
+
+int bella_hip_graph_get_realign_ops(bella_ctx* c, uint64_t* nops, uint32_t* ops, uint32_t* table) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, REALIGN)) return r;
+    if (nops) *nops = c->as.realign.ops.size();
+    copy_out(ops, c->as.realign.ops);
+    copy_out(table, c->as.realign.table);
+    return 0;
+}
+
+int bella_hip_graph_get_realign_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    return get_stats(c, REALIGN, out, struct_size, [](const StageState& a) { return a.realign.stats; });
 }
 
 int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,

@@ -1,0 +1,370 @@
+// realign.hpp -- every read aligned against the current sequence of its unitig, the votes piled up in unitig coordinates, on gfx950
+// (DESIGN.md section 18).
+//
+// Nothing in the reference does this; the definition is this project's own (include/bella_hip.h; the tests hold
+// a numpy statement of it).  Everything is an integer, so the result is that statement's exactly.
+//
+// Placement.  k_rea_backbone (one thread per vertex) gives every read its first vertex; k_rea_anchor (one thread per record) gives
+// every contained read the record that joins it to a backbone read over the longest span -- one 64-bit atomicMax per candidate, the key
+// span << 32 | ~index, so the choice does not depend on the order the threads run in; k_rea_place (one thread per read) turns vertex or
+// record into the unitig, the orientation and the window [s, e) on the current sequence.
+//
+// DP.  trace.hpp's row sweep, called as it stands: one wavefront per read, the band of B = 64 C diagonals across the lanes, scores in
+// VGPRs, one prefix maximum per row.  What differs from k_trace_dp: row 0 is 0 in every cell of the band (the start is free along the
+// unitig), the band's diagonals are q - i - c for the read's centre diagonal c (the column origin moves, the row code does not know), the
+// rows are the read's clip in its orientation on the unitig (reversed and complemented for orientation 1) and the columns the 2-bit
+// pack of the unitig's bases, and the end is the best cell of row n alone: the running best is cleared before the last row, so the tie
+// rule of trace_best_take (smallest i + j) is the smallest q.  Per row that is one scalar compare more than k_trace_dp.
+// The kernel is bound by VALU issue, as k_trace_dp is: ~30 C instructions per row against one C-byte store per lane.
+//
+// Walks.  One thread per read from (n, q_end) up to row 0: a counting walk (runs, op totals, whether the path touched the band's first
+// or last diagonal, q_begin), and once the host has laid the runs out a writing walk, backwards from the read's last run.
+// Votes.  One wavefront per read over its runs, pileup.hpp's mapping (64 runs per chunk, their columns dealt to the lanes): a column of
+// '=' / 'X' votes the read's base at q, 'D' votes del at q, a run of 'I' one ins vote with its first base in the junction before q.
+#pragma once
+#include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
+#include "../../include/bella_hip.h"
+#include "pileup.hpp"
+#include "trace.hpp"
+
+namespace bella {
+
+constexpr uint32_t kReaNone = 0xFFFFFFFFu;
+constexpr uint64_t kReaMaxUnitig = 1ull << 30;       // bases of one unitig: column indices stay far inside an int
+
+// one read of a DP batch, filled by the host from the read's placement
+struct ReaJob {
+    int64_t gH;            // first base of the unitig among all unitig bases (2-bit pack and table row)
+    int64_t gV;            // base of the packed reads that is row 1
+    uint64_t dir_off;      // bytes into the direction buffer: rows 1 .. n, B / 4 bytes each
+    uint64_t scr_off;      // wide kernel: ints into the scratch (2 B per read)
+    uint64_t op_off;       // first run in the batch's op array; ~0: the read does not vote
+    uint32_t n;            // rows: bases of the clip
+    int32_t m;             // columns: bases of the unitig
+    int32_t c;             // centre diagonal
+    uint32_t band;
+    int32_t dV;            // +1, or -1 for orientation 1
+    uint32_t comp;         // 3 for orientation 1
+};
+struct ReaRes { int32_t score; int32_t q_end; };
+struct ReaCnt { uint32_t nops, n_eq, n_x, n_ins, n_del, touch; int32_t q_begin; uint32_t pad; };
+
+// raw unitig coordinate -> coordinate on the current sequence; segments [lo, hi) are the unitig's, len / plen its lengths
+BELLA_HD int64_t rea_map(int64_t x, const uint64_t* pos, const uint32_t* nb, const uint64_t* cpos, const uint32_t* cnb, uint64_t lo, uint64_t hi, int64_t len, int64_t plen) {
+    if (x < 0) return x;
+    if (x >= len) return plen + (x - len);
+    uint64_t a = lo, b = hi;                                          // the last segment with pos <= x
+    while (b - a > 1) {
+        const uint64_t mid = a + (b - a) / 2;
+        if ((int64_t)pos[mid] <= x) a = mid; else b = mid;
+    }
+    if (!nb[a]) return (int64_t)cpos[a];
+    return (int64_t)cpos[a] + (x - (int64_t)pos[a]) * (int64_t)cnb[a] / (int64_t)nb[a];
+}
+
+#if defined(__HIPCC__)
+__global__ void k_rea_backbone(const uint32_t* verts, uint32_t nseg, uint32_t* bvert) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nseg) atomicMin(bvert + (verts[i] >> 1), i);
+}
+
+// key[c] = max over the records that join the contained read c to a backbone read of span on c << 32 | ~index (0: none)
+__global__ void k_rea_anchor(const bella_overlap* recs, uint32_t nrec, const uint32_t* bvert, const uint8_t* contained, const uint8_t* removed, unsigned long long* key) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= nrec) return;
+    const bella_overlap r = recs[x];
+    const unsigned long long low = (unsigned long long)(0xFFFFFFFFu - x);
+    if (contained[r.cid] == 1 && !removed[r.cid] && bvert[r.cid] == kReaNone && bvert[r.rid] != kReaNone)
+        atomicMax(key + r.cid, ((unsigned long long)(uint32_t)(r.endV - r.begV) << 32) | low);
+    if (contained[r.rid] == 1 && !removed[r.rid] && bvert[r.rid] == kReaNone && bvert[r.cid] != kReaNone)
+        atomicMax(key + r.rid, ((unsigned long long)(uint32_t)(r.endH - r.begH) << 32) | low);
+}
+
+// rbeg / rend: the reads' clips among all bases (whole reads: roff and roff + 1).  uoff: raw unitig offsets, coffs: current ones.
+__global__ void k_rea_place(uint32_t nreads, const uint64_t* roff, const uint64_t* rbeg, const uint64_t* rend, const uint32_t* bvert, const unsigned long long* key,
+                            const bella_overlap* recs, const uint8_t* contained, const uint8_t* removed, const uint32_t* verts, const uint32_t* slot_utg,
+                            const uint64_t* pos, const uint32_t* nb, const uint64_t* cpos, const uint32_t* cnb, const uint64_t* uvoff, const uint64_t* uoff,
+                            const uint64_t* coffs, uint32_t band0, bella_realign_placement* out) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nreads) return;
+    bella_realign_placement P{};
+    P.unitig = kReaNone; P.anchor = kReaNone; P.status = BELLA_REALIGN_NONE;
+    const int64_t L = (int64_t)(roff[r + 1] - roff[r]), beg = (int64_t)(rbeg[r] - roff[r]), end = (int64_t)(rend[r] - roff[r]);
+    int64_t x0 = 0;
+    uint32_t o = 0, u = kReaNone;
+    if (bvert[r] != kReaNone) {
+        const uint32_t i = bvert[r];
+        o = verts[i] & 1u; u = slot_utg[i];
+        x0 = (int64_t)pos[i] - (o ? L - end : beg);
+    } else if (contained[r] == 1 && !removed[r]) {
+        const unsigned long long k = key[r];
+        if (!k) P.status = BELLA_REALIGN_UNPLACED;
+        else {
+            const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull);
+            const bella_overlap rec = recs[idx];
+            const bool isV = rec.cid != r;                             // the backbone read is V
+            const uint32_t b = isV ? rec.cid : rec.rid;
+            const int64_t Lb = (int64_t)(roff[b + 1] - roff[b]), bb = (int64_t)(rbeg[b] - roff[b]), be = (int64_t)(rend[b] - roff[b]);
+            int64_t d;
+            uint32_t s;
+            if (isV) { d = (int64_t)rec.begV - rec.begH; s = rec.strand; }             // H' = this read, in V's frame
+            else if (!rec.strand) { d = (int64_t)rec.begH - rec.begV; s = 0; }         // V = this read, in the frame of H' = H
+            else { d = Lb - ((int64_t)rec.begH - rec.begV) - L; s = 1; }               // ... of H' = rc(H): mirrored by H's length
+            const uint32_t i = bvert[b], ob = verts[i] & 1u;
+            const int64_t x0b = (int64_t)pos[i] - (ob ? Lb - be : bb);
+            u = slot_utg[i];
+            x0 = ob ? x0b + (Lb - d - L) : x0b + d;
+            o = ob ? s ^ 1u : s;
+            P.anchor = idx;
+        }
+    }
+    if (u != kReaNone && end > beg) {
+        const int64_t n = end - beg, x = x0 + (o ? L - end : beg);
+        const uint64_t lo = uvoff[u], hi = uvoff[u + 1];
+        const int64_t len = (int64_t)(uoff[u + 1] - uoff[u]), plen = (int64_t)(coffs[u + 1] - coffs[u]);
+        P.unitig = u; P.orient = o;
+        P.s = rea_map(x, pos, nb, cpos, cnb, lo, hi, len, plen);
+        P.e = rea_map(x + n, pos, nb, cpos, cnb, lo, hi, len, plen);
+        const int64_t h = (int64_t)(band0 / 2);
+        P.status = (P.s < -h || P.e > plen + h || P.e < P.s) ? BELLA_REALIGN_OUTSIDE : BELLA_REALIGN_VOTED;       // (VOTED: a candidate until the DP has spoken)
+    }
+    out[r] = P;
+}
+
+// 16 ASCII bases -> one word of the 2-bit pack
+__global__ void k_rea_pack(const uint8_t* ascii, uint64_t total, uint32_t* packed) {
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w * 16 >= total) return;
+    uint32_t v = 0;
+    for (uint32_t k = 0; k < 16 && w * 16 + k < total; ++k) {
+        const uint8_t ch = ascii[w * 16 + k];
+        v |= (ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 0u) << (2 * k);
+    }
+    packed[w] = v;
+}
+
+// band of 64 * C diagonals in registers; wavefront w runs jobs[w]
+template <int C>
+__global__ __launch_bounds__(kTraceBlock) void k_rea_dp(const ReaJob* jobs, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, uint8_t* dirs, ReaRes* res) {
+    using Word = typename TraceDirWord<C>::type;
+    const uint32_t w = (uint32_t)(((uint64_t)blockIdx.x * kTraceBlock + threadIdx.x) >> 6);
+    if (w >= njobs) return;                                           // (whole wavefronts leave)
+    const int lane = (int)(threadIdx.x & 63);
+    const ReaJob e = jobs[w];
+    constexpr int B = 64 * C, half = B / 2;
+    const int n = (int)e.n, m = e.m;
+    const int p0 = lane * C;
+    const int j0 = e.c + p0 - half;                                   // column of the lane's first cell in row 0
+    int prev[C];
+    uint32_t hwin = 0;                                                // the lane's bases of the unitig for row 1: cell c is column j0 + c + 1, its base u[j0 + c]
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int j = j0 + c;
+        prev[c] = (j >= 0 && j <= m) ? 0 : kTrNeg;
+        if (j >= 0 && j < m) hwin |= (uint32_t)trace_base(upacked, e.gH, 1, 0u, j) << (2 * c);
+    }
+    Word* const drow = (Word*)(dirs + e.dir_off) + lane;
+    TraceBest best{kTrNeg, 0, 0};
+    uint32_t vw = 0;
+    int64_t vwi = -1;
+    for (int i = 1; i <= n; ++i) {
+        const int64_t gv = e.gV + (int64_t)e.dV * (i - 1);
+        if ((gv >> 4) != vwi) { vwi = gv >> 4; vw = rpacked[vwi]; }
+        const int vb = (int)(((vw >> ((uint32_t)(gv & 15) * 2)) & 3u) ^ e.comp);
+        int upn = __shfl_down(prev[0], 1, 64);
+        if (lane == 63) upn = kTrNeg;
+        int carry = kTrNeg;
+        if (i == n) best = TraceBest{kTrNeg, 0, 0};                   // the end is a cell of the last row
+        const uint32_t bits = trace_row_tile<C>(prev, upn, hwin, vb, i + j0, m, p0, carry, i, best);
+        drow[(size_t)(i - 1) * 64] = (Word)bits;
+        const int t = i + j0 + C - 1;                                 // the column j - 1 of the lane's last cell in row i + 1
+        uint32_t nbase = 0;
+        if (t >= 0 && t < m) nbase = (uint32_t)trace_base(upacked, e.gH, 1, 0u, t);
+        hwin = (C == 16 ? (hwin >> 2) : ((hwin >> 2) & ((1u << (2 * (C - 1))) - 1u))) | (nbase << (2 * (C - 1)));
+    }
+    trace_best_reduce(best);
+    if (lane == 0) res[w] = ReaRes{best.s, best.sum - best.i};
+}
+
+// any band: tiles of 256 cells, the previous row in global scratch, one wavefront per block -- k_trace_dp_wide's shape, and its
+// invariant: a row computes the tiles that hold a column 0 .. m, and trace_row_tile masks every neighbour by its column.
+__global__ __launch_bounds__(64) void k_rea_dp_wide(const ReaJob* jobs, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, uint8_t* dirs, int* scratch,
+                                                    ReaRes* res) {
+    const uint32_t w = blockIdx.x;
+    if (w >= njobs) return;
+    const int lane = (int)threadIdx.x;
+    const ReaJob e = jobs[w];
+    const int B = (int)e.band, half = B / 2;
+    const int n = (int)e.n, m = e.m;
+    int* bufP = scratch + e.scr_off;
+    int* bufC = bufP + B;
+    for (int p = lane; p < B; p += 64) {
+        const int j = e.c + p - half;
+        bufP[p] = (j >= 0 && j <= m) ? 0 : kTrNeg;
+    }
+    __syncthreads();
+    TraceBest best{kTrNeg, 0, 0};
+    uint8_t* const dbase = dirs + e.dir_off;
+    const size_t rowbytes = (size_t)B / 4;
+    for (int i = 1; i <= n; ++i) {
+        const int vb = trace_base(rpacked, e.gV, e.dV, e.comp, i - 1);
+        const int org = i + e.c - half;                               // column of position 0 in this row
+        const int plo = -org > 0 ? -org : 0;                          // positions of the columns 0 .. m
+        const int phi = m - org < B - 1 ? m - org : B - 1;
+        int carry = kTrNeg;
+        if (i == n) best = TraceBest{kTrNeg, 0, 0};
+        if (plo <= phi) {
+            for (int t = plo >> 8; t <= (phi >> 8); ++t) {
+                const int p0 = t * 256 + lane * 4;
+                int prev[4];
+                const int4 q = *(const int4*)(bufP + p0);
+                prev[0] = q.x; prev[1] = q.y; prev[2] = q.z; prev[3] = q.w;
+                const int upn = p0 + 4 < B ? bufP[p0 + 4] : kTrNeg;
+                const int jb = org + p0;
+                uint32_t hwin = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int tt = jb + c - 1;
+                    if (tt >= 0 && tt < m) hwin |= (uint32_t)trace_base(upacked, e.gH, 1, 0u, tt) << (2 * c);
+                }
+                const uint32_t bits = trace_row_tile<4>(prev, upn, hwin, vb, jb, m, p0, carry, i, best);
+                *(int4*)(bufC + p0) = make_int4(prev[0], prev[1], prev[2], prev[3]);
+                dbase[(size_t)(i - 1) * rowbytes + (size_t)(p0 >> 2)] = (uint8_t)bits;
+            }
+        }
+        __syncthreads();                                              // the row is in memory before the next one reads it
+        int* tmp = bufP; bufP = bufC; bufC = tmp;
+    }
+    trace_best_reduce(best);
+    if (lane == 0) res[w] = ReaRes{best.s, best.sum - best.i};
+}
+
+// Walks one read from (n, q_end) back to row 0 and hands every op to `put` (the read's last base first).  Returns whether the path
+// touched the first or the last diagonal of the band; qb = the junction where it reached row 0.
+template <class Put>
+__device__ __forceinline__ bool rea_walk(const ReaJob& e, const ReaRes& r, const uint32_t* rpacked, const uint32_t* upacked, const uint8_t* dirs, int& qb, Put&& put) {
+    int i = (int)e.n, q = r.q_end;
+    const int B = (int)e.band, half = B / 2;
+    const uint8_t* const d0 = dirs + e.dir_off;
+    const size_t rowbytes = (size_t)B / 4;
+    bool touch = false;
+    while (i > 0) {
+        int p = q - i - e.c + half;
+        if (p <= 0 || p >= B - 1) { touch = true; p = p < 0 ? 0 : (p > B - 1 ? B - 1 : p); }      // (the clamp keeps the read in bounds whatever the bytes say)
+        uint32_t d = q <= 0 ? 1u : (uint32_t)((d0[(size_t)(i - 1) * rowbytes + (size_t)(p >> 2)] >> (2 * (p & 3))) & 3u);
+        if (d == 3) d = 2;
+        if (d == 0) {
+            const int hb = trace_base(upacked, e.gH, 1, 0u, q - 1), vb = trace_base(rpacked, e.gV, e.dV, e.comp, i - 1);
+            put(hb == vb ? kOpEq : kOpX);
+            --i; --q;
+        } else if (d == 1) { put(kOpIns); --i; }
+        else { put(kOpDel); --q; }
+    }
+    qb = q;
+    return touch;
+}
+
+constexpr int kReaNoEnd = kTrNeg / 2;      // a best score at or below this: row n has no cell that a path from row 0 reaches
+
+__global__ void k_rea_count(const ReaJob* jobs, const ReaRes* res, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, const uint8_t* dirs, ReaCnt* out) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= njobs) return;
+    ReaCnt o{};
+    const ReaRes r = res[x];
+    if (r.score <= kReaNoEnd || r.q_end < 0 || r.q_end > jobs[x].m) { o.touch = 1; out[x] = o; return; }
+    TraceRuns runs;
+    int qb = 0;
+    const bool t = rea_walk(jobs[x], r, rpacked, upacked, dirs, qb, runs);
+    o.nops = runs.nruns;
+    o.n_eq = runs.cnt[0]; o.n_x = runs.cnt[1]; o.n_ins = runs.cnt[2]; o.n_del = runs.cnt[3];
+    o.touch = t ? 1u : 0u;
+    o.q_begin = qb;
+    out[x] = o;
+}
+
+// one thread per read that votes: ops[op_off .. op_off + nops) in read order
+__global__ void k_rea_write(const ReaJob* jobs, const ReaRes* res, const ReaCnt* cnt, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, const uint8_t* dirs,
+                            uint32_t* ops) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= njobs) return;
+    const ReaJob e = jobs[x];
+    if (e.op_off == ~0ull) return;
+    TraceEmit bw{ops, (int64_t)(e.op_off + cnt[x].nops), -1};
+    int qb = 0;
+    rea_walk(e, res[x], rpacked, upacked, dirs, qb, bw);
+    bw.flush();
+}
+
+// one wavefront per read; table: nine counters per base of all unitigs
+__global__ __launch_bounds__(kPileBlock) void k_rea_vote(const ReaJob* jobs, const ReaCnt* cnt, uint32_t njobs, const uint32_t* ops, const uint32_t* rpacked, uint32_t* table,
+                                                         unsigned long long* votes) {
+    const uint32_t x = (uint32_t)(((uint64_t)blockIdx.x * kPileBlock + threadIdx.x) >> 6);
+    if (x >= njobs) return;                                           // (whole wavefronts leave)
+    const int lane = (int)(threadIdx.x & 63);
+    const ReaJob e = jobs[x];
+    if (e.op_off == ~0ull) return;
+    const uint32_t nops = cnt[x].nops, m = (uint32_t)e.m;
+    const uint32_t* const po = ops + e.op_off;
+    uint32_t ci = 0, cj = (uint32_t)cnt[x].q_begin;                   // where the chunk's first run starts: row (0-based base of the read), column
+    uint32_t nv = 0;
+    for (uint32_t c0 = 0; c0 < nops; c0 += 64) {
+        const uint32_t w = c0 + lane < nops ? po[c0 + lane] : 0u;
+        const uint32_t op = w & 15u, len = w >> 4;
+        const uint32_t di = op != kOpDel ? len : 0u, dj = op != kOpIns ? len : 0u;
+        const uint32_t ei = pile_scan_incl(di, lane), ej = pile_scan_incl(dj, lane), ec = pile_scan_incl(len, lane);
+        const uint32_t si = ci + ei - di, sj = cj + ej - dj;
+        const uint32_t total = __shfl(ec, 63, 64);
+        for (uint32_t t0 = 0; t0 < total; t0 += 64) {
+            const bool live = t0 + lane < total;
+            const uint32_t t = live ? t0 + lane : total - 1;
+            int r = 0;                                                // the first run whose columns end behind t
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) {
+                const uint32_t en = __shfl(ec, r + s - 1, 64);
+                if (en <= t) r += s;
+            }
+            const uint32_t rw = __shfl(w, r, 64), rend = __shfl(ec, r, 64), ri = __shfl(si, r, 64), rj = __shfl(sj, r, 64);
+            if (!live) continue;
+            const uint32_t rop = rw & 15u, rlen = rw >> 4;
+            const uint32_t o = t - (rend - rlen);
+            const uint32_t i = ri + (rop != kOpDel ? o : 0u), j = rj + (rop != kOpIns ? o : 0u);
+            if (rop <= kOpX) {
+                if (i < e.n && j < m) {
+                    atomicAdd(table + ((uint64_t)e.gH + j) * kPileCounters + (uint32_t)trace_base(rpacked, e.gV, e.dV, e.comp, i), 1u);
+                    ++nv;
+                }
+            } else if (rop == kOpIns) {                               // bases of the read only: one vote for the run, in the junction before rj
+                if (o == 0 && ri < e.n && rj < m) {
+                    atomicAdd(table + ((uint64_t)e.gH + rj) * kPileCounters + kPileIns + (uint32_t)trace_base(rpacked, e.gV, e.dV, e.comp, ri), 1u);
+                    ++nv;
+                }
+            } else if (rop == kOpDel) {                               // a base of the unitig only
+                if (j < m) { atomicAdd(table + ((uint64_t)e.gH + j) * kPileCounters + kPileDel, 1u); ++nv; }
+            }
+        }
+        ci += __shfl(ei, 63, 64);
+        cj += __shfl(ej, 63, 64);
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) nv += __shfl_xor(nv, d, 64);
+    if (lane == 0 && nv) atomicAdd(votes, (unsigned long long)nv);
+}
+
+// Where the segments of the sequence that was aligned against begin in the new one: scan[g] = bases emitted before position g of all
+// unitig bases (k_cons_write's scan).  npos[i] / nnb[i] per vertex.
+__global__ void k_rea_segpos(const uint64_t* scan, const uint64_t* cpos, const uint32_t* slot_utg, const uint64_t* uvoff, const uint64_t* coffs, uint32_t nseg, uint64_t* npos,
+                             uint32_t* nnb) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nseg) return;
+    const uint32_t u = slot_utg[i];
+    const uint64_t base = scan[coffs[u]], a = scan[coffs[u] + cpos[i]];
+    const uint64_t b = (uint64_t)i + 1 < uvoff[u + 1] ? scan[coffs[u] + cpos[i + 1]] : scan[coffs[u + 1]];
+    npos[i] = a - base;
+    nnb[i] = (uint32_t)(b - a);
+}
+#endif
+
+}  // namespace bella

@@ -21,6 +21,7 @@
 //
 // --polish: unitig consensus: every stage's traced pairs vote as with --correct, the unitigs are polished from
 // the pileup on the device after the last stage; --unitigs / --unitigs-fasta then carry the polished sequences and coordinates.
+// --polish-rounds N: N - 1 realignment rounds follow, each aligning the reads against the unitigs of the round before.
 //
 // --trim: coverage trimming: after the last stage every read is clipped, on the device, to its longest stretch that
 // --trim-depth overlap records cover; the graph is built from the records cut to the clips, and --gfa / --unitigs / --unitigs-fasta are in
@@ -58,6 +59,8 @@ struct Options {
     bool pop_bubbles = false, bubble_param_given = false;
     int polish_min_depth = 3;
     bool polish = false, polish_param_given = false;
+    int polish_rounds = 1, realign_band = 512, realign_min_identity = 700;
+    bool realign_param_given = false;
     int trim_depth = 3, trim_end_clip = 500;
     std::string trimmed_reads;
     bool trim = false, trim_param_given = false;
@@ -115,6 +118,10 @@ const char* kHelp =
     "      --weak-steps arg       ... and the steps from the first to the last: steps + 1 cuts (default: 2; at most 16)\n"
     "      --polish               with --unitigs / --unitigs-fasta: unitig consensus from the pileup of the base-level alignments, on the device\n"
     "      --polish-min-depth arg with --polish: votes a position needs before it is changed (default: 3)\n"
+    "      --polish-rounds arg    with --polish: consensus rounds (default: 1; at most 4); every round after the first aligns the reads against the\n"
+    "                             unitigs of the round before, on the device, and takes the consensus of those alignments\n"
+    "      --realign-band arg     with --polish: the first band of those alignments, a power of two from 256 to 4096 (default: 512)\n"
+    "      --realign-min-identity arg  with --polish: permille of matches below which a read's alignment does not vote (default: 700)\n"
     "      --trim                 with --gfa / --unitigs / --unitigs-fasta: clip every read to its longest stretch that --trim-depth overlaps cover, on the\n"
     "                             device, before the graph is built (shortest stretch: --gfa-min-overlap); the graph files are in clipped coordinates\n"
     "      --trim-depth arg       with --trim: overlaps a position needs to count as covered (default: 3)\n"
@@ -144,6 +151,7 @@ Options parse(int argc, char** argv) {
         {"pop-bubbles", 0, 0, &o.pop_bubbles}, {"bubble-reads", 0, 1, &o.bubble_reads}, {"bubble-dist", 0, 1, &o.bubble_dist}, {"bubble-rounds", 0, 1, &o.bubble_rounds},
         {"cut-weak", 0, 0, &o.cut_weak}, {"weak-min", 0, 1, &o.weak_min}, {"weak-max", 0, 1, &o.weak_max}, {"weak-steps", 0, 1, &o.weak_steps},
         {"polish", 0, 0, &o.polish}, {"polish-min-depth", 0, 1, &o.polish_min_depth},
+        {"polish-rounds", 0, 1, &o.polish_rounds}, {"realign-band", 0, 1, &o.realign_band}, {"realign-min-identity", 0, 1, &o.realign_min_identity},
         {"trim", 0, 0, &o.trim}, {"trim-depth", 0, 1, &o.trim_depth}, {"trim-end-clip", 0, 1, &o.trim_end_clip}, {"trimmed-reads", 0, 3, &o.trimmed_reads},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
@@ -185,6 +193,7 @@ Options parse(int argc, char** argv) {
         if (sp->dst == &o.bubble_reads || sp->dst == &o.bubble_dist || sp->dst == &o.bubble_rounds) o.bubble_param_given = true;
         if (sp->dst == &o.weak_min || sp->dst == &o.weak_max || sp->dst == &o.weak_steps) o.weak_param_given = true;
         if (sp->dst == &o.polish_min_depth) o.polish_param_given = true;
+        if (sp->dst == &o.polish_rounds || sp->dst == &o.realign_band || sp->dst == &o.realign_min_identity) o.realign_param_given = true;
         if (sp->dst == &o.trim_depth || sp->dst == &o.trim_end_clip || sp->dst == &o.trimmed_reads) o.trim_param_given = true;
     }
     return o;
@@ -258,6 +267,10 @@ int main(int argc, char** argv) {
     if (o.polish && o.unitigs.empty() && o.unitigs_fasta.empty()) die("--polish needs --unitigs or --unitigs-fasta");
     if (o.polish && o.gfa_no_seq && o.unitigs_fasta.empty()) die("--polish with --gfa-no-seq needs --unitigs-fasta (there is no sequence to polish into)");
     if (o.polish && o.polish_min_depth < 1) die("--polish-min-depth must be at least 1");
+    if (o.realign_param_given && !o.polish) die("--polish-rounds, --realign-band and --realign-min-identity need --polish");
+    if (o.polish_rounds < 1 || o.polish_rounds > 4) die("--polish-rounds must be in [1, 4]");
+    if (o.realign_band < 256 || o.realign_band > 4096 || (o.realign_band & (o.realign_band - 1))) die("--realign-band must be a power of two in [256, 4096]");
+    if (o.realign_min_identity < 0 || o.realign_min_identity > 1000) die("--realign-min-identity is in permille: [0, 1000]");
     if (o.trim_param_given && !o.trim) die("--trim-depth, --trim-end-clip and --trimmed-reads need --trim");
     if (o.trim && !o.graph()) die("--trim needs --gfa, --unitigs or --unitigs-fasta");
     if (o.trim && (o.trim_depth < 1 || o.trim_end_clip < 0)) die("--trim-depth must be at least 1 and --trim-end-clip must not be negative");
@@ -416,6 +429,7 @@ int main(int argc, char** argv) {
     so.weak_min = (uint32_t)o.weak_min; so.weak_max = (uint32_t)o.weak_max; so.weak_steps = (uint32_t)o.weak_steps;
     so.polish = o.polish ? 1 : 0;
     so.polish_min_depth = (uint32_t)o.polish_min_depth;
+    so.polish_rounds = (uint32_t)o.polish_rounds; so.realign_band = (uint32_t)o.realign_band; so.realign_min_identity = (uint32_t)o.realign_min_identity;
     so.trim = o.trim ? 1 : 0;
     so.trim_depth = (uint32_t)o.trim_depth; so.trim_end_clip = (uint32_t)o.trim_end_clip;
     so.trimmed_reads = o.trimmed_reads.empty() ? nullptr : o.trimmed_reads.c_str();

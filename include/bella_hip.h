@@ -652,7 +652,7 @@ int bella_hip_graph_get_weak_stats(bella_ctx* ctx, void* out, uint64_t struct_si
  * own positions and nothing else (the junction in front of the first position behind a forward segment is not part of it: an edge effect
  * of at most one base per segment).  With an all-zero table the result is the raw unitigs.  Limits as in the read correction: one
  * inserted base per junction, plain majority; the segment boundaries stay where the raw unitig has them; the links keep their raw
- * overlaps; there is no second round and no re-alignment of reads to the unitig. */
+ * overlaps; a second round, with the reads re-aligned to the unitig, is the realignment section below. */
 typedef struct {
     uint32_t struct_size;         /* sizeof(bella_polish_params) of the caller's header (the struct may grow)               */
     uint32_t min_depth;           /* >= 1; the documented default is 3                                                     */
@@ -680,6 +680,74 @@ int bella_hip_graph_polish_unitigs(bella_ctx* ctx, const bella_polish_params* pa
  * them in place of pos / nbases / len / base_offsets / bases. */
 int bella_hip_graph_get_polished(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases, uint64_t* ppos, uint32_t* pnbases, bella_polish_unitig* per_unitig);
 int bella_hip_graph_get_polish_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+
+/* ---- realignment: every read aligned against its polished unitig, a second consensus (no counterpart in the
+ * reference) -----------------------------------------------------------------------------------------------------------------------
+ * One ROUND takes the newest sequence of every unitig (the polish's, or the round before's), aligns the backbone reads and the contained
+ * reads against it base by base, piles their votes up in a nine-counter table indexed by unitig position and applies
+ * bella_hip_consensus's rule to every unitig as if it were one read.  Section 18 states the placement, the semi-global banded DP (read
+ * global, unitig window free; the trace's scoring and direction choice), the band rule and the votes in full; the tests hold a numpy
+ * statement of it, and the device result equals it.  Limits: one inserted base per junction, plain majority, a fixed
+ * centre diagonal per read, reads across the origin of a circular unitig are skipped, removed reads do not vote, the links keep their raw
+ * overlaps, a unitig has fewer than 2^31 - band_max bases. */
+#define BELLA_REALIGN_DEFAULT_BAND 512
+#define BELLA_REALIGN_DEFAULT_BAND_MAX 4096
+#define BELLA_REALIGN_DEFAULT_MIN_IDENTITY 700
+enum {
+    BELLA_REALIGN_NONE = 0,          /* the read takes no part: removed, uncovered, or not loaded on a unitig                 */
+    BELLA_REALIGN_VOTED = 1,
+    BELLA_REALIGN_UNPLACED = 2,      /* contained, and no record joins it to a backbone read                                  */
+    BELLA_REALIGN_OUTSIDE = 3,       /* its window leaves the unitig by more than band0 / 2                                   */
+    BELLA_REALIGN_BAND_CAPPED = 4,   /* the path still touched the band's edge at band_max                                    */
+    BELLA_REALIGN_LOW_IDENTITY = 5
+};
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_realign_params) of the caller's header (the struct may grow)              */
+    uint32_t band0;               /* a power of two in [256, band_max]; the documented default is 512                      */
+    uint32_t band_max;            /* a power of two <= 262144; 4096                                                        */
+    uint32_t min_identity;        /* permille of '=' among the alignment's columns below which a read does not vote; 700   */
+    uint32_t min_depth;           /* >= 1; 3                                                                               */
+    uint32_t keep_ops;            /* tests: != 0 keeps the voters' runs for bella_hip_graph_get_realign_ops                */
+} bella_realign_params;
+typedef struct {
+    uint32_t unitig;              /* ~0: status NONE or UNPLACED                                                           */
+    uint32_t orient;              /* 1: the read lies on the unitig reverse-complemented                                   */
+    int64_t s, e;                 /* the window expected for the read's clip on the current sequence                       */
+    uint32_t anchor;              /* contained reads: the record that placed it; ~0 otherwise                              */
+    uint32_t status;              /* BELLA_REALIGN_*                                                                       */
+    uint32_t band;                /* the last band the read was aligned with (0: never aligned)                            */
+    uint32_t n_eq, n_x, n_ins, n_del;
+    int32_t score;
+    int64_t q_begin, q_end;       /* the unitig junctions the alignment spans                                              */
+    uint64_t op_off;              /* keep_ops: first run among the kept runs                                               */
+    uint32_t nops, pad;
+} bella_realign_placement;
+/* What the last round did.  A sized struct: bella_hip_graph_get_realign_stats writes at most struct_size bytes. */
+typedef struct {
+    uint32_t round;               /* 1 = the first realignment (the second consensus round)                                */
+    uint32_t batches;             /* DP launches' batches                                                                  */
+    uint64_t backbone, contained; /* reads that were placed as a unitig's vertex / through an anchor record                */
+    uint64_t unplaced, outside, band_capped, low_identity, voted;
+    uint64_t repeated;            /* reads on more than one vertex: the first vertex counts                                */
+    uint64_t dp_cells;            /* rows x band summed over every DP that ran                                             */
+    uint64_t dir_bytes_peak;      /* the largest batch's direction bytes                                                   */
+    uint64_t votes;
+    uint64_t bases_before, bases_after;
+    uint64_t substituted, deleted, inserted;
+    double place_ms, dp_ms, walk_ms, vote_ms, decide_ms;      /* device time between events                               */
+} bella_realign_stats;
+/* One round on the device.  params == NULL: the defaults.  BELLA_ERR_STATE without a polish; BELLA_ERR_BAD_ARG for a band that is no
+ * power of two or out of range, min_depth < 1, min_identity > 1000, a struct_size too small; BELLA_ERR_NOMEM when the table (36 bytes per
+ * unitig base) does not fit.  The result replaces the last round's and goes with the polish.  Zero unitigs launch nothing. */
+int bella_hip_graph_realign_unitigs(bella_ctx* ctx, const bella_realign_params* params, uint64_t* total_bases);
+/* As bella_hip_graph_get_polished: pos / nbases are where the polish's segments begin in the new sequence.  Any pointer may be NULL. */
+int bella_hip_graph_get_realigned(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases, uint64_t* pos, uint32_t* nbases, bella_polish_unitig* per_unitig);
+/* out[nreads] */
+int bella_hip_graph_get_realign_placements(bella_ctx* ctx, bella_realign_placement* out);
+/* tests: *nops = the kept runs; ops (nullable) receives them, table (nullable) the round's counters (9 uint32 per base of the sequence the
+ * round aligned against).  Both are empty unless the round ran with keep_ops. */
+int bella_hip_graph_get_realign_ops(bella_ctx* ctx, uint64_t* nops, uint32_t* ops, uint32_t* table);
+int bella_hip_graph_get_realign_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 
 /* ---- coverage trimming: clip every read to its longest well-covered stretch before the graph (no counterpart in
  * the reference; the stage is miniasm's ma_hit_sub / ma_hit_cut) ---------------------------------------------------------------------

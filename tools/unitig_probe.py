@@ -11,7 +11,9 @@ with the stage next to those without it.  Last, the unitig consensus (DESIGN.md 
 launch each), the table bytes the decision read over its time, and the unitigs' total length raw and polished against the genome span.
 --cut-weak: one more pass per repeat -- build, clean, pop, then the command line's weak-overlap schedule (cuts at 500,
 600 and 700 permille, tips and bubbles again after a cut that took an edge), unitigs -- and per set the edges cut, forks and weak edges per
-step, cut_ms per step next to clean_ms and pop_ms of the same run, and unitigs, largest and N50 with the schedule next to those without."""
+step, cut_ms per step next to clean_ms and pop_ms of the same run, and unitigs, largest and N50 with the schedule next to those without.
+--polish-rounds N: N - 1 realignment rounds after the polish, and per round the reads by status, place_ms, dp_ms,
+walk_ms, vote_ms and decide_ms next to the first trace's dp_ms of the same set, the DP cells, the batches and the length after the round."""
 import argparse
 import json
 import os
@@ -51,7 +53,17 @@ def weak_pass(eng):
                 unitigs=int(us["unitigs"]), largest=int(us["largest"]), n50=int(us["n50"]), total_bases=int(us["total_bases"]))
 
 
-def probe(nreads, seed, repeats, fast, cut_weak=False):
+def realign_rounds(eng, rounds):
+    """rounds - 1 realignment rounds on the polish the context holds: -> one dict per round"""
+    out = []
+    for _ in range(max(0, rounds - 1)):
+        eng.graph_realign_unitigs()
+        st = eng.realign_stats()
+        out.append({k: (float(v) if k.endswith("_ms") else int(v)) for k, v in st.items()})
+    return out
+
+
+def probe(nreads, seed, repeats, fast, cut_weak=False, polish_rounds=1):
     rs = (synth.make_reads_fast if fast else synth.make_reads)(nreads, read_len=10000, err=0.15, seed=seed)
     meta = [[int(x) for x in n.split("_")[1:]] for n in rs.names]     # (start, length, strand)
     span = max(m[0] + m[1] for m in meta) - min(m[0] for m in meta)
@@ -65,6 +77,7 @@ def probe(nreads, seed, repeats, fast, cut_weak=False):
     eng.align_pairs(pars)
     eng.pileup_reset()
     eng.trace_pairs(pars, pileup=True, keep_ops=False)
+    trace_dp_ms = eng.trace_stats().dp_ms
     eng.graph_reset()
     eng.graph_add_traced()
     runs = []
@@ -80,7 +93,9 @@ def probe(nreads, seed, repeats, fast, cut_weak=False):
         bs = eng.bubble_stats()
         eng.graph_unitigs()
         eng.graph_polish_unitigs()
-        runs.append((gs, us, bs, eng.unitig_stats(), eng.polish_stats(), weak_pass(eng) if cut_weak else None))
+        pst = eng.polish_stats()
+        rea = realign_rounds(eng, polish_rounds)
+        runs.append((gs, us, bs, eng.unitig_stats(), pst, weak_pass(eng) if cut_weak else None, rea))
     gs, us = min(runs, key=lambda r: r[1]["rank_ms"] + r[1]["gather_ms"])[:2]
     bs, ps = min(runs, key=lambda r: r[2]["pop_ms"])[2:4]
     pol = min((r[4] for r in runs), key=lambda q: q["decide_ms"] + q["write_ms"])
@@ -105,6 +120,8 @@ def probe(nreads, seed, repeats, fast, cut_weak=False):
                          write_gb_per_s=(pol["bases_before"] + pol["bases_after"]) / max(1e-9, pol["write_ms"] * 1e6))
     if cut_weak:                                                      # (the unitigs "without" are the pop pass's: clean and pop, no schedule)
         out["weak"] = dict(min((r[5] for r in runs), key=lambda w: w["cut_ms"]), unitigs_without=int(ps["unitigs"]), largest_without=int(ps["largest"]), n50_without=int(ps["n50"]))
+    if polish_rounds > 1:                                             # (the run whose first round's DP was the fastest)
+        out["realign"] = dict(rounds=min((r[6] for r in runs), key=lambda q: q[0]["dp_ms"]), trace_dp_ms=trace_dp_ms, genome_span=int(span))
     eng.close()
     return out
 
@@ -115,11 +132,12 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "unitig_probe.json"))
     ap.add_argument("--cut-weak", action="store_true", help="also run the weak-overlap schedule after the clean and the pop (DESIGN.md section 17)")
+    ap.add_argument("--polish-rounds", type=int, default=1, help="consensus rounds: N - 1 realignment rounds after the polish (DESIGN.md section 18)")
     a = ap.parse_args()
     res = []
     for s in a.sets:
         n, seed, gen = s.split(":")
-        res.append(probe(int(n), int(seed), a.repeats, gen == "fast", a.cut_weak))
+        res.append(probe(int(n), int(seed), a.repeats, gen == "fast", a.cut_weak, a.polish_rounds))
         print(json.dumps(res[-1]), flush=True)
     with open(a.out, "w") as f:
         json.dump(dict(sets=res), f, indent=1)

@@ -261,6 +261,8 @@ SIGNATURES = [
     ("bella_hip_graph_get_polished", C.c_int, [vp, vp, vp, vp, vp, vp]),
     ("bella_hip_graph_get_polish_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_graph_realign_unitigs", C.c_int, [vp, C.POINTER(RealignParams), C.POINTER(C.c_uint64)]),
+    ("bella_hip_graph_realign_unitigs_circular", C.c_int, [vp, C.POINTER(RealignParams), C.POINTER(C.c_uint64)]),
+    ("bella_hip_graph_get_realign_wrapped", C.c_int, [vp, C.POINTER(C.c_uint64)]),
     ("bella_hip_graph_get_realigned", C.c_int, [vp, vp, vp, vp, vp, vp]),
     ("bella_hip_graph_get_realign_placements", C.c_int, [vp, vp]),
     ("bella_hip_graph_get_realign_ops", C.c_int, [vp, C.POINTER(C.c_uint64), vp, vp]),

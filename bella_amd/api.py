@@ -541,12 +541,14 @@ class Engine:
     # ---- realignment ----
     REALIGN_DEFAULTS = dict(band0=512, band_max=4096, min_identity=700, min_depth=3, keep_ops=0)
 
-    def graph_realign_unitigs(self, **params) -> dict:
+    def graph_realign_unitigs(self, circular: bool = False, **params) -> dict:
         """one realignment round against the newest sequence of the unitigs (the polish's, or the last round's), on the device: the
-        result in the shape of graph_polish_unitigs -- pos / nbases are where the polish's segments begin in the new sequence"""
+        result in the shape of graph_polish_unitigs -- pos / nbases are where the polish's segments begin in the new sequence.
+        circular=True: the reads of circular unitigs are placed on the unrolled circle"""
         rp = RealignParams(C.sizeof(RealignParams), *(_over(self.REALIGN_DEFAULTS, params, "graph_realign_unitigs")[k] for k in ("band0", "band_max", "min_identity", "min_depth", "keep_ops")))
         tot = C.c_uint64(0)
-        self._chk(self.lib.bella_hip_graph_realign_unitigs(self.h, C.byref(rp), C.byref(tot)))
+        run = self.lib.bella_hip_graph_realign_unitigs_circular if circular else self.lib.bella_hip_graph_realign_unitigs
+        self._chk(run(self.h, C.byref(rp), C.byref(tot)))
         return self.realigned()
 
     def realigned(self) -> dict:
@@ -572,7 +574,12 @@ class Engine:
         return ops, table
 
     def realign_stats(self) -> dict:
-        return self._stats(self.lib.bella_hip_graph_get_realign_stats, RealignStats)
+        """bella_realign_stats as a dict, plus `wrapped` (its own getter: the voters that reach across an origin)"""
+        st = self._stats(self.lib.bella_hip_graph_get_realign_stats, RealignStats)
+        w = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_graph_get_realign_wrapped(self.h, C.byref(w)))
+        st["wrapped"] = w.value
+        return st
 
     # ---- coverage trimming (DESIGN.md section 15) ----
     TRIM_DEFAULTS = dict(min_depth=3, end_clip=500, min_span=1000)

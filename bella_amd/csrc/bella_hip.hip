@@ -179,6 +179,7 @@ struct StageState {
         std::vector<bella_realign_placement> placements;
         std::vector<uint32_t> ops, table;    // kept for the tests only (keep_ops)
         bella_realign_stats stats{};
+        uint64_t wrapped = 0;                // voters that reach across an origin (section 19); apart from the stats, whose struct keeps its size
     } realign;
     // READS .. BATCH_OPS, PILE and CONS (pileup.hpp; section 10) are members of the context: only their bits are here
 };
@@ -5006,8 +5007,9 @@ int bella_hip_graph_get_polish_stats(bella_ctx* c, void* out, uint64_t struct_si
     return get_stats(c, POLISH, out, struct_size, [](const StageState& a) { return a.polish.stats; });
 }
 
-// ---- realignment (realign.hpp) ------------------------------------------------------------------------------------
-int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* params, uint64_t* total_bases) {
+// ---- realignment (realign.hpp; DESIGN.md sections 18 and 19) -----------------------------------------------------------------------------
+// unroll: the round places the reads of circular unitigs on the unrolled circle (section 19)
+static int realign_round(bella_ctx* c, const bella_realign_params* params, uint64_t* total_bases, bool unroll) {
     if (!c) return BELLA_ERR_BAD_ARG;
     bella_realign_params rp{};
     rp.band0 = BELLA_REALIGN_DEFAULT_BAND; rp.band_max = BELLA_REALIGN_DEFAULT_BAND_MAX; rp.min_identity = BELLA_REALIGN_DEFAULT_MIN_IDENTITY; rp.min_depth = 3;
@@ -5048,7 +5050,23 @@ int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* pa
             for (uint64_t i = u.voff[j]; i < u.voff[j + 1]; ++i) slot[(size_t)i] = j;
         const size_t nrec = c->as.records.size();
         const size_t npw = (size_t)(total / 16 + 1);
-        TmpBuf recs, verts, slot_utg, pos, nb, dcpos, dcnb, uvoff, uboff, dcoffs, cont, rem, bvert, key, place, ascii, upk, table, votes;
+        // the pack the DP reads: the unitigs as they are, or (section 19) every circular unitig of fewer than 2^29 bases twice in a row
+        std::vector<uint64_t> poffs(coffs.begin(), coffs.begin() + nutg + 1);
+        bool any_unrolled = false;
+        if (unroll) {
+            uint64_t at = 0;
+            for (uint32_t j = 0; j < nutg; ++j) {
+                const uint64_t plen = coffs[j + 1] - coffs[j];
+                const bool twice = u.circ[j] && plen && plen < kReaMaxUnrolled;
+                poffs[j] = at;
+                at += twice ? 2 * plen : plen;
+                any_unrolled |= twice;
+            }
+            poffs[nutg] = at;
+        }
+        const uint64_t ptotal = poffs[nutg];
+        const size_t nppw = (size_t)(ptotal / 16 + 1);
+        TmpBuf recs, verts, slot_utg, pos, nb, dcpos, dcnb, uvoff, uboff, dcoffs, cont, rem, bvert, key, place, ascii, upk, table, votes, dcirc, dpoffs, upk2;
         int rc = upload_records(c, recs);
         if (rc) return rc;
         ENSURE(c, verts, 4 * (size_t)nseg); ENSURE(c, slot_utg, 4 * (size_t)nseg); ENSURE(c, nb, 4 * (size_t)nseg); ENSURE(c, dcnb, 4 * (size_t)nseg);
@@ -5059,6 +5077,8 @@ int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* pa
         ENSURE(c, place, sizeof(bella_realign_placement) * (size_t)nr);
         ENSURE(c, ascii, (size_t)total); ENSURE(c, upk, 4 * npw);
         ENSURE(c, votes, 8);
+        ENSURE(c, dcirc, nutg);
+        if (any_unrolled) { ENSURE(c, dpoffs, 8 * ((size_t)nutg + 1)); ENSURE(c, upk2, 4 * nppw); }
         const size_t tbytes = (size_t)total * kPileCounters * 4;
         if (ensure_bytes(c, table, tbytes))
             return fail(c, BELLA_ERR_NOMEM, "the realignment table needs %zu bytes of device memory (36 per base of %llu unitig bases) and they do not fit", tbytes,
@@ -5074,6 +5094,8 @@ int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* pa
         HIPCHK(c, c->stager.h2d(dcoffs.p, coffs.data(), 8 * ((size_t)nutg + 1), c->stream));
         HIPCHK(c, c->stager.h2d(cont.p, g.contained.data(), nr, c->stream));
         HIPCHK(c, c->stager.h2d(rem.p, g.removed.data(), nr, c->stream));
+        HIPCHK(c, c->stager.h2d(dcirc.p, u.circ.data(), nutg, c->stream));
+        if (any_unrolled) HIPCHK(c, c->stager.h2d(dpoffs.p, poffs.data(), 8 * ((size_t)nutg + 1), c->stream));
         if (total) HIPCHK(c, c->stager.h2d(ascii.p, cbases.data(), (size_t)total, c->stream));
         HIPCHK(c, hipMemsetAsync(bvert.p, 0xFF, 4 * (size_t)nr, c->stream));
         HIPCHK(c, hipMemsetAsync(key.p, 0, 8 * (size_t)nr, c->stream));
@@ -5084,7 +5106,8 @@ int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* pa
         EventSet ev;
         if ((rc = ev.create(c, 3))) return rc;
         const uint32_t* const rpacked = ptr<uint32_t>(c->packed);
-        const uint32_t* const upacked = ptr<uint32_t>(upk);
+        const uint32_t* const cpacked = ptr<uint32_t>(upk);             // the consensus reads the unitigs as they are
+        const uint32_t* const upacked = any_unrolled ? ptr<uint32_t>(upk2) : cpacked;
         // ---- placement
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
         k_rea_backbone<<<nblk(nseg), 256, 0, c->stream>>>(ptr<uint32_t>(verts), nseg, ptr<uint32_t>(bvert));
@@ -5097,10 +5120,14 @@ int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* pa
         k_rea_place<<<nblk(nr), 256, 0, c->stream>>>(nr, ptr<uint64_t>(c->roff), spans.beg, spans.end, ptr<uint32_t>(bvert), ptr<unsigned long long>(key), ptr<bella_overlap>(recs),
                                                      ptr<uint8_t>(cont), ptr<uint8_t>(rem), ptr<uint32_t>(verts), ptr<uint32_t>(slot_utg), ptr<uint64_t>(pos), ptr<uint32_t>(nb),
                                                      ptr<uint64_t>(dcpos), ptr<uint32_t>(dcnb), ptr<uint64_t>(uvoff), ptr<uint64_t>(uboff), ptr<uint64_t>(dcoffs), rp.band0,
-                                                     ptr<bella_realign_placement>(place));
+                                                     ptr<uint8_t>(dcirc), rp.band_max, unroll ? 1u : 0u, ptr<bella_realign_placement>(place));
         KCHK(c);
         if (total) {
             k_rea_pack<<<nblk(npw), 256, 0, c->stream>>>(ptr<uint8_t>(ascii), total, ptr<uint32_t>(upk));
+            KCHK(c);
+        }
+        if (any_unrolled) {
+            k_rea_pack_unrolled<<<nblk(nppw), 256, 0, c->stream>>>(ptr<uint8_t>(ascii), ptr<uint64_t>(dcoffs), ptr<uint64_t>(dpoffs), nutg, ptotal, ptr<uint32_t>(upk2));
             KCHK(c);
         }
         HIPCHK(c, hipEventRecord(ev.b, c->stream));
@@ -5145,10 +5172,11 @@ int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* pa
                     const uint64_t n = end - beg, need_bytes = n * (B / 4);
                     if (!hj.empty() && (dbytes + need_bytes > budget || hj.size() >= (1u << 20))) break;
                     ReaJob j{};
-                    j.gH = (int64_t)coffs[P.unitig];
+                    const int32_t plen = (int32_t)(coffs[P.unitig + 1] - coffs[P.unitig]);
+                    j.gH = (int64_t)poffs[P.unitig]; j.gT = (int64_t)coffs[P.unitig];
                     j.gV = (int64_t)(hroff[r] + (P.orient ? end - 1 : beg));
                     j.dir_off = dbytes; j.scr_off = sints; j.op_off = ~0ull;
-                    j.n = (uint32_t)n; j.m = (int32_t)(coffs[P.unitig + 1] - coffs[P.unitig]);
+                    j.n = (uint32_t)n; j.m = P.pad ? 2 * plen : plen; j.mt = P.pad ? plen : j.m;       // (pad: placed on the unrolled circle)
                     const int64_t slack = (P.e - P.s) - (int64_t)n;
                     j.c = (int32_t)(P.s + (slack >= 0 ? slack / 2 : -((-slack + 1) / 2)));      // floor
                     j.band = B; j.dV = P.orient ? -1 : 1; j.comp = P.orient ? 3u : 0u;
@@ -5198,6 +5226,7 @@ int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* pa
                         P.status = BELLA_REALIGN_LOW_IDENTITY; ++st.low_identity;
                     } else {
                         P.status = BELLA_REALIGN_VOTED; ++st.voted;
+                        if (P.pad && (P.e > hj[x].mt || P.q_end > hj[x].mt)) ++out.wrapped;
                         hj[x].op_off = nops;
                         P.nops = k.nops;
                         if (rp.keep_ops) P.op_off = out.ops.size() + nops;
@@ -5244,7 +5273,7 @@ int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* pa
         HIPCHK(c, hipMemsetAsync(ptr<uint8_t>(emit) + total, 0, 1, c->stream));
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
         if (total) {
-            k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(table), upacked, ptr<uint64_t>(dcoffs), nutg, total, rp.min_depth, ptr<uint8_t>(emit),
+            k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(table), cpacked, ptr<uint64_t>(dcoffs), nutg, total, rp.min_depth, ptr<uint8_t>(emit),
                                                               ptr<bella_consensus_read>(cstats));
             KCHK(c);
         }
@@ -5293,6 +5322,10 @@ int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* pa
     return 0;
 }
 
+int bella_hip_graph_realign_unitigs(bella_ctx* c, const bella_realign_params* params, uint64_t* total_bases) { return realign_round(c, params, total_bases, false); }
+
+int bella_hip_graph_realign_unitigs_circular(bella_ctx* c, const bella_realign_params* params, uint64_t* total_bases) { return realign_round(c, params, total_bases, true); }
+
 int bella_hip_graph_get_realigned(bella_ctx* c, uint64_t* offsets, uint8_t* bases, uint64_t* pos, uint32_t* nbases, bella_polish_unitig* per_unitig) {
     if (!c) return BELLA_ERR_BAD_ARG;
     if (int r = need(c, REALIGN)) return r;
@@ -5318,6 +5351,13 @@ int bella_hip_graph_get_realign_ops(bella_ctx* c, uint64_t* nops, uint32_t* ops,
     if (nops) *nops = c->as.realign.ops.size();
     copy_out(ops, c->as.realign.ops);
     copy_out(table, c->as.realign.table);
+    return 0;
+}
+
+int bella_hip_graph_get_realign_wrapped(bella_ctx* c, uint64_t* wrapped) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, REALIGN)) return r;
+    if (wrapped) *wrapped = c->as.realign.wrapped;
     return 0;
 }
 

@@ -21,6 +21,12 @@
 // or last diagonal, q_begin), and once the host has laid the runs out a writing walk, backwards from the read's last run.
 // Votes.  One wavefront per read over its runs, pileup.hpp's mapping (64 runs per chunk, their columns dealt to the lanes): a column of
 // '=' / 'X' votes the read's base at q, 'D' votes del at q, a run of 'I' one ins vote with its first base in the junction before q.
+//
+// Circles (opt-in).  k_rea_place may put a read of a circular unitig on the UNROLLED circle: the window's start
+// taken modulo the raw length, the window moved on by plen when it begins in the first band_max / 2 bases, so no band leaves
+// [0, 2 plen].  k_rea_pack_unrolled writes such a unitig's bases twice in a row; a ReaJob names the pack offset (gH), the table's row
+// base (gT) and the modulus (mt) apart; the DP and the walks see a target of m = 2 plen columns, and k_rea_vote folds a column j >= mt
+// back by one subtraction.  With the switch off none of this runs: gH = gT, mt = m.
 #pragma once
 #include <stdint.h>
 #if defined(__HIPCC__)
@@ -34,10 +40,11 @@ namespace bella {
 
 constexpr uint32_t kReaNone = 0xFFFFFFFFu;
 constexpr uint64_t kReaMaxUnitig = 1ull << 30;       // bases of one unitig: column indices stay far inside an int
+constexpr uint64_t kReaMaxUnrolled = 1ull << 29;     // ... of one that is aligned against twice in a row (section 19)
 
 // one read of a DP batch, filled by the host from the read's placement
 struct ReaJob {
-    int64_t gH;            // first base of the unitig among all unitig bases (2-bit pack and table row)
+    int64_t gH;            // first base of the unitig in the 2-bit pack (the unrolled layout when the round unrolls circles: section 19)
     int64_t gV;            // base of the packed reads that is row 1
     uint64_t dir_off;      // bytes into the direction buffer: rows 1 .. n, B / 4 bytes each
     uint64_t scr_off;      // wide kernel: ints into the scratch (2 B per read)
@@ -48,6 +55,8 @@ struct ReaJob {
     uint32_t band;
     int32_t dV;            // +1, or -1 for orientation 1
     uint32_t comp;         // 3 for orientation 1
+    int32_t mt;            // rows of the unitig in the table: a vote at column j >= mt goes to row j - mt (m: never; plen on the unrolled circle)
+    int64_t gT;            // first row of the unitig in the table
 };
 struct ReaRes { int32_t score; int32_t q_end; };
 struct ReaCnt { uint32_t nops, n_eq, n_x, n_ins, n_del, touch; int32_t q_begin; uint32_t pad; };
@@ -87,7 +96,7 @@ __global__ void k_rea_anchor(const bella_overlap* recs, uint32_t nrec, const uin
 __global__ void k_rea_place(uint32_t nreads, const uint64_t* roff, const uint64_t* rbeg, const uint64_t* rend, const uint32_t* bvert, const unsigned long long* key,
                             const bella_overlap* recs, const uint8_t* contained, const uint8_t* removed, const uint32_t* verts, const uint32_t* slot_utg,
                             const uint64_t* pos, const uint32_t* nb, const uint64_t* cpos, const uint32_t* cnb, const uint64_t* uvoff, const uint64_t* uoff,
-                            const uint64_t* coffs, uint32_t band0, bella_realign_placement* out) {
+                            const uint64_t* coffs, uint32_t band0, const uint8_t* circular, uint32_t band_max, uint32_t unroll, bella_realign_placement* out) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nreads) return;
     bella_realign_placement P{};
@@ -126,10 +135,29 @@ __global__ void k_rea_place(uint32_t nreads, const uint64_t* roff, const uint64_
         const uint64_t lo = uvoff[u], hi = uvoff[u + 1];
         const int64_t len = (int64_t)(uoff[u + 1] - uoff[u]), plen = (int64_t)(coffs[u + 1] - coffs[u]);
         P.unitig = u; P.orient = o;
-        P.s = rea_map(x, pos, nb, cpos, cnb, lo, hi, len, plen);
-        P.e = rea_map(x + n, pos, nb, cpos, cnb, lo, hi, len, plen);
-        const int64_t h = (int64_t)(band0 / 2);
-        P.status = (P.s < -h || P.e > plen + h || P.e < P.s) ? BELLA_REALIGN_OUTSIDE : BELLA_REALIGN_VOTED;       // (VOTED: a candidate until the DP has spoken)
+        bool unrolled = false;
+        if (unroll && circular[u] && len > 0 && (uint64_t)plen < kReaMaxUnrolled) {      // section 19: on the unrolled circle, if the read cannot lap itself
+            int64_t xm = x % len;
+            if (xm < 0) xm += len;
+            const int64_t ym = xm + n, bm = (int64_t)band_max;
+            if (ym - len < len) {
+                const int64_t s0 = rea_map(xm, pos, nb, cpos, cnb, lo, hi, len, plen);
+                const int64_t e0 = ym < len ? rea_map(ym, pos, nb, cpos, cnb, lo, hi, len, plen) : plen + rea_map(ym - len, pos, nb, cpos, cnb, lo, hi, len, plen);
+                const int64_t w = e0 - s0;
+                if (w >= 0 && (n > w ? n : w) + bm <= plen) {
+                    P.s = s0 < bm / 2 ? s0 + plen : s0;
+                    P.e = P.s + w;
+                    P.status = BELLA_REALIGN_VOTED; P.pad = 1;
+                    unrolled = true;
+                }
+            }
+        }
+        if (!unrolled) {
+            P.s = rea_map(x, pos, nb, cpos, cnb, lo, hi, len, plen);
+            P.e = rea_map(x + n, pos, nb, cpos, cnb, lo, hi, len, plen);
+            const int64_t h = (int64_t)(band0 / 2);
+            P.status = (P.s < -h || P.e > plen + h || P.e < P.s) ? BELLA_REALIGN_OUTSIDE : BELLA_REALIGN_VOTED;   // (VOTED: a candidate until the DP has spoken)
+        }
     }
     out[r] = P;
 }
@@ -141,6 +169,29 @@ __global__ void k_rea_pack(const uint8_t* ascii, uint64_t total, uint32_t* packe
     uint32_t v = 0;
     for (uint32_t k = 0; k < 16 && w * 16 + k < total; ++k) {
         const uint8_t ch = ascii[w * 16 + k];
+        v |= (ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 0u) << (2 * k);
+    }
+    packed[w] = v;
+}
+
+// The unrolled layout (section 19): unitig u's bases start at poffs[u] and, where poffs[u + 1] - poffs[u] is twice its length, stand
+// there twice in a row.  One thread per word of 16 bases; a word that straddles a seam or a unitig's end gathers from two places.
+__global__ void k_rea_pack_unrolled(const uint8_t* ascii, const uint64_t* coffs, const uint64_t* poffs, uint32_t nutg, uint64_t ptotal, uint32_t* packed) {
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w * 16 >= ptotal) return;
+    uint32_t a = 0, b = nutg;                                         // the unitig of the word's first base: the last u with poffs[u] <= g
+    while (b - a > 1) {
+        const uint32_t mid = a + (b - a) / 2;
+        if (poffs[mid] <= w * 16) a = mid; else b = mid;
+    }
+    uint32_t u = a;
+    uint64_t pb = poffs[u], pe = poffs[u + 1], cb = coffs[u], plen = coffs[u + 1] - cb;
+    uint32_t v = 0;
+    for (uint32_t k = 0; k < 16 && w * 16 + k < ptotal; ++k) {
+        const uint64_t g = w * 16 + k;
+        while (g >= pe) { ++u; pb = pe; pe = poffs[u + 1]; cb = coffs[u]; plen = coffs[u + 1] - cb; }       // (g < ptotal = poffs[nutg]: u stays below nutg)
+        const uint64_t j = g - pb;
+        const uint8_t ch = ascii[cb + (j >= plen ? j - plen : j)];
         v |= (ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 0u) << (2 * k);
     }
     packed[w] = v;
@@ -298,7 +349,8 @@ __global__ void k_rea_write(const ReaJob* jobs, const ReaRes* res, const ReaCnt*
     bw.flush();
 }
 
-// one wavefront per read; table: nine counters per base of all unitigs
+// one wavefront per read; table: nine counters per base of all unitigs.  A column j of the unrolled circle (m = 2 mt) votes in row
+// j - mt once it is past the seam: one compare and one subtraction per vote.
 __global__ __launch_bounds__(kPileBlock) void k_rea_vote(const ReaJob* jobs, const ReaCnt* cnt, uint32_t njobs, const uint32_t* ops, const uint32_t* rpacked, uint32_t* table,
                                                          unsigned long long* votes) {
     const uint32_t x = (uint32_t)(((uint64_t)blockIdx.x * kPileBlock + threadIdx.x) >> 6);
@@ -306,7 +358,7 @@ __global__ __launch_bounds__(kPileBlock) void k_rea_vote(const ReaJob* jobs, con
     const int lane = (int)(threadIdx.x & 63);
     const ReaJob e = jobs[x];
     if (e.op_off == ~0ull) return;
-    const uint32_t nops = cnt[x].nops, m = (uint32_t)e.m;
+    const uint32_t nops = cnt[x].nops, m = (uint32_t)e.m, mt = (uint32_t)e.mt;
     const uint32_t* const po = ops + e.op_off;
     uint32_t ci = 0, cj = (uint32_t)cnt[x].q_begin;                   // where the chunk's first run starts: row (0-based base of the read), column
     uint32_t nv = 0;
@@ -333,16 +385,16 @@ __global__ __launch_bounds__(kPileBlock) void k_rea_vote(const ReaJob* jobs, con
             const uint32_t i = ri + (rop != kOpDel ? o : 0u), j = rj + (rop != kOpIns ? o : 0u);
             if (rop <= kOpX) {
                 if (i < e.n && j < m) {
-                    atomicAdd(table + ((uint64_t)e.gH + j) * kPileCounters + (uint32_t)trace_base(rpacked, e.gV, e.dV, e.comp, i), 1u);
+                    atomicAdd(table + ((uint64_t)e.gT + (j >= mt ? j - mt : j)) * kPileCounters + (uint32_t)trace_base(rpacked, e.gV, e.dV, e.comp, i), 1u);
                     ++nv;
                 }
             } else if (rop == kOpIns) {                               // bases of the read only: one vote for the run, in the junction before rj
                 if (o == 0 && ri < e.n && rj < m) {
-                    atomicAdd(table + ((uint64_t)e.gH + rj) * kPileCounters + kPileIns + (uint32_t)trace_base(rpacked, e.gV, e.dV, e.comp, ri), 1u);
+                    atomicAdd(table + ((uint64_t)e.gT + (rj >= mt ? rj - mt : rj)) * kPileCounters + kPileIns + (uint32_t)trace_base(rpacked, e.gV, e.dV, e.comp, ri), 1u);
                     ++nv;
                 }
             } else if (rop == kOpDel) {                               // a base of the unitig only
-                if (j < m) { atomicAdd(table + ((uint64_t)e.gH + j) * kPileCounters + kPileDel, 1u); ++nv; }
+                if (j < m) { atomicAdd(table + ((uint64_t)e.gT + (j >= mt ? j - mt : j)) * kPileCounters + kPileDel, 1u); ++nv; }
             }
         }
         ci += __shfl(ei, 63, 64);

@@ -124,6 +124,7 @@ struct StageOpts {
     uint32_t polish_min_depth = 3;   // polished sequences and coordinates
     uint32_t polish_rounds = 1;      // consensus rounds: polish_rounds - 1 realignment rounds follow the polish, each aligning the reads
     uint32_t realign_band = 512, realign_min_identity = 700;    // against the round before; the files carry the last round's sequences and coordinates
+    bool realign_circular = false;   // those rounds place the reads of circular unitigs on the unrolled circle
     int trim = 0;                    // coverage trimming: the reads are clipped to their longest well-covered stretch before the graph
     uint32_t trim_depth = 3, trim_end_clip = 500;     // is built (min_span = gfa_min_overlap); every graph file is in clipped coordinates
     const char* trimmed_reads = nullptr;              // the clipped reads as FASTA, in input order, without the uncovered ones
@@ -303,15 +304,19 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
             rp.struct_size = (uint32_t)sizeof(rp);
             rp.band0 = o.realign_band; rp.band_max = o.realign_band > BELLA_REALIGN_DEFAULT_BAND_MAX ? o.realign_band : BELLA_REALIGN_DEFAULT_BAND_MAX;
             rp.min_identity = o.realign_min_identity; rp.min_depth = o.polish_min_depth;
-            check(c0, bella_hip_graph_realign_unitigs(c0, &rp, &ptotal), "bella_hip_graph_realign_unitigs");
+            if (o.realign_circular) check(c0, bella_hip_graph_realign_unitigs_circular(c0, &rp, &ptotal), "bella_hip_graph_realign_unitigs_circular");
+            else check(c0, bella_hip_graph_realign_unitigs(c0, &rp, &ptotal), "bella_hip_graph_realign_unitigs");
             ubases.resize((size_t)ptotal + 1);
             check(c0, bella_hip_graph_get_realigned(c0, uboff.data(), ubases.data(), pos.data(), nb.data(), pu.data()), "bella_hip_graph_get_realigned");
             for (uint64_t u = 0; u < nu; ++u) ulen[(size_t)u] = pu[(size_t)u].len_after;
             bella_realign_stats rs{};
             check(c0, bella_hip_graph_get_realign_stats(c0, &rs, sizeof(rs)), "bella_hip_graph_get_realign_stats");
+            uint64_t wrapped = 0;
+            check(c0, bella_hip_graph_get_realign_wrapped(c0, &wrapped), "bella_hip_graph_get_realign_wrapped");
             const std::string Realigned = "round " + std::to_string(round) + ": " + std::to_string(rs.voted) + " of " + std::to_string(rs.backbone + rs.contained + rs.unplaced) +
                                       " reads realigned (" + std::to_string(rs.unplaced) + " unplaced, " + std::to_string(rs.outside) + " outside, " +
                                       std::to_string(rs.band_capped) + " band-capped, " + std::to_string(rs.low_identity) + " of low identity), " +
+                                      (o.realign_circular ? std::to_string(wrapped) + " across an origin, " : std::string()) +
                                       std::to_string(rs.bases_before) + " -> " + std::to_string(rs.bases_after) + " bases";
             BELLA_HIP_LOGT(o.tag, Realigned);
         }

@@ -22,6 +22,7 @@
 // --polish: unitig consensus: every stage's traced pairs vote as with --correct, the unitigs are polished from
 // the pileup on the device after the last stage; --unitigs / --unitigs-fasta then carry the polished sequences and coordinates.
 // --polish-rounds N: N - 1 realignment rounds follow, each aligning the reads against the unitigs of the round before.
+// --realign-circular: those rounds place the reads of a circular unitig on the unrolled circle, across its origin too.
 //
 // --trim: coverage trimming: after the last stage every read is clipped, on the device, to its longest stretch that
 // --trim-depth overlap records cover; the graph is built from the records cut to the clips, and --gfa / --unitigs / --unitigs-fasta are in
@@ -60,7 +61,7 @@ struct Options {
     int polish_min_depth = 3;
     bool polish = false, polish_param_given = false;
     int polish_rounds = 1, realign_band = 512, realign_min_identity = 700;
-    bool realign_param_given = false;
+    bool realign_param_given = false, realign_circular = false;
     int trim_depth = 3, trim_end_clip = 500;
     std::string trimmed_reads;
     bool trim = false, trim_param_given = false;
@@ -122,6 +123,7 @@ const char* kHelp =
     "                             unitigs of the round before, on the device, and takes the consensus of those alignments\n"
     "      --realign-band arg     with --polish: the first band of those alignments, a power of two from 256 to 4096 (default: 512)\n"
     "      --realign-min-identity arg  with --polish: permille of matches below which a read's alignment does not vote (default: 700)\n"
+    "      --realign-circular     with --polish: those alignments treat a circular unitig as a circle, so the reads across its origin vote too\n"
     "      --trim                 with --gfa / --unitigs / --unitigs-fasta: clip every read to its longest stretch that --trim-depth overlaps cover, on the\n"
     "                             device, before the graph is built (shortest stretch: --gfa-min-overlap); the graph files are in clipped coordinates\n"
     "      --trim-depth arg       with --trim: overlaps a position needs to count as covered (default: 3)\n"
@@ -152,6 +154,7 @@ Options parse(int argc, char** argv) {
         {"cut-weak", 0, 0, &o.cut_weak}, {"weak-min", 0, 1, &o.weak_min}, {"weak-max", 0, 1, &o.weak_max}, {"weak-steps", 0, 1, &o.weak_steps},
         {"polish", 0, 0, &o.polish}, {"polish-min-depth", 0, 1, &o.polish_min_depth},
         {"polish-rounds", 0, 1, &o.polish_rounds}, {"realign-band", 0, 1, &o.realign_band}, {"realign-min-identity", 0, 1, &o.realign_min_identity},
+        {"realign-circular", 0, 0, &o.realign_circular},
         {"trim", 0, 0, &o.trim}, {"trim-depth", 0, 1, &o.trim_depth}, {"trim-end-clip", 0, 1, &o.trim_end_clip}, {"trimmed-reads", 0, 3, &o.trimmed_reads},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
@@ -180,6 +183,7 @@ Options parse(int argc, char** argv) {
             if (val) die("option " + a + " takes no value");
             *(bool*)sp->dst = true;
             if (sp->dst == &o.gfa_no_seq) o.gfa_param_given = true;
+            if (sp->dst == &o.realign_circular) o.realign_param_given = true;
             continue;
         }
         if (!val) {
@@ -267,6 +271,7 @@ int main(int argc, char** argv) {
     if (o.polish && o.unitigs.empty() && o.unitigs_fasta.empty()) die("--polish needs --unitigs or --unitigs-fasta");
     if (o.polish && o.gfa_no_seq && o.unitigs_fasta.empty()) die("--polish with --gfa-no-seq needs --unitigs-fasta (there is no sequence to polish into)");
     if (o.polish && o.polish_min_depth < 1) die("--polish-min-depth must be at least 1");
+    if (o.realign_circular && !o.polish) die("--realign-circular needs --polish");
     if (o.realign_param_given && !o.polish) die("--polish-rounds, --realign-band and --realign-min-identity need --polish");
     if (o.polish_rounds < 1 || o.polish_rounds > 4) die("--polish-rounds must be in [1, 4]");
     if (o.realign_band < 256 || o.realign_band > 4096 || (o.realign_band & (o.realign_band - 1))) die("--realign-band must be a power of two in [256, 4096]");
@@ -429,7 +434,7 @@ int main(int argc, char** argv) {
     so.weak_min = (uint32_t)o.weak_min; so.weak_max = (uint32_t)o.weak_max; so.weak_steps = (uint32_t)o.weak_steps;
     so.polish = o.polish ? 1 : 0;
     so.polish_min_depth = (uint32_t)o.polish_min_depth;
-    so.polish_rounds = (uint32_t)o.polish_rounds; so.realign_band = (uint32_t)o.realign_band; so.realign_min_identity = (uint32_t)o.realign_min_identity;
+    so.polish_rounds = (uint32_t)o.polish_rounds; so.realign_band = (uint32_t)o.realign_band; so.realign_min_identity = (uint32_t)o.realign_min_identity; so.realign_circular = o.realign_circular;
     so.trim = o.trim ? 1 : 0;
     so.trim_depth = (uint32_t)o.trim_depth; so.trim_end_clip = (uint32_t)o.trim_end_clip;
     so.trimmed_reads = o.trimmed_reads.empty() ? nullptr : o.trimmed_reads.c_str();

@@ -33,7 +33,13 @@ that a path reaches counts as touched.  B starts at band0 and doubles while the 
 band_max is BAND_CAPPED.  A read with 1000 n_eq < min_identity (n_eq + n_x + n_ins + n_del) is LOW_IDENTITY.  The others vote:
 '=' / 'X' base[read base] at q, 'D' del at q, a run of 'I' one ins vote with its first base in the junction before q (q == plen: dropped).
 Consensus: pileup_mirror.consensus on every unitig, its own bases the sequence that was aligned against; the new pos of a vertex is
-the new offset of its old segment start."""
+the new offset of its old segment start.
+
+Circles (circular=True, off by default).  A read on a circular unitig is placed on the UNROLLED circle when
+place_unrolled admits it: xm = x mod len, s0 = P(xm), e0 = P(xm + n) or plen + P(xm + n - len), e0 >= s0 and max(n, e0 - s0) + band_max
+<= plen; s = s0, or s0 + plen when s0 < band_max / 2; status VOTED, pad = 1.  Such a read is aligned against its unitig twice in a row
+(2 plen columns), a vote at q goes to row q mod plen, and it is counted as `wrapped` when it votes with e > plen or q_end > plen.  Every
+other read is placed, aligned and counted as without the option."""
 from __future__ import annotations
 
 import numpy as np
@@ -169,31 +175,59 @@ def replay(ops, read: bytes, unitig: bytes, q_begin: int, q_end: int):
     return dict(n_eq=cnt[0], n_x=cnt[1], n_ins=cnt[2], n_del=cnt[3], score=cnt[0] - cnt[1] - cnt[2] - cnt[3])
 
 
-def vote(table, row0: int, plen: int, read: bytes, q_begin: int, op_list) -> int:
-    """adds one read's votes to table[row0 : row0 + plen]; returns how many"""
+def vote(table, row0: int, plen: int, read: bytes, q_begin: int, op_list, unrolled: bool = False) -> int:
+    """adds one read's votes to table[row0 : row0 + plen]; returns how many.  unrolled (section 19): the columns are those of the
+    unitig twice in a row, a vote at q goes to row q mod plen, and the read votes at most once per position."""
     rb = P.codes(read)
     i, q, nv, last = 0, int(q_begin), 0, -1
+    m = 2 * plen if unrolled else plen
+    row = (lambda x: row0 + (x - plen if x >= plen else x)) if unrolled else (lambda x: row0 + x)
+    seen = set()
     for op in op_list:
         if op <= 1:
-            table[row0 + q, rb[i]] += 1
+            table[row(q), rb[i]] += 1
+            seen.add(row(q))
             nv += 1
             i, q = i + 1, q + 1
         elif op == 2:
-            if last != 2 and q < plen:
-                table[row0 + q, P.INS + rb[i]] += 1
+            if last != 2 and q < m:
+                table[row(q), P.INS + rb[i]] += 1
                 nv += 1
             i += 1
         else:
-            table[row0 + q, P.DEL] += 1
+            table[row(q), P.DEL] += 1
+            seen.add(row(q))
             nv += 1
             q += 1
         last = op
+    assert not unrolled or (q - int(q_begin) <= plen and len(seen) == q - int(q_begin)), "a read on the unrolled circle voted twice for one position"
     return nv
 
 
-def place(u, cur, lens, recs, contained, removed, clips=None, band0=512):
+def place_unrolled(x: int, n: int, pos, nb, cpos, cnb, length: int, plen: int, band_max: int):
+    """Section 19's rule for one read on a circular unitig: (s, e) on the unrolled circle, or None when the read is not eligible.
+    x: the raw coordinate where the clip starts, n: the clip's length; the segment arrays are the unitig's."""
+    if plen >= 1 << 29 or length <= 0:
+        return None
+    xm = x % length                                                   # (Python's %: the floor modulo)
+    ym = xm + n
+    s0 = to_current(xm, pos, nb, cpos, cnb, length, plen)
+    if ym < length:
+        e0 = to_current(ym, pos, nb, cpos, cnb, length, plen)
+    elif ym - length < length:
+        e0 = plen + to_current(ym - length, pos, nb, cpos, cnb, length, plen)
+    else:
+        return None
+    if e0 < s0 or max(n, e0 - s0) + band_max > plen:
+        return None
+    s = s0 + plen if s0 < band_max // 2 else s0
+    return s, s + (e0 - s0)
+
+
+def place(u, cur, lens, recs, contained, removed, clips=None, band0=512, band_max=4096, circular=False):
     """The placements before any DP: records of PLACE_DT (status VOTED = a candidate) and the counts backbone, contained, unplaced,
-    outside, repeated.  clips: None or (beg, end) arrays."""
+    outside, repeated.  clips: None or (beg, end) arrays.  circular (section 19): a read on a circular unitig is placed on the unrolled
+    circle when place_unrolled admits it (its pad word is 1); every other read is placed as without the option."""
     nr = len(lens)
     lens = [int(x) for x in lens]
     beg = [0] * nr if clips is None else [int(x) for x in clips[0]]
@@ -239,6 +273,10 @@ def place(u, cur, lens, recs, contained, removed, clips=None, band0=512):
         x = x0 + lead(beg[r], end[r], L, o)
         a, z = voff[k], voff[k + 1]
         length, plen = int(u["len"][k]), int(coffs[k + 1] - coffs[k])
+        un = place_unrolled(x, n, pos[a:z], nb[a:z], cpos[a:z], cnb[a:z], length, plen, band_max) if circular and int(u["circular"][k]) else None
+        if un is not None:
+            out[r]["unitig"], out[r]["orient"], out[r]["s"], out[r]["e"], out[r]["status"], out[r]["pad"] = k, o, un[0], un[1], VOTED, 1
+            continue
         s_ = to_current(x, pos[a:z], nb[a:z], cpos[a:z], cnb[a:z], length, plen)
         e_ = to_current(x + n, pos[a:z], nb[a:z], cpos[a:z], cnb[a:z], length, plen)
         out[r]["unitig"], out[r]["orient"], out[r]["s"], out[r]["e"] = k, o, s_, e_
@@ -250,17 +288,21 @@ def place(u, cur, lens, recs, contained, removed, clips=None, band0=512):
     return out, cnt
 
 
-def realign_round(u, cur, seqs, recs, contained, removed, clips=None, band0=512, band_max=4096, min_identity=700, min_depth=3):
+def realign_round(u, cur, seqs, recs, contained, removed, clips=None, band0=512, band_max=4096, min_identity=700, min_depth=3, circular=False):
     """One round: -> dict(offsets, bases, pos, nbases, len, stats of POLISH_DT, placements of PLACE_DT, ops {read: uint32 runs}, table,
-    counts).  cur: dict(offsets, bases, pos, nbases) of the sequence to align against (graph_polish_unitigs' result, or a round's)."""
+    counts).  cur: dict(offsets, bases, pos, nbases) of the sequence to align against (graph_polish_unitigs' result, or a round's).
+    circular (section 19): a read that place() put on the unrolled circle is aligned against its unitig twice in a row and votes modulo
+    the unitig's length; the counts gain `wrapped`, the voters among them with e > plen or q_end > plen."""
     lens = [len(s) for s in seqs]
-    pl, cnt = place(u, cur, lens, recs, contained, removed, clips, band0)
+    pl, cnt = place(u, cur, lens, recs, contained, removed, clips, band0, band_max, circular)
     coffs = cur["offsets"].astype(np.int64)
     cb = bytes(cur["bases"].tobytes() if hasattr(cur["bases"], "tobytes") else cur["bases"])
     total = int(coffs[-1])
     table = np.zeros((total, P.NCOUNTERS), np.int64)
     ops = {}
     cnt.update(band_capped=0, low_identity=0, voted=0, votes=0, dp_cells=0)
+    if circular:
+        cnt["wrapped"] = 0
     for r in np.flatnonzero(pl["status"] == VOTED).tolist():
         k, o = int(pl[r]["unitig"]), int(pl[r]["orient"])
         b, e = (0, lens[r]) if clips is None else (int(clips[0][r]), int(clips[1][r]))
@@ -268,6 +310,9 @@ def realign_round(u, cur, seqs, recs, contained, removed, clips=None, band0=512,
         if o:
             read = revcomp(read)
         utg = cb[int(coffs[k]):int(coffs[k + 1])]
+        plen, unrolled = len(utg), bool(pl[r]["pad"])
+        if unrolled:
+            utg = utg + utg
         n = len(read)
         c = int(pl[r]["s"]) + ((int(pl[r]["e"]) - int(pl[r]["s"])) - n) // 2
         B = band0
@@ -292,7 +337,9 @@ def realign_round(u, cur, seqs, recs, contained, removed, clips=None, band0=512,
             cnt["voted"] += 1
             ops[r] = run_lengths(res["ops"])
             pl[r]["nops"] = len(ops[r])
-            cnt["votes"] += vote(table, int(coffs[k]), len(utg), read, res["q_begin"], res["ops"])
+            cnt["votes"] += vote(table, int(coffs[k]), plen, read, res["q_begin"], res["ops"], unrolled)
+            if unrolled and (int(pl[r]["e"]) > plen or res["q_end"] > plen):
+                cnt["wrapped"] += 1
     # consensus per unitig, and the old segment starts in the new coordinates
     nutg = len(u["len"])
     voff = u["voff"].astype(np.int64).tolist()

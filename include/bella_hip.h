@@ -688,8 +688,21 @@ int bella_hip_graph_get_polish_stats(bella_ctx* ctx, void* out, uint64_t struct_
  * bella_hip_consensus's rule to every unitig as if it were one read.  Section 18 states the placement, the semi-global banded DP (read
  * global, unitig window free; the trace's scoring and direction choice), the band rule and the votes in full; the tests hold a numpy
  * statement of it, and the device result equals it.  Limits: one inserted base per junction, plain majority, a fixed
- * centre diagonal per read, reads across the origin of a circular unitig are skipped, removed reads do not vote, the links keep their raw
- * overlaps, a unitig has fewer than 2^31 - band_max bases. */
+ * centre diagonal per read, reads across the origin of a circular unitig are skipped (bella_hip_graph_realign_unitigs_circular below
+ * does not skip them), removed reads do not vote, the links keep their raw overlaps, a unitig has fewer than 2^31 - band_max bases.
+ *
+ * Circles (opt-in: bella_hip_graph_realign_unitigs_circular).  Notation of section 18; u a circular unitig, len its
+ * raw and plen its current length, x the raw coordinate where the read's clip starts, n the clip's length.  A read on u is placed on the
+ * UNROLLED circle iff (1) plen < 2^29; (2) with xm = x mod len (floor modulo), s0 = P(xm) and ym = xm + n: e0 = P(ym) if ym < len,
+ * e0 = plen + P(ym - len) if ym - len < len, otherwise the read is not eligible (P is used inside [0, len) only); (3) e0 >= s0 and
+ * max(n, e0 - s0) + band_max <= plen: the read cannot lap itself at the widest band.  Its window is s = s0, or s0 + plen if
+ * s0 < band_max / 2, and e = s + (e0 - s0), so s lies in [band_max / 2, plen + band_max / 2); its status is VOTED (a candidate), never
+ * OUTSIDE, and its placement's pad word is 1.  A read that is not eligible -- any read on a linear unitig, a circle shorter than
+ * n + band_max -- keeps section 18's placement and status, so the option never loses a voter.  The DP is section 18's against the
+ * unitig's current sequence twice in a row (2 plen columns; with the window rule no row reaches column 2 plen); s, e, q_begin and q_end
+ * are in unrolled coordinates and may exceed plen.  A vote at column or junction q goes to row q mod plen of the unitig's table (an
+ * alignment spans at most plen columns: one vote per position and read); an insertion votes for q < 2 plen.  Consensus and segment
+ * positions are unchanged.  Limit: the junction before base 0 still takes no insertion. */
 #define BELLA_REALIGN_DEFAULT_BAND 512
 #define BELLA_REALIGN_DEFAULT_BAND_MAX 4096
 #define BELLA_REALIGN_DEFAULT_MIN_IDENTITY 700
@@ -720,7 +733,7 @@ typedef struct {
     int32_t score;
     int64_t q_begin, q_end;       /* the unitig junctions the alignment spans                                              */
     uint64_t op_off;              /* keep_ops: first run among the kept runs                                               */
-    uint32_t nops, pad;
+    uint32_t nops, pad;           /* pad: 1 when the read was placed on the unrolled circle (section 19), otherwise 0          */
 } bella_realign_placement;
 /* What the last round did.  A sized struct: bella_hip_graph_get_realign_stats writes at most struct_size bytes. */
 typedef struct {
@@ -740,6 +753,12 @@ typedef struct {
  * power of two or out of range, min_depth < 1, min_identity > 1000, a struct_size too small; BELLA_ERR_NOMEM when the table (36 bytes per
  * unitig base) does not fit.  The result replaces the last round's and goes with the polish.  Zero unitigs launch nothing. */
 int bella_hip_graph_realign_unitigs(bella_ctx* ctx, const bella_realign_params* params, uint64_t* total_bases);
+/* The same round with the circle rule above: the same parameters, errors, state rules and getters.  Without a circular unitig the result
+ * is bella_hip_graph_realign_unitigs' exactly; `outside` counts what is still outside. */
+int bella_hip_graph_realign_unitigs_circular(bella_ctx* ctx, const bella_realign_params* params, uint64_t* total_bases);
+/* *wrapped = the last round's voters on the unrolled circle with e > plen or q_end > plen: the reads that reach across an origin (0 after
+ * a plain round).  A getter of its own: bella_realign_stats keeps its 176 bytes.  BELLA_ERR_STATE without a round; wrapped may be NULL. */
+int bella_hip_graph_get_realign_wrapped(bella_ctx* ctx, uint64_t* wrapped);
 /* As bella_hip_graph_get_polished: pos / nbases are where the polish's segments begin in the new sequence.  Any pointer may be NULL. */
 int bella_hip_graph_get_realigned(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases, uint64_t* pos, uint32_t* nbases, bella_polish_unitig* per_unitig);
 /* out[nreads] */

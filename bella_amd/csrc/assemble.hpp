@@ -587,6 +587,57 @@ __global__ __launch_bounds__(kBlock) void k_layout_compact(const uint32_t* Bloc,
     }
 }
 
+// ---- B' with one entry per PRODUCT ------------------------------------------------------------------------------------------------
+// What the row kernels' expansion (phase X1/X2, spgemm.hpp) writes into LDS for product t of a plain entry is {a_ptr + t, side word}:
+// itself a plain entry with count 1.  None of it depends on the pass, so the compaction can write it once: every live plain entry
+// `cnt` times as {a_ptr + t, side word with count := 1}, every INLINE entry as it is.  Row i of B' is then the product list of column
+// i in product order (entry by entry, then down the list), its length is rowF[i] and the new row pointers are the scan of rowF.  The
+// entries are ordinary entries: every reader that goes through bent_count / bent_product / bent_partner works on them unchanged; the
+// LDS-tier row kernels read item p of a column straight from Bent[b0 + p] and have no expansion phase.  8 B per product instead of
+// 8 B per live entry (1.4 against 1.0 GB at 100k PacBio-like reads): taken when that stays within 12 B per owned nonzero (bella_hip.hip).
+// One wavefront per row, 64 entries at a time: a prefix sum over their counts, then the unit entries of the chunk leave 64 at a
+// time -- lane q finds its source entry by a binary search over the 64 prefix sums in LDS -- so that a store instruction writes 64
+// neighbouring entries whatever the counts are.  start = the 64-bit scan of rowF (the host has checked that its total fits 32 bits);
+// Bnew receives the new row pointers.
+__global__ __launch_bounds__(64) void k_layout_compact_products(const uint32_t* Bloc, const uint64_t* start, uint32_t* Bnew, const uint2* Bent,
+                                                                uint32_t nreads, uint32_t inl, uint2* out) {
+    __shared__ uint32_t s_ex[64];
+    __shared__ uint2 s_be[64];
+    const uint32_t i = blockIdx.x;
+    if (i >= nreads) return;
+    const uint32_t b0 = Bloc[i], b1 = Bloc[i + 1];
+    const uint32_t lane = threadIdx.x;
+    uint32_t o = (uint32_t)start[i];
+    if (lane == 0) { Bnew[i] = o; if (i + 1 == nreads) Bnew[nreads] = (uint32_t)start[nreads]; }
+    for (uint32_t e0 = b0; e0 < b1; e0 += 64) {
+        const uint32_t e = e0 + lane;
+        uint2 be = make_uint2(0u, 0u);
+        if (e < b1) be = Bent[e];
+        const uint32_t cnt = e < b1 ? bent_count(be, inl) : 0u;
+        const uint32_t inc = wave_incl_scan(cnt);
+        const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+        if ((uint32_t)__popcll(__ballot(cnt != 0)) == T) {            // every live entry of the chunk has one later read: they move as they are
+            if (cnt) out[o + inc - 1] = bent_is_inline(be, inl) ? be : make_uint2(be.x, (be.y & 0xC000FFFFu) | 0x10000u);
+            o += T;
+            continue;
+        }
+        __syncthreads();                                              // (the searches of the chunk before are done)
+        s_ex[lane] = inc - cnt;
+        s_be[lane] = be;
+        __syncthreads();
+        for (uint32_t q = lane; q < T; q += 64) {
+            uint32_t j = 0;                                           // the last lane whose prefix is <= q: it has a count, and q falls into its run
+#pragma unroll
+            for (uint32_t step = 32; step > 0; step >>= 1)
+                if (s_ex[j + step] <= q) j += step;
+            const uint2 sb = s_be[j];
+            const uint32_t t = q - s_ex[j];
+            out[o + q] = bent_is_inline(sb, inl) ? sb : make_uint2(sb.x + t, (sb.y & 0xC000FFFFu) | 0x10000u);
+        }
+        o += T;
+    }
+}
+
 // ---- row lists: the products of every column, ready-made, in product order -----------------------------------------------------
 // The SpGEMM of column i reads, for each entry of row i, the tail of that k-mer's list in A' (the later reads): with A' alone that is
 // one random 8..56-byte read per entry and pass, plus the expansion of the entries into products and the overlap estimate of every

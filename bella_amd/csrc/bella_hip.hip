@@ -275,11 +275,13 @@ struct bella_ctx {
     uint64_t xdrop_class_min = 4ull * 4096 * 64;   // extensions of a batch from which on the slices run it as four classes (BELLA_TUNE_XDROP_CLASS_MIN)
     BufPool pool;                        // released device buffers waiting for the next request they fit
     uint32_t layout_inline = 0;          // the device layout holds B' entries in the INLINE form (util.hpp); 0 / 1
+    bool layout_products = false;        // the device layout holds B' with one entry per PRODUCT (assemble.hpp: k_layout_compact_products)
     // layout and path choices (bella_hip_set_tuning; the matching bella_hip_set_debug bits of earlier rounds are still read as aliases)
     uint32_t tune_layout_order = 0;      // BELLA_TUNE_LAYOUT_ORDER: 0 lists of A' in k-mer order, 1 in order of first appearance in B'
     uint32_t tune_inline = 0;            // BELLA_TUNE_INLINE_ENTRIES: 0 by the size of A' against the last-level cache, 1 never, 2 always
     uint32_t tune_row_path = 0;          // BELLA_TUNE_ROW_PATH: 0 LDS tiers, 1 every column on the global-workspace (repairing) path
     uint32_t tune_compact_b = 0;         // BELLA_TUNE_COMPACT_B: 0 the layout drops the B' entries that have no later read, 1 keeps them
+    uint32_t tune_product_entries = 0;   // BELLA_TUNE_PRODUCT_ENTRIES: 0 one B' entry per product when it stays within 12 B per owned nonzero, 1 never, 2 always
     uint32_t tune_dist_layout = 2;       // BELLA_TUNE_DIST_LAYOUT: bella_hip_allgather_panels forms A' by k-mer id ranges over the communicator's ranks
                                          // (1: always, 0: never, 2 = default: on the in-process transport only -- over RCCL the path has not run on
                                          // more than one device yet, and its extra 20 B per nonzero of traffic want a measurement first)
@@ -287,7 +289,7 @@ struct bella_ctx {
     bool layout_dist = false;            // ... and the current layout was built that way
     uint64_t tune_cache_bytes = 192ull << 20;   // BELLA_TUNE_CACHE_BYTES: A' above this size counts as "larger than the last-level cache"
     uint32_t xdrop_variant = 1;          // 0: one launch in length-sorted order; 1 (default): slices with compaction; 2: packed kernel in pair order; 3: scalar statement
-    size_t lds_attr[24] = {};             // largest dynamic-LDS size already granted to each row-kernel instantiation
+    size_t lds_attr[40] = {};             // largest dynamic-LDS size already granted to each row-kernel instantiation
     hipStream_t side[kNumTiers + 1]{};   // independent tier launches / fold instances run concurrently
     hipEvent_t fork = nullptr, join[kNumTiers + 1]{};
 };
@@ -604,6 +606,8 @@ int build_layout(bella_ctx* c, bool collective = false) {
     drop(c, MATRIX);
     c->have_rowlists = false;
     c->layout_inline = 0;
+    c->layout_products = false;
+    c->live_nnz = 0;
     c->tm.expand_ms = 0.f;
     // shared formation of A' (layout_dist): every rank agreed to it in bella_hip_allgather_panels, so a rank that fails BEFORE it gets
     // there still says so in the formation's metadata exchange -- the others leave instead of waiting for it
@@ -643,6 +647,8 @@ int build_layout(bella_ctx* c, bool collective = false) {
     }
     c->owned_nnz = 0;
     uint32_t ratio1024 = 1024;
+    uint64_t rowF_total = 0;                                       // the products of the owned rows, once rowF has been scanned in 64 bits ...
+    bool rowF_scanned = false;                                     // ... into lk_rinfo
     c->long_list_sample = false;
     const uint32_t* Bloc = ptr<uint32_t>(c->Bloc);                 // the rows of the owned columns
     // (buffers only ever grow; a context that goes from a whole layout to a partition's gives the difference back)
@@ -741,12 +747,49 @@ int build_layout(bella_ctx* c, bool collective = false) {
             k_layout_live<<<nblk((uint64_t)c->nreads + 1, kWaves), kBlock, 0, c->stream>>>(Bloc, ptr<uint2>(c->Bent), c->nreads, inl, compact ? len : nullptr,
                                                                                          ptr<uint32_t>(c->rowF));
             KCHK(c);
+            // One entry per PRODUCT (assemble.hpp: k_layout_compact_products) instead of one per live entry: the row pointers are the scan
+            // of rowF, the LDS-tier row kernels then have no expansion phase.  Not next to the row lists (they replace B' in the pass); the
+            // products must fit a 32-bit row pointer; and 8 B per product may not exceed 12 B per owned nonzero -- that keeps B' inside the
+            // 13 B per owned nonzero the layout promises, and long-list inputs (HiFi-like, ~14 products per nonzero), which get the row
+            // lists anyway, on the per-entry form.  If the buffer cannot be had (debug bit 11: tests, as if), the per-entry form stands.
+            // (both scans -- live entries, products -- and both totals before ONE wait: an input that stays on the per-entry form pays no
+            // host round trip for having been asked; the row lists below start from the same 64-bit scan)
+            uint32_t live = 0;
             if (compact) {
                 int rc = scan_u32(c, len, bnew, (uint64_t)c->nreads + 1);
                 if (rc) return rc;
-                uint32_t live = 0;
                 HIPCHK(c, hipMemcpyAsync(&live, bnew + c->nreads, 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
+            }
+            // (auto additionally asks that A' be larger than the last-level cache, the rule of the inline entries: at 10k reads, A' = 92 MB,
+            // the form saves no time and its longer B' -- there 1.67 x the live entries -- costs 2 % of the step)
+            const bool ask_products = compact && c->tune_product_entries != 1 &&
+                                      (c->tune_product_entries == 2 || (!c->want_rowlists && 8ull * nnz > c->tune_cache_bytes));
+            if (ask_products) {
+                int rc = scan_u32_to_u64(c, ptr<uint32_t>(c->rowF), ptr<uint64_t>(c->lk_rinfo), (uint64_t)c->nreads + 1);   // (rowF[nreads] = 0)
+                if (rc) return rc;
+                HIPCHK(c, hipMemcpyAsync(&rowF_total, ptr<uint64_t>(c->lk_rinfo) + c->nreads, 8, hipMemcpyDeviceToHost, c->stream));
+                rowF_scanned = true;
+            }
+            if (compact) HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (ask_products) {
+                Buf& start = c->lk_rinfo;                          // (free since k_layout_emit) the 64-bit scan of rowF: the new row pointers, and their total
+                const uint64_t F = rowF_total;
+                const bool small = 8ull * F <= 12ull * nown_nnz || c->tune_product_entries == 2;
+                if (F && F < 0xFFFFFFF0ull && small && !(c->debug & 2048u)) {
+                    TmpBuf out;
+                    if (!ensure_bytes(c, out, 8 * (size_t)F)) {
+                        k_layout_compact_products<<<c->nreads, 64, 0, c->stream>>>(Bloc, ptr<uint64_t>(start), bnew, ptr<uint2>(c->Bent), c->nreads, inl,
+                                                                                   ptr<uint2>(out));
+                        if (hipGetLastError() != hipSuccess) return fail(c, BELLA_ERR_HIP, "k_layout_compact_products failed to launch");
+                        HIPCHK(c, hipMemcpyAsync(c->Bloc.p, bnew, 4 * ((size_t)c->nreads + 1), hipMemcpyDeviceToDevice, c->stream));
+                        HIPCHK(c, hipStreamSynchronize(c->stream));
+                        out.give_to(c->Bent);
+                        c->live_nnz = F;
+                        c->layout_products = true;
+                    } else c->err.clear();
+                }
+            }
+            if (compact && !c->layout_products) {
                 TmpBuf out;
                 ENSURE(c, out, 8 * (size_t)live);
                 k_layout_compact<<<nblk(c->nreads, kWaves), kBlock, 0, c->stream>>>(Bloc, bnew, ptr<uint2>(c->Bent), c->nreads, inl, ptr<uint2>(out));
@@ -784,7 +827,10 @@ int build_layout(bella_ctx* c, bool collective = false) {
             // Optional in every respect: if they do not fit next to what a pass needs, or an allocation fails, the layout stands without them.
             int rc = ensure_bytes(c, c->Arow, 8 * ((size_t)c->nreads + 2));
             uint64_t F = 0;
-            if (!rc) {
+            if (!rc && rowF_scanned) {                             // (the compaction above already scanned rowF in 64 bits and knows the total)
+                HIPCHK(c, hipMemcpyAsync(c->Arow.p, c->lk_rinfo.p, 8 * ((size_t)c->nreads + 1), hipMemcpyDeviceToDevice, c->stream));
+                F = rowF_total;
+            } else if (!rc) {
                 rc = scan_u32_to_u64(c, ptr<uint32_t>(c->rowF), ptr<uint64_t>(c->Arow), (uint64_t)c->nreads + 1);   // (rowF[nreads] = 0)
                 if (rc) return rc;
                 HIPCHK(c, hipMemcpyAsync(&F, ptr<uint64_t>(c->Arow) + c->nreads, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1012,6 +1058,11 @@ int bella_hip_set_tuning(bella_ctx* c, uint32_t what, const uint64_t* values, ui
         case BELLA_TUNE_COMPACT_B:
             if (n && values[0] > 1) return fail(c, BELLA_ERR_BAD_ARG, "compact B': 0 (drop the entries without a later read) or 1 (keep them)");
             c->tune_compact_b = n ? (uint32_t)values[0] : 0u;
+            return 0;
+        case BELLA_TUNE_PRODUCT_ENTRIES:
+            if (n && values[0] > 2) return fail(c, BELLA_ERR_BAD_ARG, "product entries: 0 (by size), 1 (never) or 2 (always)");
+            c->tune_product_entries = n ? (uint32_t)values[0] : 0u;
+            c->pass_known = false;
             return 0;
     }
     return fail(c, BELLA_ERR_BAD_ARG, "unknown tuning parameter %u", what);
@@ -2891,7 +2942,8 @@ static int run_spgemm(bella_ctx* c, const bella_params* p, uint32_t* status_out,
         int ki;
         void (*kern)(SpgemmArgs);
         const bool rl = c->have_rowlists;
-#define BELLA_ROWS_KERN(NX, B) (rl ? k_spgemm_rows_lds<NX, B, true> : k_spgemm_rows_lds<NX, B, false>)
+        const bool pe = c->layout_products && !rl;                // B' with one entry per product: the instantiations without an expansion phase
+#define BELLA_ROWS_KERN(NX, B) (rl ? k_spgemm_rows_lds<NX, B, true> : pe ? k_spgemm_rows_lds<NX, B, false, true> : k_spgemm_rows_lds<NX, B, false>)
         if (blk == 512) {
             ki = a.cap <= 8 * 512 ? 0 : a.cap <= 16 * 512 ? 1 : 2;
             kern = ki == 0 ? BELLA_ROWS_KERN(8, 512) : ki == 1 ? BELLA_ROWS_KERN(16, 512) : BELLA_ROWS_KERN(22, 512);
@@ -2916,6 +2968,7 @@ static int run_spgemm(bella_ctx* c, const bella_params* p, uint32_t* status_out,
         }
 #undef BELLA_ROWS_KERN
         if (rl) ki += ki >= 18 ? 2 : 9;
+        else if (pe) ki += ki >= 18 ? 13 : 22;
         if (lds > c->lds_attr[ki]) {                             // once per kernel and size, not per launch
             HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             c->lds_attr[ki] = lds;

@@ -27,6 +27,7 @@
 //
 // Data layout in HBM (built by assemble.hpp):
 //   Bent[e] = { a_ptr, posV | cnt << 16 (14 bit) | pal << 30 | ori << 31 }  e in B' order (MergeDuplicates slot order)
+//             (per-product form, assemble.hpp k_layout_compact_products: every plain entry once per later read, cnt = 1, a_ptr + t)
 //   rowF[i] = products of column i (the sum of its entries' counts: estimateFLOP, written once at layout time)
 //   Aent[x] = { read | ori << 31, posH | readlen << 16 }  k-mer lists, ascending read id, stored in order of first
 //                                                          appearance in B' (streaming for the owner row)
@@ -165,7 +166,10 @@ __device__ __forceinline__ RowMem carve(uint8_t* base, uint32_t cap, uint32_t dc
 // Returns false if the key table overflowed or a list came out of order (no global side effect happened yet; the caller queues
 // the column again).
 // RL: the column's products come ready-made from the row lists (arow = Arow[i], Fdesc = flops[i]); b0 / n / lenV are unused then.
-template <bool OVERLAY, uint32_t NX, int BLK = BELLA_ROW_BLOCK, bool RL = false>
+// PE (LDS tiers, not with RL): B' has one entry per PRODUCT (assemble.hpp: k_layout_compact_products) -- the column's n entries are its
+// products in product order, entry p is what phases X1/X2 would have put into A_hv[p] / A_gov[p]: there is no expansion, no scan and
+// no barrier before X3, which takes its items straight from B' (coalesced, one batch ahead of the gathers).
+template <bool OVERLAY, uint32_t NX, int BLK = BELLA_ROW_BLOCK, bool RL = false, bool PE = false>
 __device__ __forceinline__ bool process_row(const SpgemmArgs& a, const uint32_t i, const uint32_t b0, const uint32_t n, const uint32_t lenV,
                                             const RowMem& m, const uint64_t arow = 0, const uint32_t Fdesc = 0) {
     constexpr int kRowBlock = BLK;                            // threads of this workgroup
@@ -199,9 +203,38 @@ __device__ __forceinline__ bool process_row(const SpgemmArgs& a, const uint32_t 
     // B' entries per thread and round (registers: 1024-thread workgroups run at 64 VGPRs).  A read of the PacBio-like sets has ~2,050
     // entries: a workgroup of 256 threads covers them in one round with ten entries per thread and needs a second round -- one more
     // dependent trip to HBM, one more scan -- with eight
+    static_assert(!(PE && RL), "the row lists replace B' in the pass");
+    constexpr uint32_t XB = BELLA_GATHER_BATCH(kRowBlock);    // A' loads in flight per lane (phase X3)
     constexpr uint32_t RMAX = kRowBlock >= 1024 ? 4 : kRowBlock >= 512 ? 8 : BELLA_RMAX_SMALL;
     uint2 be0[RMAX];
-    if (!RL) {
+    uint2 itn[XB];                                            // PE: the items of the next X3 batch (the first one travels from here)
+    // BELLA_PE_HEAD 1 (default): ALL of a thread's items travel from the head of the column, while the tables are initialised, as be0
+    // does in the per-entry form -- at most NX items, for the instantiations with NX <= BELLA_PE_HEAD_MAX (8: the registers be0[8] took);
+    // phase X3 is then unrolled over its <= NX / XB batches.  0: every instantiation loads one batch ahead, as the larger ones do.
+    // 100k reads, row kernels: 3.14 ms one batch ahead, 3.06 ms from the head (parent 3.25; profiles/r07_product_entries.md)
+#ifndef BELLA_PE_HEAD
+#define BELLA_PE_HEAD 1
+#endif
+#ifndef BELLA_PE_HEAD_MAX
+#define BELLA_PE_HEAD_MAX 8
+#endif
+    constexpr bool HEAD = PE && BELLA_PE_HEAD != 0 && NX <= BELLA_PE_HEAD_MAX;
+    uint2 ith[HEAD ? NX : 1];
+    if (HEAD) {
+#pragma unroll
+        for (uint32_t u = 0; u < NX; ++u) {
+            const uint32_t p = u * kRowBlock + tid;
+            ith[u] = make_uint2(0u, 0u);
+            if (p < n) ith[u] = a.Bent[b0 + p];
+        }
+    } else if (PE) {
+#pragma unroll
+        for (uint32_t u = 0; u < XB; ++u) {
+            const uint32_t p = u * kRowBlock + tid;
+            itn[u] = make_uint2(0u, 0u);
+            if (p < n) itn[u] = a.Bent[b0 + p];
+        }
+    } else if (!RL) {
         const uint32_t nn = n < RMAX * kRowBlock ? n : RMAX * kRowBlock;
         const uint32_t R = (nn + kRowBlock - 1) / kRowBlock;
         const uint32_t j0 = tid * R;
@@ -221,8 +254,8 @@ __device__ __forceinline__ bool process_row(const SpgemmArgs& a, const uint32_t 
     // ---- X: expand products in reference order, group keys --------------------------------------------
     // X1/X2: each thread owns a CONTIGUOUS run of B' entries (so one block scan orders all products); it only records,
     // per product, where its A' entry lives and the B' side word -- LDS writes, no dependent global loads.
-    uint32_t running = RL ? Fdesc : 0u;
-    if (!RL)
+    uint32_t running = RL ? Fdesc : PE ? n : 0u;
+    if (!RL && !PE)
     for (uint32_t jb = 0; jb < n; jb += RMAX * kRowBlock) {
         const uint32_t nn = n - jb < RMAX * kRowBlock ? n - jb : RMAX * kRowBlock;
         const uint32_t R = (nn + kRowBlock - 1) / kRowBlock;
@@ -248,12 +281,11 @@ __device__ __forceinline__ bool process_row(const SpgemmArgs& a, const uint32_t 
     // The products are cut into four ranges of whole 64-product chunks: a key counts its products per range (four u16 fields in
     // T1cnt / T1first), so that in phase S four wavefronts append to the per-pair lists independently, each in product order.
     const uint32_t RB = ((F + 255u) >> 8) << 6;
-    __syncthreads();
+    if (!PE) __syncthreads();
     BELLA_BPROF(0)
     // X3: product-parallel gather of the A' entries (balanced: every lane has work; four independent loads in flight).  Per
     // product ONE compare-and-swap (claim or find the key's slot) and one add (the key's count in the product's range).
-    constexpr uint32_t XB = BELLA_GATHER_BATCH(kRowBlock);    // A' loads in flight per lane
-    for (uint32_t base = 0; base < F; base += XB * kRowBlock) {
+    auto x3_batch = [&](const uint32_t base, const uint2 (&it)[XB]) __attribute__((always_inline)) {
         uint2 ae[XB];
         uint32_t bw[XB], ax[XB];
         bool inl[XB];
@@ -266,8 +298,8 @@ __device__ __forceinline__ bool process_row(const SpgemmArgs& a, const uint32_t 
             if (p < F) {
                 if (RL) { ae[u] = a.Aent2[arow + p]; bw[u] = a.Aov[arow + p]; }
                 else {
-                    const uint32_t at = m.A_hv[p];
-                    bw[u] = m.A_gov[p];
+                    const uint32_t at = PE ? it[u].x : m.A_hv[p];
+                    bw[u] = PE ? it[u].y : m.A_gov[p];
                     inl[u] = a.inl && (at >> 31);
                     ax[u] = at;
                     if (inl[u]) {                              // no gather: the partner's length only -- the two offsets travel like a gathered entry
@@ -275,6 +307,13 @@ __device__ __forceinline__ bool process_row(const SpgemmArgs& a, const uint32_t 
                         ae[u] = make_uint2(ro[0], ro[2]);
                     } else ae[u] = a.Aent[at];
                 }
+            }
+        }
+        if (PE && !HEAD) {                                     // the next batch's items: in flight together with this batch's gathers
+#pragma unroll
+            for (uint32_t u = 0; u < XB; ++u) {
+                const uint32_t p = base + (XB + u) * kRowBlock + tid;
+                if (p < F) itn[u] = a.Bent[b0 + p];
             }
         }
         // Decode all products of the batch, then the FIRST probe of every product back to back (two compare-and-swaps in flight per
@@ -329,6 +368,24 @@ __device__ __forceinline__ bool process_row(const SpgemmArgs& a, const uint32_t 
             m.A_hv[p] = hv[u];
             if (OVERLAY) m.A_gov[p] = (ovf[u] & 0xC000FFFFu) | (h << 16);
             else { m.A_gov[p] = (h << 16) | (ovf[u] & 0xFFFFu); m.A_fl[p] = (uint8_t)(ovf[u] >> 30); }
+        }
+    };
+    if (HEAD) {
+        constexpr uint32_t NB = (NX + XB - 1) / XB;
+#pragma unroll
+        for (uint32_t b = 0; b < NB; ++b) {
+            if (b * XB * kRowBlock >= F) break;
+            uint2 it[XB];
+#pragma unroll
+            for (uint32_t u = 0; u < XB; ++u) it[u] = b * XB + u < NX ? ith[(b * XB + u) % (HEAD ? NX : 1)] : make_uint2(0u, 0u);
+            x3_batch(b * XB * kRowBlock, it);
+        }
+    } else {
+        for (uint32_t base = 0; base < F; base += XB * kRowBlock) {
+            uint2 it[XB];
+#pragma unroll
+            for (uint32_t u = 0; u < XB; ++u) it[u] = PE ? itn[u] : make_uint2(0u, 0u);
+            x3_batch(base, it);
         }
     }
     __syncthreads();
@@ -733,7 +790,7 @@ __device__ __forceinline__ bool process_row(const SpgemmArgs& a, const uint32_t 
 
 // LDS tiers: one column per workgroup, dynamic LDS = row_mem_bytes(cap, dcap); NX * 512 >= cap (8: the tiers up to 4096 products,
 // 16: the two big tiers that keep HiFi-like columns with long lists off the global path)
-template <uint32_t NX, int BLK = BELLA_ROW_BLOCK, bool RL = false>
+template <uint32_t NX, int BLK = BELLA_ROW_BLOCK, bool RL = false, bool PE = false>
 __global__ __launch_bounds__(BLK, (BLK == 64 ? (NX <= 11 ? 4 : 2) : BLK == 1024 ? (NX <= 4 ? 8 : 4) : BLK <= 256 ? 8 : (NX <= 8 ? 6 : 2))) void k_spgemm_rows_lds(SpgemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     // the launch covers the tiers of one LDS class, largest columns first: workgroup x -> (tier, place in the tier's list)
@@ -755,7 +812,7 @@ __global__ __launch_bounds__(BLK, (BLK == 64 ? (NX <= 11 ? 4 : 2) : BLK == 1024 
     const RowMem m = carve(smem, a.cap, a.dcap, true);
     // row lists: the descriptor carries the column's first product (48 bits: y, low half of z) and its product count (w)
     const bool ok = RL ? process_row<true, NX, BLK, true>(a, i, 0u, 0u, ds.z >> 16, m, (uint64_t)ds.y | ((uint64_t)(ds.z & 0xFFFFu) << 32), ds.w)
-                       : process_row<true, NX, BLK, false>(a, i, ds.y, ds.z & 0xFFFFu, ds.z >> 16, m);
+                       : process_row<true, NX, BLK, false, PE>(a, i, ds.y, ds.z & 0xFFFFu, ds.z >> 16, m);   // (PE: the entries ARE the products, <= cap)
     if (!ok && threadIdx.x == 0) a.retry[atomicAdd(&a.ctl[kCtlRetry], 1u)] = i;
 }
 
@@ -985,7 +1042,10 @@ __global__ __launch_bounds__(kBlock) void k_tier_lists(const uint32_t* flops, ui
             if (f <= caps[t]) { tier = t; break; }
         const uint32_t b0 = Bptr[i];
         ds.y = b0;
-        ds.z = (Bptr[i + 1] - b0) | ((uint32_t)(roff[i + 1] - roff[i]) << 16);   // both < 65536 (checked at set_reads / assembly)
+        // entries (16 bits) | read length.  A row of the reference's B has < 65,536 entries (checked where B arrives), B' never more -- except
+        // with one entry per PRODUCT, where the count is the column's products: the LDS tiers hold <= 11,008 and the tier above them
+        // < 65,536, so it fits for every column whose descriptor is read; a wide column (>= 65,536, list number ntiers) keeps no descriptor
+        ds.z = ((Bptr[i + 1] - b0) & 0xFFFFu) | ((uint32_t)(roff[i + 1] - roff[i]) << 16);
         if (Arow) {                                        // row lists: first product (48 bits) instead of the entries, and the product count
             const uint64_t ar = Arow[i];
             ds.y = (uint32_t)ar;

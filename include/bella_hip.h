@@ -873,7 +873,8 @@ int bella_hip_get_memory_sized(bella_ctx* ctx, void* m, uint64_t struct_size);
  * sorts on 64-bit keys on any input (default: 32-bit keys when column bits + read-id bits fit); bit8 = tests: the exact X-drop mode
  * launches its extensions in chunks of 1,000 (default 2^24: grid x block stays below 2^32 threads); bit10 (read when the operands are
  * assembled) = tests: the lists of A' in order of first appearance in B' (default: k-mer order), no row lists; bit11 (same moment) =
- * tests: as if the row lists BELLA_TUNE_ROW_LISTS asks for did not fit in memory (the layout stands without them);
+ * tests: as if the row lists BELLA_TUNE_ROW_LISTS asks for, and the per-product B' of BELLA_TUNE_PRODUCT_ENTRIES, did not fit in memory
+ * (the layout stands without them);
  * bit12 = tests: the columns above the LDS tiers are grouped by the radix sort also when the row lists would allow grouping in LDS;
  * bit13 = tests: the symbolic phase (bella_hip_count_pairs) keeps its bitmaps in global memory also when they fit in LDS;
  * bit14 = tests: k-mer counting looks every position up in a hash table over the dictionary (the path of syncmer mode, of k-mers too
@@ -929,10 +930,18 @@ int bella_hip_trim(bella_ctx* ctx);
  *                             BELLA_TUNE_LAYOUT_ORDER 0 (the call asks all ranks and falls back to the replicated formation on all of them).
  *   BELLA_TUNE_COMPACT_B      values[0] = 0 (default): the device layout drops the entries of B' whose k-mer has no later read (they have
  *                             no product in the strict lower triangle, overlap.hpp:157-202); 1: every entry stays.  Read at layout time.
+ *   BELLA_TUNE_PRODUCT_ENTRIES values[0] = 0 (default): the compacting layout writes B' with one entry per PRODUCT (a plain entry with c
+ *                             later reads becomes c entries of count 1 pointing at consecutive places of its list in A'; row i of B' is then
+ *                             the product list of column i and the LDS-tier row kernels skip the expansion) when the row lists are not
+ *                             asked for, A' is larger than BELLA_TUNE_CACHE_BYTES, the products fit 32-bit row pointers and 8 bytes per product stay within 12 bytes per owned
+ *                             nonzero; 1: never (one entry per live nonzero); 2: whenever the compaction runs and the products fit.  If
+ *                             the buffer cannot be had (bella_hip_set_debug bit 11: tests, as if) the per-entry layout stands.
+ *                             BELLA_TUNE_COMPACT_B 1 implies the per-entry form.  Read at layout time.
  * (bella_hip_set_debug bits 0, 10, 15 and 16 of earlier rounds still select the same things: aliases, no longer needed)
  */
 enum { BELLA_TUNE_LDS_TIERS = 0, BELLA_TUNE_KCOUNT_BUDGET = 1, BELLA_TUNE_WIDE_BUDGET = 2, BELLA_TUNE_XDROP_VARIANT = 3, BELLA_TUNE_ROW_LISTS = 4,
-       BELLA_TUNE_XDROP_CLASS_MIN = 5, BELLA_TUNE_LAYOUT_ORDER = 6, BELLA_TUNE_INLINE_ENTRIES = 7, BELLA_TUNE_ROW_PATH = 8, BELLA_TUNE_CACHE_BYTES = 9, BELLA_TUNE_DIST_LAYOUT = 10, BELLA_TUNE_COMPACT_B = 11 };
+       BELLA_TUNE_XDROP_CLASS_MIN = 5, BELLA_TUNE_LAYOUT_ORDER = 6, BELLA_TUNE_INLINE_ENTRIES = 7, BELLA_TUNE_ROW_PATH = 8, BELLA_TUNE_CACHE_BYTES = 9, BELLA_TUNE_DIST_LAYOUT = 10, BELLA_TUNE_COMPACT_B = 11,
+       BELLA_TUNE_PRODUCT_ENTRIES = 12 };
 int bella_hip_set_tuning(bella_ctx* ctx, uint32_t what, const uint64_t* values, uint32_t n);
 
 #ifdef __cplusplus

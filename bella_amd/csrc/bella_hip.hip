@@ -282,6 +282,7 @@ struct bella_ctx {
     uint32_t tune_row_path = 0;          // BELLA_TUNE_ROW_PATH: 0 LDS tiers, 1 every column on the global-workspace (repairing) path
     uint32_t tune_compact_b = 0;         // BELLA_TUNE_COMPACT_B: 0 the layout drops the B' entries that have no later read, 1 keeps them
     uint32_t tune_product_entries = 0;   // BELLA_TUNE_PRODUCT_ENTRIES: 0 one B' entry per product when it stays within 12 B per owned nonzero, 1 never, 2 always
+    uint32_t tune_order_split = kOrderOneLaunchMax;   // BELLA_TUNE_ORDER_SPLIT: owned columns of a pass above which k_order_wave runs as two instances
     uint32_t tune_dist_layout = 2;       // BELLA_TUNE_DIST_LAYOUT: bella_hip_allgather_panels forms A' by k-mer id ranges over the communicator's ranks
                                          // (1: always, 0: never, 2 = default: on the in-process transport only -- over RCCL the path has not run on
                                          // more than one device yet, and its extra 20 B per nonzero of traffic want a measurement first)
@@ -1063,6 +1064,9 @@ int bella_hip_set_tuning(bella_ctx* c, uint32_t what, const uint64_t* values, ui
             if (n && values[0] > 2) return fail(c, BELLA_ERR_BAD_ARG, "product entries: 0 (by size), 1 (never) or 2 (always)");
             c->tune_product_entries = n ? (uint32_t)values[0] : 0u;
             c->pass_known = false;
+            return 0;
+        case BELLA_TUNE_ORDER_SPLIT:
+            c->tune_order_split = n ? (uint32_t)(values[0] < 0xFFFFFFFFull ? values[0] : 0xFFFFFFFFull) : kOrderOneLaunchMax;
             return 0;
     }
     return fail(c, BELLA_ERR_BAD_ARG, "unknown tuning parameter %u", what);
@@ -3113,7 +3117,7 @@ static int run_spgemm(bella_ctx* c, const bella_params* p, uint32_t* status_out,
             // two instances share the columns by table size (the small one keeps more columns in flight per CU: tuned at 100k reads);
             // on a small pass the second launch costs more than it buys (10k reads: two launches and the gap between them for 0.3 M
             // records), so one instance takes all tables up to 1,024 slots there
-            if (nown <= kOrderOneLaunchMax) {
+            if (nown <= c->tune_order_split) {
                 k_order_wave<kOrderWaveHt, 0><<<nblk(nown ? nown : 1, kOrderBlock / 64), kOrderBlock, 0, c->stream>>>(oa);
                 KCHK(c);
             } else {

@@ -144,6 +144,25 @@ class RealignStats(C.Structure):
                 ("decide_ms", C.c_double)]
 
 
+class RecorrectParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("band0", C.c_uint32), ("band_max", C.c_uint32), ("min_identity", C.c_uint32), ("min_depth", C.c_uint32),
+                ("keep_ops", C.c_uint32)]
+
+
+class RecorrectStats(C.Structure):
+    _fields_ = [("round", C.c_uint32), ("batches", C.c_uint32), ("jobs", C.c_uint64), ("none", C.c_uint64), ("band_capped", C.c_uint64), ("low_identity", C.c_uint64),
+                ("voted", C.c_uint64), ("dp_cells", C.c_uint64), ("dir_bytes_peak", C.c_uint64), ("votes", C.c_uint64), ("bases_before", C.c_uint64),
+                ("bases_after", C.c_uint64), ("substituted", C.c_uint64), ("deleted", C.c_uint64), ("inserted", C.c_uint64), ("place_ms", C.c_double),
+                ("dp_ms", C.c_double), ("walk_ms", C.c_double), ("vote_ms", C.c_double), ("decide_ms", C.c_double)]
+
+
+RECJOB_DT = np.dtype([("record", "<u4"), ("side", "<u4"), ("target", "<u4"), ("query", "<u4"), ("orient", "<u4"), ("status", "<u4"), ("qbeg", "<u4"), ("qend", "<u4"),
+                      ("s", "<i8"), ("e", "<i8"), ("band", "<u4"), ("n_eq", "<u4"), ("n_x", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("score", "<i4"), ("q_begin", "<i8"),
+                      ("q_end", "<i8"), ("op_off", "<u8"), ("nops", "<u4"), ("pad", "<u4")])
+assert RECJOB_DT.itemsize == 104 and C.sizeof(RecorrectStats) == 152
+RECORRECT_ANCHOR_STEP = 256
+
+
 class PolishStats(C.Structure):
     _fields_ = [("unitigs", C.c_uint64), ("vertices", C.c_uint64), ("bases_before", C.c_uint64), ("bases_after", C.c_uint64), ("substituted", C.c_uint64),
                 ("deleted", C.c_uint64), ("inserted", C.c_uint64), ("covered", C.c_uint64), ("depth_sum", C.c_uint64), ("table_bytes", C.c_uint64),
@@ -267,6 +286,12 @@ SIGNATURES = [
     ("bella_hip_graph_get_realign_placements", C.c_int, [vp, vp]),
     ("bella_hip_graph_get_realign_ops", C.c_int, [vp, C.POINTER(C.c_uint64), vp, vp]),
     ("bella_hip_graph_get_realign_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_recorrect", C.c_int, [vp, C.POINTER(RecorrectParams), C.POINTER(C.c_uint64)]),
+    ("bella_hip_get_recorrected", C.c_int, [vp, vp, vp, vp]),
+    ("bella_hip_get_recorrect_jobs", C.c_int, [vp, C.POINTER(C.c_uint64), vp]),
+    ("bella_hip_get_recorrect_ops", C.c_int, [vp, C.POINTER(C.c_uint64), vp, vp]),
+    ("bella_hip_get_recorrect_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_get_recorrect_anchors", C.c_int, [vp, vp, vp]),
     ("bella_hip_graph_trim", C.c_int, [vp, C.POINTER(GraphTrimParams)]),
     ("bella_hip_graph_get_trim", C.c_int, [vp, vp]),
     ("bella_hip_graph_get_trim_stats", C.c_int, [vp, vp, C.c_uint64]),

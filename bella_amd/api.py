@@ -394,6 +394,53 @@ class Engine:
         self._chk(self.lib.bella_hip_get_consensus(self.h, offs.ctypes.data, _p(bases), _p(stats)))
         return offs, bases, stats
 
+    # ---- read correction rounds ----
+    RECORRECT_DEFAULTS = dict(band0=512, band_max=4096, min_identity=700, min_depth=3, keep_ops=0)
+
+    def recorrect(self, **params):
+        """one correction round on the device: for every accumulated overlap record each read's raw clip is aligned against the newest
+        corrected sequence of the other read (consensus()'s, or the last round's), the votes decide every corrected read again:
+        (offsets uint64[nreads + 1], bases uint8 ASCII, stats of CONS_DT relative to the round's input)"""
+        p = _over(self.RECORRECT_DEFAULTS, params, "recorrect")
+        rp = _lib.RecorrectParams(C.sizeof(_lib.RecorrectParams), *(p[k] for k in ("band0", "band_max", "min_identity", "min_depth", "keep_ops")))
+        tot = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_recorrect(self.h, C.byref(rp), C.byref(tot)))
+        return self.recorrected()
+
+    def recorrected(self):
+        st = self.recorrect_stats()
+        offs, bases, stats = np.zeros(self.nreads + 1, np.uint64), np.zeros(st["bases_after"], np.uint8), np.zeros(self.nreads, CONS_DT)
+        self._chk(self.lib.bella_hip_get_recorrected(self.h, offs.ctypes.data, _p(bases), _p(stats)))
+        return offs, bases, stats
+
+    def recorrect_jobs(self) -> np.ndarray:
+        """two records of RECJOB_DT per overlap record of the last round: job 2 x targets V, job 2 x + 1 targets H"""
+        n = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_get_recorrect_jobs(self.h, C.byref(n), None))
+        out = np.zeros(n.value, _lib.RECJOB_DT)
+        self._chk(self.lib.bella_hip_get_recorrect_jobs(self.h, C.byref(n), _p(out)))
+        return out
+
+    def recorrect_ops(self):
+        """tests: (runs, table) of a round that ran with keep_ops -- the voters' runs (a job's op_off / nops index them) and the round's
+        counters, (bases_before, 9) uint32"""
+        n = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_get_recorrect_ops(self.h, C.byref(n), None, None))
+        ops, table = np.zeros(n.value, np.uint32), np.zeros((self.recorrect_stats()["bases_before"], PILEUP_COUNTERS), np.uint32)
+        self._chk(self.lib.bella_hip_get_recorrect_ops(self.h, C.byref(n), _p(ops), _p(table)))
+        return ops, table
+
+    def recorrect_stats(self) -> dict:
+        return self._stats(self.lib.bella_hip_get_recorrect_stats, _lib.RecorrectStats)
+
+    def recorrect_anchors(self):
+        """tests: (offsets uint64[nreads + 1], anchors uint64) of the newest corrected sequences: where every 256th raw base of a read lies"""
+        offs = np.zeros(self.nreads + 1, np.uint64)
+        self._chk(self.lib.bella_hip_get_recorrect_anchors(self.h, offs.ctypes.data, None))
+        a = np.zeros(int(offs[-1]), np.uint64)
+        self._chk(self.lib.bella_hip_get_recorrect_anchors(self.h, None, _p(a)))
+        return offs, a
+
     # ---- string graph: overlap classes, containment, transitive reduction (DESIGN.md section 11) ----
     GRAPH_DEFAULTS = dict(min_overlap=1000, max_overhang=1000, overhang_permille=800, fuzz=1000)
 

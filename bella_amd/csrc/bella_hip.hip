@@ -30,6 +30,7 @@
 #include "pileup.hpp"
 #include "polish.hpp"
 #include "realign.hpp"
+#include "recorrect.hpp"
 #include "spgemm.hpp"
 #include "trace.hpp"
 #include "unitig.hpp"
@@ -140,7 +141,7 @@ struct CountU64 {                                        // pair counts: without
 // drop / changed / made / has / need (below) are the only code that touches `valid`.  The stages up to the traces keep their results in
 // members of the context (device buffers, mostly), PILE and CONS too; those of the stages that follow the alignment are here, one member
 // per stage, on the host: the graph is small next to what it was made from, and a stage uploads what it reads.
-enum Stage : uint32_t { READS, TUPLES, PANEL, MATRIX, PAIRS, ALNS, TRACES, BATCH_OPS, RECORDS, TRIM, GRAPH, UNITIGS, POLISH, REALIGN, PILE, CONS, kStages };
+enum Stage : uint32_t { READS, TUPLES, PANEL, MATRIX, PAIRS, ALNS, TRACES, BATCH_OPS, RECORDS, TRIM, GRAPH, UNITIGS, POLISH, REALIGN, PILE, CONS, RECORRECT, kStages };
 struct StageState {
     uint32_t valid = 1u << RECORDS;          // one bit per Stage (the records are always there: possibly none)
     std::vector<bella_overlap> records;      // accumulated by bella_hip_graph_add_overlaps (graph.hpp)
@@ -181,6 +182,11 @@ struct StageState {
         bella_realign_stats stats{};
         uint64_t wrapped = 0;                // voters that reach across an origin (section 19); apart from the stats, whose struct keeps its size
     } realign;
+    struct Recorrect {                       // the last round of bella_hip_recorrect (recorrect.hpp; section 20).  Sequences, per-read
+        uint64_t total = 0, njobs = 0;       // statistics, anchors and job records stay on the device, with the context (rc_*)
+        std::vector<uint32_t> ops, table;    // kept for the tests only (keep_ops)
+        bella_recorrect_stats stats{};
+    } recorrect;
     // READS .. BATCH_OPS, PILE and CONS (pileup.hpp; section 10) are members of the context: only their bits are here
 };
 
@@ -249,6 +255,9 @@ struct bella_ctx {
     // read correction (pileup.hpp): the table of the loaded reads, and the last consensus
     uint64_t cons_total = 0;
     Buf pile, pile_pairs, pile_cnt, pile_tmp, cons_emit, cons_scan, cons_out, cons_offs, cons_stats;
+    // correction rounds (recorrect.hpp; section 20): the anchors' offsets (one list per read), the consensus's anchors, and the last round
+    uint64_t rc_nanch = 0;
+    Buf rc_aoff, cons_anch, rc_out, rc_offs, rc_stats, rc_anch, rc_jobs;
     StageState as;                       // overlap records, clips, graph, unitigs, polish; which of all the stages' results are valid
     bella_timings tm{};
     hipEvent_t ev[12]{};
@@ -506,7 +515,8 @@ constexpr uint32_t kBuiltFrom[kStages] = {
     /* POLISH  */ stage_bit(REALIGN),
     /* REALIGN */ 0,                         // (a round reads the round before and replaces it)
     /* PILE    */ stage_bit(CONS) | stage_bit(POLISH),
-    /* CONS    */ 0,
+    /* CONS    */ stage_bit(RECORRECT),
+    /* RECORRECT */ 0,                       // (a round reads the round before and replaces it)
 };
 void drop(bella_ctx* c, Stage s);
 void changed(bella_ctx* c, Stage s) {
@@ -524,7 +534,8 @@ int need(bella_ctx* c, Stage s) {
     static const char* const first[kStages] = {"set_reads first", "count_kmers first", "assemble_panel first", "set_B / assemble_tuples first",
                                                "overlap first", "align_pairs first", "trace_pairs first", "trace_batch first",
                                                "", "bella_hip_graph_trim first", "bella_hip_graph_build first", "bella_hip_graph_unitigs first",
-                                               "bella_hip_graph_polish_unitigs first", "bella_hip_graph_realign_unitigs first", "bella_hip_pileup_reset first", "bella_hip_consensus first"};
+                                               "bella_hip_graph_polish_unitigs first", "bella_hip_graph_realign_unitigs first", "bella_hip_pileup_reset first", "bella_hip_consensus first",
+                                               "bella_hip_recorrect first"};
     return has(c, s) ? 0 : fail(c, BELLA_ERR_STATE, "%s", first[s]);
 }
 
@@ -986,7 +997,8 @@ void bella_hip_destroy(bella_ctx* c) {
                   &c->w_plist, &c->w_scr, &c->w_rlen, &c->w_rstart, &c->w_rrank, &c->w_redo, &c->w_segfirst, &c->w_toff, &c->w_table, &c->w_nruns, &c->w_desc, &c->w_gtab, &c->w_gcount, &c->w_gbase, &c->w_rfirst, &c->w_aent2, &c->w_aov, &c->kc_nk, &c->kc_koff, &c->kc_hist, &c->kc_keys, &c->kc_alt, &c->kc_runlen,
                   &c->kc_flag, &c->kc_slot, &c->kc_nruns, &c->kc_dcode, &c->kc_dcount, &c->kc_hkey, &c->kc_hval, &c->kc_found, &c->kc_tstart, &c->kc_cursor, &c->kc_sel, &c->kc_ringo, &c->kc_ringp, &c->kc_opos, &c->kc_oid, &c->kc_opos2, &c->kc_oid2, &c->xest, &c->xest2, &c->xids, &c->xorder, &c->xres, &c->xstate, &c->xlive, &c->lg_res, &c->lg_redo, &c->lg_scratch,
                   &c->tr_exts, &c->tr_lists, &c->tr_res, &c->tr_pres, &c->tr_opoff, &c->tr_dirs, &c->tr_scr, &c->tr_ops,
-                  &c->pile, &c->pile_pairs, &c->pile_cnt, &c->pile_tmp, &c->cons_emit, &c->cons_scan, &c->cons_out, &c->cons_offs, &c->cons_stats};
+                  &c->pile, &c->pile_pairs, &c->pile_cnt, &c->pile_tmp, &c->cons_emit, &c->cons_scan, &c->cons_out, &c->cons_offs, &c->cons_stats,
+                  &c->rc_aoff, &c->cons_anch, &c->rc_out, &c->rc_offs, &c->rc_stats, &c->rc_anch, &c->rc_jobs};
     for (Buf* b : all) release(*b);
     trim_pool(c->pool);
     if (c->pool.arena.base) { (void)hipFree(c->pool.arena.base); c->pool.arena = Arena(); }
@@ -1169,7 +1181,8 @@ static int set_reads_impl(bella_ctx* c, const uint64_t* offsets, uint32_t nreads
     c->names.clear();
     c->host_lens.resize(nreads);
     for (uint32_t r = 0; r < nreads; ++r) c->host_lens[r] = (uint32_t)(offsets[r + 1] - offsets[r]);
-    for (Buf* b : {&c->pile, &c->cons_out, &c->cons_offs, &c->cons_stats}) release(*b);      // (the pileup belongs to the reads it was sized for)
+    for (Buf* b : {&c->pile, &c->cons_out, &c->cons_offs, &c->cons_stats, &c->rc_aoff, &c->cons_anch, &c->rc_out, &c->rc_offs, &c->rc_stats, &c->rc_anch, &c->rc_jobs})
+        release(*b);                                                  // (the pileup belongs to the reads it was sized for)
     c->as.records.clear();                                            // (so do the overlap records)
     changed(c, READS);                                                // (... and everything else but the runs of a trace_batch)
     made(c, READS);
@@ -4165,6 +4178,19 @@ int bella_hip_consensus(bella_ctx* c, const bella_consensus_params* params, uint
     k_cons_reads<<<nblk((uint64_t)nr + 1), 256, 0, c->stream>>>(ptr<uint64_t>(c->roff), ptr<uint64_t>(c->cons_scan), nr, ptr<uint64_t>(c->cons_offs),
                                                                  ptr<bella_consensus_read>(c->cons_stats));
     KCHK(c);
+    std::vector<uint64_t> aoff((size_t)nr + 1, 0);
+    {   // the anchors of the correction rounds (section 20): where every 256th raw base went, from the scan before it is released
+        for (uint32_t r = 0; r < nr; ++r) aoff[r + 1] = aoff[r] + rec_nanchors(c->host_lens[r]);
+        c->rc_nanch = aoff[nr];
+        ENSURE(c, c->rc_aoff, 8 * ((size_t)nr + 1));
+        ENSURE(c, c->cons_anch, 8 * (size_t)c->rc_nanch);
+        HIPCHK(c, c->stager.h2d(c->rc_aoff.p, aoff.data(), 8 * ((size_t)nr + 1), c->stream));
+        if (nr) {
+            k_rec_anchors<<<nblk(c->rc_nanch), 256, 0, c->stream>>>(ptr<uint64_t>(c->roff), ptr<uint64_t>(c->cons_scan), ptr<uint64_t>(c->rc_aoff), nullptr, nr, c->rc_nanch,
+                                                                  ptr<uint64_t>(c->cons_anch));
+            KCHK(c);
+        }
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     release(c->cons_emit);
     release(c->cons_scan);
@@ -5420,6 +5446,280 @@ int bella_hip_graph_get_realign_wrapped(bella_ctx* c, uint64_t* wrapped) {
 
 int bella_hip_graph_get_realign_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     return get_stats(c, REALIGN, out, struct_size, [](const StageState& a) { return a.realign.stats; });
+}
+
+// ---- read correction rounds (recorrect.hpp) -------------------------------------------------------------------------
+// Section 18's round with the jobs placed, batched and sorted into bands on the device: per band the host reads the pending count, per
+// batch its end, its direction bytes and its runs -- nothing per job.  The new sequences, statistics, anchors and job records are built in
+// buffers of the call and handed to the context when everything has succeeded: a failed round leaves the round before.
+int bella_hip_recorrect(bella_ctx* c, const bella_recorrect_params* params, uint64_t* total_bases) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    bella_recorrect_params rp{};
+    rp.band0 = BELLA_RECORRECT_DEFAULT_BAND; rp.band_max = BELLA_RECORRECT_DEFAULT_BAND_MAX; rp.min_identity = BELLA_RECORRECT_DEFAULT_MIN_IDENTITY; rp.min_depth = 3;
+    if (int r = take_params(c, rp, params, "bella_recorrect_params")) return r;
+    auto pow2 = [](uint32_t x) { return x && !(x & (x - 1)); };
+    if (!pow2(rp.band0) || !pow2(rp.band_max) || rp.band0 < kTrMinBand || rp.band_max > kTrMaxBand || rp.band0 > rp.band_max)
+        return fail(c, BELLA_ERR_BAD_ARG, "recorrect: band0 and band_max must be powers of two with 256 <= band0 <= band_max <= 262144");
+    if (rp.min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
+    if (rp.min_identity > 1000) return fail(c, BELLA_ERR_BAD_ARG, "min_identity is in permille: at most 1000");
+    if (int r = need(c, CONS)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool again = has(c, RECORRECT);                             // the sequences to align against: the last round's, or the consensus's
+    const Buf& coffs = again ? c->rc_offs : c->cons_offs;
+    const Buf& cbases = again ? c->rc_out : c->cons_out;
+    const Buf& canch = again ? c->rc_anch : c->cons_anch;
+    const uint64_t total = again ? c->as.recorrect.total : c->cons_total;
+    const uint32_t nr = c->nreads;
+    const size_t nrec = c->as.records.size();
+    const uint64_t njobs = 2 * (uint64_t)nrec;
+    if (total >= 0x7FFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "recorrect: the corrected reads must have fewer than 2^31 bases");
+    StageState::Recorrect out;
+    bella_recorrect_stats st{};
+    st.round = again ? c->as.recorrect.stats.round + 1 : 2;
+    st.bases_before = total;
+    st.jobs = njobs;
+    const size_t nst = sizeof(bella_consensus_read) * std::max<size_t>(nr, 1);
+    TmpBuf nbases, noffs, nstats, nanch, jrec;                        // the round's result
+    uint64_t nout = total;
+    ENSURE(c, noffs, 8 * ((size_t)nr + 1)); ENSURE(c, nstats, nst); ENSURE(c, nanch, 8 * (size_t)c->rc_nanch);
+    std::vector<bella_consensus_read> hs(nr);
+    if (!nrec) {                                                      // (no record: nothing is launched, the input is the result)
+        st.none = njobs;
+        std::vector<uint64_t> ho((size_t)nr + 1, 0);
+        HIPCHK(c, hipMemcpyAsync(ho.data(), coffs.p, 8 * ((size_t)nr + 1), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (uint32_t r = 0; r < nr; ++r) hs[r].len_before = hs[r].len_after = (uint32_t)(ho[r + 1] - ho[r]);
+        ENSURE(c, nbases, (size_t)total);
+        ENSURE(c, jrec, sizeof(bella_recorrect_job) * (size_t)njobs);
+        HIPCHK(c, hipMemsetAsync(jrec.p, 0, sizeof(bella_recorrect_job) * (size_t)njobs, c->stream));
+        HIPCHK(c, hipMemcpyAsync(noffs.p, coffs.p, 8 * ((size_t)nr + 1), hipMemcpyDeviceToDevice, c->stream));
+        if (total) HIPCHK(c, hipMemcpyAsync(nbases.p, cbases.p, (size_t)total, hipMemcpyDeviceToDevice, c->stream));
+        if (c->rc_nanch) HIPCHK(c, hipMemcpyAsync(nanch.p, canch.p, 8 * (size_t)c->rc_nanch, hipMemcpyDeviceToDevice, c->stream));
+        if (nr) HIPCHK(c, c->stager.h2d(nstats.p, hs.data(), sizeof(bella_consensus_read) * (size_t)nr, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {
+        if (njobs >= 0x7FFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "recorrect: fewer than 2^30 overlap records");
+        const uint32_t nj_all = (uint32_t)njobs;
+        const size_t npw = (size_t)(total / 16 + 1);
+        TmpBuf recs, upk, table, votes, counts, jbase, live, pend, next, bytes, pre, ctl, touch;
+        int rc = upload_records(c, recs);
+        if (rc) return rc;
+        ENSURE(c, upk, 4 * npw);
+        const size_t tbytes = (size_t)total * kPileCounters * 4;
+        if (ensure_bytes(c, table, tbytes))
+            return fail(c, BELLA_ERR_NOMEM, "the correction round's table needs %zu bytes of device memory (36 per base of %llu corrected bases) and they do not fit", tbytes,
+                        (unsigned long long)total);
+        ENSURE(c, jrec, sizeof(bella_recorrect_job) * (size_t)njobs); ENSURE(c, jbase, sizeof(ReaJob) * (size_t)njobs);
+        ENSURE(c, live, (size_t)njobs); ENSURE(c, touch, (size_t)njobs);
+        ENSURE(c, pend, 4 * (size_t)njobs); ENSURE(c, next, 4 * (size_t)njobs);
+        ENSURE(c, bytes, 8 * ((size_t)njobs + 1)); ENSURE(c, pre, 8 * ((size_t)njobs + 1));
+        ENSURE(c, ctl, 32); ENSURE(c, votes, 8); ENSURE(c, counts, sizeof(RecCounts));
+        uint64_t* const dctl = ptr<uint64_t>(ctl);
+        uint32_t* const dcount = (uint32_t*)(dctl + 2);
+        HIPCHK(c, hipMemsetAsync(table.p, 0, tbytes ? tbytes : 16, c->stream));
+        HIPCHK(c, hipMemsetAsync(votes.p, 0, 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(counts.p, 0, sizeof(RecCounts), c->stream));
+        EventSet ev;
+        if ((rc = ev.create(c, 3))) return rc;
+        const uint32_t* const rpacked = ptr<uint32_t>(c->packed);
+        const uint32_t* const upacked = ptr<uint32_t>(upk);
+        bella_recorrect_job* const djrec = ptr<bella_recorrect_job>(jrec);
+        // ---- placement, and the list of the jobs that take part
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        k_rec_place<<<nblk(njobs), 256, 0, c->stream>>>(ptr<bella_overlap>(recs), (uint32_t)nrec, ptr<uint64_t>(c->roff), ptr<uint64_t>(coffs), ptr<uint64_t>(c->rc_aoff),
+                                                        ptr<uint64_t>(canch), djrec, ptr<ReaJob>(jbase), ptr<uint8_t>(live));
+        KCHK(c);
+        k_rea_pack<<<nblk(npw), 256, 0, c->stream>>>(ptr<uint8_t>(cbases), total, ptr<uint32_t>(upk));
+        KCHK(c);
+        CUB(c, hipcub::DeviceSelect::Flagged, hipcub::CountingInputIterator<uint32_t>(0u), ptr<uint8_t>(live), ptr<uint32_t>(pend), dcount, (int)nj_all, c->stream);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        uint32_t np = 0;
+        HIPCHK(c, hipMemcpyAsync(&np, dcount, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.place_ms = ev_ms(ev.a, ev.b);
+        st.none = njobs - np;
+        live.reset();
+        // ---- DP, walks and votes: band by band, batch by batch
+        size_t mfree = 0, mtotal = 0;
+        HIPCHK(c, hipMemGetInfo(&mfree, &mtotal));
+        const uint64_t budget = std::max<uint64_t>(64ull << 20, std::min<uint64_t>((uint64_t)mfree / 2, 8ull << 30));       // direction bytes of a batch
+        TmpBuf jobs, res, cnt, dirs, scr, ops, vnops, opscan;
+        for (uint32_t B = rp.band0; np; B *= 2) {
+            k_rec_bytes<<<nblk((uint64_t)np + 1), 256, 0, c->stream>>>(ptr<uint32_t>(pend), np, ptr<ReaJob>(jbase), B, ptr<uint64_t>(bytes));
+            KCHK(c);
+            CUB(c, hipcub::DeviceScan::ExclusiveSum, ptr<uint64_t>(bytes), ptr<uint64_t>(pre), (int)(np + 1), c->stream);
+            uint64_t band_bytes = 0;
+            HIPCHK(c, hipMemcpyAsync(&band_bytes, ptr<uint64_t>(pre) + np, 8, hipMemcpyDeviceToHost, c->stream));
+            // (the wide kernel keeps two rows of B ints per job in scratch: a batch's scratch stays within the budget too)
+            const uint32_t maxjobs = B > kTrRegBand ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kRecMaxBatch, budget / (8ull * B))) : kRecMaxBatch;
+            for (uint32_t b0 = 0; b0 < np;) {
+                k_rec_cut<<<1, 64, 0, c->stream>>>(ptr<uint64_t>(pre), np, b0, budget, maxjobs, dctl);
+                KCHK(c);
+                uint64_t cut[2] = {0, 0};
+                HIPCHK(c, hipMemcpyAsync(cut, dctl, 16, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                const uint32_t b1 = (uint32_t)cut[0], nj = b1 - b0;
+                const uint64_t dbytes = cut[1];
+                if (b1 <= b0 || b1 > np) return fail(c, BELLA_ERR_STATE, "recorrect: a batch [%u, %u) of %u pending jobs", b0, b1, np);
+                ENSURE(c, jobs, sizeof(ReaJob) * (size_t)nj); ENSURE(c, res, sizeof(ReaRes) * (size_t)nj); ENSURE(c, cnt, sizeof(ReaCnt) * (size_t)nj);
+                ENSURE(c, vnops, 4 * ((size_t)nj + 1)); ENSURE(c, opscan, 8 * ((size_t)nj + 1));
+                if (ensure_bytes(c, dirs, (size_t)dbytes))
+                    return fail(c, BELLA_ERR_NOMEM, "recorrect: %llu direction bytes for a batch of %u jobs do not fit", (unsigned long long)dbytes, nj);
+                if (B > kTrRegBand) ENSURE(c, scr, 8 * (size_t)nj * B);
+                st.dir_bytes_peak = std::max<uint64_t>(st.dir_bytes_peak, dbytes);
+                ++st.batches;
+                k_rec_gather<<<nblk(nj), 256, 0, c->stream>>>(ptr<uint32_t>(pend), b0, nj, ptr<ReaJob>(jbase), ptr<uint64_t>(pre), B, ptr<ReaJob>(jobs));
+                KCHK(c);
+                HIPCHK(c, hipEventRecord(ev.a, c->stream));
+                const unsigned grid = nblk((uint64_t)nj * 64, kTraceBlock);
+                if (B == 256) k_rea_dp<4><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
+                else if (B == 512) k_rea_dp<8><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
+                else if (B == 1024) k_rea_dp<16><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
+                else k_rea_dp_wide<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<ReaRes>(res));
+                KCHK(c);
+                HIPCHK(c, hipEventRecord(ev.b, c->stream));
+                k_rea_count<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
+                KCHK(c);
+                k_rec_settle<<<nblk((uint64_t)nj + 1), 256, 0, c->stream>>>(ptr<uint32_t>(pend), b0, nj, ptr<ReaRes>(res), ptr<ReaCnt>(cnt), B, rp.band_max, rp.min_identity, djrec,
+                                                                           ptr<uint8_t>(touch), ptr<uint32_t>(vnops), ptr<RecCounts>(counts));
+                KCHK(c);
+                HIPCHK(c, hipEventRecord(ev.d, c->stream));
+                if ((rc = scan_u32_to_u64(c, ptr<uint32_t>(vnops), ptr<uint64_t>(opscan), (uint64_t)nj + 1))) return rc;
+                uint64_t nops = 0;
+                HIPCHK(c, hipMemcpyAsync(&nops, ptr<uint64_t>(opscan) + nj, 8, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                st.dp_ms += ev_ms(ev.a, ev.b);
+                st.walk_ms += ev_ms(ev.b, ev.d);
+                if (nops) {
+                    ENSURE(c, ops, 4 * (size_t)nops);
+                    k_rec_opoff<<<nblk(nj), 256, 0, c->stream>>>(ptr<uint32_t>(pend), b0, nj, ptr<uint32_t>(vnops), ptr<uint64_t>(opscan),
+                                                                 rp.keep_ops ? (uint64_t)out.ops.size() : ~0ull, ptr<ReaJob>(jobs), djrec);
+                    KCHK(c);
+                    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+                    k_rea_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
+                    KCHK(c);
+                    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+                    k_rea_vote<<<nblk((uint64_t)nj * 64, kPileBlock), kPileBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaCnt>(cnt), nj, ptr<uint32_t>(ops), rpacked,
+                                                                                                 ptr<uint32_t>(table), ptr<unsigned long long>(votes));
+                    KCHK(c);
+                    HIPCHK(c, hipEventRecord(ev.d, c->stream));
+                    if (rp.keep_ops) {
+                        const size_t at = out.ops.size();
+                        out.ops.resize(at + (size_t)nops);
+                        HIPCHK(c, c->stager.d2h(out.ops.data() + at, ops.p, 4 * (size_t)nops, c->stream));
+                    }
+                    HIPCHK(c, hipStreamSynchronize(c->stream));
+                    st.walk_ms += ev_ms(ev.a, ev.b);
+                    st.vote_ms += ev_ms(ev.b, ev.d);
+                }
+                b0 = b1;
+            }
+            st.dp_cells += 4 * band_bytes;                            // (n B / 4 bytes per job)
+            if (B >= rp.band_max) break;
+            CUB(c, hipcub::DeviceSelect::Flagged, ptr<uint32_t>(pend), ptr<uint8_t>(touch), ptr<uint32_t>(next), dcount, (int)np, c->stream);
+            HIPCHK(c, hipMemcpyAsync(&np, dcount, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            pend.swap(next);
+        }
+        dirs.reset(); scr.reset(); ops.reset(); jbase.reset(); pend.reset(); next.reset(); bytes.reset(); pre.reset(); touch.reset();
+        RecCounts hc{};
+        HIPCHK(c, hipMemcpyAsync(&st.votes, votes.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&hc, counts.p, sizeof(RecCounts), hipMemcpyDeviceToHost, c->stream));
+        if (rp.keep_ops) {
+            out.table.resize((size_t)total * kPileCounters);
+            HIPCHK(c, c->stager.d2h(out.table.data(), table.p, tbytes, c->stream));
+        }
+        // ---- consensus: every current sequence a read whose own bases are the sequence that was aligned against; the new anchors
+        TmpBuf emit, scan;
+        ENSURE(c, emit, (size_t)total + 1); ENSURE(c, scan, 8 * ((size_t)total + 1));
+        HIPCHK(c, hipMemsetAsync(nstats.p, 0, nst, c->stream));
+        HIPCHK(c, hipMemsetAsync(ptr<uint8_t>(emit) + total, 0, 1, c->stream));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        if (total) {                                                  // (every current sequence empty: the jobs are all NONE, nothing is decided)
+            k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(table), upacked, ptr<uint64_t>(coffs), nr, total, rp.min_depth, ptr<uint8_t>(emit),
+                                                              ptr<bella_consensus_read>(nstats));
+            KCHK(c);
+        }
+        {
+            hipcub::TransformInputIterator<uint64_t, EmitCount, const uint8_t*> it(ptr<uint8_t>(emit), EmitCount());
+            CUB(c, hipcub::DeviceScan::ExclusiveSum, it, ptr<uint64_t>(scan), (int)(total + 1), c->stream);
+        }
+        HIPCHK(c, hipMemcpyAsync(&nout, ptr<uint64_t>(scan) + total, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.band_capped = hc.band_capped; st.low_identity = hc.low_identity; st.voted = hc.voted;
+        ENSURE(c, nbases, (size_t)nout);
+        if (total) {
+            k_cons_write<<<nblk(total), 256, 0, c->stream>>>(ptr<uint8_t>(emit), ptr<uint64_t>(scan), total, ptr<uint8_t>(nbases));
+            KCHK(c);
+        }
+        k_cons_reads<<<nblk((uint64_t)nr + 1), 256, 0, c->stream>>>(ptr<uint64_t>(coffs), ptr<uint64_t>(scan), nr, ptr<uint64_t>(noffs), ptr<bella_consensus_read>(nstats));
+        KCHK(c);
+        k_rec_anchors<<<nblk(c->rc_nanch), 256, 0, c->stream>>>(ptr<uint64_t>(coffs), ptr<uint64_t>(scan), ptr<uint64_t>(c->rc_aoff), ptr<uint64_t>(canch), nr, c->rc_nanch,
+                                                              ptr<uint64_t>(nanch));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        HIPCHK(c, c->stager.d2h(hs.data(), nstats.p, sizeof(bella_consensus_read) * (size_t)nr, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.decide_ms = ev_ms(ev.a, ev.b);
+        for (uint32_t r = 0; r < nr; ++r) { st.substituted += hs[r].substituted; st.deleted += hs[r].deleted; st.inserted += hs[r].inserted; }
+    }
+    st.bases_after = nout;
+    out.stats = st;
+    out.total = nout;
+    out.njobs = njobs;
+    nbases.give_to(c->rc_out); noffs.give_to(c->rc_offs); nstats.give_to(c->rc_stats); nanch.give_to(c->rc_anch); jrec.give_to(c->rc_jobs);
+    c->as.recorrect = std::move(out);
+    made(c, RECORRECT);
+    if (total_bases) *total_bases = nout;
+    return 0;
+}
+
+int bella_hip_get_recorrected(bella_ctx* c, uint64_t* offsets, uint8_t* bases, bella_consensus_read* stats) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, RECORRECT)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (offsets) HIPCHK(c, c->stager.d2h(offsets, c->rc_offs.p, 8 * ((size_t)c->nreads + 1), c->stream));
+    if (bases && c->as.recorrect.total) HIPCHK(c, c->stager.d2h(bases, c->rc_out.p, (size_t)c->as.recorrect.total, c->stream));
+    if (stats && c->nreads) HIPCHK(c, c->stager.d2h(stats, c->rc_stats.p, sizeof(bella_consensus_read) * (size_t)c->nreads, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bella_hip_get_recorrect_jobs(bella_ctx* c, uint64_t* njobs, bella_recorrect_job* out) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, RECORRECT)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t n = c->as.recorrect.njobs;
+    if (njobs) *njobs = n;
+    if (out && n) {
+        HIPCHK(c, c->stager.d2h(out, c->rc_jobs.p, sizeof(bella_recorrect_job) * (size_t)n, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int bella_hip_get_recorrect_ops(bella_ctx* c, uint64_t* nops, uint32_t* ops, uint32_t* table) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, RECORRECT)) return r;
+    if (nops) *nops = c->as.recorrect.ops.size();
+    copy_out(ops, c->as.recorrect.ops);
+    copy_out(table, c->as.recorrect.table);
+    return 0;
+}
+
+int bella_hip_get_recorrect_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    return get_stats(c, RECORRECT, out, struct_size, [](const StageState& a) { return a.recorrect.stats; });
+}
+
+int bella_hip_get_recorrect_anchors(bella_ctx* c, uint64_t* offsets, uint64_t* anchors) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, CONS)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const Buf& a = has(c, RECORRECT) ? c->rc_anch : c->cons_anch;
+    if (offsets) HIPCHK(c, c->stager.d2h(offsets, c->rc_aoff.p, 8 * ((size_t)c->nreads + 1), c->stream));
+    if (anchors && c->rc_nanch) HIPCHK(c, c->stager.d2h(anchors, a.p, 8 * (size_t)c->rc_nanch, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,

@@ -130,14 +130,17 @@ struct StageOpts {
     const char* trimmed_reads = nullptr;              // the clipped reads as FASTA, in input order, without the uncovered ones
     int cut_weak = 0;                // weak-overlap removal after the tip clipping and the bubble popping: weak_steps + 1 cuts with the
     uint32_t weak_min = 500, weak_max = 700, weak_steps = 2;   // ratio rising from weak_min to weak_max permille, tips and bubbles again after each that cut
+    uint32_t correct_rounds = 1;     // correction rounds: correct_rounds - 1 rounds follow the consensus, each aligning the partners'
+    uint32_t correct_band = 512, correct_min_identity = 700;    // raw clips against the corrected reads of the round before; the file carries the last round
     bool graph() const { return gfa || unitigs || unitigs_fasta; }
     bool pileup() const { return correct || polish; }
+    bool records() const { return graph() || (correct && correct_rounds > 1); }      // every stage adds its traced passed pairs as overlap records
 };
 
-// The string graph after the last stage: the records of the contexts 1 .. N-1 (each added its own columns' pairs) are gathered into
-// context 0 in the single-context order -- column ascending; a column's pairs all come from one context, in its order -- then the build
-// on the device and the GFA file.
-inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* const* names, const uint32_t* lens) {
+// After the last stage: the records of the contexts 1 .. N-1 (each added its own columns' pairs) are gathered into context 0 in the
+// single-context order -- column ascending; a column's pairs all come from one context, in its order.  Once, before the correction rounds
+// and the graph.
+inline void gather_records(std::vector<Worker>& W, const StageOpts& o) {
     bella_ctx* const c0 = W[0].ctx;
     if (o.N > 1) {
         std::vector<bella_overlap> all;
@@ -153,6 +156,11 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
         check(c0, bella_hip_graph_reset(c0), "bella_hip_graph_reset");
         check(c0, bella_hip_graph_add_overlaps(c0, all.data(), all.size()), "bella_hip_graph_add_overlaps");
     }
+}
+
+// The string graph from context 0's (gathered) records: the build on the device and the GFA file.
+inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* const* names, const uint32_t* lens) {
+    bella_ctx* const c0 = W[0].ctx;
     std::vector<bella_read_clip> clips;                              // --trim: on context 0, after the records are gathered: -m and -g change nothing
     if (o.trim) {
         bella_graph_trim_params tp;
@@ -386,14 +394,36 @@ inline void write_corrected(std::vector<Worker>& W, const StageOpts& o, const ch
     RawBuf<uint8_t> bases;
     bases.resize((size_t)total);
     std::vector<bella_consensus_read> st(nreads);
-    check(c0, bella_hip_get_consensus(c0, offs.data(), bases.data(), st.data()), "bella_hip_get_consensus");
-    const int wrc = bella_hip_write_fasta(o.correct, nreads, names, offs.data(), bases.data(), 0);
-    if (wrc) check(nullptr, wrc, "bella_hip_write_fasta");
+    check(c0, bella_hip_get_consensus(c0, offs.data(), o.correct_rounds > 1 ? nullptr : bases.data(), st.data()), "bella_hip_get_consensus");
+    if (o.correct_rounds <= 1) {
+        const int wrc = bella_hip_write_fasta(o.correct, nreads, names, offs.data(), bases.data(), 0);
+        if (wrc) check(nullptr, wrc, "bella_hip_write_fasta");
+    }
     uint64_t sub = 0, del = 0, ins = 0, cov = 0, all = 0;
     for (const auto& s : st) { sub += s.substituted; del += s.deleted; ins += s.inserted; cov += s.covered; all += s.len_before; }
     const std::string CorrectedReads = std::to_string(nreads) + " reads, " + std::to_string(all) + " -> " + std::to_string(total) + " bases, " + std::to_string(cov) +
                                        " positions covered, " + std::to_string(sub) + " substituted, " + std::to_string(del) + " deleted, " + std::to_string(ins) + " inserted";
     BELLA_HIP_LOGT(o.tag, CorrectedReads);
+    if (o.correct_rounds <= 1) return;
+    // correction rounds on context 0's gathered records; the file carries the last round
+    for (uint32_t round = 2; round <= o.correct_rounds; ++round) {
+        bella_recorrect_params rp{};
+        rp.struct_size = (uint32_t)sizeof(rp);
+        rp.band0 = o.correct_band; rp.band_max = o.correct_band > BELLA_RECORRECT_DEFAULT_BAND_MAX ? o.correct_band : BELLA_RECORRECT_DEFAULT_BAND_MAX;
+        rp.min_identity = o.correct_min_identity; rp.min_depth = o.min_depth;
+        check(c0, bella_hip_recorrect(c0, &rp, &total), "bella_hip_recorrect");
+        bella_recorrect_stats rs{};
+        check(c0, bella_hip_get_recorrect_stats(c0, &rs, sizeof(rs)), "bella_hip_get_recorrect_stats");
+        const std::string Recorrected = "round " + std::to_string(round) + ": " + std::to_string(rs.voted) + " of " + std::to_string(rs.jobs) + " alignments voted (" +
+                                        std::to_string(rs.none) + " without a target, " + std::to_string(rs.band_capped) + " band-capped, " + std::to_string(rs.low_identity) +
+                                        " of low identity), " + std::to_string(rs.bases_before) + " -> " + std::to_string(rs.bases_after) + " bases, " +
+                                        std::to_string(rs.substituted) + " substituted, " + std::to_string(rs.deleted) + " deleted, " + std::to_string(rs.inserted) + " inserted";
+        BELLA_HIP_LOGT(o.tag, Recorrected);
+    }
+    bases.resize((size_t)total);
+    check(c0, bella_hip_get_recorrected(c0, offs.data(), bases.data(), nullptr), "bella_hip_get_recorrected");
+    const int wrc = bella_hip_write_fasta(o.correct, nreads, names, offs.data(), bases.data(), 0);
+    if (wrc) check(nullptr, wrc, "bella_hip_write_fasta");
 }
 
 // Stage plan (overlap.hpp:365-404,682-710), passes, alignment, output.  W[g].ctx holds the operands, laid out for the output columns
@@ -434,8 +464,8 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
                 if (o.pileup()) check(w.ctx, bella_hip_trace_pairs_pileup(w.ctx, &p, o.trace_band, o.cigar ? 1 : 0, &ntr, &nops), "bella_hip_trace_pairs_pileup");
                 else if (o.cigar) check(w.ctx, bella_hip_trace_pairs(w.ctx, &p, o.trace_band, 1, &ntr, &nops), "bella_hip_trace_pairs");
                 // (--gfa alone: the records are all the graph reads; no run is written or staged)
-                else if (o.graph()) check(w.ctx, bella_hip_trace_pairs_flags(w.ctx, &p, o.trace_band, BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS, &ntr, &nops), "bella_hip_trace_pairs_flags");
-                if (o.graph()) check(w.ctx, bella_hip_graph_add_traced(w.ctx, nullptr), "bella_hip_graph_add_traced");
+                else if (o.records()) check(w.ctx, bella_hip_trace_pairs_flags(w.ctx, &p, o.trace_band, BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS, &ntr, &nops), "bella_hip_trace_pairs_flags");
+                if (o.records()) check(w.ctx, bella_hip_graph_add_traced(w.ctx, nullptr), "bella_hip_graph_add_traced");
                 if (o.cigar) {
                     w.traces.resize(w.nnzc);
                     w.ops.resize(nops);                                       // (host memory: 4 bytes per run; -m stages bound it as they bound the records)
@@ -452,7 +482,7 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         }
     };
     if (o.pileup()) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_pileup_reset(W[(size_t)g].ctx), "bella_hip_pileup_reset"); });
-    if (o.graph()) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_graph_reset(W[(size_t)g].ctx), "bella_hip_graph_reset"); });
+    if (o.records()) on_all(N, [&](int g) { check(W[(size_t)g].ctx, bella_hip_graph_reset(W[(size_t)g].ctx), "bella_hip_graph_reset"); });
     CallStats& cs = last_call_stats();
     cs = CallStats();
     const double free_memory = o.total_memory_mb * 1024 * 1024;               // estimateMemory, overlap.hpp:365-404 (no LINUX/OSX define)
@@ -561,6 +591,7 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         BELLA_HIP_LOGT(tag, OutputtingTime);
     }
     if (o.pileup()) merge_pileups(W, o, lens);
+    if (o.records()) gather_records(W, o);
     if (o.correct) write_corrected(W, o, names);
     if (o.graph()) write_graph(W, o, names, lens);
     cs.nreads = nreads; cs.stages = stages; cs.contexts = N; cs.nnzc = nnzc;

@@ -18,6 +18,8 @@
 // --paf --cigar: true PAF: every stage traces its passed pairs on the device before it writes them.
 // --correct FILE: read correction: every stage's traced pairs vote into a per-read pileup on the device, the
 // consensus of every read goes to FILE as FASTA after the last stage; the main output file is what it is without the option.
+// --correct-rounds N: N - 1 correction rounds follow the consensus, each aligning the raw partners of every traced
+// pair against the corrected reads of the round before; FILE then holds the last round.
 //
 // --polish: unitig consensus: every stage's traced pairs vote as with --correct, the unitigs are polished from
 // the pileup on the device after the last stage; --unitigs / --unitigs-fasta then carry the polished sequences and coordinates.
@@ -52,6 +54,8 @@ struct Options {
     bool estimate = false, skip_alignment = false, paf = false, hopc = false, syncmer = false, help = false, exact = false, cigar = false;
     int trace_band = 0, min_depth = 3;
     bool min_depth_given = false;
+    int correct_rounds = 1, correct_band = 512, correct_min_identity = 700;
+    bool correct_param_given = false;
     int gfa_fuzz = 1000, gfa_max_overhang = 1000, gfa_min_overlap = 1000;
     bool gfa_no_seq = false, gfa_param_given = false;
     int tip_reads = 4, tip_rounds = 3;
@@ -98,6 +102,10 @@ const char* kHelp =
     "      --trace-band arg       first band of the base-level alignments, in diagonals (default: 256; doubled where a path touches it)\n"
     "      --correct arg          corrected reads (FASTA): per-read pileup of the base-level alignments on the device, majority consensus\n"
     "      --min-depth arg        with --correct: votes a position needs before it is changed (default: 3)\n"
+    "      --correct-rounds arg   with --correct: correction rounds (default: 1; at most 4); every round after the first aligns the raw partners of every\n"
+    "                             overlap against the corrected reads of the round before, on the device, and takes the consensus of those alignments\n"
+    "      --correct-band arg     with --correct: the first band of those alignments, a power of two from 256 to 4096 (default: 512)\n"
+    "      --correct-min-identity arg  with --correct: permille of matches below which an alignment does not vote (default: 700)\n"
     "      --gfa arg              string graph (GFA 1): overlap classes, contained reads dropped, transitive reduction, on the device\n"
     "      --gfa-min-overlap arg  with --gfa: shortest overlap that counts (default: 1000)\n"
     "      --gfa-max-overhang arg with --gfa: longest unaligned end of a dovetail or containment (default: 1000)\n"
@@ -147,6 +155,7 @@ Options parse(int argc, char** argv) {
         {"split-count", 0, 1, &o.split_count}, {"hopc", 0, 0, &o.hopc}, {"window", 'w', 1, &o.window}, {"syncmer", 's', 0, &o.syncmer},
         {"upper-freq", 'u', 1, &o.upper}, {"lower-freq", 'l', 1, &o.lower}, {"tuples", 0, 3, &o.tuples}, {"exact-xdrop", 0, 0, &o.exact}, {"cigar", 0, 0, &o.cigar}, {"trace-band", 0, 1, &o.trace_band},
         {"correct", 0, 3, &o.correct}, {"min-depth", 0, 1, &o.min_depth},
+        {"correct-rounds", 0, 1, &o.correct_rounds}, {"correct-band", 0, 1, &o.correct_band}, {"correct-min-identity", 0, 1, &o.correct_min_identity},
         {"gfa", 0, 3, &o.gfa}, {"gfa-fuzz", 0, 1, &o.gfa_fuzz}, {"gfa-max-overhang", 0, 1, &o.gfa_max_overhang}, {"gfa-min-overlap", 0, 1, &o.gfa_min_overlap},
         {"gfa-no-seq", 0, 0, &o.gfa_no_seq},
         {"unitigs", 0, 3, &o.unitigs}, {"unitigs-fasta", 0, 3, &o.unitigs_fasta}, {"tip-reads", 0, 1, &o.tip_reads}, {"tip-rounds", 0, 1, &o.tip_rounds}, {"gfa-clean", 0, 0, &o.gfa_clean},
@@ -192,6 +201,7 @@ Options parse(int argc, char** argv) {
         }
         assign(*sp, val, a);
         if (sp->dst == &o.min_depth) o.min_depth_given = true;
+        if (sp->dst == &o.correct_rounds || sp->dst == &o.correct_band || sp->dst == &o.correct_min_identity) o.correct_param_given = true;
         if (sp->dst == &o.gfa_fuzz || sp->dst == &o.gfa_max_overhang || sp->dst == &o.gfa_min_overlap) o.gfa_param_given = true;
         if (sp->dst == &o.tip_reads || sp->dst == &o.tip_rounds) o.tip_param_given = true;
         if (sp->dst == &o.bubble_reads || sp->dst == &o.bubble_dist || sp->dst == &o.bubble_rounds) o.bubble_param_given = true;
@@ -283,6 +293,10 @@ int main(int argc, char** argv) {
     if (!o.correct.empty() && o.skip_alignment) die("--correct cannot be combined with --skip-alignment (the pileup is made of base-level alignments)");
     if (o.min_depth_given && o.min_depth < 1) die("--min-depth must be at least 1");
     if (o.min_depth_given && o.correct.empty()) die("--min-depth needs --correct");
+    if (o.correct_param_given && o.correct.empty()) die("--correct-rounds, --correct-band and --correct-min-identity need --correct");
+    if (o.correct_rounds < 1 || o.correct_rounds > 4) die("--correct-rounds must be in [1, 4]");
+    if (o.correct_band < 256 || o.correct_band > 4096 || (o.correct_band & (o.correct_band - 1))) die("--correct-band must be a power of two in [256, 4096]");
+    if (o.correct_min_identity < 0 || o.correct_min_identity > 1000) die("--correct-min-identity is in permille: [0, 1000]");
     if (o.kmer < 1 || o.kmer > 32) die("-k must be in [1,32] (one 64-bit word per k-mer, Kmer.hpp:27-28)");
     const std::string outfile = o.output + ".out";                  // main.cpp:113-130
     std::remove(outfile.c_str());
@@ -435,6 +449,7 @@ int main(int argc, char** argv) {
     so.polish = o.polish ? 1 : 0;
     so.polish_min_depth = (uint32_t)o.polish_min_depth;
     so.polish_rounds = (uint32_t)o.polish_rounds; so.realign_band = (uint32_t)o.realign_band; so.realign_min_identity = (uint32_t)o.realign_min_identity; so.realign_circular = o.realign_circular;
+    so.correct_rounds = (uint32_t)o.correct_rounds; so.correct_band = (uint32_t)o.correct_band; so.correct_min_identity = (uint32_t)o.correct_min_identity;
     so.trim = o.trim ? 1 : 0;
     so.trim_depth = (uint32_t)o.trim_depth; so.trim_end_clip = (uint32_t)o.trim_end_clip;
     so.trimmed_reads = o.trimmed_reads.empty() ? nullptr : o.trimmed_reads.c_str();

@@ -768,6 +768,87 @@ int bella_hip_graph_get_realign_placements(bella_ctx* ctx, bella_realign_placeme
 int bella_hip_graph_get_realign_ops(bella_ctx* ctx, uint64_t* nops, uint32_t* ops, uint32_t* table);
 int bella_hip_graph_get_realign_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 
+/* ---- read correction rounds: the partners' raw clips aligned against the corrected read, one more consensus (no
+ * counterpart in the reference) ------------------------------------------------------------------------------------------------------
+ * One ROUND aligns, for every accumulated overlap record, each of the two reads' RAW clips against the CURRENT corrected sequence of the
+ * other read, votes into a nine-counter table in corrected coordinates and applies bella_hip_consensus's rule to every current sequence
+ * as if it were a read.  Round 1 is bella_hip_consensus; round k reads round k - 1.  Everything is an integer; the tests hold a numpy
+ * statement (bella_testkit/recorrect_mirror.py), and the device result equals it.
+ *   Coordinate map.  bella_hip_consensus keeps, per read r of L_r bases, the anchors a_r[j], j = 0 .. ceil(L_r / 256): the offset inside
+ * the corrected read at which raw base min(256 j, L_r) was emitted (its emit scan), so the last anchor is the corrected length; 8 bytes per
+ * 256 bases.  P_r(x), 0 <= x <= L_r, is section 18's P over the segments pos = 256 j, nb = min(256, L_r - 256 j), cpos = a_r[j],
+ * cnb = a_r[j + 1] - a_r[j]: P_r(x) = a_r[j] + (x - 256 j) cnb / nb (floor) with j = floor(x / 256), and P_r(L_r) = the current length.  A
+ * round's new anchor j is its own emit scan at the old anchor j: the anchors stay exact, the interpolation between them is approximate.
+ *   Jobs.  Record x (V = cid, H = rid, strand, [begV, endV) on V, [begH, endH) on H') gives job 2 x (side 0, target V) and 2 x + 1
+ * (side 1, target H):
+ *     2 x,     strand 0: rows H[begH, endH);                              raw window on V [begV, endV)
+ *     2 x,     strand 1: rows the reverse complement of H[L_H - endH, L_H - begH);   raw window on V [begV, endV)
+ *     2 x + 1, strand 0: rows V[begV, endV);                              raw window on H [begH, endH)
+ *     2 x + 1, strand 1: rows the reverse complement of V[begV, endV);    raw window on H [L_H - endH, L_H - begH)
+ * Every record votes, whatever class the graph would give it, two records of one read pair both; the clips of bella_hip_graph_trim are
+ * ignored.  n = the rows, s = P_t(window begin), e = P_t(window end), plen = the target's current length; plen == 0: status NONE.
+ *   Alignment, band rule, statuses (BAND_CAPPED, LOW_IDENTITY, VOTED: the BELLA_REALIGN_* values), votes and consensus: section 18's,
+ * with the target as the voted side -- c = s + floor(((e - s) - n) / 2), cell (i, q) iff -B/2 <= q - i - c < B/2 and 0 <= q <= plen, B from
+ * band0 doubling up to band_max while the walk touches the band's first or last diagonal.  The consensus takes the current sequence's own
+ * bases as b[p] (with their + 1 vote); a read nobody voted on comes out as it went in.
+ *   Limits: one inserted base per junction, plain majority, a fixed centre diagonal, the interpolation between anchors, all current bases
+ * together fewer than 2^31. */
+#define BELLA_RECORRECT_DEFAULT_BAND 512
+#define BELLA_RECORRECT_DEFAULT_BAND_MAX 4096
+#define BELLA_RECORRECT_DEFAULT_MIN_IDENTITY 700
+#define BELLA_RECORRECT_ANCHOR_STEP 256
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_recorrect_params) of the caller's header (the struct may grow)            */
+    uint32_t band0;               /* a power of two in [256, band_max]; the documented default is 512                      */
+    uint32_t band_max;            /* a power of two <= 262144; 4096                                                        */
+    uint32_t min_identity;        /* permille of '=' among the alignment's columns below which a job does not vote; 700    */
+    uint32_t min_depth;           /* >= 1; 3                                                                               */
+    uint32_t keep_ops;            /* tests: != 0 keeps the voters' runs and the table for bella_hip_get_recorrect_ops      */
+} bella_recorrect_params;
+typedef struct {
+    uint32_t record, side;        /* job 2 record + side; side 0: the target is V, 1: the target is H                      */
+    uint32_t target, query;       /* reads                                                                                 */
+    uint32_t orient;              /* 1: the rows are the query clip reverse-complemented (the record's strand)             */
+    uint32_t status;              /* BELLA_REALIGN_NONE, _VOTED, _BAND_CAPPED or _LOW_IDENTITY                             */
+    uint32_t qbeg, qend;          /* the query clip, on the query read as given                                            */
+    int64_t s, e;                 /* the window expected for the clip on the target's current sequence                     */
+    uint32_t band;                /* the last band the job was aligned with (0: never aligned)                             */
+    uint32_t n_eq, n_x, n_ins, n_del;
+    int32_t score;
+    int64_t q_begin, q_end;       /* the junctions of the target's current sequence the alignment spans                    */
+    uint64_t op_off;              /* keep_ops: first run among the kept runs                                               */
+    uint32_t nops, pad;
+} bella_recorrect_job;
+/* What the last round did.  A sized struct: bella_hip_get_recorrect_stats writes at most struct_size bytes. */
+typedef struct {
+    uint32_t round;               /* 2 = the first round after bella_hip_consensus                                         */
+    uint32_t batches;             /* DP launches' batches                                                                  */
+    uint64_t jobs, none, band_capped, low_identity, voted;
+    uint64_t dp_cells;            /* rows x band summed over every DP that ran                                             */
+    uint64_t dir_bytes_peak;      /* the largest batch's direction bytes                                                   */
+    uint64_t votes;
+    uint64_t bases_before, bases_after;
+    uint64_t substituted, deleted, inserted;
+    double place_ms, dp_ms, walk_ms, vote_ms, decide_ms;      /* device time between events                               */
+} bella_recorrect_stats;
+/* One round on the device, over the records accumulated at the time of the call.  params == NULL: the defaults.  BELLA_ERR_STATE without a
+ * consensus; BELLA_ERR_BAD_ARG for a band that is no power of two or out of range, min_depth < 1, min_identity > 1000, a struct_size too
+ * small; BELLA_ERR_NOMEM when the table (36 bytes per current base) does not fit.  The result replaces the last round's; a failed round
+ * leaves the round before; whatever drops the consensus (a new consensus, a change of the table, new reads) drops the rounds.
+ * bella_hip_get_consensus keeps returning round 1.  Zero records launch nothing and return the input.  total_bases may be NULL. */
+int bella_hip_recorrect(bella_ctx* ctx, const bella_recorrect_params* params, uint64_t* total_bases);
+/* offsets[nreads + 1] into bases[total_bases] (upper-case ASCII); stats[nreads] relative to the round's input.  Any pointer may be NULL. */
+int bella_hip_get_recorrected(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases, bella_consensus_read* stats);
+/* *njobs = 2 x the records of the last round; out (nullable) receives them. */
+int bella_hip_get_recorrect_jobs(bella_ctx* ctx, uint64_t* njobs, bella_recorrect_job* out);
+/* tests: *nops = the kept runs; ops (nullable) receives them, table (nullable) the round's counters (9 uint32 per base of the round's
+ * input).  Both are empty unless the round ran with keep_ops. */
+int bella_hip_get_recorrect_ops(bella_ctx* ctx, uint64_t* nops, uint32_t* ops, uint32_t* table);
+int bella_hip_get_recorrect_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+/* tests: the anchors of the newest sequences (the last round's, or the consensus's): offsets[nreads + 1] into anchors[]; either may be
+ * NULL.  BELLA_ERR_STATE without a consensus. */
+int bella_hip_get_recorrect_anchors(bella_ctx* ctx, uint64_t* offsets, uint64_t* anchors);
+
 /* ---- coverage trimming: clip every read to its longest well-covered stretch before the graph (no counterpart in
  * the reference; the stage is miniasm's ma_hit_sub / ma_hit_cut) ---------------------------------------------------------------------
  * Notation of the string graph section.  A record whose e1 - b1 or e2 - b2 is below min_span gives nothing.  Every other record gives

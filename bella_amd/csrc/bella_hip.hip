@@ -292,6 +292,7 @@ struct bella_ctx {
     uint32_t tune_compact_b = 0;         // BELLA_TUNE_COMPACT_B: 0 the layout drops the B' entries that have no later read, 1 keeps them
     uint32_t tune_product_entries = 0;   // BELLA_TUNE_PRODUCT_ENTRIES: 0 one B' entry per product when it stays within 12 B per owned nonzero, 1 never, 2 always
     uint32_t tune_order_split = kOrderOneLaunchMax;   // BELLA_TUNE_ORDER_SPLIT: owned columns of a pass above which k_order_wave runs as two instances
+    uint64_t tune_round_budget = 0;      // BELLA_TUNE_ROUND_BUDGET: direction bytes of a batch of a realignment / correction round; 0 by the free memory (round_budget)
     uint32_t tune_dist_layout = 2;       // BELLA_TUNE_DIST_LAYOUT: bella_hip_allgather_panels forms A' by k-mer id ranges over the communicator's ranks
                                          // (1: always, 0: never, 2 = default: on the in-process transport only -- over RCCL the path has not run on
                                          // more than one device yet, and its extra 20 B per nonzero of traffic want a measurement first)
@@ -1080,6 +1081,7 @@ int bella_hip_set_tuning(bella_ctx* c, uint32_t what, const uint64_t* values, ui
         case BELLA_TUNE_ORDER_SPLIT:
             c->tune_order_split = n ? (uint32_t)(values[0] < 0xFFFFFFFFull ? values[0] : 0xFFFFFFFFull) : kOrderOneLaunchMax;
             return 0;
+        case BELLA_TUNE_ROUND_BUDGET: c->tune_round_budget = n ? values[0] : 0; return 0;
     }
     return fail(c, BELLA_ERR_BAD_ARG, "unknown tuning parameter %u", what);
 }
@@ -4069,10 +4071,127 @@ int bella_hip_get_trace_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     return put_sized(out, struct_size, c->trace_stats);
 }
 
+}  // extern "C"
+
 // ---- read correction (pileup.hpp) ----------------------------------------------------------------------------
+namespace {
 struct EmitCount {
     __host__ __device__ uint64_t operator()(const uint8_t& v) const { return (uint64_t)(v & 3u); }
 };
+
+// A vote table into the sequence it emits, for the consensus and for the rounds of sections 18 and 20: `table` is about the `nseq`
+// sequences of `packed` that begin at `offs` (`total` bases); the emitted bases go to `out` (*nout of them), their offsets to `noffs`,
+// the per-sequence statistics to `stats`.  Waits for the device once, to size `out`.  `scan` stays alive: where every old base went,
+// which the callers' own kernels read afterwards.
+int consensus_tail(bella_ctx* c, const Buf& table, const uint32_t* packed, const Buf& offs, uint32_t nseq, uint64_t total, uint32_t min_depth, Buf& emit, Buf& scan,
+                   Buf& stats, Buf& noffs, Buf& out, uint64_t* nout) {
+    const size_t nst = sizeof(bella_consensus_read) * std::max<size_t>(nseq, 1);
+    ENSURE(c, emit, (size_t)total + 1); ENSURE(c, scan, 8 * ((size_t)total + 1));
+    ENSURE(c, noffs, 8 * ((size_t)nseq + 1)); ENSURE(c, stats, nst);
+    HIPCHK(c, hipMemsetAsync(stats.p, 0, nst, c->stream));
+    HIPCHK(c, hipMemsetAsync(ptr<uint8_t>(emit) + total, 0, 1, c->stream));
+    if (total) {
+        k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(table), packed, ptr<uint64_t>(offs), nseq, total, min_depth, ptr<uint8_t>(emit),
+                                                          ptr<bella_consensus_read>(stats));
+        KCHK(c);
+    }
+    {
+        hipcub::TransformInputIterator<uint64_t, EmitCount, const uint8_t*> it(ptr<uint8_t>(emit), EmitCount());
+        CUB(c, hipcub::DeviceScan::ExclusiveSum, it, ptr<uint64_t>(scan), (int)(total + 1), c->stream);
+    }
+    HIPCHK(c, hipMemcpyAsync(nout, ptr<uint64_t>(scan) + total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ENSURE(c, out, (size_t)*nout);
+    if (total) {
+        k_cons_write<<<nblk(total), 256, 0, c->stream>>>(ptr<uint8_t>(emit), ptr<uint64_t>(scan), total, ptr<uint8_t>(out));
+        KCHK(c);
+    }
+    k_cons_reads<<<nblk((uint64_t)nseq + 1), 256, 0, c->stream>>>(ptr<uint64_t>(offs), ptr<uint64_t>(scan), nseq, ptr<uint64_t>(noffs), ptr<bella_consensus_read>(stats));
+    KCHK(c);
+    return 0;
+}
+
+// ---- what the realignment rounds (section 18) and the correction rounds (section 20) share -----------------------------------------------
+int check_round_params(bella_ctx* c, const char* who, uint32_t band0, uint32_t band_max, uint32_t min_depth, uint32_t min_identity) {
+    auto pow2 = [](uint32_t x) { return x && !(x & (x - 1)); };
+    if (!pow2(band0) || !pow2(band_max) || band0 < kTrMinBand || band_max > kTrMaxBand || band0 > band_max)
+        return fail(c, BELLA_ERR_BAD_ARG, "%s: band0 and band_max must be powers of two with 256 <= band0 <= band_max <= 262144", who);
+    if (min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
+    if (min_identity > 1000) return fail(c, BELLA_ERR_BAD_ARG, "min_identity is in permille: at most 1000");
+    return 0;
+}
+
+// direction bytes of a batch: BELLA_TUNE_ROUND_BUDGET as given, else half of what is free, 64 MB .. 8 GB
+int round_budget(bella_ctx* c, uint64_t* budget) {
+    size_t mfree = 0, mtotal = 0;
+    if (!c->tune_round_budget) HIPCHK(c, hipMemGetInfo(&mfree, &mtotal));
+    *budget = c->tune_round_budget ? c->tune_round_budget : std::max<uint64_t>(64ull << 20, std::min<uint64_t>((uint64_t)mfree / 2, 8ull << 30));
+    return 0;
+}
+
+// jobs of a batch at most: the wide kernel keeps two rows of B ints per job in scratch, and a batch's scratch stays within the budget too
+uint32_t round_max_jobs(uint32_t B, uint64_t budget) {
+    return B > kTrRegBand ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kRecMaxBatch, budget / (8ull * B))) : kRecMaxBatch;
+}
+
+// A round's batches on the device.  The round cuts a batch -- `nj` jobs of band `B` in `jobs`, `dbytes` direction bytes -- and owns what
+// happens between the two steps: the read-backs, what becomes of every job, the jobs' op_off.
+struct RoundBatches {
+    bella_ctx* c;
+    const char *who, *unit;                                           // for the messages: "realign" and its "reads", "recorrect" and its "jobs"
+    EventSet& ev;
+    const uint32_t *rpacked, *upacked;
+    uint32_t* table;
+    unsigned long long* votes;
+    bool keep_ops;
+    std::vector<uint32_t>& kept;                                      // ... where the ops of every batch are appended
+    double &dp_ms, &walk_ms, &vote_ms;
+    TmpBuf jobs, res, cnt, dirs, scr, ops;
+
+    // DP and the counting walk.  The caller launches what is its own behind them, records ev.d, reads back, waits, and calls counted().
+    int dp_count(uint32_t nj, uint32_t B, uint64_t dbytes) {
+        ENSURE(c, res, sizeof(ReaRes) * (size_t)nj); ENSURE(c, cnt, sizeof(ReaCnt) * (size_t)nj);
+        if (ensure_bytes(c, dirs, (size_t)dbytes))
+            return fail(c, BELLA_ERR_NOMEM, "%s: %llu direction bytes for a batch of %u %s do not fit", who, (unsigned long long)dbytes, nj, unit);
+        if (B > kTrRegBand) ENSURE(c, scr, 8 * (size_t)nj * B);
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        const unsigned grid = nblk((uint64_t)nj * 64, kTraceBlock);
+        if (B == 256) k_rea_dp<4><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
+        else if (B == 512) k_rea_dp<8><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
+        else if (B == 1024) k_rea_dp<16><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
+        else k_rea_dp_wide<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<ReaRes>(res));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        k_rea_count<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
+        KCHK(c);
+        return 0;
+    }
+    void counted() { dp_ms += ev_ms(ev.a, ev.b); walk_ms += ev_ms(ev.b, ev.d); }
+
+    // the writing walk and the votes of a batch with ops (the jobs' op_off set); waits for the device
+    int write_vote(uint32_t nj, uint64_t nops) {
+        ENSURE(c, ops, 4 * (size_t)nops);
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        k_rea_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        k_rea_vote<<<nblk((uint64_t)nj * 64, kPileBlock), kPileBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaCnt>(cnt), nj, ptr<uint32_t>(ops), rpacked, table, votes);
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.d, c->stream));
+        if (keep_ops) {
+            const size_t at = kept.size();
+            kept.resize(at + (size_t)nops);
+            HIPCHK(c, c->stager.d2h(kept.data() + at, ops.p, 4 * (size_t)nops, c->stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        walk_ms += ev_ms(ev.a, ev.b);
+        vote_ms += ev_ms(ev.b, ev.d);
+        return 0;
+    }
+};
+}  // namespace
+
+extern "C" {
 
 int bella_hip_pileup_reset(bella_ctx* c) {
     if (!c) return BELLA_ERR_BAD_ARG;
@@ -4152,32 +4271,9 @@ int bella_hip_consensus(bella_ctx* c, const bella_consensus_params* params, uint
     const uint64_t total = c->total_bases;
     const uint32_t nr = c->nreads;
     if (total >= 0x7FFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "consensus: the read set must have fewer than 2^31 bases");
-    ENSURE(c, c->cons_emit, (size_t)total + 1);
-    ENSURE(c, c->cons_scan, 8 * ((size_t)total + 1));
-    ENSURE(c, c->cons_offs, 8 * ((size_t)nr + 1));
-    ENSURE(c, c->cons_stats, sizeof(bella_consensus_read) * std::max<size_t>(nr, 1));
-    HIPCHK(c, hipMemsetAsync(c->cons_stats.p, 0, sizeof(bella_consensus_read) * std::max<size_t>(nr, 1), c->stream));
-    HIPCHK(c, hipMemsetAsync(ptr<uint8_t>(c->cons_emit) + total, 0, 1, c->stream));
-    if (total) {
-        k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(c->pile), ptr<uint32_t>(c->packed), ptr<uint64_t>(c->roff), nr, total, cp.min_depth,
-                                                          ptr<uint8_t>(c->cons_emit), ptr<bella_consensus_read>(c->cons_stats));
-        KCHK(c);
-    }
-    {
-        hipcub::TransformInputIterator<uint64_t, EmitCount, const uint8_t*> it(ptr<uint8_t>(c->cons_emit), EmitCount());
-        CUB(c, hipcub::DeviceScan::ExclusiveSum, it, ptr<uint64_t>(c->cons_scan), (int)(total + 1), c->stream);
-    }
     uint64_t nout = 0;
-    HIPCHK(c, hipMemcpyAsync(&nout, ptr<uint64_t>(c->cons_scan) + total, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    ENSURE(c, c->cons_out, (size_t)nout);
-    if (total) {
-        k_cons_write<<<nblk(total), 256, 0, c->stream>>>(ptr<uint8_t>(c->cons_emit), ptr<uint64_t>(c->cons_scan), total, ptr<uint8_t>(c->cons_out));
-        KCHK(c);
-    }
-    k_cons_reads<<<nblk((uint64_t)nr + 1), 256, 0, c->stream>>>(ptr<uint64_t>(c->roff), ptr<uint64_t>(c->cons_scan), nr, ptr<uint64_t>(c->cons_offs),
-                                                                 ptr<bella_consensus_read>(c->cons_stats));
-    KCHK(c);
+    if (int r = consensus_tail(c, c->pile, ptr<uint32_t>(c->packed), c->roff, nr, total, cp.min_depth, c->cons_emit, c->cons_scan, c->cons_stats, c->cons_offs, c->cons_out, &nout))
+        return r;
     std::vector<uint64_t> aoff((size_t)nr + 1, 0);
     {   // the anchors of the correction rounds (section 20): where every 256th raw base went, from the scan before it is released
         for (uint32_t r = 0; r < nr; ++r) aoff[r + 1] = aoff[r] + rec_nanchors(c->host_lens[r]);
@@ -4557,6 +4653,28 @@ struct ReadSpans {
         k_trim_spans<<<nblk(nr), 256, 0, c->stream>>>(ptr<bella_read_clip>(clipb), ptr<uint64_t>(c->roff), nr, ptr<uint64_t>(begs), ptr<uint64_t>(ends));
         KCHK(c);
         beg = ptr<uint64_t>(begs); end = ptr<uint64_t>(ends);
+        return 0;
+    }
+};
+
+// The context's unitigs on the device, for the kernels that go along their vertices (polish, realignment): the vertices, the unitig of
+// every vertex slot, where a vertex's bases begin in its unitig, and the unitigs' offsets among the slots and among the bases.
+struct UnitigLayout {
+    TmpBuf verts, slot_utg, pos, uvoff, uboff;
+    std::vector<uint32_t> slot;
+    int upload(bella_ctx* c) {
+        const StageState::Unitigs& u = c->as.unitigs;
+        const size_t nutg = u.len.size(), nseg = u.verts.size();
+        slot.resize(nseg);
+        for (size_t j = 0; j < nutg; ++j)
+            for (uint64_t i = u.voff[j]; i < u.voff[j + 1]; ++i) slot[(size_t)i] = (uint32_t)j;
+        ENSURE(c, verts, 4 * nseg); ENSURE(c, slot_utg, 4 * nseg); ENSURE(c, pos, 8 * nseg);
+        ENSURE(c, uvoff, 8 * (nutg + 1)); ENSURE(c, uboff, 8 * (nutg + 1));
+        HIPCHK(c, c->stager.h2d(verts.p, u.verts.data(), 4 * nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(slot_utg.p, slot.data(), 4 * nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(pos.p, u.pos.data(), 8 * nseg, c->stream));
+        HIPCHK(c, c->stager.h2d(uvoff.p, u.voff.data(), 8 * (nutg + 1), c->stream));
+        HIPCHK(c, c->stager.h2d(uboff.p, u.boff.data(), 8 * (nutg + 1), c->stream));
         return 0;
     }
 };
@@ -5008,33 +5126,26 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
         if (ntiles >= 0x7FFFFFFFull) return fail(c, BELLA_ERR_BAD_ARG, "polish: fewer than 2^31 tiles of unitig positions");
         st.tiles = (uint32_t)ntiles;
         st.table_bytes = total * kPileCounters * 4;
-        std::vector<uint32_t> slot(nseg);
-        for (uint32_t j = 0; j < nutg; ++j)
-            for (uint64_t i = u.voff[j]; i < u.voff[j + 1]; ++i) slot[(size_t)i] = j;
-        TmpBuf verts, slot_utg, pos, uvoff, uboff, gseg, emit, tcnt, tpref, gp, ppos, pnb, poffs, recs, out;
-        ENSURE(c, verts, 4 * (size_t)nseg); ENSURE(c, slot_utg, 4 * (size_t)nseg); ENSURE(c, pnb, 4 * (size_t)nseg);
-        ENSURE(c, pos, 8 * (size_t)nseg); ENSURE(c, ppos, 8 * (size_t)nseg);
+        UnitigLayout ul;
+        int rc = ul.upload(c);
+        if (rc) return rc;
+        TmpBuf gseg, emit, tcnt, tpref, gp, ppos, pnb, poffs, recs, out;
+        ENSURE(c, pnb, 4 * (size_t)nseg); ENSURE(c, ppos, 8 * (size_t)nseg);
         ENSURE(c, gseg, 8 * ((size_t)nseg + 1)); ENSURE(c, gp, 8 * ((size_t)nseg + 1));
-        ENSURE(c, uvoff, 8 * ((size_t)nutg + 1)); ENSURE(c, uboff, 8 * ((size_t)nutg + 1)); ENSURE(c, poffs, 8 * ((size_t)nutg + 1));
+        ENSURE(c, poffs, 8 * ((size_t)nutg + 1));
         ENSURE(c, recs, sizeof(bella_polish_unitig) * (size_t)nutg);
         ENSURE(c, emit, (size_t)(ntiles * kPolTile));
         ENSURE(c, tcnt, 4 * ((size_t)ntiles + 1)); ENSURE(c, tpref, 8 * ((size_t)ntiles + 1));
-        HIPCHK(c, c->stager.h2d(verts.p, u.verts.data(), 4 * (size_t)nseg, c->stream));
-        HIPCHK(c, c->stager.h2d(slot_utg.p, slot.data(), 4 * (size_t)nseg, c->stream));
-        HIPCHK(c, c->stager.h2d(pos.p, u.pos.data(), 8 * (size_t)nseg, c->stream));
-        HIPCHK(c, c->stager.h2d(uvoff.p, u.voff.data(), 8 * ((size_t)nutg + 1), c->stream));
-        HIPCHK(c, c->stager.h2d(uboff.p, u.boff.data(), 8 * ((size_t)nutg + 1), c->stream));
         HIPCHK(c, hipMemsetAsync(recs.p, 0, sizeof(bella_polish_unitig) * (size_t)nutg, c->stream));
         HIPCHK(c, hipMemsetAsync(ptr<uint32_t>(tcnt) + ntiles, 0, 4, c->stream));
-        k_utg_segoff<<<nblk((uint64_t)nseg + 1), 256, 0, c->stream>>>(ptr<uint32_t>(slot_utg), ptr<uint64_t>(pos), ptr<uint64_t>(uboff), nseg, nutg, ptr<uint64_t>(gseg));
+        k_utg_segoff<<<nblk((uint64_t)nseg + 1), 256, 0, c->stream>>>(ptr<uint32_t>(ul.slot_utg), ptr<uint64_t>(ul.pos), ptr<uint64_t>(ul.uboff), nseg, nutg, ptr<uint64_t>(gseg));
         KCHK(c);
         EventSet ev;
-        int rc = ev.create(c, 4);
-        if (rc) return rc;
+        if ((rc = ev.create(c, 4))) return rc;
         ReadSpans spans;
         if ((rc = spans.make(c))) return rc;
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
-        k_pol_decide<<<(uint32_t)ntiles, kPolBlock, 0, c->stream>>>(ptr<uint64_t>(gseg), ptr<uint32_t>(verts), ptr<uint32_t>(slot_utg), nseg, total, ptr<uint64_t>(c->roff),
+        k_pol_decide<<<(uint32_t)ntiles, kPolBlock, 0, c->stream>>>(ptr<uint64_t>(gseg), ptr<uint32_t>(ul.verts), ptr<uint32_t>(ul.slot_utg), nseg, total, ptr<uint64_t>(c->roff),
                                                                     spans.beg, spans.end, ptr<uint32_t>(c->packed), ptr<uint32_t>(c->pile), pp.min_depth, ptr<uint8_t>(emit),
                                                                     ptr<bella_polish_unitig>(recs), ptr<uint32_t>(tcnt));
         KCHK(c);
@@ -5043,7 +5154,7 @@ int bella_hip_graph_polish_unitigs(bella_ctx* c, const bella_polish_params* para
         k_pol_segoff<<<nblk(((uint64_t)nseg + 1) * 64, kPolBlock), kPolBlock, 0, c->stream>>>(ptr<uint64_t>(gseg), nseg, ptr<uint8_t>(emit), ptr<uint64_t>(tpref),
                                                                                               ptr<uint64_t>(gp));
         KCHK(c);
-        k_pol_finish<<<nblk((uint64_t)std::max(nseg, nutg) + 1), 256, 0, c->stream>>>(ptr<uint64_t>(gp), ptr<uint32_t>(slot_utg), ptr<uint64_t>(uvoff), ptr<uint64_t>(uboff), nseg,
+        k_pol_finish<<<nblk((uint64_t)std::max(nseg, nutg) + 1), 256, 0, c->stream>>>(ptr<uint64_t>(gp), ptr<uint32_t>(ul.slot_utg), ptr<uint64_t>(ul.uvoff), ptr<uint64_t>(ul.uboff), nseg,
                                                                                        nutg, ptr<uint64_t>(ppos), ptr<uint32_t>(pnb), ptr<uint64_t>(poffs),
                                                                                        ptr<bella_polish_unitig>(recs));
         KCHK(c);
@@ -5097,11 +5208,7 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
     bella_realign_params rp{};
     rp.band0 = BELLA_REALIGN_DEFAULT_BAND; rp.band_max = BELLA_REALIGN_DEFAULT_BAND_MAX; rp.min_identity = BELLA_REALIGN_DEFAULT_MIN_IDENTITY; rp.min_depth = 3;
     if (int r = take_params(c, rp, params, "bella_realign_params")) return r;
-    auto pow2 = [](uint32_t x) { return x && !(x & (x - 1)); };
-    if (!pow2(rp.band0) || !pow2(rp.band_max) || rp.band0 < kTrMinBand || rp.band_max > kTrMaxBand || rp.band0 > rp.band_max)
-        return fail(c, BELLA_ERR_BAD_ARG, "realign: band0 and band_max must be powers of two with 256 <= band0 <= band_max <= 262144");
-    if (rp.min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
-    if (rp.min_identity > 1000) return fail(c, BELLA_ERR_BAD_ARG, "min_identity is in permille: at most 1000");
+    if (int r = check_round_params(c, "realign", rp.band0, rp.band_max, rp.min_depth, rp.min_identity)) return r;
     if (int r = need(c, POLISH)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const StageState::Unitigs& u = c->as.unitigs;
@@ -5128,9 +5235,6 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
         if (total >= 0x7FFFFFF0ull) return fail(c, BELLA_ERR_BAD_ARG, "realign: the unitigs must have fewer than 2^31 bases");
         for (uint32_t j = 0; j < nutg; ++j)
             if (coffs[j + 1] - coffs[j] >= kReaMaxUnitig) return fail(c, BELLA_ERR_BAD_ARG, "realign: unitig %u has 2^30 bases or more", j);
-        std::vector<uint32_t> slot(nseg);
-        for (uint32_t j = 0; j < nutg; ++j)
-            for (uint64_t i = u.voff[j]; i < u.voff[j + 1]; ++i) slot[(size_t)i] = j;
         const size_t nrec = c->as.records.size();
         const size_t npw = (size_t)(total / 16 + 1);
         // the pack the DP reads: the unitigs as they are, or (section 19) every circular unitig of fewer than 2^29 bases twice in a row
@@ -5149,12 +5253,12 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
         }
         const uint64_t ptotal = poffs[nutg];
         const size_t nppw = (size_t)(ptotal / 16 + 1);
-        TmpBuf recs, verts, slot_utg, pos, nb, dcpos, dcnb, uvoff, uboff, dcoffs, cont, rem, bvert, key, place, ascii, upk, table, votes, dcirc, dpoffs, upk2;
+        TmpBuf recs, nb, dcpos, dcnb, dcoffs, cont, rem, bvert, key, place, ascii, upk, table, votes, dcirc, dpoffs, upk2;
+        UnitigLayout ul;
         int rc = upload_records(c, recs);
-        if (rc) return rc;
-        ENSURE(c, verts, 4 * (size_t)nseg); ENSURE(c, slot_utg, 4 * (size_t)nseg); ENSURE(c, nb, 4 * (size_t)nseg); ENSURE(c, dcnb, 4 * (size_t)nseg);
-        ENSURE(c, pos, 8 * (size_t)nseg); ENSURE(c, dcpos, 8 * (size_t)nseg);
-        ENSURE(c, uvoff, 8 * ((size_t)nutg + 1)); ENSURE(c, uboff, 8 * ((size_t)nutg + 1)); ENSURE(c, dcoffs, 8 * ((size_t)nutg + 1));
+        if (rc || (rc = ul.upload(c))) return rc;
+        ENSURE(c, nb, 4 * (size_t)nseg); ENSURE(c, dcnb, 4 * (size_t)nseg); ENSURE(c, dcpos, 8 * (size_t)nseg);
+        ENSURE(c, dcoffs, 8 * ((size_t)nutg + 1));
         ENSURE(c, cont, nr); ENSURE(c, rem, nr);
         ENSURE(c, bvert, 4 * (size_t)nr); ENSURE(c, key, 8 * (size_t)nr);
         ENSURE(c, place, sizeof(bella_realign_placement) * (size_t)nr);
@@ -5166,14 +5270,9 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
         if (ensure_bytes(c, table, tbytes))
             return fail(c, BELLA_ERR_NOMEM, "the realignment table needs %zu bytes of device memory (36 per base of %llu unitig bases) and they do not fit", tbytes,
                         (unsigned long long)total);
-        HIPCHK(c, c->stager.h2d(verts.p, u.verts.data(), 4 * (size_t)nseg, c->stream));
-        HIPCHK(c, c->stager.h2d(slot_utg.p, slot.data(), 4 * (size_t)nseg, c->stream));
         HIPCHK(c, c->stager.h2d(nb.p, u.nb.data(), 4 * (size_t)nseg, c->stream));
-        HIPCHK(c, c->stager.h2d(pos.p, u.pos.data(), 8 * (size_t)nseg, c->stream));
         HIPCHK(c, c->stager.h2d(dcnb.p, cnb.data(), 4 * (size_t)nseg, c->stream));
         HIPCHK(c, c->stager.h2d(dcpos.p, cpos.data(), 8 * (size_t)nseg, c->stream));
-        HIPCHK(c, c->stager.h2d(uvoff.p, u.voff.data(), 8 * ((size_t)nutg + 1), c->stream));
-        HIPCHK(c, c->stager.h2d(uboff.p, u.boff.data(), 8 * ((size_t)nutg + 1), c->stream));
         HIPCHK(c, c->stager.h2d(dcoffs.p, coffs.data(), 8 * ((size_t)nutg + 1), c->stream));
         HIPCHK(c, c->stager.h2d(cont.p, g.contained.data(), nr, c->stream));
         HIPCHK(c, c->stager.h2d(rem.p, g.removed.data(), nr, c->stream));
@@ -5193,7 +5292,7 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
         const uint32_t* const upacked = any_unrolled ? ptr<uint32_t>(upk2) : cpacked;
         // ---- placement
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
-        k_rea_backbone<<<nblk(nseg), 256, 0, c->stream>>>(ptr<uint32_t>(verts), nseg, ptr<uint32_t>(bvert));
+        k_rea_backbone<<<nblk(nseg), 256, 0, c->stream>>>(ptr<uint32_t>(ul.verts), nseg, ptr<uint32_t>(bvert));
         KCHK(c);
         if (nrec) {
             k_rea_anchor<<<nblk(nrec), 256, 0, c->stream>>>(ptr<bella_overlap>(recs), (uint32_t)nrec, ptr<uint32_t>(bvert), ptr<uint8_t>(cont), ptr<uint8_t>(rem),
@@ -5201,8 +5300,8 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
             KCHK(c);
         }
         k_rea_place<<<nblk(nr), 256, 0, c->stream>>>(nr, ptr<uint64_t>(c->roff), spans.beg, spans.end, ptr<uint32_t>(bvert), ptr<unsigned long long>(key), ptr<bella_overlap>(recs),
-                                                     ptr<uint8_t>(cont), ptr<uint8_t>(rem), ptr<uint32_t>(verts), ptr<uint32_t>(slot_utg), ptr<uint64_t>(pos), ptr<uint32_t>(nb),
-                                                     ptr<uint64_t>(dcpos), ptr<uint32_t>(dcnb), ptr<uint64_t>(uvoff), ptr<uint64_t>(uboff), ptr<uint64_t>(dcoffs), rp.band0,
+                                                     ptr<uint8_t>(cont), ptr<uint8_t>(rem), ptr<uint32_t>(ul.verts), ptr<uint32_t>(ul.slot_utg), ptr<uint64_t>(ul.pos), ptr<uint32_t>(nb),
+                                                     ptr<uint64_t>(dcpos), ptr<uint32_t>(dcnb), ptr<uint64_t>(ul.uvoff), ptr<uint64_t>(ul.uboff), ptr<uint64_t>(dcoffs), rp.band0,
                                                      ptr<uint8_t>(dcirc), rp.band_max, unroll ? 1u : 0u, ptr<bella_realign_placement>(place));
         KCHK(c);
         if (total) {
@@ -5235,63 +5334,50 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
         }
         st.repeated = nseg - nvert_reads;
         // ---- DP, walks and votes: band by band, batch by batch
-        size_t mfree = 0, mtotal = 0;
-        HIPCHK(c, hipMemGetInfo(&mfree, &mtotal));
-        const uint64_t budget = std::max<uint64_t>(64ull << 20, std::min<uint64_t>((uint64_t)mfree / 2, 8ull << 30));       // direction bytes of a batch
-        TmpBuf jobs, res, cnt, dirs, scr, ops;
+        uint64_t budget = 0;
+        if ((rc = round_budget(c, &budget))) return rc;
+        RoundBatches rb{c, "realign", "reads", ev, rpacked, upacked, ptr<uint32_t>(table), ptr<unsigned long long>(votes), rp.keep_ops != 0, out.ops, st.dp_ms, st.walk_ms, st.vote_ms};
         std::vector<ReaJob> hj;
         std::vector<ReaRes> hres;
         std::vector<ReaCnt> hcnt;
         for (uint32_t B = rp.band0; !pending.empty(); B *= 2) {
             std::vector<uint32_t> next;
+            const uint32_t maxjobs = round_max_jobs(B, budget);
             for (size_t b0 = 0; b0 < pending.size();) {
                 hj.clear();
-                uint64_t dbytes = 0, sints = 0;
+                uint64_t dbytes = 0;
                 size_t b1 = b0;
                 for (; b1 < pending.size(); ++b1) {
                     const uint32_t r = pending[b1];
                     const bella_realign_placement& P = out.placements[r];
                     const uint64_t beg = clipped ? c->as.trim.clips[r].beg : 0, end = clipped ? c->as.trim.clips[r].end : c->host_lens[r];
                     const uint64_t n = end - beg, need_bytes = n * (B / 4);
-                    if (!hj.empty() && (dbytes + need_bytes > budget || hj.size() >= (1u << 20))) break;
+                    if (!hj.empty() && (dbytes + need_bytes > budget || hj.size() >= maxjobs)) break;
                     ReaJob j{};
                     const int32_t plen = (int32_t)(coffs[P.unitig + 1] - coffs[P.unitig]);
                     j.gH = (int64_t)poffs[P.unitig]; j.gT = (int64_t)coffs[P.unitig];
                     j.gV = (int64_t)(hroff[r] + (P.orient ? end - 1 : beg));
-                    j.dir_off = dbytes; j.scr_off = sints; j.op_off = ~0ull;
+                    j.dir_off = dbytes; j.scr_off = 2ull * B * hj.size(); j.op_off = ~0ull;
                     j.n = (uint32_t)n; j.m = P.pad ? 2 * plen : plen; j.mt = P.pad ? plen : j.m;       // (pad: placed on the unrolled circle)
                     const int64_t slack = (P.e - P.s) - (int64_t)n;
                     j.c = (int32_t)(P.s + (slack >= 0 ? slack / 2 : -((-slack + 1) / 2)));      // floor
                     j.band = B; j.dV = P.orient ? -1 : 1; j.comp = P.orient ? 3u : 0u;
                     hj.push_back(j);
-                    dbytes += need_bytes; sints += 2ull * B;
+                    dbytes += need_bytes;
                     st.dp_cells += n * B;
                 }
                 const uint32_t nj = (uint32_t)hj.size();
-                ENSURE(c, jobs, sizeof(ReaJob) * (size_t)nj); ENSURE(c, res, sizeof(ReaRes) * (size_t)nj); ENSURE(c, cnt, sizeof(ReaCnt) * (size_t)nj);
-                if (ensure_bytes(c, dirs, (size_t)dbytes))
-                    return fail(c, BELLA_ERR_NOMEM, "realign: %llu direction bytes for a batch of %u reads do not fit", (unsigned long long)dbytes, nj);
-                if (B > kTrRegBand) ENSURE(c, scr, 4 * (size_t)sints);
+                ENSURE(c, rb.jobs, sizeof(ReaJob) * (size_t)nj);
                 st.dir_bytes_peak = std::max<uint64_t>(st.dir_bytes_peak, dbytes);
                 ++st.batches;
-                HIPCHK(c, c->stager.h2d(jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
-                HIPCHK(c, hipEventRecord(ev.a, c->stream));
-                const unsigned grid = nblk((uint64_t)nj * 64, kTraceBlock);
-                if (B == 256) k_rea_dp<4><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
-                else if (B == 512) k_rea_dp<8><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
-                else if (B == 1024) k_rea_dp<16><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
-                else k_rea_dp_wide<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<ReaRes>(res));
-                KCHK(c);
-                HIPCHK(c, hipEventRecord(ev.b, c->stream));
-                k_rea_count<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
-                KCHK(c);
+                HIPCHK(c, c->stager.h2d(rb.jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
+                if ((rc = rb.dp_count(nj, B, dbytes))) return rc;
                 HIPCHK(c, hipEventRecord(ev.d, c->stream));
                 hres.resize(nj); hcnt.resize(nj);
-                HIPCHK(c, c->stager.d2h(hres.data(), res.p, sizeof(ReaRes) * (size_t)nj, c->stream));
-                HIPCHK(c, c->stager.d2h(hcnt.data(), cnt.p, sizeof(ReaCnt) * (size_t)nj, c->stream));
+                HIPCHK(c, c->stager.d2h(hres.data(), rb.res.p, sizeof(ReaRes) * (size_t)nj, c->stream));
+                HIPCHK(c, c->stager.d2h(hcnt.data(), rb.cnt.p, sizeof(ReaCnt) * (size_t)nj, c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->stream));
-                st.dp_ms += ev_ms(ev.a, ev.b);
-                st.walk_ms += ev_ms(ev.b, ev.d);
+                rb.counted();
                 uint64_t nops = 0;
                 for (uint32_t x = 0; x < nj; ++x) {
                     const uint32_t r = pending[b0 + x];
@@ -5317,31 +5403,15 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
                     }
                 }
                 if (nops) {
-                    ENSURE(c, ops, 4 * (size_t)nops);
-                    HIPCHK(c, c->stager.h2d(jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
-                    HIPCHK(c, hipEventRecord(ev.a, c->stream));
-                    k_rea_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
-                    KCHK(c);
-                    HIPCHK(c, hipEventRecord(ev.b, c->stream));
-                    k_rea_vote<<<nblk((uint64_t)nj * 64, kPileBlock), kPileBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaCnt>(cnt), nj, ptr<uint32_t>(ops), rpacked,
-                                                                                                 ptr<uint32_t>(table), ptr<unsigned long long>(votes));
-                    KCHK(c);
-                    HIPCHK(c, hipEventRecord(ev.d, c->stream));
-                    if (rp.keep_ops) {
-                        const size_t at = out.ops.size();
-                        out.ops.resize(at + (size_t)nops);
-                        HIPCHK(c, c->stager.d2h(out.ops.data() + at, ops.p, 4 * (size_t)nops, c->stream));
-                    }
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    st.walk_ms += ev_ms(ev.a, ev.b);
-                    st.vote_ms += ev_ms(ev.b, ev.d);
+                    HIPCHK(c, c->stager.h2d(rb.jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
+                    if ((rc = rb.write_vote(nj, nops))) return rc;
                 }
                 b0 = b1;
             }
             pending.swap(next);
             if (B >= rp.band_max) break;
         }
-        dirs.reset(); scr.reset(); ops.reset();
+        rb.dirs.reset(); rb.scr.reset(); rb.ops.reset();
         HIPCHK(c, hipMemcpyAsync(&st.votes, votes.p, 8, hipMemcpyDeviceToHost, c->stream));
         if (rp.keep_ops && total) {
             out.table.resize((size_t)total * kPileCounters);
@@ -5349,32 +5419,11 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
         }
         // ---- consensus: every unitig a read whose own bases are the sequence it was aligned against
         TmpBuf emit, scan, outb, noffs, cstats, npos, nnb;
-        ENSURE(c, emit, (size_t)total + 1); ENSURE(c, scan, 8 * ((size_t)total + 1));
-        ENSURE(c, noffs, 8 * ((size_t)nutg + 1)); ENSURE(c, cstats, sizeof(bella_consensus_read) * (size_t)nutg);
         ENSURE(c, npos, 8 * (size_t)nseg); ENSURE(c, nnb, 4 * (size_t)nseg);
-        HIPCHK(c, hipMemsetAsync(cstats.p, 0, sizeof(bella_consensus_read) * (size_t)nutg, c->stream));
-        HIPCHK(c, hipMemsetAsync(ptr<uint8_t>(emit) + total, 0, 1, c->stream));
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
-        if (total) {
-            k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(table), cpacked, ptr<uint64_t>(dcoffs), nutg, total, rp.min_depth, ptr<uint8_t>(emit),
-                                                              ptr<bella_consensus_read>(cstats));
-            KCHK(c);
-        }
-        {
-            hipcub::TransformInputIterator<uint64_t, EmitCount, const uint8_t*> it(ptr<uint8_t>(emit), EmitCount());
-            CUB(c, hipcub::DeviceScan::ExclusiveSum, it, ptr<uint64_t>(scan), (int)(total + 1), c->stream);
-        }
-        HIPCHK(c, hipMemcpyAsync(&nout, ptr<uint64_t>(scan) + total, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        ENSURE(c, outb, (size_t)nout);
-        if (total) {
-            k_cons_write<<<nblk(total), 256, 0, c->stream>>>(ptr<uint8_t>(emit), ptr<uint64_t>(scan), total, ptr<uint8_t>(outb));
-            KCHK(c);
-        }
-        k_cons_reads<<<nblk((uint64_t)nutg + 1), 256, 0, c->stream>>>(ptr<uint64_t>(dcoffs), ptr<uint64_t>(scan), nutg, ptr<uint64_t>(noffs), ptr<bella_consensus_read>(cstats));
-        KCHK(c);
+        if ((rc = consensus_tail(c, table, cpacked, dcoffs, nutg, total, rp.min_depth, emit, scan, cstats, noffs, outb, &nout))) return rc;
         if (nseg) {
-            k_rea_segpos<<<nblk(nseg), 256, 0, c->stream>>>(ptr<uint64_t>(scan), ptr<uint64_t>(dcpos), ptr<uint32_t>(slot_utg), ptr<uint64_t>(uvoff), ptr<uint64_t>(dcoffs), nseg,
+            k_rea_segpos<<<nblk(nseg), 256, 0, c->stream>>>(ptr<uint64_t>(scan), ptr<uint64_t>(dcpos), ptr<uint32_t>(ul.slot_utg), ptr<uint64_t>(ul.uvoff), ptr<uint64_t>(dcoffs), nseg,
                                                             ptr<uint64_t>(npos), ptr<uint32_t>(nnb));
             KCHK(c);
         }
@@ -5457,11 +5506,7 @@ int bella_hip_recorrect(bella_ctx* c, const bella_recorrect_params* params, uint
     bella_recorrect_params rp{};
     rp.band0 = BELLA_RECORRECT_DEFAULT_BAND; rp.band_max = BELLA_RECORRECT_DEFAULT_BAND_MAX; rp.min_identity = BELLA_RECORRECT_DEFAULT_MIN_IDENTITY; rp.min_depth = 3;
     if (int r = take_params(c, rp, params, "bella_recorrect_params")) return r;
-    auto pow2 = [](uint32_t x) { return x && !(x & (x - 1)); };
-    if (!pow2(rp.band0) || !pow2(rp.band_max) || rp.band0 < kTrMinBand || rp.band_max > kTrMaxBand || rp.band0 > rp.band_max)
-        return fail(c, BELLA_ERR_BAD_ARG, "recorrect: band0 and band_max must be powers of two with 256 <= band0 <= band_max <= 262144");
-    if (rp.min_depth < 1) return fail(c, BELLA_ERR_BAD_ARG, "min_depth must be >= 1");
-    if (rp.min_identity > 1000) return fail(c, BELLA_ERR_BAD_ARG, "min_identity is in permille: at most 1000");
+    if (int r = check_round_params(c, "recorrect", rp.band0, rp.band_max, rp.min_depth, rp.min_identity)) return r;
     if (int r = need(c, CONS)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const bool again = has(c, RECORRECT);                             // the sequences to align against: the last round's, or the consensus's
@@ -5540,18 +5585,17 @@ int bella_hip_recorrect(bella_ctx* c, const bella_recorrect_params* params, uint
         st.none = njobs - np;
         live.reset();
         // ---- DP, walks and votes: band by band, batch by batch
-        size_t mfree = 0, mtotal = 0;
-        HIPCHK(c, hipMemGetInfo(&mfree, &mtotal));
-        const uint64_t budget = std::max<uint64_t>(64ull << 20, std::min<uint64_t>((uint64_t)mfree / 2, 8ull << 30));       // direction bytes of a batch
-        TmpBuf jobs, res, cnt, dirs, scr, ops, vnops, opscan;
+        uint64_t budget = 0;
+        if ((rc = round_budget(c, &budget))) return rc;
+        RoundBatches rb{c, "recorrect", "jobs", ev, rpacked, upacked, ptr<uint32_t>(table), ptr<unsigned long long>(votes), rp.keep_ops != 0, out.ops, st.dp_ms, st.walk_ms, st.vote_ms};
+        TmpBuf vnops, opscan;
         for (uint32_t B = rp.band0; np; B *= 2) {
             k_rec_bytes<<<nblk((uint64_t)np + 1), 256, 0, c->stream>>>(ptr<uint32_t>(pend), np, ptr<ReaJob>(jbase), B, ptr<uint64_t>(bytes));
             KCHK(c);
             CUB(c, hipcub::DeviceScan::ExclusiveSum, ptr<uint64_t>(bytes), ptr<uint64_t>(pre), (int)(np + 1), c->stream);
             uint64_t band_bytes = 0;
             HIPCHK(c, hipMemcpyAsync(&band_bytes, ptr<uint64_t>(pre) + np, 8, hipMemcpyDeviceToHost, c->stream));
-            // (the wide kernel keeps two rows of B ints per job in scratch: a batch's scratch stays within the budget too)
-            const uint32_t maxjobs = B > kTrRegBand ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kRecMaxBatch, budget / (8ull * B))) : kRecMaxBatch;
+            const uint32_t maxjobs = round_max_jobs(B, budget);
             for (uint32_t b0 = 0; b0 < np;) {
                 k_rec_cut<<<1, 64, 0, c->stream>>>(ptr<uint64_t>(pre), np, b0, budget, maxjobs, dctl);
                 KCHK(c);
@@ -5561,26 +5605,14 @@ int bella_hip_recorrect(bella_ctx* c, const bella_recorrect_params* params, uint
                 const uint32_t b1 = (uint32_t)cut[0], nj = b1 - b0;
                 const uint64_t dbytes = cut[1];
                 if (b1 <= b0 || b1 > np) return fail(c, BELLA_ERR_STATE, "recorrect: a batch [%u, %u) of %u pending jobs", b0, b1, np);
-                ENSURE(c, jobs, sizeof(ReaJob) * (size_t)nj); ENSURE(c, res, sizeof(ReaRes) * (size_t)nj); ENSURE(c, cnt, sizeof(ReaCnt) * (size_t)nj);
+                ENSURE(c, rb.jobs, sizeof(ReaJob) * (size_t)nj);
                 ENSURE(c, vnops, 4 * ((size_t)nj + 1)); ENSURE(c, opscan, 8 * ((size_t)nj + 1));
-                if (ensure_bytes(c, dirs, (size_t)dbytes))
-                    return fail(c, BELLA_ERR_NOMEM, "recorrect: %llu direction bytes for a batch of %u jobs do not fit", (unsigned long long)dbytes, nj);
-                if (B > kTrRegBand) ENSURE(c, scr, 8 * (size_t)nj * B);
                 st.dir_bytes_peak = std::max<uint64_t>(st.dir_bytes_peak, dbytes);
                 ++st.batches;
-                k_rec_gather<<<nblk(nj), 256, 0, c->stream>>>(ptr<uint32_t>(pend), b0, nj, ptr<ReaJob>(jbase), ptr<uint64_t>(pre), B, ptr<ReaJob>(jobs));
+                k_rec_gather<<<nblk(nj), 256, 0, c->stream>>>(ptr<uint32_t>(pend), b0, nj, ptr<ReaJob>(jbase), ptr<uint64_t>(pre), B, ptr<ReaJob>(rb.jobs));
                 KCHK(c);
-                HIPCHK(c, hipEventRecord(ev.a, c->stream));
-                const unsigned grid = nblk((uint64_t)nj * 64, kTraceBlock);
-                if (B == 256) k_rea_dp<4><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
-                else if (B == 512) k_rea_dp<8><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
-                else if (B == 1024) k_rea_dp<16><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
-                else k_rea_dp_wide<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<ReaRes>(res));
-                KCHK(c);
-                HIPCHK(c, hipEventRecord(ev.b, c->stream));
-                k_rea_count<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
-                KCHK(c);
-                k_rec_settle<<<nblk((uint64_t)nj + 1), 256, 0, c->stream>>>(ptr<uint32_t>(pend), b0, nj, ptr<ReaRes>(res), ptr<ReaCnt>(cnt), B, rp.band_max, rp.min_identity, djrec,
+                if ((rc = rb.dp_count(nj, B, dbytes))) return rc;
+                k_rec_settle<<<nblk((uint64_t)nj + 1), 256, 0, c->stream>>>(ptr<uint32_t>(pend), b0, nj, ptr<ReaRes>(rb.res), ptr<ReaCnt>(rb.cnt), B, rp.band_max, rp.min_identity, djrec,
                                                                            ptr<uint8_t>(touch), ptr<uint32_t>(vnops), ptr<RecCounts>(counts));
                 KCHK(c);
                 HIPCHK(c, hipEventRecord(ev.d, c->stream));
@@ -5588,29 +5620,12 @@ int bella_hip_recorrect(bella_ctx* c, const bella_recorrect_params* params, uint
                 uint64_t nops = 0;
                 HIPCHK(c, hipMemcpyAsync(&nops, ptr<uint64_t>(opscan) + nj, 8, hipMemcpyDeviceToHost, c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->stream));
-                st.dp_ms += ev_ms(ev.a, ev.b);
-                st.walk_ms += ev_ms(ev.b, ev.d);
+                rb.counted();
                 if (nops) {
-                    ENSURE(c, ops, 4 * (size_t)nops);
                     k_rec_opoff<<<nblk(nj), 256, 0, c->stream>>>(ptr<uint32_t>(pend), b0, nj, ptr<uint32_t>(vnops), ptr<uint64_t>(opscan),
-                                                                 rp.keep_ops ? (uint64_t)out.ops.size() : ~0ull, ptr<ReaJob>(jobs), djrec);
+                                                                 rp.keep_ops ? (uint64_t)out.ops.size() : ~0ull, ptr<ReaJob>(rb.jobs), djrec);
                     KCHK(c);
-                    HIPCHK(c, hipEventRecord(ev.a, c->stream));
-                    k_rea_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
-                    KCHK(c);
-                    HIPCHK(c, hipEventRecord(ev.b, c->stream));
-                    k_rea_vote<<<nblk((uint64_t)nj * 64, kPileBlock), kPileBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaCnt>(cnt), nj, ptr<uint32_t>(ops), rpacked,
-                                                                                                 ptr<uint32_t>(table), ptr<unsigned long long>(votes));
-                    KCHK(c);
-                    HIPCHK(c, hipEventRecord(ev.d, c->stream));
-                    if (rp.keep_ops) {
-                        const size_t at = out.ops.size();
-                        out.ops.resize(at + (size_t)nops);
-                        HIPCHK(c, c->stager.d2h(out.ops.data() + at, ops.p, 4 * (size_t)nops, c->stream));
-                    }
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    st.walk_ms += ev_ms(ev.a, ev.b);
-                    st.vote_ms += ev_ms(ev.b, ev.d);
+                    if ((rc = rb.write_vote(nj, nops))) return rc;
                 }
                 b0 = b1;
             }
@@ -5621,7 +5636,7 @@ int bella_hip_recorrect(bella_ctx* c, const bella_recorrect_params* params, uint
             HIPCHK(c, hipStreamSynchronize(c->stream));
             pend.swap(next);
         }
-        dirs.reset(); scr.reset(); ops.reset(); jbase.reset(); pend.reset(); next.reset(); bytes.reset(); pre.reset(); touch.reset();
+        rb.dirs.reset(); rb.scr.reset(); rb.ops.reset(); jbase.reset(); pend.reset(); next.reset(); bytes.reset(); pre.reset(); touch.reset();
         RecCounts hc{};
         HIPCHK(c, hipMemcpyAsync(&st.votes, votes.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(&hc, counts.p, sizeof(RecCounts), hipMemcpyDeviceToHost, c->stream));
@@ -5631,29 +5646,9 @@ int bella_hip_recorrect(bella_ctx* c, const bella_recorrect_params* params, uint
         }
         // ---- consensus: every current sequence a read whose own bases are the sequence that was aligned against; the new anchors
         TmpBuf emit, scan;
-        ENSURE(c, emit, (size_t)total + 1); ENSURE(c, scan, 8 * ((size_t)total + 1));
-        HIPCHK(c, hipMemsetAsync(nstats.p, 0, nst, c->stream));
-        HIPCHK(c, hipMemsetAsync(ptr<uint8_t>(emit) + total, 0, 1, c->stream));
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
-        if (total) {                                                  // (every current sequence empty: the jobs are all NONE, nothing is decided)
-            k_cons_decide<<<nblk(total), 256, 0, c->stream>>>(ptr<uint32_t>(table), upacked, ptr<uint64_t>(coffs), nr, total, rp.min_depth, ptr<uint8_t>(emit),
-                                                              ptr<bella_consensus_read>(nstats));
-            KCHK(c);
-        }
-        {
-            hipcub::TransformInputIterator<uint64_t, EmitCount, const uint8_t*> it(ptr<uint8_t>(emit), EmitCount());
-            CUB(c, hipcub::DeviceScan::ExclusiveSum, it, ptr<uint64_t>(scan), (int)(total + 1), c->stream);
-        }
-        HIPCHK(c, hipMemcpyAsync(&nout, ptr<uint64_t>(scan) + total, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        st.band_capped = hc.band_capped; st.low_identity = hc.low_identity; st.voted = hc.voted;
-        ENSURE(c, nbases, (size_t)nout);
-        if (total) {
-            k_cons_write<<<nblk(total), 256, 0, c->stream>>>(ptr<uint8_t>(emit), ptr<uint64_t>(scan), total, ptr<uint8_t>(nbases));
-            KCHK(c);
-        }
-        k_cons_reads<<<nblk((uint64_t)nr + 1), 256, 0, c->stream>>>(ptr<uint64_t>(coffs), ptr<uint64_t>(scan), nr, ptr<uint64_t>(noffs), ptr<bella_consensus_read>(nstats));
-        KCHK(c);
+        if ((rc = consensus_tail(c, table, upacked, coffs, nr, total, rp.min_depth, emit, scan, nstats, noffs, nbases, &nout))) return rc;
+        st.band_capped = hc.band_capped; st.low_identity = hc.low_identity; st.voted = hc.voted;      // (the tail has waited for the device)
         k_rec_anchors<<<nblk(c->rc_nanch), 256, 0, c->stream>>>(ptr<uint64_t>(coffs), ptr<uint64_t>(scan), ptr<uint64_t>(c->rc_aoff), ptr<uint64_t>(canch), nr, c->rc_nanch,
                                                               ptr<uint64_t>(nanch));
         KCHK(c);

@@ -53,6 +53,57 @@ def raises(code, fn, *a, **kw):
     assert ex.value.code == code, (fn, ex.value.code)
 
 
+# ---- the rounds of DESIGN.md sections 18 to 20 under BELLA_TUNE_ROUND_BUDGET: the batching changes, the result does not
+def with_round_budget(eng, budget, run):
+    """run() with `budget` direction bytes per batch of a round (None: the default rule); the default rule again on every way out"""
+    try:
+        if budget is not None:
+            eng.set_tuning("round_budget", budget)
+        return run()
+    finally:
+        eng.set_tuning("round_budget")
+
+
+def realign_getters(eng, **params):
+    """one realignment round: what every getter returns afterwards, the stats (with `wrapped`) under "st" """
+    out = dict(eng.graph_realign_unitigs(**params))
+    out["placements"] = eng.realign_placements()
+    out["ops"], out["table"] = eng.realign_ops()
+    out["st"] = eng.realign_stats()
+    return out
+
+
+def recorrect_getters(eng, **params):
+    """one correction round: what every getter returns afterwards, the stats under "st" """
+    out = dict(zip(("offsets", "bases", "stats"), eng.recorrect(**params)))
+    out["jobs"] = eng.recorrect_jobs()
+    out["ops"], out["table"] = eng.recorrect_ops()
+    out["anchor_offsets"], out["anchors"] = eng.recorrect_anchors()
+    out["st"] = eng.recorrect_stats()
+    return out
+
+
+def same_but_for_the_batching(a, b):
+    """two rounds' getters: every array equal in type, shape and every byte of every field (records with their op_off and nops), the
+    stats in every field but the timers, `batches` and `dir_bytes_peak`"""
+    assert a.keys() == b.keys()
+    for k in a:
+        if k == "st":
+            skip = [f for f in a[k] if f.endswith("_ms") or f in ("batches", "dir_bytes_peak")]
+            assert {f: v for f, v in a[k].items() if f not in skip} == {f: v for f, v in b[k].items() if f not in skip}
+            continue
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, k
+        for f in a[k].dtype.names or [None]:
+            assert (a[k] if f is None else a[k][f]).tobytes() == (b[k] if f is None else b[k][f]).tobytes(), (k, f)
+
+
+def dps_and_largest_job(band, n, band0):
+    """from the last band and the length of every job whose DP ran: (the DPs that ran -- a job whose last band is B ran log2(B / band0) + 1
+    times --, the largest single job's direction bytes, n x B / 4)"""
+    band, n = np.asarray(band, np.int64), np.asarray(n, np.int64)
+    return int((np.log2(band // band0).astype(np.int64) + 1).sum()), int((n * band // 4).max())
+
+
 def run_ranks(nranks, body, timeout=300):
     """one host thread per context (ctypes releases the GIL): the collective entry points rendezvous inside the library"""
     out, err = [None] * nranks, []

@@ -1021,11 +1021,15 @@ int bella_hip_trim(bella_ctx* ctx);
  *   BELLA_TUNE_ORDER_SPLIT    values[0] = owned columns of a pass above which the slot-order pass runs as TWO launches, one per table
  *                             size class (order.hpp), instead of one launch for all tables of up to 1,024 slots (default, n = 0: 32,768;
  *                             0: always two launches -- tests run both instances on small inputs).  Read by every pass.
+ *   BELLA_TUNE_ROUND_BUDGET   values[0] = direction bytes of one batch of a realignment or correction round, taken as given (no 64 MB
+ *                             floor; a batch always takes at least one job, so 1 means one job per batch -- tests run many batches on
+ *                             small inputs).  Default (n = 0 or 0): half of the free device memory, 64 MB .. 8 GB.  Read at the start of
+ *                             each round.  The trace's budget is not touched.
  * (bella_hip_set_debug bits 0, 10, 15 and 16 of earlier rounds still select the same things: aliases, no longer needed)
  */
 enum { BELLA_TUNE_LDS_TIERS = 0, BELLA_TUNE_KCOUNT_BUDGET = 1, BELLA_TUNE_WIDE_BUDGET = 2, BELLA_TUNE_XDROP_VARIANT = 3, BELLA_TUNE_ROW_LISTS = 4,
        BELLA_TUNE_XDROP_CLASS_MIN = 5, BELLA_TUNE_LAYOUT_ORDER = 6, BELLA_TUNE_INLINE_ENTRIES = 7, BELLA_TUNE_ROW_PATH = 8, BELLA_TUNE_CACHE_BYTES = 9, BELLA_TUNE_DIST_LAYOUT = 10, BELLA_TUNE_COMPACT_B = 11,
-       BELLA_TUNE_PRODUCT_ENTRIES = 12, BELLA_TUNE_ORDER_SPLIT = 13 };
+       BELLA_TUNE_PRODUCT_ENTRIES = 12, BELLA_TUNE_ORDER_SPLIT = 13, BELLA_TUNE_ROUND_BUDGET = 14 };
 int bella_hip_set_tuning(bella_ctx* ctx, uint32_t what, const uint64_t* values, uint32_t n);
 
 #ifdef __cplusplus

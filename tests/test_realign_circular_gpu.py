@@ -1,6 +1,6 @@
 """GPU tests of the circular realignment round: the device result EQUALS the mirror (bella_testkit/realign_mirror.py
 with circular=True) -- placements with their pad word, alignment records, runs, table, bases, pos / nbases, counts with `wrapped` -- on the
-circles of bella_testkit/realign_cases.py and realign_circle_cases.py under four band settings, over two rounds and with a trim in
+circles of bella_testkit/realign_cases.py and realign_circle_cases.py under four band settings, over two rounds, in many batches (BELLA_TUNE_ROUND_BUDGET) and with a trim in
 force; nothing else moves: a line, a circle that is too short for band_max and the plain entry point give what they gave; state and
 errors of the new entry point; and bella-hip --realign-circular end to end on a noisy circle of 48 kb."""
 import ctypes as C
@@ -14,7 +14,7 @@ from bella_testkit import realign_circle_cases as CC
 from bella_testkit import realign_mirror as R
 from bella_testkit import synth
 from bella_testkit import unitig_mirror as U
-from bella_testkit.pipeline import raises, run_cli
+from bella_testkit.pipeline import dps_and_largest_job, raises, realign_getters, run_cli, same_but_for_the_batching, with_round_budget
 
 pytestmark = pytest.mark.gpu
 
@@ -111,6 +111,25 @@ def test_the_circles_equal_the_mirror(eng, case, bands):
     SEEN["shifted"] |= bool((voted & (pl["s"] >= plen)).any())
     SEEN["begins_behind_the_seam"] |= bool((voted & (pl["q_begin"] >= plen)).any())
     SEEN["spans_the_seam"] |= bool((voted & (pl["q_begin"] < plen) & (pl["q_end"] > plen)).any())
+
+
+@pytest.mark.parametrize("bands", ["b256", "b2048"])
+def test_the_circle_in_one_job_per_batch(eng, bands):
+    """circle_plus with round_budget = 1 against the default budget: the jobs on the unrolled circle (`pad`, the doubled pack) go through
+    the batches one at a time -- k_rea_dp<4> doubling to <8>, and the wide kernel -- and everything comes out the same"""
+    seqs, recs = CC.circle_plus()
+    got = []
+    for budget in (None, 1):
+        _install(eng, seqs, recs, RC.GRAPH)
+        _polish(eng, CC.gentle_table(seqs, 3))
+        got.append(with_round_budget(eng, budget, lambda: realign_getters(eng, circular=True, keep_ops=1, **BANDS[bands])))
+    one, many = got
+    same_but_for_the_batching(one, many)
+    pl = many["placements"]
+    assert (pl["status"] == R.VOTED).all() and (pl["pad"] == 1).all() and many["st"]["wrapped"] > 0
+    ndp, largest = dps_and_largest_job(pl["band"], [len(s) for s in seqs], BANDS[bands]["band0"])
+    print("REALIGN circular circle_plus %s: %d batches by default, %d with one job per batch" % (bands, one["st"]["batches"], many["st"]["batches"]))
+    assert many["st"]["batches"] == ndp > one["st"]["batches"] and many["st"]["dir_bytes_peak"] == largest
 
 
 def test_two_rounds_equal_the_mirrors_two_rounds(eng):

@@ -1,6 +1,7 @@
 """GPU tests of the realignment round: the device result EQUALS the mirror (bella_testkit/realign_mirror.py) --
 placements, alignment records, runs, table, bases, pos / nbases, counts -- on the synthetic layouts of bella_testkit/realign_cases.py,
-over two rounds, on real traces; state and errors; and the measured effect on 2,000 reads of 10 kb at 15 % error."""
+over two rounds, on real traces; the same round in many batches (BELLA_TUNE_ROUND_BUDGET); state and errors; and the measured effect
+on 2,000 reads of 10 kb at 15 % error."""
 import ctypes as C
 import gzip
 import os
@@ -15,7 +16,7 @@ from bella_testkit import realign_mirror as R
 from bella_testkit import synth
 from bella_testkit import unitig_mirror as U
 from bella_testkit import pileup_mirror as P
-from bella_testkit.pipeline import aligned as _aligned, raises, run_cli
+from bella_testkit.pipeline import aligned as _aligned, dps_and_largest_job, raises, realign_getters, run_cli, same_but_for_the_batching, with_round_budget
 from conftest import GOLD, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -108,6 +109,57 @@ def test_the_line_equals_the_mirror(eng, run):
         SEEN["anchor_h_strand1"] |= int(rec["cid"]) == r and int(rec["strand"]) == 1
     both = [x for x, rec in enumerate(recs) if 2 in (int(rec["cid"]), int(rec["rid"])) and {int(rec["cid"]), int(rec["rid"])} & set(RC.BACKBONE)]
     SEEN["tie"] |= len(both) == 2 and int(pl[2]["anchor"]) == min(both) and int(recs[both[0]]["endH"] - recs[both[0]]["begH"]) == int(recs[both[1]]["endV"] - recs[both[1]]["begV"])
+
+
+# ---- the line in many batches (BELLA_TUNE_ROUND_BUDGET) ----------------------------------------------------------------------------
+DP_RAN = (R.VOTED, R.LOW_IDENTITY, R.BAND_CAPPED)
+LINE_RUNS = {}                                                          # run -> the line's round under the default budget, made once
+
+
+def _line_round(eng, run, budget=None):
+    """the line polished with its table, one round of RUNS[run] under round_budget = budget (None: the default rule): -> realign_getters"""
+    if budget is None and run in LINE_RUNS:
+        return LINE_RUNS[run]
+    seqs, recs = RC.line_case()
+    _install(eng, seqs, recs, RC.GRAPH)
+    _polish(eng, RC.line_table(seqs))
+    out = with_round_budget(eng, budget, lambda: realign_getters(eng, keep_ops=1, **RUNS[run]))
+    if budget is None:
+        LINE_RUNS[run] = out
+    return out
+
+
+def _dps(x, band0):
+    """of the reads whose DP ran (no trim: a job's n is its read's length)"""
+    ran = np.isin(x["placements"]["status"], DP_RAN)
+    return dps_and_largest_job(x["placements"]["band"][ran], np.array([len(s) for s in RC.line_case()[0]])[ran], band0)
+
+
+@pytest.mark.parametrize("run", list(RUNS))
+def test_the_line_in_one_job_per_batch(eng, run):
+    """round_budget = 1: every batch takes exactly one job, so dir_off, op_off and the pending list carry over after every job"""
+    one, many = _line_round(eng, run), _line_round(eng, run, 1)
+    same_but_for_the_batching(one, many)
+    ndp, largest = _dps(many, RUNS[run]["band0"])
+    print("REALIGN line %s: %d batches by default, %d with one job per batch, peak %d -> %d direction bytes" % (run, one["st"]["batches"], many["st"]["batches"],
+                                                                                                             one["st"]["dir_bytes_peak"], many["st"]["dir_bytes_peak"]))
+    assert many["st"]["batches"] == ndp > one["st"]["batches"]
+    assert many["st"]["dir_bytes_peak"] == largest
+
+
+def test_a_budget_that_cuts_inside_a_band(eng):
+    """`doubling` with room for two of the largest job at band0: a batch ends because the next job would not fit, the jobs of one band
+    are spread over several batches and dir_off starts again in each"""
+    one = _line_round(eng, "doubling")
+    band0 = RUNS["doubling"]["band0"]
+    ndp, largest = _dps(one, band0)
+    ran = np.isin(one["placements"]["status"], DP_RAN)
+    budget = 2 * max(len(s) for s, r in zip(RC.line_case()[0], ran) if r) * band0 // 4
+    some = _line_round(eng, "doubling", budget)
+    same_but_for_the_batching(one, some)
+    print("REALIGN line doubling: budget %d: %d batches of %d DPs, peak %d" % (budget, some["st"]["batches"], ndp, some["st"]["dir_bytes_peak"]))
+    assert 1 < some["st"]["batches"] < ndp
+    assert some["st"]["dir_bytes_peak"] <= max(budget, largest)                     # (a job that does not fit runs alone)
 
 
 def test_two_rounds_equal_the_mirrors_two_rounds(eng):
@@ -211,6 +263,19 @@ def test_state_and_errors():
         assert e.lib.bella_hip_graph_realign_unitigs(e.h, C.byref(small), None) == BAD
         assert e.lib.bella_hip_graph_realign_unitigs(e.h, None, None) == 0                  # the defaults; total_bases may be NULL
         assert e.lib.bella_hip_graph_get_realigned(e.h, None, None, None, None, None) == 0
+
+        def batches():                                                  # of the first round after a polish
+            e.graph_polish_unitigs()
+            e.graph_realign_unitigs(band0=256)
+            return e.realign_stats()["batches"]
+        by_default = batches()
+        e.set_tuning("round_budget", 1)
+        assert batches() > by_default
+        e.set_tuning("round_budget")                                    # no value: the default rule again
+        assert batches() == by_default
+        e.set_tuning("round_budget", 1)
+        e.set_tuning("round_budget", 0)                                 # and so does 0
+        assert batches() == by_default
         for drop in (lambda: e.graph_cut_weak(), lambda: e.pileup_reset(), lambda: e.graph_polish_unitigs(), lambda: e.graph_unitigs()):
             e.graph_unitigs()
             e.pileup_reset()

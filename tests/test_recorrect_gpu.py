@@ -1,6 +1,6 @@
 """GPU tests of the read correction rounds: the device result EQUALS the mirror (bella_testkit/recorrect_mirror.py)
 -- jobs, runs, table, offsets, bases, per-read statistics, anchors, counts -- on realign_cases.line_case, on the layout of
-bella_testkit/recorrect_cases.py under three band settings, over two rounds, on real traces; state and errors; the command line; and
+bella_testkit/recorrect_cases.py under three band settings, in many batches (BELLA_TUNE_ROUND_BUDGET), over two rounds, on real traces; state and errors; the command line; and
 the measured effect on 2,000 reads of 10 kb at 15 % error."""
 import ctypes as C
 import gzip
@@ -19,7 +19,7 @@ from bella_testkit import recorrect_mirror as M
 from bella_testkit import synth
 from bella_testkit import trace_mirror as T
 from bella_testkit import unitig_mirror as U
-from bella_testkit.pipeline import aligned as _aligned, raises, run_cli
+from bella_testkit.pipeline import aligned as _aligned, dps_and_largest_job, raises, recorrect_getters, run_cli, same_but_for_the_batching, with_round_budget
 from conftest import GOLD, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -129,6 +129,38 @@ def test_the_mixed_case_equals_the_mirror(eng, run):
     b, y = (int(x) for x in m["offsets"][RC.NO_RECORD:RC.NO_RECORD + 2])
     SEEN["no_record"] |= not (set(recs["cid"].tolist()) | set(recs["rid"].tolist())) & {RC.NO_RECORD} and m["bases"][b:y] == cur["bases"][a:z] == seqs[RC.NO_RECORD]
     SEEN["empty_target"] |= plen[RC.EMPTY] == 0 and bool(((J["status"] == M.NONE) & (J["target"] == RC.EMPTY)).any())
+
+
+@pytest.mark.parametrize("run", list(RC.RUNS))
+def test_the_mixed_case_in_many_batches(eng, run):
+    """BELLA_TUNE_ROUND_BUDGET: the mixed case with one job per batch (budget 1) and with room for two of the largest job at band0 (a
+    batch ends because the next job would not fit) against the default budget -- sequences, offsets, per-read statistics, anchors, job
+    records with op_off, kept runs, table and counts are the same; then a second round on top with one job per batch EQUALS the mirror's
+    second round: the round's buffers are handed to the context as before"""
+    seqs, recs = RC.mixed_case()
+    cur = _round1(eng, seqs, recs, RC.mixed_table(seqs))
+    params = RC.RUNS[run]
+
+    def round2(budget):
+        eng.consensus(3)                                               # (round 1 again: the round before goes)
+        return with_round_budget(eng, budget, lambda: recorrect_getters(eng, keep_ops=1, **params))
+    one = round2(None)
+    J = one["jobs"]
+    ran = np.isin(J["status"], (M.VOTED, M.LOW_IDENTITY, M.BAND_CAPPED))
+    n = J["qend"][ran].astype(np.int64) - J["qbeg"][ran]               # (a job's rows: the query's clip)
+    ndp, largest = dps_and_largest_job(J["band"][ran], n, params["band0"])
+    two_jobs = 2 * int(n.max()) * params["band0"] // 4
+    many, some = round2(1), round2(two_jobs)
+    same_but_for_the_batching(one, many)
+    same_but_for_the_batching(one, some)
+    print("RECORRECT mixed %s: %d batches by default, %d with budget %d, %d with one job per batch (%d DPs)"
+          % (run, one["st"]["batches"], some["st"]["batches"], two_jobs, many["st"]["batches"], ndp))
+    assert many["st"]["batches"] == ndp > one["st"]["batches"] and many["st"]["dir_bytes_peak"] == largest
+    assert 1 < some["st"]["batches"] < ndp and some["st"]["dir_bytes_peak"] <= max(two_jobs, largest)     # (a job that does not fit runs alone)
+    eng.consensus(3)
+    m, _ = with_round_budget(eng, 1, lambda: _same(eng, cur, seqs, recs, **params))
+    with_round_budget(eng, 1, lambda: _same(eng, m, seqs, recs, **params))
+    assert eng.recorrect_stats()["round"] == 3 and eng.recorrect_stats()["batches"] > one["st"]["batches"]
 
 
 def test_the_synthetic_set_covers_what_it_should():

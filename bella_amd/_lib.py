@@ -62,7 +62,7 @@ class Timings(C.Structure):
                 ("compact_ms", C.c_float), ("xdrop_ms", C.c_float), ("overlap_total_ms", C.c_float), ("spgemm_launches", C.c_uint32),
                 ("kcount_ms", C.c_float), ("retry_columns", C.c_uint32), ("overflow_pairs", C.c_uint32), ("layout_ms", C.c_float),
                 ("rows_ms", C.c_float), ("lane_order", C.c_uint32), ("expand_ms", C.c_float), ("numeric_passes", C.c_uint32),
-                ("symbolic_passes", C.c_uint32), ("pad", C.c_uint32), ("numeric_columns", C.c_uint64)]
+                ("symbolic_passes", C.c_uint32), ("wide_batches", C.c_uint32), ("numeric_columns", C.c_uint64)]
 
 
 class Memory(C.Structure):

@@ -2612,6 +2612,10 @@ static int wide_batch_finish(bella_ctx* c, WideBatch& wb, bool sync_at_end) {
             }
         }
     }
+    {   // bella_timings.wide_batches: which of the two ran, batch by batch (two saturating 16-bit counts)
+        const uint32_t sh = grouped ? 0u : 16u;
+        if (((c->tm.wide_batches >> sh) & 0xFFFFu) != 0xFFFFu) c->tm.wide_batches += 1u << sh;
+    }
     if (!grouped) {
         // the sort-based path: 38 bytes per product of the batch in flight (only allocated when this path runs)
         const int rbits = wb.rbits, seg_bits = wb.seg_bits;
@@ -2795,6 +2799,7 @@ static int run_spgemm(bella_ctx* c, const bella_params* p, uint32_t* status_out,
     int nl = 0;
     auto enqueue = [&]() -> int {
     EVREC(2);
+    c->tm.wide_batches = 0;                                    // (counted by wide_batch_finish)
     if (c->caps_state != want_state) {                         // the tier caps only change with the operands or the debug switch
         HIPCHK(c, hipMemcpyAsync(c->tiercaps.p, caps, sizeof(caps), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));            // caps[] is a stack array

@@ -115,7 +115,10 @@ typedef struct {
                                  BELLA_TUNE_ROW_LISTS; 0 in the default layout, where every pass expands B' x A' itself)   */
     uint32_t numeric_passes;  /* since bella_hip_init: calls of bella_hip_overlap that ran the numeric phase ...          */
     uint32_t symbolic_passes; /* ... and calls of bella_hip_count_pairs (symbolic phase only)                            */
-    uint32_t pad;
+    uint32_t wide_batches;    /* last pass, the path of the columns above the LDS tiers: low 16 bits = batches whose
+                                 products were grouped by partner in LDS, high 16 bits = batches that took the sort-based path
+                                 (debug bit 12, a failed lane-order self-test, no room for the batch's lists, or a column with
+                                 more partners than the grouping table holds); both halves saturate at 65,535             */
     uint64_t numeric_columns; /* since bella_hip_init: output columns the numeric phase computed (a staged run that computes
                                  every column once ends at nreads)                                                        */
 } bella_timings;

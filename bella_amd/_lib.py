@@ -36,7 +36,9 @@ PLACE_DT = np.dtype([("unitig", "<u4"), ("orient", "<u4"), ("s", "<i8"), ("e", "
                      ("n_ins", "<u4"), ("n_del", "<u4"), ("score", "<i4"), ("q_begin", "<i8"), ("q_end", "<i8"), ("op_off", "<u8"), ("nops", "<u4"), ("pad", "<u4")])
 assert PLACE_DT.itemsize == 88
 REALIGN_NONE, REALIGN_VOTED, REALIGN_UNPLACED, REALIGN_OUTSIDE, REALIGN_BAND_CAPPED, REALIGN_LOW_IDENTITY = range(6)
-TRACE_PASSED_ONLY, TRACE_DROP_OPS, TRACE_PILEUP = 1, 2, 4
+TRACE_PASSED_ONLY, TRACE_DROP_OPS, TRACE_PILEUP, TRACE_NORMALIZE = 1, 2, 4, 8
+VOTE_PAIR_DT = np.dtype([("rid", "<u4"), ("cid", "<u4"), ("tbegV", "<i4"), ("tbegH", "<i4"), ("op_off", "<u8"), ("nops", "<u4"), ("strand", "u1"), ("pad", "u1", (3,))])
+assert VOTE_PAIR_DT.itemsize == 32
 PILEUP_COUNTERS = 9      # per base: votes for A C G T, del, one inserted A C G T in the junction before the base
 assert PAIR_DT.itemsize == 16 and EXT_DT.itemsize == 8 and ALN_DT.itemsize == 32 and SEED_DT.itemsize == 12
 
@@ -76,6 +78,11 @@ class TraceStats(C.Structure):
                 ("widened_extensions", C.c_uint64), ("repeated_pairs", C.c_uint64), ("dp_cells", C.c_uint64), ("dir_bytes", C.c_uint64), ("dir_bytes_peak", C.c_uint64),
                 ("ops", C.c_uint64), ("batches", C.c_uint32), ("band0", C.c_uint32), ("vote_ms", C.c_double), ("votes", C.c_uint64),
                 ("ops_host_bytes", C.c_uint64)]
+
+
+class VoteStats(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("runs", C.c_uint64), ("gap_runs", C.c_uint64), ("shifted_runs", C.c_uint64), ("shifted_columns", C.c_uint64),
+                ("votes", C.c_uint64), ("vote_ms", C.c_double), ("normalized", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class ConsensusParams(C.Structure):
@@ -250,6 +257,8 @@ SIGNATURES = [
                                                 C.POINTER(WriteStats)]),
     ("bella_hip_pileup_reset", C.c_int, [vp]),
     ("bella_hip_trace_pairs_pileup", C.c_int, [vp, C.POINTER(Params), C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("bella_hip_get_vote_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_pileup_vote", C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32]),
     ("bella_hip_get_pileup", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
     ("bella_hip_add_pileup", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
     ("bella_hip_get_pileup_bytes", C.c_int, [vp, C.POINTER(C.c_uint64)]),

@@ -337,16 +337,23 @@ class Engine:
         return out
 
     # ---- traced alignments (base-level: run-length ops, len << 4 | op, op 0 '=' 1 'X' 2 'I' 3 'D') ----
-    def trace_pairs(self, pars: BellaPars, band0: int = 0, passed_only: bool = True, pileup: bool = False, keep_ops: bool = True):
+    def trace_pairs(self, pars: BellaPars, band0: int = 0, passed_only: bool = True, pileup: bool = False, keep_ops: bool = True, normalize: bool = False):
         """Traces the pairs of the last align_pairs.  Returns (traces[npairs] of TRACE_DT, untraced: nops == 0; ops uint32).
         pileup=True (needs pileup_reset, passed pairs only): every traced pair also votes into the pileup table on the device; with
-        keep_ops=False the runs never reach the host and `ops` comes back empty (the records are the same)."""
+        keep_ops=False the runs never reach the host and `ops` comes back empty (the records are the same).  normalize=True (with
+        pileup): every gap run votes at its canonical position; records and runs are the same."""
         nt, no = C.c_uint64(0), C.c_uint64(0)
         cp = pars.c()
+        if normalize and not pileup:
+            raise ValueError("normalize=True normalises the votes: it needs pileup=True")
         if pileup:
             if not passed_only:
                 raise ValueError("pileup=True traces the passed pairs only")
-            self._chk(self.lib.bella_hip_trace_pairs_pileup(self.h, C.byref(cp), band0, 1 if keep_ops else 0, C.byref(nt), C.byref(no)))
+            if normalize:
+                flags = _lib.TRACE_PASSED_ONLY | _lib.TRACE_PILEUP | _lib.TRACE_NORMALIZE | (0 if keep_ops else _lib.TRACE_DROP_OPS)
+                self._chk(self.lib.bella_hip_trace_pairs_flags(self.h, C.byref(cp), band0, flags, C.byref(nt), C.byref(no)))
+            else:
+                self._chk(    self.lib.bella_hip_trace_pairs_pileup(self.h, C.byref(cp), band0, 1 if keep_ops else 0, C.byref(nt), C.byref(no)))
         else:
             self._chk(self.lib.bella_hip_trace_pairs(self.h, C.byref(cp), band0, 1 if passed_only else 0, C.byref(nt), C.byref(no)))
         tr = np.zeros(self.npairs, TRACE_DT)
@@ -358,6 +365,17 @@ class Engine:
     def pileup_reset(self):
         """allocates (first use) and zeroes the pileup table of the loaded reads: 9 uint32 per base"""
         self._chk(self.lib.bella_hip_pileup_reset(self.h))
+
+    def pileup_vote(self, pairs: np.ndarray, ops: np.ndarray, normalize: bool = False):
+        """votes caller-supplied traced pairs (VOTE_PAIR_DT; runs len << 4 | op in `ops`) into the table; normalize=True: with every gap
+        run at its canonical position.  Everything is validated before anything is voted."""
+        pr = np.ascontiguousarray(pairs, _lib.VOTE_PAIR_DT)
+        op = np.ascontiguousarray(ops, np.uint32)
+        self._chk(self.lib.bella_hip_pileup_vote(self.h, _p(pr), len(pr), _p(op), len(op), _lib.TRACE_NORMALIZE if normalize else 0))
+
+    def vote_stats(self) -> dict:
+        """what the last voting call did: the fields of bella_vote_stats"""
+        return self._stats(self.lib.bella_hip_get_vote_stats, _lib.VoteStats)
 
     def _range_bases(self, first, n):
         if first < 0 or n < 0 or first + n > self.nreads:

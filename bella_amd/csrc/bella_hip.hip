@@ -254,6 +254,7 @@ struct bella_ctx {
     bool trace_ops_kept = true;          // false: the last call piled its runs up on the device and did not stage them (keep_ops == 0)
     // read correction (pileup.hpp): the table of the loaded reads, and the last consensus
     uint64_t cons_total = 0;
+    bella_vote_stats vote_stats{};       // the last voting call (section 21)
     Buf pile, pile_pairs, pile_cnt, pile_tmp, cons_emit, cons_scan, cons_out, cons_offs, cons_stats;
     // correction rounds (recorrect.hpp; section 20): the anchors' offsets (one list per read), the consensus's anchors, and the last round
     uint64_t rc_nanch = 0;
@@ -3749,16 +3750,39 @@ int bella_hip_get_timings(bella_ctx* c, bella_timings* t) {
 namespace {
 struct TraceJob { uint32_t rid, cid, seedH, seedV; bella_aln a; };
 
+// The vote kernel on n pairs whose runs are in `ops` (device): section 10's, or with normalize section 21's.  The counters go to
+// c->pile_cnt, a zeroed PileNormCnt of which k_pile_vote writes the first field only.
+void launch_pile_vote(bella_ctx* c, bool normalize, const PilePair* pp, size_t n, const uint32_t* ops) {
+    const unsigned blocks = nblk(n, kPileBlock / 64);
+    if (normalize)
+        k_pile_vote_norm<<<blocks, kPileBlock, 0, c->stream>>>(pp, (uint32_t)n, ops, ptr<uint32_t>(c->packed), ptr<uint32_t>(c->pile), ptr<PileNormCnt>(c->pile_cnt));
+    else
+        k_pile_vote<<<blocks, kPileBlock, 0, c->stream>>>(pp, (uint32_t)n, ops, ptr<uint32_t>(c->packed), ptr<uint32_t>(c->pile), ptr<unsigned long long>(c->pile_cnt));
+}
+// c->pile_cnt into the counters of `vs`; waits for the device
+int read_vote_counts(bella_ctx* c, bella_vote_stats& vs) {
+    static_assert(offsetof(PileNormCnt, votes) == 0, "k_pile_vote adds its votes to the first field");
+    PileNormCnt nc{};
+    HIPCHK(c, hipMemcpyAsync(&nc, c->pile_cnt.p, sizeof(nc), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    vs.votes = nc.votes; vs.gap_runs = nc.gap_runs; vs.shifted_runs = nc.shifted_runs; vs.shifted_columns = nc.shifted_columns;
+    return 0;
+}
+
 // Traces jobs[0 .. n): out[n] records, ops appended to `ops` (op_off counts from the vector's start).  Pairs run in batches sized by
 // the free device memory (the direction bytes dominate); a pair whose path touched its band's edge on a side goes back into the queue
 // with that side's band doubled, until no side touches or the band holds the side's whole rectangle.
 // vote: every finished pair's runs also vote into the context's pileup table (pileup.hpp), from the batch's op array on the device;
 // keep_ops == false: the runs are not copied to the host (`ops` stays as it is; the records' op_off count as if they had been).
+// normalize (with vote): the votes are k_pile_vote_norm's (section 21); what the votes did goes to c->vote_stats either way.
 int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& jobs, uint32_t band0, bella_trace* out, std::vector<uint32_t>& ops,
-              bella_trace_stats& st, bool vote = false, bool keep_ops = true) {
+              bella_trace_stats& st, bool vote = false, bool keep_ops = true, bool normalize = false) {
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     st = bella_trace_stats{};
+    bella_vote_stats vs{};
+    vs.normalized = normalize ? 1u : 0u;
+    if (vote) c->vote_stats = vs;
     if (band0 == 0) band0 = BELLA_TRACE_DEFAULT_BAND;
     uint32_t b0 = kTrMinBand;
     while (b0 < band0 && b0 < kTrMaxBand) b0 <<= 1;
@@ -3818,8 +3842,8 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
     std::vector<PilePair> votep;
     uint64_t ops_seen = ops.size();                                   // runs written so far (= ops.size() while the runs are kept)
     if (vote) {
-        ENSURE(c, c->pile_cnt, 8);
-        HIPCHK(c, hipMemsetAsync(c->pile_cnt.p, 0, 8, c->stream));
+        ENSURE(c, c->pile_cnt, sizeof(PileNormCnt));
+        HIPCHK(c, hipMemsetAsync(c->pile_cnt.p, 0, sizeof(PileNormCnt), c->stream));
     }
     const uint32_t* const packed = ptr<uint32_t>(c->packed);
     while (!queue.empty()) {
@@ -3939,9 +3963,10 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                     ENSURE(c, c->pile_pairs, sizeof(PilePair) * votep.size());
                     HIPCHK(c, hipMemcpyAsync(c->pile_pairs.p, votep.data(), sizeof(PilePair) * votep.size(), hipMemcpyHostToDevice, c->stream));
                     HIPCHK(c, hipEventRecord(ev.d, c->stream));
-                    k_pile_vote<<<nblk(votep.size(), kPileBlock / 64), kPileBlock, 0, c->stream>>>(ptr<PilePair>(c->pile_pairs), (uint32_t)votep.size(), ptr<uint32_t>(c->tr_ops),
-                                                                                                   packed, ptr<uint32_t>(c->pile), ptr<unsigned long long>(c->pile_cnt));
+                    launch_pile_vote(c, normalize, ptr<PilePair>(c->pile_pairs), votep.size(), ptr<uint32_t>(c->tr_ops));
                     KCHK(c);
+                    vs.pairs += votep.size();
+                    for (const PilePair& vp : votep) vs.runs += vp.nops;
                     HIPCHK(c, hipEventRecord(ev.e, c->stream));
                 }
                 if (keep_ops) {
@@ -3961,10 +3986,10 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
         queue.swap(next);
     }
     if (vote) {
-        unsigned long long nv = 0;
-        HIPCHK(c, hipMemcpyAsync(&nv, c->pile_cnt.p, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        st.votes = nv;
+        if (int r = read_vote_counts(c, vs)) return r;
+        st.votes = vs.votes;
+        vs.vote_ms = st.vote_ms;
+        c->vote_stats = vs;
     }
     st.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
     return 0;
@@ -3975,7 +4000,8 @@ void trace_release(bella_ctx* c) {      // the batch buffers go back (directions
 }
 }  // namespace
 
-static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0, int passed_only, bool vote, bool keep_ops, uint64_t* ntraced, uint64_t* nops) {
+static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0, int passed_only, bool vote, bool keep_ops, uint64_t* ntraced, uint64_t* nops,
+                            bool normalize = false) {
     if (!c) return BELLA_ERR_BAD_ARG;
     if (int r = need(c, ALNS)) return r;
     if (vote) if (int r = need(c, PILE)) return r;
@@ -3999,7 +4025,7 @@ static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0,
     c->trace_ops.clear();
     if (!keep_ops) std::vector<uint32_t>().swap(c->trace_ops);
     if (vote) changed(c, PILE);
-    rc = run_trace(c, p, jobs, band0, tr.data(), c->trace_ops, c->trace_stats, vote, keep_ops);
+    rc = run_trace(c, p, jobs, band0, tr.data(), c->trace_ops, c->trace_stats, vote, keep_ops, normalize);
     trace_release(c);
     if (vote) release(c->pile_pairs);
     if (rc) { (void)hipDeviceSynchronize(); return rc; }
@@ -4024,10 +4050,11 @@ int bella_hip_trace_pairs_pileup(bella_ctx* c, const bella_params* p, uint32_t b
 
 int bella_hip_trace_pairs_flags(bella_ctx* c, const bella_params* p, uint32_t band0, uint32_t flags, uint64_t* ntraced, uint64_t* nops) {
     if (!c) return BELLA_ERR_BAD_ARG;
-    if (flags & ~(BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS | BELLA_TRACE_PILEUP)) return fail(c, BELLA_ERR_BAD_ARG, "trace_pairs_flags: unknown flag");
+    if (flags & ~(BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS | BELLA_TRACE_PILEUP | BELLA_TRACE_NORMALIZE)) return fail(c, BELLA_ERR_BAD_ARG, "trace_pairs_flags: unknown flag");
     const bool vote = (flags & BELLA_TRACE_PILEUP) != 0;
+    if ((flags & BELLA_TRACE_NORMALIZE) && !vote) return fail(c, BELLA_ERR_BAD_ARG, "trace_pairs_flags: BELLA_TRACE_NORMALIZE normalises the votes: it needs BELLA_TRACE_PILEUP");
     if (vote && !(flags & BELLA_TRACE_PASSED_ONLY)) return fail(c, BELLA_ERR_BAD_ARG, "trace_pairs_flags: the pileup takes the passed pairs only");
-    return trace_pairs_impl(c, p, band0, (flags & BELLA_TRACE_PASSED_ONLY) ? 1 : 0, vote, !(flags & BELLA_TRACE_DROP_OPS), ntraced, nops);
+    return trace_pairs_impl(c, p, band0, (flags & BELLA_TRACE_PASSED_ONLY) ? 1 : 0, vote, !(flags & BELLA_TRACE_DROP_OPS), ntraced, nops, (flags & BELLA_TRACE_NORMALIZE) != 0);
 }
 
 int bella_hip_get_traces(bella_ctx* c, bella_trace* out, uint32_t* ops) {
@@ -4216,6 +4243,68 @@ int bella_hip_pileup_reset(bella_ctx* c) {
 int bella_hip_get_pileup_bytes(bella_ctx* c, uint64_t* bytes) {
     if (!c || !bytes) return BELLA_ERR_BAD_ARG;
     *bytes = has(c, PILE) ? (uint64_t)c->total_bases * kPileCounters * 4 : 0;
+    return 0;
+}
+
+int bella_hip_get_vote_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    return put_sized(out, struct_size, c->vote_stats);
+}
+
+int bella_hip_pileup_vote(bella_ctx* c, const bella_vote_pair* pairs, uint64_t npairs, const uint32_t* ops, uint64_t nops_total, uint32_t flags) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if ((npairs && !pairs) || (nops_total && !ops)) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: null argument");
+    if (flags & ~BELLA_TRACE_NORMALIZE) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: flags is 0 or BELLA_TRACE_NORMALIZE");
+    if (npairs > 0xffffffffull) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: at most 2^32 - 1 pairs a call");
+    if (int r = need(c, PILE)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<uint64_t> off((size_t)c->nreads + 1);
+    HIPCHK(c, hipMemcpy(off.data(), c->roff.p, 8 * ((size_t)c->nreads + 1), hipMemcpyDeviceToHost));
+    // ---- everything is checked before anything is launched
+    std::vector<PilePair> vp;
+    vp.reserve((size_t)npairs);
+    bella_vote_stats vs{};
+    vs.normalized = flags ? 1u : 0u;
+    for (uint64_t q = 0; q < npairs; ++q) {
+        const bella_vote_pair& a = pairs[q];
+        if (a.rid >= c->nreads || a.cid >= c->nreads) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: pair %llu: read id out of range", (unsigned long long)q);
+        if (a.strand > 1) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: pair %llu: strand must be 0 or 1", (unsigned long long)q);
+        if (a.op_off > nops_total || a.nops > nops_total - a.op_off) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: pair %llu: its runs lie outside ops", (unsigned long long)q);
+        if (a.tbegV < 0 || a.tbegH < 0) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: pair %llu: negative start", (unsigned long long)q);
+        const uint64_t lenV = off[a.cid + 1] - off[a.cid], lenH = off[a.rid + 1] - off[a.rid];
+        uint64_t i = (uint64_t)a.tbegV, j = (uint64_t)a.tbegH;
+        for (uint32_t k = 0; k < a.nops; ++k) {
+            const uint32_t w = ops[a.op_off + k], op = w & 15u, len = w >> 4;
+            if (op > kOpDel) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: pair %llu run %u: op %u is none of = X I D", (unsigned long long)q, k, op);
+            if (!len) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: pair %llu run %u: length 0", (unsigned long long)q, k);
+            if (op != kOpDel) i += len;
+            if (op != kOpIns) j += len;
+        }
+        if (i > lenV || j > lenH) return fail(c, BELLA_ERR_BAD_ARG, "pileup_vote: pair %llu: its runs leave a read", (unsigned long long)q);
+        if (!a.nops) continue;
+        vp.push_back(PilePair{off[a.cid], off[a.rid], a.op_off, a.nops, (uint32_t)lenV, (uint32_t)lenH, (uint32_t)a.strand, a.tbegV, a.tbegH});
+        vs.pairs++;
+        vs.runs += a.nops;
+    }
+    changed(c, PILE);
+    if (!vp.empty()) {
+        TmpBuf dp, dops;
+        EventSet ev;
+        if (int r = ev.create(c, 2)) return r;
+        ENSURE(c, dp, sizeof(PilePair) * vp.size());
+        ENSURE(c, dops, 4 * (size_t)nops_total);
+        ENSURE(c, c->pile_cnt, sizeof(PileNormCnt));
+        HIPCHK(c, hipMemsetAsync(c->pile_cnt.p, 0, sizeof(PileNormCnt), c->stream));
+        HIPCHK(c, hipMemcpyAsync(dp.p, vp.data(), sizeof(PilePair) * vp.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dops.p, ops, 4 * (size_t)nops_total, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        launch_pile_vote(c, flags != 0, ptr<PilePair>(dp), vp.size(), ptr<uint32_t>(dops));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        if (int r = read_vote_counts(c, vs)) return r;                // (waits: vp and the caller's ops are free again)
+        vs.vote_ms = ev_ms(ev.a, ev.b);
+    }
+    c->vote_stats = vs;
     return 0;
 }
 

@@ -124,6 +124,160 @@ __global__ __launch_bounds__(kPileBlock) void k_pile_vote(const PilePair* pp, ui
     if (lane == 0 && nv) atomicAdd(votes, (unsigned long long)nv);
 }
 
+// ---- votes with every gap run at its canonical position (the test kit states it in numpy) ---------
+// k_pile_vote's mapping -- one wavefront per pair, 64 runs per chunk in registers, no LDS -- on modified run records.  A gap lane
+// decides its own run: the left shift sL inside the '=' run before it, the right shift sR inside the '=' run behind it (strand 1
+// only: nobody else reads it), each the common suffix / prefix of S[..x) and S[..x + L) over the 2-bit bases, at most the length of
+// that '=' run.  The neighbours' words come over __shfl_up / __shfl_down; the last run of the chunk before is carried in a register
+// and lane 63 loads the first run of the chunk behind (where that run is a gap, lane 63 also works out what it takes from it).
+// Pass L deals the columns of the left-normalised runs (the '=' run gives up sL columns, the gap lane owns L + sL: its tail is '='
+// columns at the displaced coordinates) and casts the V-side votes of every pair and the H-side votes of a strand-0 pair; a strand-1
+// pair deals its columns a second time (pass R, the mirror image with sR) for its H-side votes: right in V order is left in H's own
+// direction.  The atomics per pair are what k_pile_vote issues.  The shift loop goes base by base: it is bounded by the length of
+// one '=' run (a few bases at 15 % error; a long homopolymer in an exact overlap costs its wave that many steps once).
+struct PileNormCnt { unsigned long long votes, gap_runs, shifted_runs, shifted_columns; };
+
+// S is V (row = rowV) or H' (row = rowH; rev: position a of H' is position lenS - 1 - a of H -- the complement does not matter to a
+// comparison inside S).  Both return 0 where a comparison would leave S.
+__device__ __forceinline__ uint32_t pile_sbase(const uint32_t* packed, uint64_t row, uint32_t lenS, bool rev, uint32_t a) {
+    return pile_base(packed, row + (rev ? lenS - 1 - a : a));
+}
+__device__ __forceinline__ uint32_t pile_shift_left(const uint32_t* packed, uint64_t row, uint32_t lenS, bool rev, uint32_t x, uint32_t L, uint32_t d) {
+    if ((uint64_t)x + L > lenS) return 0;
+    if (d > x) d = x;
+    uint32_t s = 0;
+    while (s < d && pile_sbase(packed, row, lenS, rev, x - 1 - s) == pile_sbase(packed, row, lenS, rev, x + L - 1 - s)) ++s;
+    return s;
+}
+__device__ __forceinline__ uint32_t pile_shift_right(const uint32_t* packed, uint64_t row, uint32_t lenS, bool rev, uint32_t x, uint32_t L, uint32_t d) {
+    if ((uint64_t)x + L >= lenS) return 0;
+    if (d > lenS - x - L) d = lenS - x - L;
+    uint32_t s = 0;
+    while (s < d && pile_sbase(packed, row, lenS, rev, x + s) == pile_sbase(packed, row, lenS, rev, x + L + s)) ++s;
+    return s;
+}
+
+__global__ __launch_bounds__(kPileBlock) void k_pile_vote_norm(const PilePair* pp, uint32_t npairs, const uint32_t* ops, const uint32_t* packed, uint32_t* table,
+                                                               PileNormCnt* cnt) {
+    const uint32_t q = (uint32_t)(((uint64_t)blockIdx.x * kPileBlock + threadIdx.x) >> 6);
+    if (q >= npairs) return;                                          // (whole wavefronts leave)
+    const int lane = (int)(threadIdx.x & 63);
+    const PilePair P = pp[q];
+    const uint32_t* const po = ops + P.op_off;
+    const uint32_t comp = P.strand ? 3u : 0u;
+    uint32_t ci = (uint32_t)P.i0, cj = (uint32_t)P.j0;               // where the chunk's first run starts
+    uint32_t prev_w = 0, prev_sR = 0;                                 // the last run of the chunk before ('=' of length 0: no shift) and its right shift
+    uint32_t nv = 0, n_gap = 0, n_shift = 0, n_cols = 0;
+    for (uint32_t c0 = 0; c0 < P.nops; c0 += 64) {
+        const uint32_t w = c0 + lane < P.nops ? po[c0 + lane] : 0u;
+        const uint32_t op = w & 15u, len = w >> 4;
+        uint32_t wp = __shfl_up(w, 1, 64), wn = __shfl_down(w, 1, 64);
+        if (lane == 0) wp = prev_w;
+        if (lane == 63) wn = c0 + 64 < P.nops ? po[c0 + 64] : 0u;
+        const uint32_t di = op != kOpDel ? len : 0u, dj = op != kOpIns ? len : 0u;
+        const uint32_t ei = pile_scan_incl(di, lane), ej = pile_scan_incl(dj, lane);
+        const uint32_t si = ci + ei - di, sj = cj + ej - dj;          // this lane's run starts at (si, sj)
+        // ---- the shifts of this lane's gap run
+        const bool gap = (op == kOpIns || op == kOpDel) && len;
+        uint32_t sL = 0, sR = 0;
+        if (gap) {
+            const bool isI = op == kOpIns;
+            const uint64_t row = isI ? P.rowV : P.rowH;
+            const uint32_t lenS = isI ? P.lenV : P.lenH, x = isI ? si : sj;
+            const bool rev = !isI && P.strand;
+            if ((wp & 15u) == kOpEq) sL = pile_shift_left(packed, row, lenS, rev, x, len, wp >> 4);
+            if (P.strand && (wn & 15u) == kOpEq) sR = pile_shift_right(packed, row, lenS, rev, x, len, wn >> 4);
+            const uint32_t sH = P.strand ? sR : sL;
+            ++n_gap;
+            n_shift += (sL ? 1u : 0u) + (sH ? 1u : 0u);
+            n_cols += sL + sH;
+        }
+        // ---- what an '=' lane gives to the gap behind it (pass L) and to the gap before it (pass R)
+        uint32_t giveL = __shfl_down(sL, 1, 64), takeR = __shfl_up(sR, 1, 64);
+        if (lane == 0) takeR = prev_sR;
+        if (lane == 63) {
+            giveL = 0;
+            const uint32_t nop = wn & 15u, nlen = wn >> 4;
+            if (op == kOpEq && (nop == kOpIns || nop == kOpDel) && nlen) {               // the first run of the chunk behind is a gap: its left shift, as its own lane will find it
+                const bool isI = nop == kOpIns;
+                giveL = pile_shift_left(packed, isI ? P.rowV : P.rowH, isI ? P.lenV : P.lenH, !isI && P.strand, (isI ? si : sj) + len, nlen, len);
+            }
+        }
+        for (uint32_t pass = 0; pass <= P.strand; ++pass) {
+            const bool voteV = pass == 0, voteH = pass == 1 || !P.strand;
+            // the lane's record of this pass: mlen columns from (ai, aj); a gap lane's first `pre` and last mlen - pre - len are '='
+            const uint32_t sh = pass ? sR : sL;
+            const uint32_t mlen = op == kOpEq ? len - (pass ? takeR : giveL) : len + sh;
+            const uint32_t back = pass ? 0u : sh, fwd = pass && op == kOpEq ? takeR : 0u;
+            const uint32_t ai = si - back + fwd, aj = sj - back + fwd, pre = pass ? sh : 0u;
+            const uint32_t ec = pile_scan_incl(mlen, lane);
+            const uint32_t total = __shfl(ec, 63, 64);
+            for (uint32_t t0 = 0; t0 < total; t0 += 64) {
+                const bool live = t0 + lane < total;
+                const uint32_t t = live ? t0 + lane : total - 1;
+                int r = 0;                                            // the first run whose columns end behind t
+#pragma unroll
+                for (int s = 32; s >= 1; s >>= 1) {
+                    const uint32_t e = __shfl(ec, r + s - 1, 64);
+                    if (e <= t) r += s;
+                }
+                const uint32_t rw = __shfl(w, r, 64), rend = __shfl(ec, r, 64), rmlen = __shfl(mlen, r, 64), ri = __shfl(ai, r, 64), rj = __shfl(aj, r, 64),
+                               rpre = __shfl(pre, r, 64);
+                const uint32_t rop = rw & 15u, rlen = rw >> 4;
+                if (!live || rop > kOpDel) continue;
+                const uint32_t o = t - (rend - rmlen);
+                const bool in_gap = rop >= kOpIns && o >= rpre && o < rpre + rlen;
+                if (!in_gap) {                                        // an aligned column: of an '=' / 'X' run, or one a gap jumped over
+                    const uint32_t skip = rop >= kOpIns && o >= rpre ? rlen : 0u;      // behind the gap: past its bases on the side that has them
+                    const uint32_t i = ri + o - skip + (rop == kOpIns ? skip : 0u), j = rj + o - skip + (rop == kOpDel ? skip : 0u);
+                    if (i < P.lenV && j < P.lenH) {
+                        const uint64_t gH = P.rowH + (P.strand ? (uint64_t)P.lenH - 1 - j : (uint64_t)j);
+                        const uint32_t vb = pile_base(packed, P.rowV + i), hb = pile_base(packed, gH) ^ comp;
+                        if (voteV) { atomicAdd(table + (P.rowV + i) * kPileCounters + hb, 1u); ++nv; }
+                        if (voteH) { atomicAdd(table + gH * kPileCounters + (vb ^ comp), 1u); ++nv; }
+                    }
+                    continue;
+                }
+                const uint32_t g = o - rpre, gi = ri + rpre, gj = rj + rpre;           // column g of the gap that starts at (gi, gj)
+                if (rop == kOpIns) {                                  // a base of V only
+                    const uint32_t i = gi + g;
+                    if (voteV && i < P.lenV) { atomicAdd(table + (P.rowV + i) * kPileCounters + kPileDel, 1u); ++nv; }
+                    if (voteH && g == 0) {                            // (k_pile_vote's junction and base)
+                        const uint32_t jn = P.strand ? P.lenH - gj : gj;
+                        const uint32_t iv = P.strand ? gi + rlen - 1 : gi;
+                        if (gj <= P.lenH && jn < P.lenH && iv < P.lenV) {
+                            atomicAdd(table + (P.rowH + jn) * kPileCounters + kPileIns + (pile_base(packed, P.rowV + iv) ^ comp), 1u);
+                            ++nv;
+                        }
+                    }
+                } else {                                              // a base of H' only
+                    const uint32_t j = gj + g;
+                    const uint64_t gH = P.rowH + (P.strand ? (uint64_t)P.lenH - 1 - j : (uint64_t)j);
+                    if (voteH && j < P.lenH) { atomicAdd(table + gH * kPileCounters + kPileDel, 1u); ++nv; }
+                    if (voteV && g == 0 && gi < P.lenV && gj < P.lenH) {
+                        atomicAdd(table + (P.rowV + gi) * kPileCounters + kPileIns + (pile_base(packed, gH) ^ comp), 1u);
+                        ++nv;
+                    }
+                }
+            }
+        }
+        ci += __shfl(ei, 63, 64);
+        cj += __shfl(ej, 63, 64);
+        prev_w = __shfl(w, 63, 64);
+        prev_sR = __shfl(sR, 63, 64);
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        nv += __shfl_xor(nv, d, 64); n_gap += __shfl_xor(n_gap, d, 64); n_shift += __shfl_xor(n_shift, d, 64); n_cols += __shfl_xor(n_cols, d, 64);
+    }
+    if (lane == 0) {
+        if (nv) atomicAdd(&cnt->votes, (unsigned long long)nv);
+        if (n_gap) atomicAdd(&cnt->gap_runs, (unsigned long long)n_gap);
+        if (n_shift) atomicAdd(&cnt->shifted_runs, (unsigned long long)n_shift);
+        if (n_cols) atomicAdd(&cnt->shifted_columns, (unsigned long long)n_cols);
+    }
+}
+
 // table[first + x] += add[x]  (bella_hip_add_pileup: another context's counters)
 __global__ void k_pile_add(uint32_t* table, const uint32_t* add, uint64_t n) {
     const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

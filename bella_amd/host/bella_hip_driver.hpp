@@ -56,6 +56,7 @@ struct Worker {
     RawBuf<bella_trace> traces;              // --cigar: the stage's traced alignments and their runs
     RawBuf<uint32_t> ops;
     uint64_t nnzc = 0;
+    uint64_t gap_runs = 0, shifted_runs = 0, shifted_columns = 0;      // normalize_gaps: summed over the stages (bella_vote_stats)
 };
 // what the last call of this process did (tests, logs): every column must be computed by the numeric phase exactly once
 struct CallStats {
@@ -132,6 +133,7 @@ struct StageOpts {
     uint32_t weak_min = 500, weak_max = 700, weak_steps = 2;   // ratio rising from weak_min to weak_max permille, tips and bubbles again after each that cut
     uint32_t correct_rounds = 1;     // correction rounds: correct_rounds - 1 rounds follow the consensus, each aligning the partners'
     uint32_t correct_band = 512, correct_min_identity = 700;    // raw clips against the corrected reads of the round before; the file carries the last round
+    int normalize_gaps = 0;          // gap normalisation of every stage's votes
     bool graph() const { return gfa || unitigs || unitigs_fasta; }
     bool pileup() const { return correct || polish; }
     bool records() const { return graph() || (correct && correct_rounds > 1); }      // every stage adds its traced passed pairs as overlap records
@@ -461,7 +463,13 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
                 if (w.nnzc) check(w.ctx, bella_hip_get_alignments(w.ctx, w.alns.data()), "bella_hip_get_alignments");
                 uint64_t ntr = 0, nops = 0;
                 // (--correct / --polish: the stage's runs vote on the device; they come to the host only when the true PAF wants them too)
-                if (o.pileup()) check(w.ctx, bella_hip_trace_pairs_pileup(w.ctx, &p, o.trace_band, o.cigar ? 1 : 0, &ntr, &nops), "bella_hip_trace_pairs_pileup");
+                if (o.pileup() && o.normalize_gaps) {
+                    const uint32_t fl = BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_PILEUP | BELLA_TRACE_NORMALIZE | (o.cigar ? 0u : BELLA_TRACE_DROP_OPS);
+                    check(w.ctx, bella_hip_trace_pairs_flags(w.ctx, &p, o.trace_band, fl, &ntr, &nops), "bella_hip_trace_pairs_flags");
+                    bella_vote_stats vs{};
+                    check(w.ctx, bella_hip_get_vote_stats(w.ctx, &vs, sizeof(vs)), "bella_hip_get_vote_stats");
+                    w.gap_runs += vs.gap_runs; w.shifted_runs += vs.shifted_runs; w.shifted_columns += vs.shifted_columns;
+                } else if (o.pileup()) check(w.ctx, bella_hip_trace_pairs_pileup(w.ctx, &p, o.trace_band, o.cigar ? 1 : 0, &ntr, &nops), "bella_hip_trace_pairs_pileup");
                 else if (o.cigar) check(w.ctx, bella_hip_trace_pairs(w.ctx, &p, o.trace_band, 1, &ntr, &nops), "bella_hip_trace_pairs");
                 // (--gfa alone: the records are all the graph reads; no run is written or staged)
                 else if (o.records()) check(w.ctx, bella_hip_trace_pairs_flags(w.ctx, &p, o.trace_band, BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS, &ntr, &nops), "bella_hip_trace_pairs_flags");
@@ -591,6 +599,12 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         BELLA_HIP_LOGT(tag, OutputtingTime);
     }
     if (o.pileup()) merge_pileups(W, o, lens);
+    if (o.pileup() && o.normalize_gaps) {                                     // the run's sums over stages and contexts
+        uint64_t gaps = 0, runs = 0, cols = 0;
+        for (const Worker& w : W) { gaps += w.gap_runs; runs += w.shifted_runs; cols += w.shifted_columns; }
+        const std::string NormalizedGaps = std::to_string(runs) + " shifted_runs, " + std::to_string(cols) + " shifted_columns (of " + std::to_string(gaps) + " gap runs, two voted reads each)";
+        BELLA_HIP_LOGT(tag, NormalizedGaps);
+    }
     if (o.records()) gather_records(W, o);
     if (o.correct) write_corrected(W, o, names);
     if (o.graph()) write_graph(W, o, names, lens);

@@ -21,6 +21,7 @@
 // --correct-rounds N: N - 1 correction rounds follow the consensus, each aligning the raw partners of every traced
 // pair against the corrected reads of the round before; FILE then holds the last round.
 //
+// --normalize-gaps: with --correct / --polish, every gap run votes at its canonical position.
 // --polish: unitig consensus: every stage's traced pairs vote as with --correct, the unitigs are polished from
 // the pileup on the device after the last stage; --unitigs / --unitigs-fasta then carry the polished sequences and coordinates.
 // --polish-rounds N: N - 1 realignment rounds follow, each aligning the reads against the unitigs of the round before.
@@ -71,6 +72,7 @@ struct Options {
     bool trim = false, trim_param_given = false;
     int weak_min = 500, weak_max = 700, weak_steps = 2;
     bool cut_weak = false, weak_param_given = false;
+    bool normalize_gaps = false;
     bool graph() const { return !gfa.empty() || !unitigs.empty() || !unitigs_fasta.empty(); }
 };
 
@@ -106,6 +108,8 @@ const char* kHelp =
     "                             overlap against the corrected reads of the round before, on the device, and takes the consensus of those alignments\n"
     "      --correct-band arg     with --correct: the first band of those alignments, a power of two from 256 to 4096 (default: 512)\n"
     "      --correct-min-identity arg  with --correct: permille of matches below which an alignment does not vote (default: 700)\n"
+    "      --normalize-gaps       with --correct / --polish: every gap of the base-level alignments votes at a canonical position (moved towards the start\n"
+    "                             of the read it votes on, inside the neighbouring run of matches), so equal indels seen from either side add up\n"
     "      --gfa arg              string graph (GFA 1): overlap classes, contained reads dropped, transitive reduction, on the device\n"
     "      --gfa-min-overlap arg  with --gfa: shortest overlap that counts (default: 1000)\n"
     "      --gfa-max-overhang arg with --gfa: longest unaligned end of a dovetail or containment (default: 1000)\n"
@@ -156,6 +160,7 @@ Options parse(int argc, char** argv) {
         {"upper-freq", 'u', 1, &o.upper}, {"lower-freq", 'l', 1, &o.lower}, {"tuples", 0, 3, &o.tuples}, {"exact-xdrop", 0, 0, &o.exact}, {"cigar", 0, 0, &o.cigar}, {"trace-band", 0, 1, &o.trace_band},
         {"correct", 0, 3, &o.correct}, {"min-depth", 0, 1, &o.min_depth},
         {"correct-rounds", 0, 1, &o.correct_rounds}, {"correct-band", 0, 1, &o.correct_band}, {"correct-min-identity", 0, 1, &o.correct_min_identity},
+        {"normalize-gaps", 0, 0, &o.normalize_gaps},
         {"gfa", 0, 3, &o.gfa}, {"gfa-fuzz", 0, 1, &o.gfa_fuzz}, {"gfa-max-overhang", 0, 1, &o.gfa_max_overhang}, {"gfa-min-overlap", 0, 1, &o.gfa_min_overlap},
         {"gfa-no-seq", 0, 0, &o.gfa_no_seq},
         {"unitigs", 0, 3, &o.unitigs}, {"unitigs-fasta", 0, 3, &o.unitigs_fasta}, {"tip-reads", 0, 1, &o.tip_reads}, {"tip-rounds", 0, 1, &o.tip_rounds}, {"gfa-clean", 0, 0, &o.gfa_clean},
@@ -297,6 +302,7 @@ int main(int argc, char** argv) {
     if (o.correct_rounds < 1 || o.correct_rounds > 4) die("--correct-rounds must be in [1, 4]");
     if (o.correct_band < 256 || o.correct_band > 4096 || (o.correct_band & (o.correct_band - 1))) die("--correct-band must be a power of two in [256, 4096]");
     if (o.correct_min_identity < 0 || o.correct_min_identity > 1000) die("--correct-min-identity is in permille: [0, 1000]");
+    if (o.normalize_gaps && o.correct.empty() && !o.polish) die("--normalize-gaps needs --correct or --polish (it changes where the gaps of the pileup vote)");
     if (o.kmer < 1 || o.kmer > 32) die("-k must be in [1,32] (one 64-bit word per k-mer, Kmer.hpp:27-28)");
     const std::string outfile = o.output + ".out";                  // main.cpp:113-130
     std::remove(outfile.c_str());
@@ -450,6 +456,7 @@ int main(int argc, char** argv) {
     so.polish_min_depth = (uint32_t)o.polish_min_depth;
     so.polish_rounds = (uint32_t)o.polish_rounds; so.realign_band = (uint32_t)o.realign_band; so.realign_min_identity = (uint32_t)o.realign_min_identity; so.realign_circular = o.realign_circular;
     so.correct_rounds = (uint32_t)o.correct_rounds; so.correct_band = (uint32_t)o.correct_band; so.correct_min_identity = (uint32_t)o.correct_min_identity;
+    so.normalize_gaps = o.normalize_gaps ? 1 : 0;
     so.trim = o.trim ? 1 : 0;
     so.trim_depth = (uint32_t)o.trim_depth; so.trim_end_clip = (uint32_t)o.trim_end_clip;
     so.trimmed_reads = o.trimmed_reads.empty() ? nullptr : o.trimmed_reads.c_str();

@@ -382,6 +382,49 @@ int bella_hip_pileup_reset(bella_ctx* ctx);
  * kept.  keep_ops != 0: the context is left exactly as bella_hip_trace_pairs leaves it.  The table accumulates over calls until the next
  * bella_hip_pileup_reset; a pair repeated with a wider band votes once, with its final trace.  BELLA_ERR_STATE without a table. */
 int bella_hip_trace_pairs_pileup(bella_ctx* ctx, const bella_params* p, uint32_t band0, int keep_ops, uint64_t* ntraced, uint64_t* nops);
+/* ---- gap normalisation of the votes --------------------------------------------------------------------------
+ * BELLA_TRACE_NORMALIZE (bella_hip_trace_pairs_flags; needs BELLA_TRACE_PILEUP) and the same flag of bella_hip_pileup_vote make every
+ * gap run vote at a canonical position: moved towards the START of the read being voted on, in that read's own forward direction.
+ * For a gap run k of length L that starts at (i_k, j_k), S = V, x = i_k for 'I' and S = H', x = j_k for 'D':
+ *   sL_k = 0 unless run k - 1 is an '=' run (length d); else the largest s in [0, d] with S[x-1-t] == S[x+L-1-t] for all t < s;
+ *   sR_k = 0 unless run k + 1 is an '=' run (length d'); else the largest s in [0, d'] with S[x+t] == S[x+L+t] for all t < s.
+ * Every gap run shifts independently and only inside its ORIGINAL neighbouring '=' run.  The votes on V, and on H when strand == 0,
+ * are those of the alignment with every gap moved left by sL (the '=' columns it jumped over follow it, still matches); the votes on H
+ * when strand == 1 are those of the alignment with every gap moved right by sR (right in V order is left in H's own direction).  A gap
+ * run still casts ONE ins vote, also where it now abuts another gap run; the junction behind a read's last base still has no counters.
+ * Only the votes change: the records and runs a call hands out are what they are without the flag. */
+#define BELLA_TRACE_NORMALIZE 8u
+/* What the last voting call (bella_hip_trace_pairs_pileup, bella_hip_trace_pairs_flags with BELLA_TRACE_PILEUP, bella_hip_pileup_vote)
+ * did.  A sized struct: bella_hip_get_vote_stats writes at most struct_size bytes. */
+typedef struct {
+    uint64_t pairs;               /* pairs that voted                                                          */
+    uint64_t runs;                /* their runs                                                                */
+    uint64_t gap_runs;            /* 'I' and 'D' runs among them (0 without BELLA_TRACE_NORMALIZE: nobody counts them) */
+    uint64_t shifted_runs;        /* (gap run, voted read) combinations with a non-zero shift: sL for V; sL (strand 0) or sR (strand 1) for H */
+    uint64_t shifted_columns;     /* the sum of those shifts                                                   */
+    uint64_t votes;               /* counter increments issued                                                 */
+    double vote_ms;               /* the vote kernel (device time, all batches)                                */
+    uint32_t normalized;          /* 1: the call ran with BELLA_TRACE_NORMALIZE                                */
+    uint32_t pad;
+} bella_vote_stats;
+int bella_hip_get_vote_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+/* One traced pair of a caller: V = read cid, H = read rid (H' = its reverse complement when strand == 1), nops runs (len << 4 | op, as
+ * bella_trace's) from ops[op_off] in V order, the first at (tbegV, tbegH) of V and H'. */
+typedef struct {
+    uint32_t rid, cid;
+    int32_t tbegV, tbegH;
+    uint64_t op_off;
+    uint32_t nops;
+    uint8_t strand;
+    uint8_t pad[3];
+} bella_vote_pair;
+/* Votes caller-supplied traced pairs into the table: the pileup counterpart of bella_hip_trace_batch, for alignments made elsewhere.
+ * flags: 0 (the votes of bella_hip_trace_pairs_pileup) or BELLA_TRACE_NORMALIZE.  The host checks everything BEFORE anything is
+ * launched -- read ids in range, strand 0 or 1, every run's op in 0..3 and its length at least 1, every pair's runs inside both
+ * reads from (tbegV, tbegH) >= 0, op_off + nops inside ops[nops_total] -- and returns BELLA_ERR_BAD_ARG with nothing voted otherwise.
+ * '=' columns are TRUSTED to be matches: they vote the other read's base like any aligned column, and the normalisation relies on
+ * them when it moves a gap across them.  BELLA_ERR_STATE without a table. */
+int bella_hip_pileup_vote(bella_ctx* ctx, const bella_vote_pair* pairs, uint64_t npairs, const uint32_t* ops, uint64_t nops_total, uint32_t flags);
 /* Copies the counters of the reads [first_read, first_read + nreads) out (out: 9 uint32 per base of those reads), or adds a caller's
  * counters into the table (how several contexts merge: each piles up its own columns, one of them adds the others' tables). */
 int bella_hip_get_pileup(bella_ctx* ctx, uint32_t first_read, uint32_t nreads, uint32_t* out);
@@ -486,8 +529,9 @@ int bella_hip_graph_get_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 /* What bella_hip_trace_pairs does, steered by flags: bit0 = passed pairs only; bit1 = the runs are DROPPED: not staged on the host, and
  * when nothing else reads them (no bit2) not written at all -- the records (end points, counts, nops, op_off as they would be) are all a
  * caller such as bella_hip_graph_add_traced needs; bella_hip_get_traces then takes ops == NULL only; bit2 = the runs vote into the pileup
- * table (needs bit0 and a table).  flags = 1 is bella_hip_trace_pairs(passed_only = 1), 5 / 7 are bella_hip_trace_pairs_pileup with
- * keep_ops 1 / 0. */
+ * table (needs bit0 and a table); bit3 = BELLA_TRACE_NORMALIZE (the read-correction section above; needs bit2, BELLA_ERR_BAD_ARG without
+ * it): those votes are cast with every gap run at its canonical position.  flags = 1 is bella_hip_trace_pairs(passed_only = 1), 5 / 7
+ * are bella_hip_trace_pairs_pileup with keep_ops 1 / 0. */
 #define BELLA_TRACE_PASSED_ONLY 1u
 #define BELLA_TRACE_DROP_OPS 2u
 #define BELLA_TRACE_PILEUP 4u

@@ -8,7 +8,11 @@ The expectation DESIGN.md section 10 checks: vote_ms below walk_ms.
 
 --correct-rounds N: the traced pairs' records are accumulated, N - 1 correction rounds follow the consensus, and
 per round the stats line (jobs by status, the phase times, DP cells, batches, bases) is printed next to the first trace's dp_ms and kept
-under "recorrect" in the set's entry."""
+under "recorrect" in the set's entry.
+
+--normalize-gaps: after the plain call the table is reset and the same pairs are traced and piled up once more
+with every gap run at its canonical position; both vote_ms and both sets of vote stats of the one run are printed and kept under
+"normalize" (the consensus and the rounds stay the plain call's)."""
 import argparse
 import json
 import os
@@ -22,7 +26,7 @@ from bella_amd import BellaPars, Engine  # noqa: E402
 from bella_testkit import synth  # noqa: E402
 
 
-def probe(nreads, band, min_depth, correct_rounds=1, correct_band=512):
+def probe(nreads, band, min_depth, correct_rounds=1, correct_band=512, normalize_gaps=False):
     rs = synth.make_reads_fast(nreads, read_len=10000, err=0.15, seed=1)
     eng = Engine(0)
     eng.reserve(44 * int(rs.offsets[-1]))
@@ -42,6 +46,21 @@ def probe(nreads, band, min_depth, correct_rounds=1, correct_band=512):
     t0 = time.time()
     offs, bases, stats = eng.consensus(min_depth)
     cons_s = time.time() - t0
+    norm = None
+    if normalize_gaps:
+        plain = eng.vote_stats()
+        eng.pileup_reset()
+        eng.trace_pairs(pars, band0=band, pileup=True, keep_ops=False, normalize=True)
+        nst, nvs = eng.trace_stats(), eng.vote_stats()
+        _, nbases, nstats = eng.consensus(min_depth)
+        norm = dict(plain=plain, normalized=nvs, vote_ms_plain=plain["vote_ms"], vote_ms_normalized=nvs["vote_ms"], walk_ms_normalized=nst.walk_ms,
+                    vote_ratio=nvs["vote_ms"] / max(1e-9, plain["vote_ms"]), corrected_bases=int(len(nbases)), substituted=int(nstats["substituted"].sum()),
+                    deleted=int(nstats["deleted"].sum()), inserted=int(nstats["inserted"].sum()))
+        print("NORMALIZE %d reads: %s" % (nreads, json.dumps(norm)))
+        if correct_rounds > 1:                                       # the rounds below start from the plain consensus, as without the option
+            eng.pileup_reset()
+            eng.trace_pairs(pars, band0=band, pileup=True, keep_ops=False)
+            eng.consensus(min_depth)
     rounds = []
     if correct_rounds > 1:
         eng.graph_reset()
@@ -61,6 +80,8 @@ def probe(nreads, band, min_depth, correct_rounds=1, correct_band=512):
                deleted=int(stats["deleted"].sum()), inserted=int(stats["inserted"].sum()))
     if rounds:
         out["recorrect"] = rounds
+    if norm:
+        out["normalize"] = norm
     eng.close()
     return out
 
@@ -72,9 +93,10 @@ if __name__ == "__main__":
     ap.add_argument("--min-depth", type=int, default=3)
     ap.add_argument("--correct-rounds", type=int, default=1)
     ap.add_argument("--correct-band", type=int, default=512)
+    ap.add_argument("--normalize-gaps", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pileup_probe.json"))
     a = ap.parse_args()
-    res = [probe(n, a.band, a.min_depth, a.correct_rounds, a.correct_band) for n in a.reads]
+    res = [probe(n, a.band, a.min_depth, a.correct_rounds, a.correct_band, a.normalize_gaps) for n in a.reads]
     for r in res:
         print(json.dumps(r))
     with open(a.out, "w") as f:

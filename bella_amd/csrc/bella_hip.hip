@@ -294,6 +294,7 @@ struct bella_ctx {
     uint32_t tune_product_entries = 0;   // BELLA_TUNE_PRODUCT_ENTRIES: 0 one B' entry per product when it stays within 12 B per owned nonzero, 1 never, 2 always
     uint32_t tune_order_split = kOrderOneLaunchMax;   // BELLA_TUNE_ORDER_SPLIT: owned columns of a pass above which k_order_wave runs as two instances
     uint64_t tune_round_budget = 0;      // BELLA_TUNE_ROUND_BUDGET: direction bytes of a batch of a realignment / correction round; 0 by the free memory (round_budget)
+    uint64_t tune_xdrop_batch = 0;       // BELLA_TUNE_XDROP_BATCH: extensions of a batch of the X-drop slices, as given; 0 by the free memory (run_xdrop)
     uint32_t tune_dist_layout = 2;       // BELLA_TUNE_DIST_LAYOUT: bella_hip_allgather_panels forms A' by k-mer id ranges over the communicator's ranks
                                          // (1: always, 0: never, 2 = default: on the in-process transport only -- over RCCL the path has not run on
                                          // more than one device yet, and its extra 20 B per nonzero of traffic want a measurement first)
@@ -897,13 +898,19 @@ int build_layout(bella_ctx* c, bool collective = false) {
     return 0;
 }
 
+// Xavier's scores are int8: the rule of align_pairs and of xdrop_batch (the LOGAN-scoring calls have no such bound)
+int check_xavier_xdrop(bella_ctx* c, const bella_params* p) {
+    if (p->xdrop > 127) return fail(c, BELLA_ERR_BAD_ARG, "params.xdrop must fit Xavier's int8 scores (<= 127)");
+    return 0;
+}
+
 int check_params(bella_ctx* c, const bella_params* p) {
     if (!p) return fail(c, BELLA_ERR_BAD_ARG, "params is NULL");
     if (p->kmer_size != c->kmer_size)
         return fail(c, BELLA_ERR_BAD_ARG, "params.kmer_size (%u) differs from the matrix's (%u)", p->kmer_size, c->kmer_size);
     // (bin_size == 0 is legal: chain.hpp:114 compares |overlap difference| < binSize, so no two products ever share a bin)
     if (!p->skip_alignment) {
-        if (p->xdrop > 127) return fail(c, BELLA_ERR_BAD_ARG, "params.xdrop must fit Xavier's int8 scores (<= 127)");
+        if (int r = check_xavier_xdrop(c, p)) return r;
         if (!(p->error_rate >= 0.0 && p->error_rate <= 1.0) || !(p->delta_chernoff >= 0.0 && p->delta_chernoff <= 1.0))
             return fail(c, BELLA_ERR_BAD_ARG, "params.error_rate and params.delta_chernoff must lie in [0, 1]");
     }
@@ -1083,6 +1090,7 @@ int bella_hip_set_tuning(bella_ctx* c, uint32_t what, const uint64_t* values, ui
             c->tune_order_split = n ? (uint32_t)(values[0] < 0xFFFFFFFFull ? values[0] : 0xFFFFFFFFull) : kOrderOneLaunchMax;
             return 0;
         case BELLA_TUNE_ROUND_BUDGET: c->tune_round_budget = n ? values[0] : 0; return 0;
+        case BELLA_TUNE_XDROP_BATCH: c->tune_xdrop_batch = n ? values[0] : 0; return 0;
     }
     return fail(c, BELLA_ERR_BAD_ARG, "unknown tuning parameter %u", what);
 }
@@ -3510,8 +3518,10 @@ static int run_xdrop(bella_ctx* c, const bella_params* p, const bella_seed* d_se
                 // every launch runs full wavefronts of survivors.  Batches bound the state memory (288 B per extension).
                 // (at most 16 M extensions = 4.8 GB, at most a quarter of the free device memory, at least 64 k; an allocation that
                 // fails all the same halves the batch, and below 64 k extensions the one-launch kernel, which needs no state, takes over)
+                // (BELLA_TUNE_XDROP_BATCH: the capacity as given -- tests run several batches on small inputs)
                 uint64_t capB = ne < (16ull << 20) ? ne : (16ull << 20);
-                {
+                if (c->tune_xdrop_batch) capB = ne < c->tune_xdrop_batch ? ne : c->tune_xdrop_batch;
+                else {
                     size_t mfree = 0, mtotal = 0;
                     if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess) {
                         const uint64_t held = c->xstate.cap + c->xlive.cap + c->pool.bytes + c->pool.arena.largest_hole();   // (one buffer: the slab's largest hole, not the sum of its holes)
@@ -3707,6 +3717,7 @@ static int xdrop_batch_impl(bella_ctx* c, const bella_seed* seeds, uint64_t n, c
     if (!c || !p || (n && (!seeds || !out))) return fail(c, BELLA_ERR_BAD_ARG, "null argument");
     if (int r = need(c, READS)) return r;
     if (p->kmer_size < 1 || p->kmer_size > 32) return fail(c, BELLA_ERR_BAD_ARG, "k must be in [1,32]");
+    if (!exact) if (int r = check_xavier_xdrop(c, p)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     // validate on the host: the kernel trusts seeds
     std::vector<uint64_t> off((size_t)c->nreads + 1);

@@ -1072,11 +1072,15 @@ int bella_hip_trim(bella_ctx* ctx);
  *                             floor; a batch always takes at least one job, so 1 means one job per batch -- tests run many batches on
  *                             small inputs).  Default (n = 0 or 0): half of the free device memory, 64 MB .. 8 GB.  Read at the start of
  *                             each round.  The trace's budget is not touched.
+ *   BELLA_TUNE_XDROP_BATCH    values[0] = extensions (two per pair) of one batch of the sliced X-drop kernels (variant 1, and variant 0's
+ *                             fall-back), taken as given: neither the free-memory rule nor the floor of 65,536 extensions applies -- tests
+ *                             run several batches, full and partial, on small inputs.  Default (n = 0 or 0): at most 16 M extensions, at
+ *                             most a quarter of the free device memory, at least 65,536.  Read by every call.
  * (bella_hip_set_debug bits 0, 10, 15 and 16 of earlier rounds still select the same things: aliases, no longer needed)
  */
 enum { BELLA_TUNE_LDS_TIERS = 0, BELLA_TUNE_KCOUNT_BUDGET = 1, BELLA_TUNE_WIDE_BUDGET = 2, BELLA_TUNE_XDROP_VARIANT = 3, BELLA_TUNE_ROW_LISTS = 4,
        BELLA_TUNE_XDROP_CLASS_MIN = 5, BELLA_TUNE_LAYOUT_ORDER = 6, BELLA_TUNE_INLINE_ENTRIES = 7, BELLA_TUNE_ROW_PATH = 8, BELLA_TUNE_CACHE_BYTES = 9, BELLA_TUNE_DIST_LAYOUT = 10, BELLA_TUNE_COMPACT_B = 11,
-       BELLA_TUNE_PRODUCT_ENTRIES = 12, BELLA_TUNE_ORDER_SPLIT = 13, BELLA_TUNE_ROUND_BUDGET = 14 };
+       BELLA_TUNE_PRODUCT_ENTRIES = 12, BELLA_TUNE_ORDER_SPLIT = 13, BELLA_TUNE_ROUND_BUDGET = 14, BELLA_TUNE_XDROP_BATCH = 15 };
 int bella_hip_set_tuning(bella_ctx* ctx, uint32_t what, const uint64_t* values, uint32_t n);
 
 #ifdef __cplusplus

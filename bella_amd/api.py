@@ -161,6 +161,18 @@ class Engine:
         self._chk(self.lib.bella_hip_get_tuples(self.h, tk.ctypes.data, tr.ctypes.data, tp.ctypes.data))
         return tk[:n], tr[:n], tp[:n]
 
+    def count_stats(self):
+        """what the host decided for the last count: dict(fast, pb, gb, slots, mode, positions, budget,
+        passes=[(first bin, end bin, words, tiles)])"""
+        n = C.c_uint32(0)
+        self._chk(self.lib.bella_hip_get_count_stats(self.h, None, 0, C.byref(n)))
+        v = np.zeros(max(n.value, 1), np.uint64)
+        self._chk(self.lib.bella_hip_get_count_stats(self.h, v.ctypes.data, n.value, C.byref(n)))
+        v = [int(x) for x in v[:n.value]]
+        assert len(v) == 8 + 4 * v[3], v
+        return dict(fast=bool(v[0]), pb=v[1], gb=v[2], slots=v[4], mode=v[5], positions=v[6], budget=v[7],
+                    passes=[tuple(v[8 + 4 * p:12 + 4 * p]) for p in range(v[3])])
+
     def assemble_counted(self):
         self._chk(self.lib.bella_hip_assemble_counted(self.h))
 

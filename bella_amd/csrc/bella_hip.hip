@@ -209,6 +209,7 @@ struct bella_ctx {
     std::vector<uint32_t> host_lens;
     uint64_t kc_ntuples = 0;             // TUPLES: the device-resident tuples + dictionary of bella_hip_count_kmers
     uint32_t kc_nkmers = 0, kc_k = 0;
+    std::vector<uint64_t> kc_stats;      // what the host decided for the last count (bella_hip_get_count_stats)
     uint32_t kc_bfirst = 0, kc_brows = 0; // the read block the device-resident tuples cover (all reads unless counted distributed)
     Buf kc_nk, kc_koff, kc_hist, kc_keys, kc_alt, kc_runlen, kc_flag, kc_slot, kc_nruns, kc_dcode, kc_dcount, kc_hkey, kc_hval, kc_found,
         kc_tstart, kc_cursor, kc_sel, kc_ringo, kc_ringp, kc_opos, kc_oid, kc_opos2, kc_oid2;
@@ -1503,6 +1504,8 @@ static int count_args(bella_ctx* c, uint16_t kmer_size, uint32_t lower, uint32_t
     return 0;
 }
 
+constexpr uint32_t kCountStatsHead = 8;                            // bella_hip_get_count_stats: words before the passes
+
 static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, uint32_t upper, uint32_t mode, uint32_t window,
                             uint32_t* nkmers_out, uint64_t* ntuples_out, uint64_t* ndistinct_out, bool dist = false, uint32_t bfirst = 0,
                             uint32_t brows = 0) {
@@ -1531,7 +1534,9 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
     uint64_t nk_total = 0, ndistinct = 0, nocc = 0;                // reliable k-mers, distinct k-mers, occurrences of reliable k-mers so far
     uint32_t *occ_pos = nullptr, *occ_id = nullptr, *occ_pos2 = nullptr, *occ_id2 = nullptr;   // the list of occurrences and what it is sorted against
     bool fast = false, one_pass_all = false;
-    uint32_t pb = 0;
+    uint32_t pb = 0, gb = 0;
+    uint64_t npos = 0, table_slots = 0;                            // positions of the read set; slots of the look-up table (0: none built)
+    std::vector<uint64_t> pass_stats;                              // per pass: first bin, end bin, words, tiles of the run kernels
     int rc = [&]() -> int {
     const unsigned rgrid = nr < 16384u ? (nr ? nr : 1u) : 16384u;
     ENSURE(c, c->kc_nk, 4 * ((size_t)nr + 2));
@@ -1572,6 +1577,7 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
         while (posbits < 63 && (1ull << posbits) < ntot) ++posbits;
         fast = NR == 1 && mode != 1 && 2 * (int)k + posbits <= 64 && posbits <= 32 && !(c->debug & 16384u);   // debug bit 14: tests, the look-up path
         pb = fast ? (uint32_t)posbits : 0u;
+        npos = ntot;
     }
     uint64_t budget = c->kcount_budget;
     if (budget > 0x7FFF0000ull) budget = 0x7FFF0000ull;               // rocPRIM item counts are 32-bit
@@ -1618,8 +1624,13 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
         b = e;
     }
     const bool single = pass_n.size() == 1 && mode == 0 && NR == 1;    // every position contributes: word j of read r has a fixed place
+    // (with the positions in the keys the run kernels handle groups of four neighbouring words: the sort may leave out the word's
+    // two lowest bits, and does when that saves it a pass of eight bits -- 32 instead of 34 bits for k = 17)
+    gb = fast && 2 * k >= 10 && (2 * k + 7) / 8 > (2 * k - 2 + 7) / 8 ? 2u : 0u;
     for (size_t p = 0; p < pass_n.size(); ++p) {
         const uint64_t np = pass_n[p];
+        const uint64_t st[4] = {pass_lo[p], pass_hi[p], np, fast && np ? (uint64_t)nblk(np, kRunTile) : 0ull};
+        pass_stats.insert(pass_stats.end(), st, st + 4);
         if (!np) continue;
         ENSURE(c, c->kc_keys, 8 * np);
         ENSURE(c, c->kc_alt, 8 * np);
@@ -1633,10 +1644,15 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
         KCHK(c);
         mark("alloc + emit codes");
         hipcub::DoubleBuffer<uint64_t> db(ptr<uint64_t>(c->kc_keys), ptr<uint64_t>(c->kc_alt));
-        // (with the positions in the keys the run kernels handle groups of four neighbouring words: the sort may leave out the word's
-        // two lowest bits, and does when that saves it a pass of eight bits -- 32 instead of 34 bits for k = 17)
-        const uint32_t gb = fast && 2 * k >= 10 && (2 * k + 7) / 8 > (2 * k - 2 + 7) / 8 ? 2u : 0u;
-        CUB(c, hipcub::DeviceRadixSort::SortKeys, db, (int)np, (int)(pb + gb), (int)pb + 2 * (int)k, c->stream);
+        // At the limit of the positions-in-the-keys path the word ends in bit 63.  For up to merge_sort_limit items rocPRIM sorts by
+        // merging under a comparator that masks the bit range, and builds the mask's upper end as (1 << end_bit) - 1: a shift by the
+        // key's width when end_bit is 64, which leaves the mask of the bits BELOW begin_bit -- the keys came back ordered by their
+        // position fields (k = 25 with 16,384 positions: 3 of 40 reliable k-mers found).  Such a pass sorts on all 64 bits: the plain
+        // comparator.  Words still stand group by group (inside a group now by low bits, then position: the run kernels count per low
+        // bits in any interleaving), and a pass of that size costs the same either way.  Larger passes take the radix path.
+        const int end_bit = (int)pb + 2 * (int)k;
+        const bool whole_key = end_bit == 64 && pb + gb > 0 && np <= ::rocprim::radix_sort_config<>::merge_sort_limit;
+        CUB(c, hipcub::DeviceRadixSort::SortKeys, db, (int)np, whole_key ? 0 : (int)(pb + gb), end_bit, c->stream);
         uint64_t* sorted = db.Current();
         mark("sort");
         if (fast) {
@@ -1814,6 +1830,7 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
     // countsreliable: open addressing at load factor <= 1/2
     uint64_t slots = 1024;
     while (slots < 2 * nk_total) slots <<= 1;
+    table_slots = slots;
     ENSURE(c, c->kc_hkey, 8 * slots);
     ENSURE(c, c->kc_hval, 4 * slots);
     k_hash_fill<<<nblk(slots), 256, 0, c->stream>>>(ptr<uint64_t>(c->kc_hkey), slots);
@@ -1861,6 +1878,11 @@ static int count_kmers_impl(bella_ctx* c, uint16_t kmer_size, uint32_t lower, ui
     c->kc_k = k;
     c->kc_bfirst = bfirst;
     c->kc_brows = brows;
+    {
+        const uint64_t head[kCountStatsHead] = {fast ? 1ull : 0ull, pb, gb, pass_stats.size() / 4, table_slots, mode, npos, c->kcount_budget};
+        c->kc_stats.assign(head, head + kCountStatsHead);
+        c->kc_stats.insert(c->kc_stats.end(), pass_stats.begin(), pass_stats.end());
+    }
     made(c, TUPLES);
     if (nkmers_out) *nkmers_out = (uint32_t)nk_total;
     if (ntuples_out) *ntuples_out = nt;
@@ -1906,6 +1928,15 @@ int bella_hip_get_dictionary(bella_ctx* c, uint64_t* codes, uint16_t* counts) {
     if (codes && c->kc_nkmers) HIPCHK(c, hipMemcpyAsync(codes, c->kc_dcode.p, 8 * (size_t)c->kc_nkmers, hipMemcpyDeviceToHost, c->stream));
     if (counts && c->kc_nkmers) HIPCHK(c, hipMemcpyAsync(counts, c->kc_dcount.p, 2 * (size_t)c->kc_nkmers, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bella_hip_get_count_stats(bella_ctx* c, uint64_t* values, uint32_t capacity, uint32_t* nvalues) {
+    if (!c || !nvalues || (capacity && !values)) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, TUPLES)) return r;
+    const size_t n = c->kc_stats.size();
+    for (size_t i = 0; i < n && i < capacity; ++i) values[i] = c->kc_stats[i];
+    *nvalues = (uint32_t)n;
     return 0;
 }
 

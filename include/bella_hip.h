@@ -187,6 +187,11 @@ int bella_hip_count_minimizers(bella_ctx* ctx, uint16_t kmer_size, uint32_t wind
 int bella_hip_get_dictionary(bella_ctx* ctx, uint64_t* codes, uint16_t* counts);
 /* the tuple list of the last bella_hip_count_kmers (what the reference's alltranstuples holds, main.cpp:339-423) */
 int bella_hip_get_tuples(bella_ctx* ctx, uint32_t* t_kmer, uint32_t* t_read, uint16_t* t_pos);
+/* what the host decided for the last count (host values only, no device work): values[0..7] = uses the sort-with-positions path
+ * (0 / 1), position bits in the sort keys, low word bits the sort leaves out, passes, slots of the look-up table (0: none built),
+ * selector (0 all, 1 syncmers, 2 minimizers), positions of the read set, k-mers per pass allowed; then per pass {first bin, end bin,
+ * words, tiles of the run kernels}.  Writes at most `capacity` values; *nvalues = how many there are. */
+int bella_hip_get_count_stats(bella_ctx* ctx, uint64_t* values, uint32_t capacity, uint32_t* nvalues);
 /* bella_hip_assemble_tuples on the device-resident tuples of bella_hip_count_kmers (no host copy) */
 int bella_hip_assemble_counted(bella_ctx* ctx);
 /* bella_hip_assemble_panel on the device-resident tuples of the reads [first_read, first_read + nreads_panel) (multi-GPU:

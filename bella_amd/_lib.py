@@ -39,6 +39,10 @@ REALIGN_NONE, REALIGN_VOTED, REALIGN_UNPLACED, REALIGN_OUTSIDE, REALIGN_BAND_CAP
 TRACE_PASSED_ONLY, TRACE_DROP_OPS, TRACE_PILEUP, TRACE_NORMALIZE = 1, 2, 4, 8
 VOTE_PAIR_DT = np.dtype([("rid", "<u4"), ("cid", "<u4"), ("tbegV", "<i4"), ("tbegH", "<i4"), ("op_off", "<u8"), ("nops", "<u4"), ("strand", "u1"), ("pad", "u1", (3,))])
 assert VOTE_PAIR_DT.itemsize == 32
+CLIP_DEFAULT_IDENTITY = 650
+CLIP_RES_DT = np.dtype([("first_run", "<u4"), ("nruns", "<u4"), ("begV", "<i4"), ("endV", "<i4"), ("begH", "<i4"), ("endH", "<i4"), ("n_eq", "<u4"), ("n_x", "<u4"),
+                        ("n_ins", "<u4"), ("n_del", "<u4"), ("score", "<i4"), ("pad", "<u4"), ("clip_score", "<i8")])
+assert CLIP_RES_DT.itemsize == 56
 PILEUP_COUNTERS = 9      # per base: votes for A C G T, del, one inserted A C G T in the junction before the base
 assert PAIR_DT.itemsize == 16 and EXT_DT.itemsize == 8 and ALN_DT.itemsize == 32 and SEED_DT.itemsize == 12
 
@@ -83,6 +87,16 @@ class TraceStats(C.Structure):
 class VoteStats(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("runs", C.c_uint64), ("gap_runs", C.c_uint64), ("shifted_runs", C.c_uint64), ("shifted_columns", C.c_uint64),
                 ("votes", C.c_uint64), ("vote_ms", C.c_double), ("normalized", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class ClipParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("identity", C.c_uint32)]
+
+
+class ClipStats(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("clipped", C.c_uint64), ("emptied", C.c_uint64), ("runs_before", C.c_uint64), ("runs_after", C.c_uint64),
+                ("columns_before", C.c_uint64), ("columns_after", C.c_uint64), ("bases_v_removed", C.c_uint64), ("bases_h_removed", C.c_uint64),
+                ("identity", C.c_uint32), ("pad", C.c_uint32), ("clip_ms", C.c_double)]
 
 
 class ConsensusParams(C.Structure):
@@ -259,6 +273,9 @@ SIGNATURES = [
     ("bella_hip_pileup_reset", C.c_int, [vp]),
     ("bella_hip_trace_pairs_pileup", C.c_int, [vp, C.POINTER(Params), C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("bella_hip_get_vote_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_trace_pairs_clip", C.c_int, [vp, C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(ClipParams), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("bella_hip_clip_ops", C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(ClipParams), vp]),
+    ("bella_hip_get_clip_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_pileup_vote", C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32]),
     ("bella_hip_get_pileup", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
     ("bella_hip_add_pileup", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),

@@ -349,18 +349,26 @@ class Engine:
         return out
 
     # ---- traced alignments (base-level: run-length ops, len << 4 | op, op 0 '=' 1 'X' 2 'I' 3 'D') ----
-    def trace_pairs(self, pars: BellaPars, band0: int = 0, passed_only: bool = True, pileup: bool = False, keep_ops: bool = True, normalize: bool = False):
+    def trace_pairs(self, pars: BellaPars, band0: int = 0, passed_only: bool = True, pileup: bool = False, keep_ops: bool = True, normalize: bool = False,
+                    clip: int = None):
         """Traces the pairs of the last align_pairs.  Returns (traces[npairs] of TRACE_DT, untraced: nops == 0; ops uint32).
         pileup=True (needs pileup_reset, passed pairs only): every traced pair also votes into the pileup table on the device; with
         keep_ops=False the runs never reach the host and `ops` comes back empty (the records are the same).  normalize=True (with
-        pileup): every gap run votes at its canonical position; records and runs are the same."""
+        pileup): every gap run votes at its canonical position; records and runs are the same.  clip=<identity in permille> (DESIGN.md
+        section 24): every traced alignment is cut to its maximum-scoring segment at that identity on the device before anything reads
+        it; the records are the clipped ones (an emptied pair: nops == 0), `ops` is the array of the call without it."""
         nt, no = C.c_uint64(0), C.c_uint64(0)
         cp = pars.c()
         if normalize and not pileup:
             raise ValueError("normalize=True normalises the votes: it needs pileup=True")
-        if pileup:
-            if not passed_only:
-                raise ValueError("pileup=True traces the passed pairs only")
+        if pileup and not passed_only:
+            raise ValueError("pileup=True traces the passed pairs only")
+        if clip is not None:
+            flags = (_lib.TRACE_PASSED_ONLY if passed_only else 0) | (_lib.TRACE_PILEUP if pileup else 0) | (_lib.TRACE_NORMALIZE if normalize else 0) \
+                | (_lib.TRACE_DROP_OPS if pileup and not keep_ops else 0)
+            kp = _lib.ClipParams(C.sizeof(_lib.ClipParams), int(clip))
+            self._chk(self.lib.bella_hip_trace_pairs_clip(self.h, C.byref(cp), band0, flags, C.byref(kp), C.byref(nt), C.byref(no)))
+        elif pileup:
             if normalize:
                 flags = _lib.TRACE_PASSED_ONLY | _lib.TRACE_PILEUP | _lib.TRACE_NORMALIZE | (0 if keep_ops else _lib.TRACE_DROP_OPS)
                 self._chk(self.lib.bella_hip_trace_pairs_flags(self.h, C.byref(cp), band0, flags, C.byref(nt), C.byref(no)))
@@ -388,6 +396,21 @@ class Engine:
     def vote_stats(self) -> dict:
         """what the last voting call did: the fields of bella_vote_stats"""
         return self._stats(self.lib.bella_hip_get_vote_stats, _lib.VoteStats)
+
+    # ---- clipped ends (DESIGN.md section 24) ----
+    def clip_ops(self, pairs: np.ndarray, ops: np.ndarray, identity: int = 650) -> np.ndarray:
+        """the clip of caller-supplied traced pairs (VOTE_PAIR_DT, of which op_off, nops, tbegV and tbegH are read; runs len << 4 | op in
+        `ops`): CLIP_RES_DT[len(pairs)].  Everything is validated before anything is launched; no reads need to be loaded."""
+        pr = np.ascontiguousarray(pairs, _lib.VOTE_PAIR_DT)
+        op = np.ascontiguousarray(ops, np.uint32)
+        out = np.zeros(len(pr), _lib.CLIP_RES_DT)
+        kp = _lib.ClipParams(C.sizeof(_lib.ClipParams), int(identity))
+        self._chk(self.lib.bella_hip_clip_ops(self.h, _p(pr), len(pr), _p(op), len(op), C.byref(kp), _p(out)))
+        return out
+
+    def clip_stats(self) -> dict:
+        """what the last clipping call (trace_pairs / trace_pairs_records with clip=, clip_ops) did: the fields of bella_clip_stats"""
+        return self._stats(self.lib.bella_hip_get_clip_stats, _lib.ClipStats)
 
     def _range_bases(self, first, n):
         if first < 0 or n < 0 or first + n > self.nreads:
@@ -474,13 +497,18 @@ class Engine:
     # ---- string graph: overlap classes, containment, transitive reduction ----
     GRAPH_DEFAULTS = dict(min_overlap=1000, max_overhang=1000, overhang_permille=800, fuzz=1000)
 
-    def trace_pairs_records(self, pars: BellaPars, band0: int = 0, passed_only: bool = True):
+    def trace_pairs_records(self, pars: BellaPars, band0: int = 0, passed_only: bool = True, clip: int = None):
         """bella_hip_trace_pairs_flags with the runs dropped: traces[npairs] of TRACE_DT only -- no run is written or staged (what the
-        graph needs: graph_add_traced reads the end points)."""
+        graph needs: graph_add_traced reads the end points).  clip=<identity in permille>: the clipped records of DESIGN.md section 24
+        (the runs are then written on the device, where the clip reads them, and still not staged)."""
         nt, no = C.c_uint64(0), C.c_uint64(0)
         cp = pars.c()
         flags = _lib.TRACE_DROP_OPS | (_lib.TRACE_PASSED_ONLY if passed_only else 0)
-        self._chk(self.lib.bella_hip_trace_pairs_flags(self.h, C.byref(cp), band0, flags, C.byref(nt), C.byref(no)))
+        if clip is not None:
+            kp = _lib.ClipParams(C.sizeof(_lib.ClipParams), int(clip))
+            self._chk(self.lib.bella_hip_trace_pairs_clip(self.h, C.byref(cp), band0, flags, C.byref(kp), C.byref(nt), C.byref(no)))
+        else:
+            self._chk(self.lib.bella_hip_trace_pairs_flags(self.h, C.byref(cp), band0, flags, C.byref(nt), C.byref(no)))
         tr = np.zeros(self.npairs, TRACE_DT)
         self._chk(self.lib.bella_hip_get_traces(self.h, _p(tr), None))
         return tr

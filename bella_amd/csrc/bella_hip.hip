@@ -19,6 +19,7 @@
 
 #include "../../include/bella_hip.h"
 #include "assemble.hpp"
+#include "clip.hpp"
 #include "comm.hpp"
 #include "core.hpp"
 #include "fastq.hpp"
@@ -256,6 +257,7 @@ struct bella_ctx {
     // read correction (pileup.hpp): the table of the loaded reads, and the last consensus
     uint64_t cons_total = 0;
     bella_vote_stats vote_stats{};       // the last voting call (section 21)
+    bella_clip_stats clip_stats{};       // the last clipping call (clip.hpp; section 24)
     Buf pile, pile_pairs, pile_cnt, pile_tmp, cons_emit, cons_scan, cons_out, cons_offs, cons_stats;
     // correction rounds (recorrect.hpp; section 20): the anchors' offsets (one list per read), the consensus's anchors, and the last round
     uint64_t rc_nanch = 0;
@@ -3792,6 +3794,25 @@ int bella_hip_get_timings(bella_ctx* c, bella_timings* t) {
 namespace {
 struct TraceJob { uint32_t rid, cid, seedH, seedV; bella_aln a; };
 
+// One pair's clip into its record and into the call's sums (section 24).  An emptied pair keeps op_off, band and widened.
+void clip_count(uint32_t nops, uint64_t cols, int64_t spanV, int64_t spanH, const bella_clip& r, bella_clip_stats& cs) {
+    cs.pairs++;
+    if (!r.nruns) cs.emptied++;
+    else if (r.nruns < nops) cs.clipped++;
+    cs.runs_before += nops; cs.runs_after += r.nruns;
+    cs.columns_before += cols; cs.columns_after += (uint64_t)r.n_eq + r.n_x + r.n_ins + r.n_del;
+    cs.bases_v_removed += (uint64_t)(spanV - ((int64_t)r.endV - r.begV));
+    cs.bases_h_removed += (uint64_t)(spanH - ((int64_t)r.endH - r.begH));
+}
+void clip_apply(bella_trace& t, const bella_clip& r, bella_clip_stats& cs) {
+    clip_count(t.nops, (uint64_t)t.n_eq + t.n_x + t.n_ins + t.n_del, (int64_t)t.tendV - t.tbegV, (int64_t)t.tendH - t.tbegH, r, cs);
+    t.op_off += r.first_run;
+    t.nops = r.nruns;
+    t.tbegV = r.begV; t.tendV = r.endV; t.tbegH = r.begH; t.tendH = r.endH;
+    t.n_eq = r.n_eq; t.n_x = r.n_x; t.n_ins = r.n_ins; t.n_del = r.n_del;
+    t.score = r.score;
+}
+
 // The vote kernel on n pairs whose runs are in `ops` (device): section 10's, or with normalize section 21's.  The counters go to
 // c->pile_cnt, a zeroed PileNormCnt of which k_pile_vote writes the first field only.
 void launch_pile_vote(bella_ctx* c, bool normalize, const PilePair* pp, size_t n, const uint32_t* ops) {
@@ -3817,11 +3838,16 @@ int read_vote_counts(bella_ctx* c, bella_vote_stats& vs) {
 // vote: every finished pair's runs also vote into the context's pileup table (pileup.hpp), from the batch's op array on the device;
 // keep_ops == false: the runs are not copied to the host (`ops` stays as it is; the records' op_off count as if they had been).
 // normalize (with vote): the votes are k_pile_vote_norm's (section 21); what the votes did goes to c->vote_stats either way.
+// clip_t != 0 (section 24): every finished pair is clipped at that identity on the device, from the batch's op array, before it votes;
+// the writing walk then always runs; out[] and the voting pairs carry the clipped records, c->clip_stats what the clips did.
 int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& jobs, uint32_t band0, bella_trace* out, std::vector<uint32_t>& ops,
-              bella_trace_stats& st, bool vote = false, bool keep_ops = true, bool normalize = false) {
+              bella_trace_stats& st, bool vote = false, bool keep_ops = true, bool normalize = false, uint32_t clip_t = 0) {
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     st = bella_trace_stats{};
+    bella_clip_stats cs{};
+    cs.identity = clip_t;
+    if (clip_t) c->clip_stats = cs;
     bella_vote_stats vs{};
     vs.normalized = normalize ? 1u : 0u;
     if (vote) c->vote_stats = vs;
@@ -3874,8 +3900,13 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
     constexpr uint32_t kMaxBatchPairs = 1u << 20;
     std::vector<uint32_t> queue(n), next;
     for (size_t q = 0; q < n; ++q) queue[q] = (uint32_t)q;
-    EventSet ev;
+    EventSet ev, evc;
     if (int r = ev.create(c, 4)) return r;
+    if (clip_t) if (int r = evc.create(c, 2)) return r;
+    TmpBuf clip_in, clip_out;
+    std::vector<ClipPair> clipp;
+    std::vector<uint32_t> clipid;                                     // the job each of them is
+    std::vector<bella_clip> clipr;
     std::vector<TraceExt> exts;
     std::vector<uint32_t> lists[4];
     std::vector<TracePairRes> pres;
@@ -3962,6 +3993,8 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
             // ---- who is done, who goes again
             opoff.assign(nb, ~0ull);
             votep.clear();
+            clipp.clear();
+            clipid.clear();
             uint64_t bops = 0;
             for (uint32_t q = 0; q < nb; ++q) {
                 const uint32_t id = queue[at + q];
@@ -3983,6 +4016,7 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                 t.tendH = w.seedHo + (int32_t)k + (int32_t)rr.bj; t.tendV = (int32_t)j.seedV + (int32_t)k + (int32_t)rr.bi;
                 t.n_eq = pres[q].n_eq; t.n_x = pres[q].n_x; t.n_ins = pres[q].n_ins; t.n_del = pres[q].n_del;
                 t.widened = w.widened;
+                if (clip_t && t.nops) { clipp.push_back(ClipPair{bops, t.nops, t.tbegV, t.tbegH, 0u}); clipid.push_back(id); }
                 if (vote && t.nops)
                     votep.push_back(PilePair{off[j.cid], off[j.rid], bops, t.nops, (uint32_t)(off[j.cid + 1] - off[j.cid]), (uint32_t)(off[j.rid + 1] - off[j.rid]),
                                              j.a.strand ? 1u : 0u, t.tbegV, t.tbegH});
@@ -3990,7 +4024,7 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                 bops += pres[q].nops;
                 st.pairs++;
             }
-            if (bops && !keep_ops && !vote) {                          // nobody reads the runs: the records are complete without the writing walk
+            if (bops && !keep_ops && !vote && !clip_t) {               // nobody reads the runs: the records are complete without the writing walk
                 ops_seen += bops;
                 st.ops += bops;
             } else if (bops) {
@@ -4001,6 +4035,30 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                                                                   ptr<uint32_t>(c->tr_ops));
                 KCHK(c);
                 HIPCHK(c, hipEventRecord(ev.b, c->stream));
+                if (clip_t && !clipp.empty()) {                         // the batch's pairs are clipped before anybody reads their records
+                    clipr.resize(clipp.size());
+                    ENSURE(c, clip_in, sizeof(ClipPair) * clipp.size());
+                    ENSURE(c, clip_out, sizeof(bella_clip) * clipp.size());
+                    HIPCHK(c, hipMemcpyAsync(clip_in.p, clipp.data(), sizeof(ClipPair) * clipp.size(), hipMemcpyHostToDevice, c->stream));
+                    HIPCHK(c, hipEventRecord(evc.a, c->stream));
+                    k_clip<<<nblk(clipp.size(), kClipBlock / 64), kClipBlock, 0, c->stream>>>(ptr<ClipPair>(clip_in), (uint32_t)clipp.size(), ptr<uint32_t>(c->tr_ops), clip_t,
+                                                                                            ptr<bella_clip>(clip_out));
+                    KCHK(c);
+                    HIPCHK(c, hipEventRecord(evc.b, c->stream));
+                    HIPCHK(c, hipMemcpyAsync(clipr.data(), clip_out.p, sizeof(bella_clip) * clipp.size(), hipMemcpyDeviceToHost, c->stream));
+                    HIPCHK(c, hipStreamSynchronize(c->stream));
+                    cs.clip_ms += ev_ms(evc.a, evc.b);
+                    size_t vq = 0, vkeep = 0;                           // votep lists the same pairs in the same order
+                    for (size_t x = 0; x < clipp.size(); ++x) {
+                        clip_apply(out[clipid[x]], clipr[x], cs);
+                        if (!vote) continue;
+                        PilePair vp = votep[vq++];
+                        if (!clipr[x].nruns) continue;                  // an emptied pair casts no vote
+                        vp.op_off += clipr[x].first_run; vp.nops = clipr[x].nruns; vp.i0 = clipr[x].begV; vp.j0 = clipr[x].begH;
+                        votep[vkeep++] = vp;
+                    }
+                    if (vote) votep.resize(vkeep);
+                }
                 if (vote && !votep.empty()) {                           // the batch's runs vote while they are in device memory
                     ENSURE(c, c->pile_pairs, sizeof(PilePair) * votep.size());
                     HIPCHK(c, hipMemcpyAsync(c->pile_pairs.p, votep.data(), sizeof(PilePair) * votep.size(), hipMemcpyHostToDevice, c->stream));
@@ -4033,6 +4091,7 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
         vs.vote_ms = st.vote_ms;
         c->vote_stats = vs;
     }
+    if (clip_t) c->clip_stats = cs;
     st.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
     return 0;
 }
@@ -4043,7 +4102,7 @@ void trace_release(bella_ctx* c) {      // the batch buffers go back (directions
 }  // namespace
 
 static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0, int passed_only, bool vote, bool keep_ops, uint64_t* ntraced, uint64_t* nops,
-                            bool normalize = false) {
+                            bool normalize = false, uint32_t clip_t = 0) {
     if (!c) return BELLA_ERR_BAD_ARG;
     if (int r = need(c, ALNS)) return r;
     if (vote) if (int r = need(c, PILE)) return r;
@@ -4067,7 +4126,7 @@ static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0,
     c->trace_ops.clear();
     if (!keep_ops) std::vector<uint32_t>().swap(c->trace_ops);
     if (vote) changed(c, PILE);
-    rc = run_trace(c, p, jobs, band0, tr.data(), c->trace_ops, c->trace_stats, vote, keep_ops, normalize);
+    rc = run_trace(c, p, jobs, band0, tr.data(), c->trace_ops, c->trace_stats, vote, keep_ops, normalize, clip_t);
     trace_release(c);
     if (vote) release(c->pile_pairs);
     if (rc) { (void)hipDeviceSynchronize(); return rc; }
@@ -4075,7 +4134,7 @@ static int trace_pairs_impl(bella_ctx* c, const bella_params* p, uint32_t band0,
     for (size_t i = 0; i < which.size(); ++i) c->traces[which[i]] = tr[i];
     made(c, TRACES);
     c->trace_ops_kept = keep_ops;
-    if (ntraced) *ntraced = jobs.size();
+    if (ntraced) *ntraced = jobs.size() - (clip_t ? c->clip_stats.emptied : 0);
     if (nops) *nops = c->trace_stats.ops;
     return 0;
 }
@@ -4090,13 +4149,93 @@ int bella_hip_trace_pairs_pileup(bella_ctx* c, const bella_params* p, uint32_t b
     return trace_pairs_impl(c, p, band0, 1, true, keep_ops != 0, ntraced, nops);
 }
 
-int bella_hip_trace_pairs_flags(bella_ctx* c, const bella_params* p, uint32_t band0, uint32_t flags, uint64_t* ntraced, uint64_t* nops) {
+// section 24's parameter: the identity a call uses, or 0 with the error set
+static uint32_t clip_identity(bella_ctx* c, const bella_clip_params* given, const char* who) {
+    bella_clip_params cp{(uint32_t)sizeof(bella_clip_params), 0};
+    if (take_params(c, cp, given, who)) return 0;
+    if (cp.identity == 0) cp.identity = BELLA_CLIP_DEFAULT_IDENTITY;
+    if (cp.identity > 999) { fail(c, BELLA_ERR_BAD_ARG, "%s: identity %u is not in 1 .. 999 permille (0: the default %d)", who, cp.identity, BELLA_CLIP_DEFAULT_IDENTITY); return 0; }
+    return cp.identity;
+}
+
+static int trace_pairs_flags_impl(bella_ctx* c, const bella_params* p, uint32_t band0, uint32_t flags, uint64_t* ntraced, uint64_t* nops, uint32_t clip_t) {
     if (!c) return BELLA_ERR_BAD_ARG;
     if (flags & ~(BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_DROP_OPS | BELLA_TRACE_PILEUP | BELLA_TRACE_NORMALIZE)) return fail(c, BELLA_ERR_BAD_ARG, "trace_pairs_flags: unknown flag");
     const bool vote = (flags & BELLA_TRACE_PILEUP) != 0;
     if ((flags & BELLA_TRACE_NORMALIZE) && !vote) return fail(c, BELLA_ERR_BAD_ARG, "trace_pairs_flags: BELLA_TRACE_NORMALIZE normalises the votes: it needs BELLA_TRACE_PILEUP");
     if (vote && !(flags & BELLA_TRACE_PASSED_ONLY)) return fail(c, BELLA_ERR_BAD_ARG, "trace_pairs_flags: the pileup takes the passed pairs only");
-    return trace_pairs_impl(c, p, band0, (flags & BELLA_TRACE_PASSED_ONLY) ? 1 : 0, vote, !(flags & BELLA_TRACE_DROP_OPS), ntraced, nops, (flags & BELLA_TRACE_NORMALIZE) != 0);
+    return trace_pairs_impl(c, p, band0, (flags & BELLA_TRACE_PASSED_ONLY) ? 1 : 0, vote, !(flags & BELLA_TRACE_DROP_OPS), ntraced, nops, (flags & BELLA_TRACE_NORMALIZE) != 0, clip_t);
+}
+
+int bella_hip_trace_pairs_flags(bella_ctx* c, const bella_params* p, uint32_t band0, uint32_t flags, uint64_t* ntraced, uint64_t* nops) {
+    return trace_pairs_flags_impl(c, p, band0, flags, ntraced, nops, 0);
+}
+
+int bella_hip_trace_pairs_clip(bella_ctx* c, const bella_params* p, uint32_t band0, uint32_t flags, const bella_clip_params* clip, uint64_t* ntraced, uint64_t* nops) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    const uint32_t t = clip_identity(c, clip, "trace_pairs_clip");
+    if (!t) return BELLA_ERR_BAD_ARG;
+    return trace_pairs_flags_impl(c, p, band0, flags, ntraced, nops, t);
+}
+
+int bella_hip_get_clip_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    return put_sized(out, struct_size, c->clip_stats);
+}
+
+int bella_hip_clip_ops(bella_ctx* c, const bella_vote_pair* pairs, uint64_t npairs, const uint32_t* ops, uint64_t nops_total, const bella_clip_params* clip, bella_clip* out) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if ((npairs && (!pairs || !out)) || (nops_total && !ops)) return fail(c, BELLA_ERR_BAD_ARG, "clip_ops: null argument");
+    if (npairs > 0xffffffffull) return fail(c, BELLA_ERR_BAD_ARG, "clip_ops: at most 2^32 - 1 pairs a call");
+    const uint32_t t = clip_identity(c, clip, "clip_ops");
+    if (!t) return BELLA_ERR_BAD_ARG;
+    // ---- everything is checked before anything is launched
+    struct Before { uint64_t cols; int64_t spanV, spanH; };
+    std::vector<ClipPair> cp((size_t)npairs);
+    std::vector<Before> before((size_t)npairs);
+    for (uint64_t q = 0; q < npairs; ++q) {
+        const bella_vote_pair& a = pairs[q];
+        if (a.op_off > nops_total || a.nops > nops_total - a.op_off) return fail(c, BELLA_ERR_BAD_ARG, "clip_ops: pair %llu: its runs lie outside ops", (unsigned long long)q);
+        if (a.tbegV < 0 || a.tbegH < 0) return fail(c, BELLA_ERR_BAD_ARG, "clip_ops: pair %llu: negative start", (unsigned long long)q);
+        uint64_t i = (uint64_t)a.tbegV, j = (uint64_t)a.tbegH, cols = 0;
+        for (uint32_t k = 0; k < a.nops; ++k) {
+            const uint32_t w = ops[a.op_off + k], op = w & 15u, len = w >> 4;
+            if (op > kOpDel) return fail(c, BELLA_ERR_BAD_ARG, "clip_ops: pair %llu run %u: op %u is none of = X I D", (unsigned long long)q, k, op);
+            if (!len) return fail(c, BELLA_ERR_BAD_ARG, "clip_ops: pair %llu run %u: length 0", (unsigned long long)q, k);
+            if (op != kOpDel) i += len;
+            if (op != kOpIns) j += len;
+            cols += len;
+            if (i >= (1ull << 31) || j >= (1ull << 31)) return fail(c, BELLA_ERR_BAD_ARG, "clip_ops: pair %llu: its runs reach base 2^31 of a read", (unsigned long long)q);
+        }
+        cp[(size_t)q] = ClipPair{a.op_off, a.nops, a.tbegV, a.tbegH, 0u};
+        before[(size_t)q] = Before{cols, (int64_t)i - a.tbegV, (int64_t)j - a.tbegH};
+    }
+    bella_clip_stats cs{};
+    cs.identity = t;
+    if (npairs) {
+        HIPCHK(c, hipSetDevice(c->device));
+        TmpBuf dp, dops, dout;
+        EventSet ev;
+        if (int r = ev.create(c, 2)) return r;
+        std::vector<bella_clip> res((size_t)npairs);
+        ENSURE(c, dp, sizeof(ClipPair) * cp.size());
+        ENSURE(c, dops, 4 * (size_t)nops_total + 4);
+        ENSURE(c, dout, sizeof(bella_clip) * cp.size());
+        HIPCHK(c, hipMemcpyAsync(dp.p, cp.data(), sizeof(ClipPair) * cp.size(), hipMemcpyHostToDevice, c->stream));
+        if (nops_total) HIPCHK(c, hipMemcpyAsync(dops.p, ops, 4 * (size_t)nops_total, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        k_clip<<<nblk(cp.size(), kClipBlock / 64), kClipBlock, 0, c->stream>>>(ptr<ClipPair>(dp), (uint32_t)cp.size(), ptr<uint32_t>(dops), t, ptr<bella_clip>(dout));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        HIPCHK(c, hipMemcpyAsync(res.data(), dout.p, sizeof(bella_clip) * cp.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        cs.clip_ms = ev_ms(ev.a, ev.b);
+        for (size_t q = 0; q < cp.size(); ++q)
+            if (cp[q].nops) clip_count(cp[q].nops, before[q].cols, before[q].spanV, before[q].spanH, res[q], cs);
+        std::memcpy(out, res.data(), sizeof(bella_clip) * res.size());
+    }
+    c->clip_stats = cs;
+    return 0;
 }
 
 int bella_hip_get_traces(bella_ctx* c, bella_trace* out, uint32_t* ops) {

@@ -57,6 +57,7 @@ struct Worker {
     RawBuf<uint32_t> ops;
     uint64_t nnzc = 0;
     uint64_t gap_runs = 0, shifted_runs = 0, shifted_columns = 0;      // normalize_gaps: summed over the stages (bella_vote_stats)
+    bella_clip_stats clip{};                 // clip_ends: summed over the stages (bella_clip_stats)
 };
 // what the last call of this process did (tests, logs): every column must be computed by the numeric phase exactly once
 struct CallStats {
@@ -134,6 +135,8 @@ struct StageOpts {
     uint32_t correct_rounds = 1;     // correction rounds: correct_rounds - 1 rounds follow the consensus, each aligning the partners'
     uint32_t correct_band = 512, correct_min_identity = 700;    // raw clips against the corrected reads of the round before; the file carries the last round
     int normalize_gaps = 0;          // gap normalisation of every stage's votes
+    int clip_ends = 0;               // every stage's traced alignments are clipped at clip_identity permille
+    uint32_t clip_identity = BELLA_CLIP_DEFAULT_IDENTITY;
     bool graph() const { return gfa || unitigs || unitigs_fasta; }
     bool pileup() const { return correct || polish; }
     bool records() const { return graph() || (correct && correct_rounds > 1); }      // every stage adds its traced passed pairs as overlap records
@@ -463,7 +466,22 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
                 if (w.nnzc) check(w.ctx, bella_hip_get_alignments(w.ctx, w.alns.data()), "bella_hip_get_alignments");
                 uint64_t ntr = 0, nops = 0;
                 // (--correct / --polish: the stage's runs vote on the device; they come to the host only when the true PAF wants them too)
-                if (o.pileup() && o.normalize_gaps) {
+                if (o.clip_ends && (o.pileup() || o.cigar || o.records())) {      // the calls below, flag for flag, through the clip
+                    const bool nz = o.pileup() && o.normalize_gaps;
+                    const uint32_t fl = BELLA_TRACE_PASSED_ONLY | (o.pileup() ? BELLA_TRACE_PILEUP : 0u) | (nz ? BELLA_TRACE_NORMALIZE : 0u) | (o.cigar ? 0u : BELLA_TRACE_DROP_OPS);
+                    const bella_clip_params kp{(uint32_t)sizeof(bella_clip_params), o.clip_identity};
+                    check(w.ctx, bella_hip_trace_pairs_clip(w.ctx, &p, o.trace_band, fl, &kp, &ntr, &nops), "bella_hip_trace_pairs_clip");
+                    bella_clip_stats ks{};
+                    check(w.ctx, bella_hip_get_clip_stats(w.ctx, &ks, sizeof(ks)), "bella_hip_get_clip_stats");
+                    w.clip.pairs += ks.pairs; w.clip.clipped += ks.clipped; w.clip.emptied += ks.emptied;
+                    w.clip.columns_before += ks.columns_before; w.clip.columns_after += ks.columns_after;
+                    w.clip.bases_v_removed += ks.bases_v_removed; w.clip.bases_h_removed += ks.bases_h_removed; w.clip.clip_ms += ks.clip_ms;
+                    if (nz) {
+                        bella_vote_stats vs{};
+                        check(w.ctx, bella_hip_get_vote_stats(w.ctx, &vs, sizeof(vs)), "bella_hip_get_vote_stats");
+                        w.gap_runs += vs.gap_runs; w.shifted_runs += vs.shifted_runs; w.shifted_columns += vs.shifted_columns;
+                    }
+                } else if (o.pileup() && o.normalize_gaps) {
                     const uint32_t fl = BELLA_TRACE_PASSED_ONLY | BELLA_TRACE_PILEUP | BELLA_TRACE_NORMALIZE | (o.cigar ? 0u : BELLA_TRACE_DROP_OPS);
                     check(w.ctx, bella_hip_trace_pairs_flags(w.ctx, &p, o.trace_band, fl, &ntr, &nops), "bella_hip_trace_pairs_flags");
                     bella_vote_stats vs{};
@@ -604,6 +622,17 @@ inline void run_stages(std::vector<Worker>& W, const StageOpts& o, const char* c
         for (const Worker& w : W) { gaps += w.gap_runs; runs += w.shifted_runs; cols += w.shifted_columns; }
         const std::string NormalizedGaps = std::to_string(runs) + " shifted_runs, " + std::to_string(cols) + " shifted_columns (of " + std::to_string(gaps) + " gap runs, two voted reads each)";
         BELLA_HIP_LOGT(tag, NormalizedGaps);
+    }
+    if (o.clip_ends) {                                                        // the run's sums over stages and contexts
+        bella_clip_stats k{};
+        for (const Worker& w : W) {
+            k.pairs += w.clip.pairs; k.clipped += w.clip.clipped; k.emptied += w.clip.emptied; k.columns_before += w.clip.columns_before;
+            k.columns_after += w.clip.columns_after; k.bases_v_removed += w.clip.bases_v_removed; k.bases_h_removed += w.clip.bases_h_removed;
+        }
+        const std::string ClippedEnds = std::to_string(k.clipped) + " clipped, " + std::to_string(k.emptied) + " emptied (of " + std::to_string(k.pairs) + " traced pairs at identity " +
+                                        std::to_string(o.clip_identity) + "), " + std::to_string(k.columns_before - k.columns_after) + " of " + std::to_string(k.columns_before) +
+                                        " columns removed, " + std::to_string(k.bases_v_removed + k.bases_h_removed) + " bases";
+        BELLA_HIP_LOGT(tag, ClippedEnds);
     }
     if (o.records()) gather_records(W, o);
     if (o.correct) write_corrected(W, o, names);

@@ -22,6 +22,8 @@
 // pair against the corrected reads of the round before; FILE then holds the last round.
 //
 // --normalize-gaps: with --correct / --polish, every gap run votes at its canonical position.
+// --clip-ends: every traced alignment of the run is cut to its maximum-scoring segment at --clip-identity
+// permille before anything reads it (records, pileup votes, the true PAF); the -o file does not change.
 // --polish: unitig consensus: every stage's traced pairs vote as with --correct, the unitigs are polished from
 // the pileup on the device after the last stage; --unitigs / --unitigs-fasta then carry the polished sequences and coordinates.
 // --polish-rounds N: N - 1 realignment rounds follow, each aligning the reads against the unitigs of the round before.
@@ -73,6 +75,8 @@ struct Options {
     int weak_min = 500, weak_max = 700, weak_steps = 2;
     bool cut_weak = false, weak_param_given = false;
     bool normalize_gaps = false;
+    bool clip_ends = false, clip_param_given = false;
+    int clip_identity = BELLA_CLIP_DEFAULT_IDENTITY;
     bool graph() const { return !gfa.empty() || !unitigs.empty() || !unitigs_fasta.empty(); }
 };
 
@@ -110,6 +114,9 @@ const char* kHelp =
     "      --correct-min-identity arg  with --correct: permille of matches below which an alignment does not vote (default: 700)\n"
     "      --normalize-gaps       with --correct / --polish: every gap of the base-level alignments votes at a canonical position (moved towards the start\n"
     "                             of the read it votes on, inside the neighbouring run of matches), so equal indels seen from either side add up\n"
+    "      --clip-ends            with an option that traces (--cigar, --correct, --gfa, --unitigs, --unitigs-fasta, --polish): every base-level alignment is\n"
+    "                             cut to its maximum-scoring segment under an identity threshold, so junk ends and chimeric halves leave the records and votes\n"
+    "      --clip-identity arg    with --clip-ends: that threshold in permille, 1 to 999 (default: 650)\n"
     "      --gfa arg              string graph (GFA 1): overlap classes, contained reads dropped, transitive reduction, on the device\n"
     "      --gfa-min-overlap arg  with --gfa: shortest overlap that counts (default: 1000)\n"
     "      --gfa-max-overhang arg with --gfa: longest unaligned end of a dovetail or containment (default: 1000)\n"
@@ -160,7 +167,7 @@ Options parse(int argc, char** argv) {
         {"upper-freq", 'u', 1, &o.upper}, {"lower-freq", 'l', 1, &o.lower}, {"tuples", 0, 3, &o.tuples}, {"exact-xdrop", 0, 0, &o.exact}, {"cigar", 0, 0, &o.cigar}, {"trace-band", 0, 1, &o.trace_band},
         {"correct", 0, 3, &o.correct}, {"min-depth", 0, 1, &o.min_depth},
         {"correct-rounds", 0, 1, &o.correct_rounds}, {"correct-band", 0, 1, &o.correct_band}, {"correct-min-identity", 0, 1, &o.correct_min_identity},
-        {"normalize-gaps", 0, 0, &o.normalize_gaps},
+        {"normalize-gaps", 0, 0, &o.normalize_gaps}, {"clip-ends", 0, 0, &o.clip_ends}, {"clip-identity", 0, 1, &o.clip_identity},
         {"gfa", 0, 3, &o.gfa}, {"gfa-fuzz", 0, 1, &o.gfa_fuzz}, {"gfa-max-overhang", 0, 1, &o.gfa_max_overhang}, {"gfa-min-overlap", 0, 1, &o.gfa_min_overlap},
         {"gfa-no-seq", 0, 0, &o.gfa_no_seq},
         {"unitigs", 0, 3, &o.unitigs}, {"unitigs-fasta", 0, 3, &o.unitigs_fasta}, {"tip-reads", 0, 1, &o.tip_reads}, {"tip-rounds", 0, 1, &o.tip_rounds}, {"gfa-clean", 0, 0, &o.gfa_clean},
@@ -214,6 +221,7 @@ Options parse(int argc, char** argv) {
         if (sp->dst == &o.polish_min_depth) o.polish_param_given = true;
         if (sp->dst == &o.polish_rounds || sp->dst == &o.realign_band || sp->dst == &o.realign_min_identity) o.realign_param_given = true;
         if (sp->dst == &o.trim_depth || sp->dst == &o.trim_end_clip || sp->dst == &o.trimmed_reads) o.trim_param_given = true;
+        if (sp->dst == &o.clip_identity) o.clip_param_given = true;
     }
     return o;
 }
@@ -303,6 +311,10 @@ int main(int argc, char** argv) {
     if (o.correct_band < 256 || o.correct_band > 4096 || (o.correct_band & (o.correct_band - 1))) die("--correct-band must be a power of two in [256, 4096]");
     if (o.correct_min_identity < 0 || o.correct_min_identity > 1000) die("--correct-min-identity is in permille: [0, 1000]");
     if (o.normalize_gaps && o.correct.empty() && !o.polish) die("--normalize-gaps needs --correct or --polish (it changes where the gaps of the pileup vote)");
+    if (o.clip_ends && !o.cigar && o.correct.empty() && !o.graph() && !o.polish)
+        die("--clip-ends needs an option that traces: --cigar, --correct, --gfa, --unitigs, --unitigs-fasta or --polish (it clips the base-level alignments)");
+    if (o.clip_param_given && !o.clip_ends) die("--clip-identity needs --clip-ends");
+    if (o.clip_identity < 1 || o.clip_identity > 999) die("--clip-identity is in permille: [1, 999]");
     if (o.kmer < 1 || o.kmer > 32) die("-k must be in [1,32] (one 64-bit word per k-mer, Kmer.hpp:27-28)");
     const std::string outfile = o.output + ".out";                  // main.cpp:113-130
     std::remove(outfile.c_str());
@@ -457,6 +469,7 @@ int main(int argc, char** argv) {
     so.polish_rounds = (uint32_t)o.polish_rounds; so.realign_band = (uint32_t)o.realign_band; so.realign_min_identity = (uint32_t)o.realign_min_identity; so.realign_circular = o.realign_circular;
     so.correct_rounds = (uint32_t)o.correct_rounds; so.correct_band = (uint32_t)o.correct_band; so.correct_min_identity = (uint32_t)o.correct_min_identity;
     so.normalize_gaps = o.normalize_gaps ? 1 : 0;
+    so.clip_ends = o.clip_ends ? 1 : 0; so.clip_identity = (uint32_t)o.clip_identity;
     so.trim = o.trim ? 1 : 0;
     so.trim_depth = (uint32_t)o.trim_depth; so.trim_end_clip = (uint32_t)o.trim_end_clip;
     so.trimmed_reads = o.trimmed_reads.empty() ? nullptr : o.trimmed_reads.c_str();

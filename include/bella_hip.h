@@ -541,6 +541,62 @@ int bella_hip_graph_get_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 #define BELLA_TRACE_DROP_OPS 2u
 #define BELLA_TRACE_PILEUP 4u
 int bella_hip_trace_pairs_flags(bella_ctx* ctx, const bella_params* p, uint32_t band0, uint32_t flags, uint64_t* ntraced, uint64_t* nops);
+
+/* ---- clipped ends: a traced alignment cut to where the similarity ends (no counterpart in the reference) --------
+ * The extension of a trace is free at its far end and scores +1 / -1 / -1, under which random DNA drifts upwards: a trace runs through
+ * junk ends, chimeric junctions and the far side of a repeat copy to the end of the read.  The clip keeps the maximum-scoring segment
+ * of the path under an identity threshold.  For a pair with runs r = 0 .. n - 1 and identity = t permille (1 <= t <= 999):
+ *   w_r = len_r (1000 - t) for an '=' run, w_r = -len_r t for 'X', 'I', 'D';  P_0 = 0, P_{r+1} = P_r + w_r (64 bits).
+ * The clip is the (a, b), 0 <= a < b <= n, that maximises P_b - P_a; ties: the smallest b, for that b the largest a.  A maximum that
+ * is not positive EMPTIES the pair.  A clipped alignment begins and ends with an '=' run.  The segment need not contain the seed: of
+ * a chimera the better half stays.  The runs themselves are never rewritten: a clip moves op_off and nops. */
+#define BELLA_CLIP_DEFAULT_IDENTITY 650
+typedef struct {
+    uint32_t struct_size;     /* sizeof(bella_clip_params)                                                   */
+    uint32_t identity;        /* t, permille; 0 = BELLA_CLIP_DEFAULT_IDENTITY; otherwise 1 .. 999             */
+} bella_clip_params;
+/* One pair's clip.  An emptied pair (also a pair without runs): nruns = 0, first_run = 0, begV = endV = the pair's tbegV, begH = endH =
+ * its tbegH, counts, score and clip_score 0. */
+typedef struct {
+    uint32_t first_run;       /* a: runs of the pair in front of the segment                                 */
+    uint32_t nruns;           /* b - a                                                                       */
+    int32_t begV, endV;       /* the segment on V and on H', in the pair's coordinates                       */
+    int32_t begH, endH;
+    uint32_t n_eq, n_x, n_ins, n_del;   /* bases of the segment                                              */
+    int32_t score;            /* n_eq - n_x - n_ins - n_del                                                  */
+    uint32_t pad;
+    int64_t clip_score;       /* P_b - P_a                                                                   */
+} bella_clip;
+/* What the last bella_hip_trace_pairs_clip / bella_hip_clip_ops did (pairs without runs are not counted).  A sized struct:
+ * bella_hip_get_clip_stats writes at most struct_size bytes. */
+typedef struct {
+    uint64_t pairs;               /* pairs with runs                                                          */
+    uint64_t clipped;             /* ... whose segment is shorter than the path (and not empty)               */
+    uint64_t emptied;             /* ... that have no positive segment                                        */
+    uint64_t runs_before, runs_after;
+    uint64_t columns_before, columns_after;
+    uint64_t bases_v_removed;     /* bases of V / of H' the alignments no longer cover (emptied pairs: all)   */
+    uint64_t bases_h_removed;
+    uint32_t identity;            /* the t the call used                                                      */
+    uint32_t pad;
+    double clip_ms;               /* the clip kernel (device time, all batches)                               */
+} bella_clip_stats;
+/* bella_hip_trace_pairs_flags with every traced alignment clipped on the device, batch by batch, while its runs are in device memory.
+ * flags: the four of bella_hip_trace_pairs_flags, with their rules.  clip == NULL: the default identity; an identity outside 1 .. 999
+ * (0: the default) or a struct_size too small is BELLA_ERR_BAD_ARG.  Everything downstream sees the clipped record: op_off += a,
+ * nops = b - a, the end points, the counts and score = n_eq - n_x - n_ins - n_del recounted over the segment; band and widened stay.
+ * An emptied pair keeps op_off, band and widened and has nops = 0 (not traced), tend = tbeg, counts and score 0; it casts no vote and
+ * is not counted in *ntraced.  The ops array and *nops are those of the call without the clip (runs outside a segment stay in it,
+ * unreferenced).  With BELLA_TRACE_DROP_OPS the runs are still written on the device (the clip reads them) but not staged. */
+int bella_hip_trace_pairs_clip(bella_ctx* ctx, const bella_params* p, uint32_t band0, uint32_t flags, const bella_clip_params* clip,
+                               uint64_t* ntraced, uint64_t* nops);
+/* The same kernel on a caller's runs: of every pair only op_off, nops, tbegV and tbegH are read; no reads need to be loaded.  out[npairs].
+ * The host checks everything BEFORE anything is launched -- every run's op in 0..3 and its length at least 1, op_off + nops inside
+ * ops[nops_total], tbegV, tbegH >= 0 and a pair's last base on either read below 2^31 -- and returns BELLA_ERR_BAD_ARG with `out`
+ * untouched otherwise. */
+int bella_hip_clip_ops(bella_ctx* ctx, const bella_vote_pair* pairs, uint64_t npairs, const uint32_t* ops, uint64_t nops_total,
+                       const bella_clip_params* clip, bella_clip* out);
+int bella_hip_get_clip_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
 /* The loaded reads as upper-case ASCII: offsets[nreads + 1] into bases[total bases].  Either may be NULL. */
 int bella_hip_get_read_bases(bella_ctx* ctx, uint64_t* offsets, uint8_t* bases);
 /* GFA 1: "H\tVN:Z:1.0"; one "S\tname\tsequence\tLN:i:len" per non-contained read in input order (sequence = base_offsets / bases, or "*"

@@ -232,6 +232,7 @@ SIGNATURES = [
     ("bella_hip_get_dictionary", C.c_int, [vp, vp, vp]),
     ("bella_hip_get_tuples", C.c_int, [vp, vp, vp, vp]),
     ("bella_hip_get_count_stats", C.c_int, [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("bella_hip_get_assemble_stats", C.c_int, [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("bella_hip_assemble_counted", C.c_int, [vp]),
     ("bella_hip_assemble_counted_panel", C.c_int, [vp, C.c_uint32, C.c_uint32]),
     ("bella_hip_assemble_tuples", C.c_int, [vp, C.c_uint16, C.c_uint32, C.c_uint64, vp, vp, vp]),

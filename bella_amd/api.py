@@ -267,6 +267,16 @@ class Engine:
         self._chk(self.lib.bella_hip_get_B(self.h, C.byref(nnz), colptr.ctypes.data, rowids.ctypes.data, values.ctypes.data))
         return colptr, rowids[:nnz.value], values[:nnz.value]
 
+    def assemble_stats(self):
+        """which path the last assembly took: dict(classes=(reads per table class of the row assembly), inline, products,
+        first_appearance, place_sorted)"""
+        n = C.c_uint32(0)
+        v = np.zeros(16, np.uint64)
+        self._chk(self.lib.bella_hip_get_assemble_stats(self.h, v.ctypes.data, len(v), C.byref(n)))
+        assert n.value == 9, n.value
+        v = [int(x) for x in v[:9]]
+        return dict(classes=tuple(v[:5]), inline=bool(v[5]), products=bool(v[6]), first_appearance=bool(v[7]), place_sorted=bool(v[8]))
+
     def set_partition(self, first, stride):
         self._chk(self.lib.bella_hip_set_partition(self.h, first, stride))
 

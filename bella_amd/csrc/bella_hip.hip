@@ -289,6 +289,10 @@ struct bella_ctx {
     BufPool pool;                        // released device buffers waiting for the next request they fit
     uint32_t layout_inline = 0;          // the device layout holds B' entries in the INLINE form (util.hpp); 0 / 1
     bool layout_products = false;        // the device layout holds B' with one entry per PRODUCT (assemble.hpp: k_layout_compact_products)
+    // which path the last assembly took (bella_hip_get_assemble_stats): the reads per table class of the last assemble_rows_device, the
+    // list order of the last build_layout and whether its place pass went through the radix pass
+    uint32_t asm_class_count[kAsmClasses] = {};
+    bool layout_first_app = false, layout_place_sorted = false;
     // layout and path choices (bella_hip_set_tuning; the matching bella_hip_set_debug bits of earlier rounds are still read as aliases)
     uint32_t tune_layout_order = 0;      // BELLA_TUNE_LAYOUT_ORDER: 0 lists of A' in k-mer order, 1 in order of first appearance in B'
     uint32_t tune_inline = 0;            // BELLA_TUNE_INLINE_ENTRIES: 0 by the size of A' against the last-level cache, 1 never, 2 always
@@ -625,6 +629,8 @@ int build_layout(bella_ctx* c, bool collective = false) {
     c->have_rowlists = false;
     c->layout_inline = 0;
     c->layout_products = false;
+    c->layout_first_app = false;
+    c->layout_place_sorted = false;
     c->live_nnz = 0;
     c->tm.expand_ms = 0.f;
     // shared formation of A' (layout_dist): every rank agreed to it in bella_hip_allgather_panels, so a rank that fails BEFORE it gets
@@ -682,6 +688,7 @@ int build_layout(bella_ctx* c, bool collective = false) {
         // expands B' x A' itself: the fastest ONE-SHOT call (layout + first pass).  BELLA_TUNE_LAYOUT_ORDER 1 (tests): the lists in
         // order of first appearance in B' (the owner row of a list streams it; three more random-access passes here).
         const uint32_t by_kmer = first_app ? 0u : 1u;
+        c->layout_first_app = first_app;
         // entries whose k-mer has exactly one later read carry that read (util.hpp: INLINE form) when bit 31 of the list index and bit 30
         // of a read id are free -- and when A' is larger than the last-level cache (256 MB): the form saves a line from HBM per such
         // entry and pass (row kernels 4.03 -> 3.69 ms at 100k reads, A' = 1.6 GB), but where the gather is a cache hit it only adds a
@@ -748,6 +755,7 @@ int build_layout(bella_ctx* c, bool collective = false) {
             hipcub::DoubleBuffer<uint32_t> ek(ekey, const_cast<uint32_t*>(skey));
             hipcub::DoubleBuffer<uint64_t> ev(eval, const_cast<uint64_t*>(sval));
             if (ebits > 12) CUB(c, hipcub::DeviceRadixSort::SortPairs, ek, ev, (uint64_t)nown_nnz, ebits - 8, ebits, c->stream);
+            c->layout_place_sorted = ebits > 12;
             k_layout_place<<<((nblk(nown_nnz) + 7u) / 8u) * 8u, 256, 0, c->stream>>>(ek.Current(), ev.Current(), nown_nnz, ptr<uint2>(c->Bent));
             KCHK(c);
         }
@@ -1380,6 +1388,7 @@ static int assemble_rows_device(bella_ctx* c, uint32_t first, uint32_t nr, uint6
     if (rc) return rc;
     rc = status_to_error(c, st);
     if (rc) return rc;
+    for (uint32_t q = 0; q < kAsmClasses; ++q) c->asm_class_count[q] = ccount[q];
     AsmArgs a;
     a.t_kmer = ptr<uint32_t>(c->t_kmer) + toff;
     a.t_pos = ptr<uint16_t>(c->t_pos) + toff;
@@ -1939,6 +1948,21 @@ int bella_hip_get_count_stats(bella_ctx* c, uint64_t* values, uint32_t capacity,
     const size_t n = c->kc_stats.size();
     for (size_t i = 0; i < n && i < capacity; ++i) values[i] = c->kc_stats[i];
     *nvalues = (uint32_t)n;
+    return 0;
+}
+
+int bella_hip_get_assemble_stats(bella_ctx* c, uint64_t* values, uint32_t capacity, uint32_t* nvalues) {
+    if (!c || !nvalues || (capacity && !values)) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, MATRIX)) return r;
+    uint64_t v[kAsmClasses + 4];
+    for (uint32_t q = 0; q < kAsmClasses; ++q) v[q] = c->asm_class_count[q];
+    v[kAsmClasses] = c->layout_inline;
+    v[kAsmClasses + 1] = c->layout_products ? 1u : 0u;
+    v[kAsmClasses + 2] = c->layout_first_app ? 1u : 0u;
+    v[kAsmClasses + 3] = c->layout_place_sorted ? 1u : 0u;
+    const uint32_t n = kAsmClasses + 4;
+    for (uint32_t i = 0; i < n && i < capacity; ++i) values[i] = v[i];
+    *nvalues = n;
     return 0;
 }
 

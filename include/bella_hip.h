@@ -192,6 +192,12 @@ int bella_hip_get_tuples(bella_ctx* ctx, uint32_t* t_kmer, uint32_t* t_read, uin
  * selector (0 all, 1 syncmers, 2 minimizers), positions of the read set, k-mers per pass allowed; then per pass {first bin, end bin,
  * words, tiles of the run kernels}.  Writes at most `capacity` values; *nvalues = how many there are. */
 int bella_hip_get_count_stats(bella_ctx* ctx, uint64_t* values, uint32_t capacity, uint32_t* nvalues);
+/* which path the last assembly took (host values only, no device work): values[0..4] = the reads per table class of the row
+ * assembly (tables of <= 1024, 2048, 4096, 8192 slots in LDS, larger ones in global memory; of the last panel where rows were
+ * assembled in panels, stale after bella_hip_set_B*), then: B' entries in the inline form (0 / 1), one B' entry per product (0 / 1),
+ * lists of A' in first-appearance order (0 / 1), the place pass went through its radix pass (0 / 1).  Writes at most `capacity`
+ * values; *nvalues = how many there are. */
+int bella_hip_get_assemble_stats(bella_ctx* ctx, uint64_t* values, uint32_t capacity, uint32_t* nvalues);
 /* bella_hip_assemble_tuples on the device-resident tuples of bella_hip_count_kmers (no host copy) */
 int bella_hip_assemble_counted(bella_ctx* ctx);
 /* bella_hip_assemble_panel on the device-resident tuples of the reads [first_read, first_read + nreads_panel) (multi-GPU:

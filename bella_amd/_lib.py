@@ -35,6 +35,11 @@ assert POLISH_DT.itemsize == 56
 PLACE_DT = np.dtype([("unitig", "<u4"), ("orient", "<u4"), ("s", "<i8"), ("e", "<i8"), ("anchor", "<u4"), ("status", "<u4"), ("band", "<u4"), ("n_eq", "<u4"), ("n_x", "<u4"),
                      ("n_ins", "<u4"), ("n_del", "<u4"), ("score", "<i4"), ("q_begin", "<i8"), ("q_end", "<i8"), ("op_off", "<u8"), ("nops", "<u4"), ("pad", "<u4")])
 assert PLACE_DT.itemsize == 88
+LINK_ALN_DT = np.dtype([("status", "<u4"), ("band", "<u4"), ("score", "<i4"), ("ovl_a", "<u4"), ("ovl_b", "<u4"), ("n_eq", "<u4"), ("n_x", "<u4"), ("n_ins", "<u4"),
+                        ("n_del", "<u4"), ("mate", "<u4"), ("op_off", "<u8"), ("nops", "<u4"), ("derived", "<u4")])
+assert LINK_ALN_DT.itemsize == 56
+LINK_ALIGNED, LINK_EMPTY, LINK_BAND_CAPPED, LINK_LOW_IDENTITY, LINK_SELF = range(5)
+LINK_NO_MATE = 0xFFFFFFFF
 REALIGN_NONE, REALIGN_VOTED, REALIGN_UNPLACED, REALIGN_OUTSIDE, REALIGN_BAND_CAPPED, REALIGN_LOW_IDENTITY = range(6)
 TRACE_PASSED_ONLY, TRACE_DROP_OPS, TRACE_PILEUP, TRACE_NORMALIZE = 1, 2, 4, 8
 VOTE_PAIR_DT = np.dtype([("rid", "<u4"), ("cid", "<u4"), ("tbegV", "<i4"), ("tbegH", "<i4"), ("op_off", "<u8"), ("nops", "<u4"), ("strand", "u1"), ("pad", "u1", (3,))])
@@ -163,6 +168,16 @@ class RealignStats(C.Structure):
                 ("dir_bytes_peak", C.c_uint64), ("votes", C.c_uint64), ("bases_before", C.c_uint64), ("bases_after", C.c_uint64), ("substituted", C.c_uint64),
                 ("deleted", C.c_uint64), ("inserted", C.c_uint64), ("place_ms", C.c_double), ("dp_ms", C.c_double), ("walk_ms", C.c_double), ("vote_ms", C.c_double),
                 ("decide_ms", C.c_double)]
+
+
+class LinkParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("band0", C.c_uint32), ("band_max", C.c_uint32), ("min_identity", C.c_uint32)]
+
+
+class LinkStats(C.Structure):
+    _fields_ = [("links", C.c_uint64), ("aligned", C.c_uint64), ("empty", C.c_uint64), ("band_capped", C.c_uint64), ("low_identity", C.c_uint64), ("self", C.c_uint64),
+                ("derived", C.c_uint64), ("overlap_before", C.c_uint64), ("overlap_after", C.c_uint64), ("jobs", C.c_uint64), ("dp_cells", C.c_uint64), ("ops", C.c_uint64),
+                ("batches", C.c_uint32), ("pad", C.c_uint32), ("pack_ms", C.c_double), ("dp_ms", C.c_double), ("walk_ms", C.c_double)]
 
 
 class RecorrectParams(C.Structure):
@@ -314,6 +329,10 @@ SIGNATURES = [
     ("bella_hip_graph_get_realign_placements", C.c_int, [vp, vp]),
     ("bella_hip_graph_get_realign_ops", C.c_int, [vp, C.POINTER(C.c_uint64), vp, vp]),
     ("bella_hip_graph_get_realign_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_graph_align_links", C.c_int, [vp, C.POINTER(LinkParams), C.POINTER(C.c_uint64)]),
+    ("bella_hip_graph_get_link_alignments", C.c_int, [vp, vp, C.POINTER(C.c_uint64), vp]),
+    ("bella_hip_graph_get_link_stats", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_write_unitig_gfa_links", C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]),
     ("bella_hip_recorrect", C.c_int, [vp, C.POINTER(RecorrectParams), C.POINTER(C.c_uint64)]),
     ("bella_hip_get_recorrected", C.c_int, [vp, vp, vp, vp]),
     ("bella_hip_get_recorrect_jobs", C.c_int, [vp, C.POINTER(C.c_uint64), vp]),

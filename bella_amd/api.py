@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CLIP_DT, GraphTrimParams, TrimStats
-from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_DT, OVL_DT, PAIR_DT, PLACE_DT, POLISH_DT, PolishParams, PolishStats, RealignParams, RealignStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphWeakParams, WeakStats, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
+from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_ALN_DT, LINK_DT, LinkParams, LinkStats, OVL_DT, PAIR_DT, PLACE_DT, POLISH_DT, PolishParams, PolishStats, RealignParams, RealignStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphWeakParams, WeakStats, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
 class BellaHipError(RuntimeError):
@@ -697,6 +697,31 @@ class Engine:
         st["wrapped"] = w.value
         return st
 
+    # ---- link alignment ----
+    LINK_DEFAULTS = dict(band0=512, band_max=4096, min_identity=700)
+
+    def graph_align_links(self, **params) -> int:
+        """aligns the ends of the unitigs that every link of the last graph_unitigs joins, on the device, against the newest sequence of
+        the unitigs (the last realignment round's, else the polish's, else the raw bases); returns the number of ALIGNED links.  band0,
+        band_max (powers of two, 256 .. 4096) and min_identity (permille) default to 512, 4096 and 700"""
+        p = _over(self.LINK_DEFAULTS, params, "graph_align_links")
+        lp = LinkParams(C.sizeof(LinkParams), p["band0"], p["band_max"], p["min_identity"])
+        n = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_graph_align_links(self.h, C.byref(lp), C.byref(n)))
+        return n.value
+
+    def link_alignments(self):
+        """(records of LINK_ALN_DT, one per link in the links' order; the runs of all links, uint32 op | len << 4)"""
+        st = self.link_stats()
+        alns, ops = np.zeros(st["links"], LINK_ALN_DT), np.zeros(st["ops"], np.uint32)
+        n = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_graph_get_link_alignments(self.h, _p(alns), C.byref(n), _p(ops)))
+        assert n.value == len(ops)
+        return alns, ops
+
+    def link_stats(self) -> dict:
+        return self._stats(self.lib.bella_hip_graph_get_link_stats, LinkStats)
+
     # ---- coverage trimming (DESIGN.md section 15) ----
     TRIM_DEFAULTS = dict(min_depth=3, end_clip=500, min_span=1000)
 
@@ -903,9 +928,10 @@ def unitig_names(circular) -> list:
     return ["utg%06d%s" % (k + 1, "c" if c else "l") for k, c in enumerate(np.asarray(circular).tolist())]
 
 
-def write_unitig_gfa(filename: str, names, unitigs: dict, offsets=None, bases=None) -> None:
+def write_unitig_gfa(filename: str, names, unitigs: dict, offsets=None, bases=None, link_alns=None, link_ops=None) -> None:
     """bella_hip_write_unitig_gfa: GFA 1 of what Engine.graph_unitigs returned: S and a lines per unitig, L lines per link; with the
-    unitigs' bases (what Engine.unitig_bases returned) or '*'"""
+    unitigs' bases (what Engine.unitig_bases returned) or '*'.  link_alns / link_ops (what Engine.link_alignments returned): the
+    ALIGNED links' lines carry their CIGAR, NM:i: and ol:i: (bella_hip_write_unitig_gfa_links)"""
     lib = _lib.load()
     n, arr = _names(names)
     u = unitigs
@@ -917,11 +943,40 @@ def write_unitig_gfa(filename: str, names, unitigs: dict, offsets=None, bases=No
         assert len(boffs) == len(a["len"]) + 1
         if not len(b):
             b = np.zeros(1, np.uint8)                                 # (no bases at all: still a pointer, NULL would mean '*')
-    rc = lib.bella_hip_write_unitig_gfa(os.fsencode(filename), n, arr, len(a["len"]), a["voff"].ctypes.data, _p(a["verts"]), _p(a["pos"]),
-                                        _p(a["nbases"]), _p(a["len"]), _p(a["circular"]), boffs.ctypes.data if boffs is not None else None,
-                                        b.ctypes.data if b is not None else None, len(a["links"]), _p(a["links"]))
+    args = (os.fsencode(filename), n, arr, len(a["len"]), a["voff"].ctypes.data, _p(a["verts"]), _p(a["pos"]), _p(a["nbases"]), _p(a["len"]), _p(a["circular"]),
+            boffs.ctypes.data if boffs is not None else None, b.ctypes.data if b is not None else None, len(a["links"]), _p(a["links"]))
+    if link_alns is None:
+        rc, who = lib.bella_hip_write_unitig_gfa(*args), "bella_hip_write_unitig_gfa"
+    else:
+        la = np.ascontiguousarray(link_alns, LINK_ALN_DT)
+        lo = np.ascontiguousarray(link_ops if link_ops is not None else np.zeros(0, np.uint32), np.uint32)
+        assert len(la) == len(a["links"])
+        assert not len(la) or int((la["op_off"] + la["nops"]).max()) <= len(lo), "the links' runs lie outside link_ops"
+        if not len(lo):
+            lo = np.zeros(1, np.uint32)
+        rc, who = lib.bella_hip_write_unitig_gfa_links(*args, _p(la), _p(lo)), "bella_hip_write_unitig_gfa_links"
     if rc:
-        raise BellaHipError(rc, "bella_hip_write_unitig_gfa failed")
+        raise BellaHipError(rc, who + " failed")
+
+
+def link_cigars(alns, ops) -> list:
+    """the CIGAR (bytes; M / I / D, '=' and 'X' merged into M) of every ALIGNED link, None for the others: what the L lines carry"""
+    out = []
+    for a in np.asarray(alns):
+        if int(a["status"]) != _lib.LINK_ALIGNED:
+            out.append(None)
+            continue
+        text, run, last = [], 0, None
+        for w in np.asarray(ops[int(a["op_off"]):int(a["op_off"]) + int(a["nops"])], np.uint32).tolist():
+            ch = b"MMID"[w & 15:(w & 15) + 1]
+            if ch != last and run:
+                text.append(b"%d%s" % (run, last))
+                run = 0
+            last, run = ch, run + (w >> 4)
+        if run:
+            text.append(b"%d%s" % (run, last))
+        out.append(b"".join(text))
+    return out
 
 
 def hash_spgemm(engine: Engine, pars: BellaPars, filename: str, stdout=sys.stdout, stages: int = 1):

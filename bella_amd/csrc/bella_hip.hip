@@ -4,6 +4,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <initializer_list>
 #include <iterator>
@@ -31,6 +32,7 @@
 #include "pileup.hpp"
 #include "polish.hpp"
 #include "realign.hpp"
+#include "links.hpp"
 #include "recorrect.hpp"
 #include "spgemm.hpp"
 #include "trace.hpp"
@@ -142,7 +144,7 @@ struct CountU64 {                                        // pair counts: without
 // drop / changed / made / has / need (below) are the only code that touches `valid`.  The stages up to the traces keep their results in
 // members of the context (device buffers, mostly), PILE and CONS too; those of the stages that follow the alignment are here, one member
 // per stage, on the host: the graph is small next to what it was made from, and a stage uploads what it reads.
-enum Stage : uint32_t { READS, TUPLES, PANEL, MATRIX, PAIRS, ALNS, TRACES, BATCH_OPS, RECORDS, TRIM, GRAPH, UNITIGS, POLISH, REALIGN, PILE, CONS, RECORRECT, kStages };
+enum Stage : uint32_t { READS, TUPLES, PANEL, MATRIX, PAIRS, ALNS, TRACES, BATCH_OPS, RECORDS, TRIM, GRAPH, UNITIGS, POLISH, REALIGN, PILE, CONS, RECORRECT, LINKS, kStages };
 struct StageState {
     uint32_t valid = 1u << RECORDS;          // one bit per Stage (the records are always there: possibly none)
     std::vector<bella_overlap> records;      // accumulated by bella_hip_graph_add_overlaps (graph.hpp)
@@ -188,6 +190,11 @@ struct StageState {
         std::vector<uint32_t> ops, table;    // kept for the tests only (keep_ops)
         bella_recorrect_stats stats{};
     } recorrect;
+    struct Links {                           // the last bella_hip_graph_align_links (links.hpp; section 26): one record per link of the unitigs,
+        std::vector<bella_link_aln> alns;    // and the runs of the ALIGNED ones
+        std::vector<uint32_t> ops;
+        bella_link_stats stats{};
+    } links;
     // READS .. BATCH_OPS, PILE and CONS (pileup.hpp; section 10) are members of the context: only their bits are here
 };
 
@@ -521,12 +528,13 @@ constexpr uint32_t kBuiltFrom[kStages] = {
     /* RECORDS */ stage_bit(TRIM) | stage_bit(GRAPH),
     /* TRIM    */ stage_bit(GRAPH),
     /* GRAPH   */ stage_bit(UNITIGS),
-    /* UNITIGS */ stage_bit(POLISH),
-    /* POLISH  */ stage_bit(REALIGN),
-    /* REALIGN */ 0,                         // (a round reads the round before and replaces it)
+    /* UNITIGS */ stage_bit(POLISH) | stage_bit(LINKS),
+    /* POLISH  */ stage_bit(REALIGN) | stage_bit(LINKS),
+    /* REALIGN */ stage_bit(LINKS),          // (a round reads the round before and replaces it: realign_round says changed(REALIGN))
     /* PILE    */ stage_bit(CONS) | stage_bit(POLISH),
     /* CONS    */ stage_bit(RECORRECT),
     /* RECORRECT */ 0,                       // (a round reads the round before and replaces it)
+    /* LINKS   */ 0,
 };
 void drop(bella_ctx* c, Stage s);
 void changed(bella_ctx* c, Stage s) {
@@ -545,7 +553,7 @@ int need(bella_ctx* c, Stage s) {
                                                "overlap first", "align_pairs first", "trace_pairs first", "trace_batch first",
                                                "", "bella_hip_graph_trim first", "bella_hip_graph_build first", "bella_hip_graph_unitigs first",
                                                "bella_hip_graph_polish_unitigs first", "bella_hip_graph_realign_unitigs first", "bella_hip_pileup_reset first", "bella_hip_consensus first",
-                                               "bella_hip_recorrect first"};
+                                               "bella_hip_recorrect first", "bella_hip_graph_align_links first"};
     return has(c, s) ? 0 : fail(c, BELLA_ERR_STATE, "%s", first[s]);
 }
 
@@ -4384,6 +4392,7 @@ struct RoundBatches {
     std::vector<uint32_t>& kept;                                      // ... where the ops of every batch are appended
     double &dp_ms, &walk_ms, &vote_ms;
     TmpBuf jobs, res, cnt, dirs, scr, ops;
+    bool links = false;                                               // the batch's jobs are links (links.hpp; section 26): their DP and walks, and no votes
 
     // DP and the counting walk.  The caller launches what is its own behind them, records ev.d, reads back, waits, and calls counted().
     int dp_count(uint32_t nj, uint32_t B, uint64_t dbytes) {
@@ -4393,6 +4402,17 @@ struct RoundBatches {
         if (B > kTrRegBand) ENSURE(c, scr, 8 * (size_t)nj * B);
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
         const unsigned grid = nblk((uint64_t)nj * 64, kTraceBlock);
+        if (links) {
+            if (B == 256) k_lnk_dp<4><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<LnkRes>(res));
+            else if (B == 512) k_lnk_dp<8><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<LnkRes>(res));
+            else if (B == 1024) k_lnk_dp<16><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<LnkRes>(res));
+            else k_lnk_dp_wide<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<LnkRes>(res));
+            KCHK(c);
+            HIPCHK(c, hipEventRecord(ev.b, c->stream));
+            k_lnk_count<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<LnkRes>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
+            KCHK(c);
+            return 0;
+        }
         if (B == 256) k_rea_dp<4><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
         else if (B == 512) k_rea_dp<8><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
         else if (B == 1024) k_rea_dp<16><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
@@ -4409,11 +4429,14 @@ struct RoundBatches {
     int write_vote(uint32_t nj, uint64_t nops) {
         ENSURE(c, ops, 4 * (size_t)nops);
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
-        k_rea_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
+        if (links) k_lnk_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<LnkRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
+        else k_rea_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.b, c->stream));
-        k_rea_vote<<<nblk((uint64_t)nj * 64, kPileBlock), kPileBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaCnt>(cnt), nj, ptr<uint32_t>(ops), rpacked, table, votes);
-        KCHK(c);
+        if (!links) {
+            k_rea_vote<<<nblk((uint64_t)nj * 64, kPileBlock), kPileBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaCnt>(cnt), nj, ptr<uint32_t>(ops), rpacked, table, votes);
+            KCHK(c);
+        }
         HIPCHK(c, hipEventRecord(ev.d, c->stream));
         if (keep_ops) {
             const size_t at = kept.size();
@@ -5748,6 +5771,7 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
     st.bases_after = nout;
     out.stats = st;
     c->as.realign = std::move(out);
+    changed(c, REALIGN);                                              // (the links were aligned on the sequence this round replaces)
     made(c, REALIGN);
     if (total_bases) *total_bases = nout;
     return 0;
@@ -5794,6 +5818,239 @@ int bella_hip_graph_get_realign_wrapped(bella_ctx* c, uint64_t* wrapped) {
 
 int bella_hip_graph_get_realign_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     return get_stats(c, REALIGN, out, struct_size, [](const StageState& a) { return a.realign.stats; });
+}
+
+// ---- link alignment (links.hpp) -------------------------------------------------------------------------------------
+// The links live on the host, so the pairing of twins, the windows and the derivation of a twin's record are host code; the pack, the DP and
+// the walks run on the device, batched and band-doubled by RoundBatches as a realignment round's reads are.
+int bella_hip_graph_align_links(bella_ctx* c, const bella_link_params* params, uint64_t* naligned) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    bella_link_params lp{};
+    lp.band0 = BELLA_LINK_DEFAULT_BAND; lp.band_max = BELLA_LINK_DEFAULT_BAND_MAX; lp.min_identity = BELLA_LINK_DEFAULT_MIN_IDENTITY;
+    if (int r = take_params(c, lp, params, "bella_link_params")) return r;
+    auto pow2 = [](uint32_t x) { return x && !(x & (x - 1)); };
+    if (!pow2(lp.band0) || !pow2(lp.band_max) || lp.band0 < kTrMinBand || lp.band_max > kLnkMaxBand || lp.band0 > lp.band_max)
+        return fail(c, BELLA_ERR_BAD_ARG, "align_links: band0 and band_max must be powers of two with 256 <= band0 <= band_max <= 4096");
+    if (lp.min_identity > 1000) return fail(c, BELLA_ERR_BAD_ARG, "min_identity is in permille: at most 1000");
+    if (int r = need(c, UNITIGS)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    drop(c, LINKS);
+    const StageState::Unitigs& u = c->as.unitigs;
+    // the newest sequence of every unitig: the last round's, else the polish's, else the raw bases (whose map is the identity)
+    const bool rea = has(c, REALIGN), pol = has(c, POLISH);
+    const std::vector<uint64_t>& coffs = rea ? c->as.realign.offs : pol ? c->as.polish.offs : u.boff;
+    const std::vector<uint64_t>& cpos = rea ? c->as.realign.pos : pol ? c->as.polish.pos : u.pos;
+    const std::vector<uint32_t>& cnb = rea ? c->as.realign.nb : pol ? c->as.polish.nb : u.nb;
+    const std::vector<uint8_t>& cbases = rea ? c->as.realign.bases : pol ? c->as.polish.bases : u.bases;
+    const uint32_t nl = (uint32_t)u.links.size();
+    const int64_t S = (int64_t)lp.band_max / 2;
+    StageState::Links out;
+    bella_link_aln none{};
+    none.mate = kLnkNone;
+    out.alns.assign(nl, none);
+    bella_link_stats st{};
+    st.links = nl;
+    // ---- twins: link k, not SELF and not yet paired, takes the smallest later unpaired link that is its twin
+    using Key = std::array<uint32_t, 5>;                              // a, its sign, b, its sign, rec
+    auto key_of = [&](uint32_t k, bool twin) {
+        const bella_unitig_link& l = u.links[k];
+        const uint32_t sa = l.flags & BELLA_UNITIG_LINK_A_MINUS ? 1u : 0u, sb = l.flags & BELLA_UNITIG_LINK_B_MINUS ? 1u : 0u;
+        return twin ? Key{l.b, sb ^ 1u, l.a, sa ^ 1u, l.rec} : Key{l.a, sa, l.b, sb, l.rec};
+    };
+    std::map<Key, std::vector<uint32_t>> by_key;
+    for (uint32_t k = 0; k < nl; ++k)
+        if (u.links[k].a != u.links[k].b) by_key[key_of(k, false)].push_back(k);
+    std::map<Key, size_t> cursor;
+    for (uint32_t k = 0; k < nl; ++k) {
+        bella_link_aln& A = out.alns[k];
+        if (u.links[k].a == u.links[k].b) { A.status = BELLA_LINK_SELF; continue; }
+        if (A.mate != kLnkNone) continue;
+        const Key tk = key_of(k, true);
+        auto it = by_key.find(tk);
+        if (it == by_key.end()) continue;
+        size_t& at = cursor[tk];                                      // (every index of the list below k is paired: it was asked for k's own key)
+        while (at < it->second.size() && (it->second[at] <= k || out.alns[it->second[at]].mate != kLnkNone)) ++at;
+        if (at == it->second.size()) continue;
+        const uint32_t t = it->second[at];
+        A.mate = t;
+        out.alns[t].mate = k; out.alns[t].derived = 1;
+    }
+    // ---- expected overlaps, windows and centre diagonals
+    struct Want { int64_t oa, m, n, c; };
+    std::vector<Want> want(nl, Want{});
+    std::vector<uint32_t> pending;                                    // the links that are aligned, in index order
+    std::vector<LnkWin> wins;
+    std::vector<uint64_t> woff(1, 0);
+    for (uint32_t k = 0; k < nl; ++k) {
+        const bella_unitig_link& l = u.links[k];
+        if (l.a == l.b) continue;
+        auto map = [&](uint32_t j, int64_t x) {
+            return rea_map(x, u.pos.data(), u.nb.data(), cpos.data(), cnb.data(), u.voff[j], u.voff[j + 1], (int64_t)u.len[j], (int64_t)(coffs[j + 1] - coffs[j]));
+        };
+        const int64_t Pa = (int64_t)(coffs[l.a + 1] - coffs[l.a]), Pb = (int64_t)(coffs[l.b + 1] - coffs[l.b]);
+        if ((uint64_t)Pa >= kReaMaxUnitig || (uint64_t)Pb >= kReaMaxUnitig) return fail(c, BELLA_ERR_BAD_ARG, "align_links: a unitig has 2^30 bases or more");
+        const int64_t la = (int64_t)u.len[l.a], lb = (int64_t)u.len[l.b];
+        const int64_t xa = std::min<int64_t>(l.ovl, la), xb = std::min<int64_t>(l.ovl, lb);
+        const bool am = (l.flags & BELLA_UNITIG_LINK_A_MINUS) != 0, bm = (l.flags & BELLA_UNITIG_LINK_B_MINUS) != 0;
+        Want& w = want[k];
+        w.oa = am ? map(l.a, xa) : Pa - map(l.a, la - xa);
+        const int64_t ob = bm ? Pb - map(l.b, lb - xb) : map(l.b, xb);
+        w.m = std::min(Pa, w.oa + S);
+        w.n = std::min(Pb, ob + S);
+        const int64_t sum = w.oa + ob;
+        w.c = w.m - (sum >= 0 ? sum / 2 : -((-sum + 1) / 2));         // floor
+        if (out.alns[k].derived) continue;
+        // X: the last m bases of A^ (minus: the first m of cur(a), reversed and complemented); Y: the first n bases of B^
+        wins.push_back(LnkWin{coffs[l.a] + (uint64_t)(am ? 0 : Pa - w.m), (uint32_t)w.m, am ? 1u : 0u});
+        woff.push_back(woff.back() + (uint64_t)(w.m + 15) / 16);
+        wins.push_back(LnkWin{coffs[l.b] + (uint64_t)(bm ? Pb - w.n : 0), (uint32_t)w.n, bm ? 1u : 0u});
+        woff.push_back(woff.back() + (uint64_t)(w.n + 15) / 16);
+        pending.push_back(k);
+    }
+    st.jobs = pending.size();
+    if (!pending.empty()) {                                           // (no link, or SELF links only: nothing is launched)
+        std::vector<uint32_t> job_of(nl, 0);                          // link -> its pair of windows
+        for (size_t x = 0; x < pending.size(); ++x) job_of[pending[x]] = (uint32_t)x;
+        const uint64_t total = coffs.back(), nwords = woff.back();
+        TmpBuf ascii, dwins, dwoff, pack;
+        ENSURE(c, ascii, (size_t)total);
+        ENSURE(c, dwins, sizeof(LnkWin) * wins.size());
+        ENSURE(c, dwoff, 8 * woff.size());
+        ENSURE(c, pack, 4 * (size_t)(nwords + 1));
+        if (total) HIPCHK(c, c->stager.h2d(ascii.p, cbases.data(), (size_t)total, c->stream));
+        HIPCHK(c, c->stager.h2d(dwins.p, wins.data(), sizeof(LnkWin) * wins.size(), c->stream));
+        HIPCHK(c, c->stager.h2d(dwoff.p, woff.data(), 8 * woff.size(), c->stream));
+        EventSet ev;
+        int rc = ev.create(c, 3);
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        if (nwords) {
+            k_lnk_pack<<<nblk(nwords), 256, 0, c->stream>>>(ptr<uint8_t>(ascii), ptr<LnkWin>(dwins), ptr<uint64_t>(dwoff), (uint32_t)wins.size(), nwords, ptr<uint32_t>(pack));
+            KCHK(c);
+        }
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.pack_ms = ev_ms(ev.a, ev.b);
+        ascii.reset();
+        // ---- DP and walks: band by band, batch by batch
+        uint64_t budget = 0;
+        if ((rc = round_budget(c, &budget))) return rc;
+        double no_votes = 0;
+        RoundBatches rb{c, "align_links", "links", ev, ptr<uint32_t>(pack), ptr<uint32_t>(pack), nullptr, nullptr, true, out.ops, st.dp_ms, st.walk_ms, no_votes};
+        rb.links = true;
+        std::vector<ReaJob> hj;
+        std::vector<LnkRes> hres;
+        std::vector<ReaCnt> hcnt;
+        for (uint32_t B = lp.band0; !pending.empty(); B *= 2) {
+            std::vector<uint32_t> next;
+            const uint32_t maxjobs = round_max_jobs(B, budget);
+            for (size_t b0 = 0; b0 < pending.size();) {
+                hj.clear();
+                uint64_t dbytes = 0;
+                size_t b1 = b0;
+                for (; b1 < pending.size(); ++b1) {
+                    const uint32_t k = pending[b1];
+                    const Want& w = want[k];
+                    const uint64_t need_bytes = (uint64_t)w.n * (B / 4);
+                    if (!hj.empty() && (dbytes + need_bytes > budget || hj.size() >= maxjobs)) break;
+                    ReaJob j{};
+                    j.gH = (int64_t)(16 * woff[2 * (size_t)job_of[k]]); j.gV = (int64_t)(16 * woff[2 * (size_t)job_of[k] + 1]);
+                    j.dir_off = dbytes; j.scr_off = 2ull * B * hj.size(); j.op_off = ~0ull;
+                    j.n = (uint32_t)w.n; j.m = (int32_t)w.m; j.mt = j.m; j.c = (int32_t)w.c;
+                    j.band = B; j.dV = 1; j.comp = 0;
+                    hj.push_back(j);
+                    dbytes += need_bytes;
+                    st.dp_cells += (uint64_t)w.n * B;
+                }
+                const uint32_t nj = (uint32_t)hj.size();
+                ENSURE(c, rb.jobs, sizeof(ReaJob) * (size_t)nj);
+                ++st.batches;
+                HIPCHK(c, c->stager.h2d(rb.jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
+                if ((rc = rb.dp_count(nj, B, dbytes))) return rc;
+                HIPCHK(c, hipEventRecord(ev.d, c->stream));
+                hres.resize(nj); hcnt.resize(nj);
+                HIPCHK(c, c->stager.d2h(hres.data(), rb.res.p, sizeof(LnkRes) * (size_t)nj, c->stream));
+                HIPCHK(c, c->stager.d2h(hcnt.data(), rb.cnt.p, sizeof(ReaCnt) * (size_t)nj, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                rb.counted();
+                uint64_t nops = 0;
+                for (uint32_t x = 0; x < nj; ++x) {
+                    const uint32_t k = pending[b0 + x];
+                    bella_link_aln& A = out.alns[k];
+                    const ReaCnt& q = hcnt[x];
+                    const bool reached = hres[x].score > kReaNoEnd;
+                    A.band = B;
+                    A.score = reached ? hres[x].score : 0;
+                    A.ovl_a = reached ? (uint32_t)(hj[x].m - q.q_begin) : 0; A.ovl_b = reached ? (uint32_t)hres[x].i_end : 0;
+                    A.n_eq = q.n_eq; A.n_x = q.n_x; A.n_ins = q.n_ins; A.n_del = q.n_del;
+                    if (q.touch) {
+                        if (B < lp.band_max) next.push_back(k);
+                        else A.status = BELLA_LINK_BAND_CAPPED;
+                    } else if (A.score <= 0) {
+                        A.status = BELLA_LINK_EMPTY;
+                    } else if (1000ull * q.n_eq < (uint64_t)lp.min_identity * ((uint64_t)q.n_eq + q.n_x + q.n_ins + q.n_del)) {
+                        A.status = BELLA_LINK_LOW_IDENTITY;
+                    } else {
+                        A.status = BELLA_LINK_ALIGNED;
+                        hj[x].op_off = nops;
+                        A.nops = q.nops;
+                        A.op_off = out.ops.size() + nops;
+                        nops += q.nops;
+                    }
+                }
+                if (nops) {
+                    HIPCHK(c, c->stager.h2d(rb.jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
+                    if ((rc = rb.write_vote(nj, nops))) return rc;
+                }
+                b0 = b1;
+            }
+            pending.swap(next);
+            if (B >= lp.band_max) break;
+        }
+    }
+    // ---- the twins' records, from their mates'; the counts
+    for (uint32_t k = 0; k < nl; ++k) {
+        bella_link_aln& A = out.alns[k];
+        if (A.derived) {
+            const bella_link_aln M = out.alns[A.mate];
+            A.status = M.status; A.band = M.band; A.score = M.score;
+            A.ovl_a = M.ovl_b; A.ovl_b = M.ovl_a;
+            A.n_eq = M.n_eq; A.n_x = M.n_x; A.n_ins = M.n_del; A.n_del = M.n_ins;
+            A.nops = M.nops; A.op_off = out.ops.size();
+            for (uint32_t x = 0; x < M.nops; ++x) {                   // reversed, 'I' and 'D' swapped
+                const uint32_t w = out.ops[(size_t)M.op_off + M.nops - 1 - x], op = w & 15u;
+                out.ops.push_back((w & ~15u) | (op == kOpIns ? (uint32_t)kOpDel : op == kOpDel ? (uint32_t)kOpIns : op));
+            }
+            if (!A.nops) A.op_off = 0;
+            ++st.derived;
+        }
+        switch (A.status) {
+            case BELLA_LINK_ALIGNED: ++st.aligned; st.overlap_before += (uint64_t)want[k].oa; st.overlap_after += A.ovl_a; break;
+            case BELLA_LINK_EMPTY: ++st.empty; break;
+            case BELLA_LINK_BAND_CAPPED: ++st.band_capped; break;
+            case BELLA_LINK_LOW_IDENTITY: ++st.low_identity; break;
+            default: ++st.self; break;
+        }
+    }
+    st.ops = out.ops.size();
+    out.stats = st;
+    c->as.links = std::move(out);
+    made(c, LINKS);
+    if (naligned) *naligned = st.aligned;
+    return 0;
+}
+
+int bella_hip_graph_get_link_alignments(bella_ctx* c, bella_link_aln* alns, uint64_t* nops, uint32_t* ops) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    if (int r = need(c, LINKS)) return r;
+    copy_out(alns, c->as.links.alns);
+    if (nops) *nops = c->as.links.ops.size();
+    copy_out(ops, c->as.links.ops);
+    return 0;
+}
+
+int bella_hip_graph_get_link_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    return get_stats(c, LINKS, out, struct_size, [](const StageState& a) { return a.links.stats; });
 }
 
 // ---- read correction rounds (recorrect.hpp) -------------------------------------------------------------------------
@@ -6016,23 +6273,26 @@ int bella_hip_get_recorrect_anchors(bella_ctx* c, uint64_t* offsets, uint64_t* a
     return 0;
 }
 
-int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,
-                               const uint64_t* pos, const uint32_t* nbases, const uint64_t* len, const uint8_t* circular, const uint64_t* base_offsets,
-                               const uint8_t* bases, uint64_t nlinks, const bella_unitig_link* links) {
-    if (!path || (nreads && !names) || (nunitigs && (!vertex_offsets || !vertices || !pos || !nbases || !len || !circular)) || (bases && !base_offsets) || (nlinks && !links)) {
-        fprintf(stderr, "bella_hip_write_unitig_gfa: null argument\n");
+// both writers of the unitig GFA: `who` is the one that was called; alns == NULL: every L line carries <ovl>M
+static int write_unitig_gfa_impl(const char* who, const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets,
+                                 const uint32_t* vertices, const uint64_t* pos, const uint32_t* nbases, const uint64_t* len, const uint8_t* circular,
+                                 const uint64_t* base_offsets, const uint8_t* bases, uint64_t nlinks, const bella_unitig_link* links, const bella_link_aln* alns,
+                                 const uint32_t* ops) {
+    if (!path || (nreads && !names) || (nunitigs && (!vertex_offsets || !vertices || !pos || !nbases || !len || !circular)) || (bases && !base_offsets) || (nlinks && !links) || (nlinks && alns && !ops)) {
+        fprintf(stderr, "%s: null argument\n", who);
         return BELLA_ERR_BAD_ARG;
     }
     const uint64_t nvert = nunitigs ? vertex_offsets[nunitigs] : 0;
     for (uint64_t i = 0; i < nvert; ++i)
-        if (vertices[i] >= 2 * (uint64_t)nreads || !names[vertices[i] >> 1]) { fprintf(stderr, "bella_hip_write_unitig_gfa: vertex %llu out of range\n", (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
+        if (vertices[i] >= 2 * (uint64_t)nreads || !names[vertices[i] >> 1]) { fprintf(stderr, "%s: vertex %llu out of range\n", who, (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
     for (uint64_t i = 0; i < nlinks; ++i)
-        if (links[i].a >= nunitigs || links[i].b >= nunitigs) { fprintf(stderr, "bella_hip_write_unitig_gfa: link %llu out of range\n", (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
-    TextFile file("bella_hip_write_unitig_gfa", path, "wb");
+        if (links[i].a >= nunitigs || links[i].b >= nunitigs) { fprintf(stderr, "%s: link %llu out of range\n", who, (unsigned long long)i); return BELLA_ERR_BAD_ARG; }
+    TextFile file(who, path, "wb");
     FILE* const f = file.f;
     if (!f) return BELLA_ERR_BAD_ARG;
     bool ok = std::fputs("H\tVN:Z:1.0\n", f) != EOF;
     char name[32], other[32];
+    std::string cigar;
     auto mk = [&](char* dst, uint64_t u) { std::snprintf(dst, 32, "utg%06llu%c", (unsigned long long)(u + 1), circular[u] ? 'c' : 'l'); };
     for (uint64_t u = 0; u < nunitigs && ok; ++u) {
         mk(name, u);
@@ -6046,10 +6306,40 @@ int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* co
     for (uint64_t i = 0; i < nlinks && ok; ++i) {
         const bella_unitig_link& l = links[i];
         mk(name, l.a); mk(other, l.b);
+        if (alns && alns[i].status == BELLA_LINK_ALIGNED) {           // the CIGAR in M / I / D: '=' and 'X' are one M
+            const bella_link_aln& a = alns[i];
+            cigar.clear();
+            uint64_t run = 0;
+            char last = 0;
+            for (uint32_t x = 0; x <= a.nops; ++x) {
+                const uint32_t w = x < a.nops ? ops[a.op_off + x] : 0u;
+                const char ch = x == a.nops ? 0 : (w & 15u) <= kOpX ? 'M' : (w & 15u) == kOpIns ? 'I' : 'D';
+                if (ch != last && run) { cigar += std::to_string(run); cigar += last; run = 0; }
+                last = ch;
+                run += w >> 4;
+            }
+            ok = std::fprintf(f, "L\t%s\t%c\t%s\t%c\t%s\trc:i:%u\tNM:i:%u\tol:i:%u\n", name, (l.flags & BELLA_UNITIG_LINK_A_MINUS) ? '-' : '+', other,
+                              (l.flags & BELLA_UNITIG_LINK_B_MINUS) ? '-' : '+', cigar.c_str(), l.rec, a.n_x + a.n_ins + a.n_del, l.ovl) > 0;
+            continue;
+        }
         ok = std::fprintf(f, "L\t%s\t%c\t%s\t%c\t%uM\trc:i:%u\n", name, (l.flags & BELLA_UNITIG_LINK_A_MINUS) ? '-' : '+', other, (l.flags & BELLA_UNITIG_LINK_B_MINUS) ? '-' : '+', l.ovl,
                          l.rec) > 0;
     }
     return file.close(ok);
+}
+
+int bella_hip_write_unitig_gfa(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,
+                               const uint64_t* pos, const uint32_t* nbases, const uint64_t* len, const uint8_t* circular, const uint64_t* base_offsets,
+                               const uint8_t* bases, uint64_t nlinks, const bella_unitig_link* links) {
+    return write_unitig_gfa_impl("bella_hip_write_unitig_gfa", path, nreads, names, nunitigs, vertex_offsets, vertices, pos, nbases, len, circular, base_offsets, bases, nlinks,
+                                 links, nullptr, nullptr);
+}
+
+int bella_hip_write_unitig_gfa_links(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,
+                                     const uint64_t* pos, const uint32_t* nbases, const uint64_t* len, const uint8_t* circular, const uint64_t* base_offsets,
+                                     const uint8_t* bases, uint64_t nlinks, const bella_unitig_link* links, const bella_link_aln* alns, const uint32_t* ops) {
+    return write_unitig_gfa_impl("bella_hip_write_unitig_gfa_links", path, nreads, names, nunitigs, vertex_offsets, vertices, pos, nbases, len, circular, base_offsets, bases,
+                                 nlinks, links, alns, ops);
 }
 
 int bella_hip_get_read_bases(bella_ctx* c, uint64_t* offsets, uint8_t* bases) {

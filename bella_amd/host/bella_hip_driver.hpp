@@ -127,6 +127,8 @@ struct StageOpts {
     uint32_t polish_rounds = 1;      // consensus rounds: polish_rounds - 1 realignment rounds follow the polish, each aligning the reads
     uint32_t realign_band = 512, realign_min_identity = 700;    // against the round before; the files carry the last round's sequences and coordinates
     bool realign_circular = false;   // those rounds place the reads of circular unitigs on the unrolled circle
+    int align_links = 0;             // link alignment: the ends of the unitigs every link joins are aligned on the device, on the sequences
+    uint32_t link_band = 512, link_min_identity = 700;          // the unitigs file carries; its ALIGNED L lines take a true CIGAR, NM:i: and ol:i:
     int trim = 0;                    // coverage trimming: the reads are clipped to their longest well-covered stretch before the graph
     uint32_t trim_depth = 3, trim_end_clip = 500;     // is built (min_span = gfa_min_overlap); every graph file is in clipped coordinates
     const char* trimmed_reads = nullptr;              // the clipped reads as FASTA, in input order, without the uncovered ones
@@ -334,10 +336,33 @@ inline void write_graph(std::vector<Worker>& W, const StageOpts& o, const char* 
             BELLA_HIP_LOGT(o.tag, Realigned);
         }
     }
+    std::vector<bella_link_aln> lalns;
+    std::vector<uint32_t> lops;
+    if (o.align_links) {                                              // on the newest sequences: the ones the files carry
+        bella_link_params lp{};
+        lp.struct_size = (uint32_t)sizeof(lp);
+        lp.band0 = o.link_band; lp.band_max = o.link_band > BELLA_LINK_DEFAULT_BAND_MAX ? o.link_band : BELLA_LINK_DEFAULT_BAND_MAX;
+        lp.min_identity = o.link_min_identity;
+        check(c0, bella_hip_graph_align_links(c0, &lp, nullptr), "bella_hip_graph_align_links");
+        bella_link_stats ls{};
+        check(c0, bella_hip_graph_get_link_stats(c0, &ls, sizeof(ls)), "bella_hip_graph_get_link_stats");
+        lalns.resize((size_t)nl);
+        lops.resize((size_t)ls.ops + 1);
+        check(c0, bella_hip_graph_get_link_alignments(c0, lalns.data(), nullptr, lops.data()), "bella_hip_graph_get_link_alignments");
+        const std::string AlignedLinks = std::to_string(ls.aligned) + " of " + std::to_string(ls.links) + " links aligned (" + std::to_string(ls.empty) + " empty, " +
+                                         std::to_string(ls.band_capped) + " band-capped, " + std::to_string(ls.low_identity) + " of low identity, " + std::to_string(ls.self) +
+                                         " self), " + std::to_string(ls.derived) + " derived from their twins, " + std::to_string(ls.overlap_before) + " -> " +
+                                         std::to_string(ls.overlap_after) + " overlap bases";
+        BELLA_HIP_LOGT(o.tag, AlignedLinks);
+    }
     if (o.unitigs) {
-        const int wrc = bella_hip_write_unitig_gfa(o.unitigs, o.nreads, names, nu, voff.data(), verts.data(), pos.data(), nb.data(), ulen.data(), circ.data(),
-                                                   o.gfa_no_seq ? nullptr : uboff.data(), o.gfa_no_seq ? nullptr : ubases.data(), nl, links.data());
-        if (wrc) check(nullptr, wrc, "bella_hip_write_unitig_gfa");
+        const uint64_t* const so = o.gfa_no_seq ? nullptr : uboff.data();
+        const uint8_t* const sb = o.gfa_no_seq ? nullptr : ubases.data();
+        const int wrc = o.align_links ? bella_hip_write_unitig_gfa_links(o.unitigs, o.nreads, names, nu, voff.data(), verts.data(), pos.data(), nb.data(), ulen.data(), circ.data(), so,
+                                                                         sb, nl, links.data(), lalns.data(), lops.data())
+                                      : bella_hip_write_unitig_gfa(o.unitigs, o.nreads, names, nu, voff.data(), verts.data(), pos.data(), nb.data(), ulen.data(), circ.data(), so, sb,
+                                                                   nl, links.data());
+        if (wrc) check(nullptr, wrc, o.align_links ? "bella_hip_write_unitig_gfa_links" : "bella_hip_write_unitig_gfa");
     }
     if (o.unitigs_fasta) {
         std::vector<std::string> unames((size_t)nu);

@@ -28,6 +28,8 @@
 // the pileup on the device after the last stage; --unitigs / --unitigs-fasta then carry the polished sequences and coordinates.
 // --polish-rounds N: N - 1 realignment rounds follow, each aligning the reads against the unitigs of the round before.
 // --realign-circular: those rounds place the reads of a circular unitig on the unrolled circle, across its origin too.
+// --align-links: the ends of the two unitigs of every link are aligned against each other on the device, on the
+// sequences the --unitigs file carries; an aligned link's L line takes the CIGAR of that alignment, NM:i: and ol:i: (the raw overlap).
 //
 // --trim: coverage trimming: after the last stage every read is clipped, on the device, to its longest stretch that
 // --trim-depth overlap records cover; the graph is built from the records cut to the clips, and --gfa / --unitigs / --unitigs-fasta are in
@@ -69,6 +71,8 @@ struct Options {
     bool polish = false, polish_param_given = false;
     int polish_rounds = 1, realign_band = 512, realign_min_identity = 700;
     bool realign_param_given = false, realign_circular = false;
+    int link_band = 512, link_min_identity = 700;
+    bool align_links = false, link_param_given = false;
     int trim_depth = 3, trim_end_clip = 500;
     std::string trimmed_reads;
     bool trim = false, trim_param_given = false;
@@ -143,6 +147,10 @@ const char* kHelp =
     "      --realign-band arg     with --polish: the first band of those alignments, a power of two from 256 to 4096 (default: 512)\n"
     "      --realign-min-identity arg  with --polish: permille of matches below which a read's alignment does not vote (default: 700)\n"
     "      --realign-circular     with --polish: those alignments treat a circular unitig as a circle, so the reads across its origin vote too\n"
+    "      --align-links          with --unitigs: align the ends of the two unitigs of every link against each other, on the device; an aligned link's L line\n"
+    "                             carries the CIGAR of that alignment (M / I / D, `from` is the reference), NM:i: and ol:i:, the overlap the graph had\n"
+    "      --link-band arg        with --align-links: the first band of those alignments, a power of two from 256 to 4096 (default: 512)\n"
+    "      --link-min-identity arg  with --align-links: permille of matches below which a link keeps its <ovl>M line (default: 700)\n"
     "      --trim                 with --gfa / --unitigs / --unitigs-fasta: clip every read to its longest stretch that --trim-depth overlaps cover, on the\n"
     "                             device, before the graph is built (shortest stretch: --gfa-min-overlap); the graph files are in clipped coordinates\n"
     "      --trim-depth arg       with --trim: overlaps a position needs to count as covered (default: 3)\n"
@@ -176,6 +184,7 @@ Options parse(int argc, char** argv) {
         {"polish", 0, 0, &o.polish}, {"polish-min-depth", 0, 1, &o.polish_min_depth},
         {"polish-rounds", 0, 1, &o.polish_rounds}, {"realign-band", 0, 1, &o.realign_band}, {"realign-min-identity", 0, 1, &o.realign_min_identity},
         {"realign-circular", 0, 0, &o.realign_circular},
+        {"align-links", 0, 0, &o.align_links}, {"link-band", 0, 1, &o.link_band}, {"link-min-identity", 0, 1, &o.link_min_identity},
         {"trim", 0, 0, &o.trim}, {"trim-depth", 0, 1, &o.trim_depth}, {"trim-end-clip", 0, 1, &o.trim_end_clip}, {"trimmed-reads", 0, 3, &o.trimmed_reads},
         {"help", 'h', 0, &o.help}};
     auto assign = [&](const Spec& s, const char* v, const std::string& shown) {
@@ -220,6 +229,7 @@ Options parse(int argc, char** argv) {
         if (sp->dst == &o.weak_min || sp->dst == &o.weak_max || sp->dst == &o.weak_steps) o.weak_param_given = true;
         if (sp->dst == &o.polish_min_depth) o.polish_param_given = true;
         if (sp->dst == &o.polish_rounds || sp->dst == &o.realign_band || sp->dst == &o.realign_min_identity) o.realign_param_given = true;
+        if (sp->dst == &o.link_band || sp->dst == &o.link_min_identity) o.link_param_given = true;
         if (sp->dst == &o.trim_depth || sp->dst == &o.trim_end_clip || sp->dst == &o.trimmed_reads) o.trim_param_given = true;
         if (sp->dst == &o.clip_identity) o.clip_param_given = true;
     }
@@ -299,6 +309,10 @@ int main(int argc, char** argv) {
     if (o.polish_rounds < 1 || o.polish_rounds > 4) die("--polish-rounds must be in [1, 4]");
     if (o.realign_band < 256 || o.realign_band > 4096 || (o.realign_band & (o.realign_band - 1))) die("--realign-band must be a power of two in [256, 4096]");
     if (o.realign_min_identity < 0 || o.realign_min_identity > 1000) die("--realign-min-identity is in permille: [0, 1000]");
+    if (o.align_links && o.unitigs.empty()) die("--align-links needs --unitigs (the alignments go into the L lines of that file)");
+    if (o.link_param_given && !o.align_links) die("--link-band and --link-min-identity need --align-links");
+    if (o.link_band < 256 || o.link_band > 4096 || (o.link_band & (o.link_band - 1))) die("--link-band must be a power of two in [256, 4096]");
+    if (o.link_min_identity < 0 || o.link_min_identity > 1000) die("--link-min-identity is in permille: [0, 1000]");
     if (o.trim_param_given && !o.trim) die("--trim-depth, --trim-end-clip and --trimmed-reads need --trim");
     if (o.trim && !o.graph()) die("--trim needs --gfa, --unitigs or --unitigs-fasta");
     if (o.trim && (o.trim_depth < 1 || o.trim_end_clip < 0)) die("--trim-depth must be at least 1 and --trim-end-clip must not be negative");
@@ -467,6 +481,7 @@ int main(int argc, char** argv) {
     so.polish = o.polish ? 1 : 0;
     so.polish_min_depth = (uint32_t)o.polish_min_depth;
     so.polish_rounds = (uint32_t)o.polish_rounds; so.realign_band = (uint32_t)o.realign_band; so.realign_min_identity = (uint32_t)o.realign_min_identity; so.realign_circular = o.realign_circular;
+    so.align_links = o.align_links ? 1 : 0; so.link_band = (uint32_t)o.link_band; so.link_min_identity = (uint32_t)o.link_min_identity;
     so.correct_rounds = (uint32_t)o.correct_rounds; so.correct_band = (uint32_t)o.correct_band; so.correct_min_identity = (uint32_t)o.correct_min_identity;
     so.normalize_gaps = o.normalize_gaps ? 1 : 0;
     so.clip_ends = o.clip_ends ? 1 : 0; so.clip_identity = (uint32_t)o.clip_identity;

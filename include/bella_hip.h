@@ -766,7 +766,7 @@ int bella_hip_graph_get_weak_stats(bella_ctx* ctx, void* out, uint64_t struct_si
  * own positions and nothing else (the junction in front of the first position behind a forward segment is not part of it: an edge effect
  * of at most one base per segment).  With an all-zero table the result is the raw unitigs.  Limits as in the read correction: one
  * inserted base per junction, plain majority; the segment boundaries stay where the raw unitig has them; the links keep their raw
- * overlaps; a second round, with the reads re-aligned to the unitig, is the realignment section below. */
+ * overlaps (the link alignment section below aligns them); a second round, with the reads re-aligned to the unitig, is the realignment section below. */
 typedef struct {
     uint32_t struct_size;         /* sizeof(bella_polish_params) of the caller's header (the struct may grow)               */
     uint32_t min_depth;           /* >= 1; the documented default is 3                                                     */
@@ -803,7 +803,7 @@ int bella_hip_graph_get_polish_stats(bella_ctx* ctx, void* out, uint64_t struct_
  * global, unitig window free; the trace's scoring and direction choice), the band rule and the votes in full; the tests hold a numpy
  * statement of it, and the device result equals it.  Limits: one inserted base per junction, plain majority, a fixed
  * centre diagonal per read, reads across the origin of a circular unitig are skipped (bella_hip_graph_realign_unitigs_circular below
- * does not skip them), removed reads do not vote, the links keep their raw overlaps, a unitig has fewer than 2^31 - band_max bases.
+ * does not skip them), removed reads do not vote, the links keep their raw overlaps (the link alignment section below aligns them), a unitig has fewer than 2^31 - band_max bases.
  *
  * Circles (opt-in: bella_hip_graph_realign_unitigs_circular).  Notation of section 18; u a circular unitig, len its
  * raw and plen its current length, x the raw coordinate where the read's clip starts, n the clip's length.  A read on u is placed on the
@@ -881,6 +881,88 @@ int bella_hip_graph_get_realign_placements(bella_ctx* ctx, bella_realign_placeme
  * round aligned against).  Both are empty unless the round ran with keep_ops. */
 int bella_hip_graph_get_realign_ops(bella_ctx* ctx, uint64_t* nops, uint32_t* ops, uint32_t* table);
 int bella_hip_graph_get_realign_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+
+/* ---- link alignment: the ends of two linked unitigs aligned against each other (no counterpart in the reference) --
+ * Link k = (a, b, ovl, rec, flags) of bella_hip_graph_unitigs claims that a suffix of A^ overlaps a prefix of B^.  cur(u) is the newest
+ * sequence of unitig u (the last realignment round's, else the polish's, else the raw bases), P_u its length, len_u the raw length,
+ * C_u the raw -> current map of the realignment section (the identity when nothing was polished); A^ = cur(a), or its reverse
+ * complement when A_MINUS is set, B^ likewise from b and B_MINUS.
+ *   Expected overlaps.  o_a = min(ovl, len_a), o_b = min(ovl, len_b); oa = P_a - C_a(len_a - o_a) when A is plus, C_a(o_a) when minus;
+ * ob = C_b(o_b) when B is plus, P_b - C_b(len_b - o_b) when minus.
+ *   Windows.  S = band_max / 2.  Columns: X, the last m = min(P_a, oa + S) bases of A^.  Rows: Y, the first n = min(P_b, ob + S) bases
+ * of B^.  Centre diagonal c = m - (oa + ob) / 2 (floor).
+ *   DP.  The realignment section's cell rule, scoring (+1 / -1 / -1), recurrence and direction preference; cell (i, q) exists iff
+ * -B/2 <= q - i - c < B/2 and 0 <= q <= m; row 0 is 0.  The end is the best existing cell of COLUMN m over the rows 0 .. n, ties to the
+ * smallest row: B^ starts at its first base, A^ ends at its last.  The walk goes from (i_end, m) back to row 0 and gives q_begin; it has
+ * TOUCHED as in the realignment section, and a column m without a reachable cell counts as touched.  B starts at band0 and doubles
+ * while the path touches, up to band_max.
+ *   Status, tested in this order: a == b: SELF (never aligned: a sequence's tail against its own head has a trivial full-length answer);
+ * touched at band_max: BAND_CAPPED; best score <= 0: EMPTY; 1000 n_eq < min_identity (n_eq + n_x + n_ins + n_del): LOW_IDENTITY; else
+ * ALIGNED.  ovl_a = m - q_begin, ovl_b = i_end; 'I' is a base of B^ only, 'D' a base of A^ only (`from` is the reference); the runs are in
+ * the order of B^, op | len << 4 with op 0 '=', 1 'X', 2 'I', 3 'D', and only ALIGNED links have runs.  A link whose column m no path
+ * reached has all-zero results.
+ *   Twins.  The twin of (a, sa, b, sb) is (b, !sb, a, !sa) with the same rec.  Links are paired in index order: link k, not SELF and not
+ * yet paired, takes the smallest later unpaired link that is its twin.  Only the lower-indexed link of a pair is aligned; the other is
+ * DERIVED: its runs are the mate's reversed with 'I' and 'D' swapped, ovl_a and ovl_b swapped, n_ins and n_del swapped, status, band,
+ * score, n_eq and n_x the mate's, and mate = the other link's index on both (~0 on a link without a twin).  The DP's tie-breaks are not
+ * reversal-symmetric, so deriving is what keeps the two L lines consistent.
+ *   Limits: SELF links and links of more than one alignment segment are not aligned; band_max is at most 4096. */
+#define BELLA_LINK_DEFAULT_BAND 512
+#define BELLA_LINK_DEFAULT_BAND_MAX 4096
+#define BELLA_LINK_DEFAULT_MIN_IDENTITY 700
+enum {
+    BELLA_LINK_ALIGNED = 0,
+    BELLA_LINK_EMPTY = 1,            /* the best score is not positive                                                        */
+    BELLA_LINK_BAND_CAPPED = 2,      /* the path still touched the band's edge at band_max                                    */
+    BELLA_LINK_LOW_IDENTITY = 3,
+    BELLA_LINK_SELF = 4              /* a == b                                                                                */
+};
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_link_params) of the caller's header (the struct may grow)                 */
+    uint32_t band0;               /* a power of two in [256, band_max]; the documented default is 512                      */
+    uint32_t band_max;            /* a power of two <= 4096; 4096                                                          */
+    uint32_t min_identity;        /* permille of '=' among the alignment's columns below which a link is LOW_IDENTITY; 700 */
+} bella_link_params;
+typedef struct {
+    uint32_t status;              /* BELLA_LINK_*                                                                          */
+    uint32_t band;                /* the last band the link was aligned with (0: SELF)                                     */
+    int32_t score;
+    uint32_t ovl_a, ovl_b;        /* bases of A^'s suffix and of B^'s prefix that the alignment spans                      */
+    uint32_t n_eq, n_x, n_ins, n_del;
+    uint32_t mate;                /* the twin's index; ~0: none                                                            */
+    uint64_t op_off;              /* first run among all runs                                                              */
+    uint32_t nops;                /* ALIGNED only                                                                          */
+    uint32_t derived;             /* 1: taken from the mate's alignment                                                    */
+} bella_link_aln;
+/* What the last bella_hip_graph_align_links did.  A sized struct: bella_hip_graph_get_link_stats writes at most struct_size bytes. */
+typedef struct {
+    uint64_t links;
+    uint64_t aligned, empty, band_capped, low_identity, self;     /* links by status, the derived ones included               */
+    uint64_t derived;
+    uint64_t overlap_before, overlap_after;   /* over the ALIGNED links: the expected overlaps oa, and ovl_a                   */
+    uint64_t jobs;                /* links that were aligned                                                               */
+    uint64_t dp_cells;            /* rows x band summed over every DP that ran                                             */
+    uint64_t ops;                 /* runs of all links                                                                     */
+    uint32_t batches, pad;
+    double pack_ms, dp_ms, walk_ms;           /* device time between events                                                    */
+} bella_link_stats;
+/* Aligns the links of the last bella_hip_graph_unitigs on the device.  params == NULL: the defaults; naligned (nullable): the ALIGNED
+ * links.  BELLA_ERR_STATE without unitigs; BELLA_ERR_BAD_ARG for a band that is no power of two or outside [256, 4096], band0 > band_max,
+ * min_identity > 1000, a struct_size too small.  The result stays with the context until the unitigs are dropped, or the sequence it was
+ * made from is replaced: a polish, a realignment round.  Zero links, or SELF links only, launch nothing. */
+int bella_hip_graph_align_links(bella_ctx* ctx, const bella_link_params* params, uint64_t* naligned);
+/* alns[nlinks] in the order of the links; *nops = the runs of all links; ops[*nops].  Any pointer may be NULL.  BELLA_ERR_STATE without
+ * an alignment of the links. */
+int bella_hip_graph_get_link_alignments(bella_ctx* ctx, bella_link_aln* alns, uint64_t* nops, uint32_t* ops);
+int bella_hip_graph_get_link_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+/* bella_hip_write_unitig_gfa with the links' alignments: an ALIGNED link's line is
+ * "L\tutgA\t+/-\tutgB\t+/-\t<CIGAR>\trc:i:<rec>\tNM:i:<n_x + n_ins + n_del>\tol:i:<ovl>", the CIGAR in M / I / D with '=' and 'X' merged into
+ * M; every other link's line is bella_hip_write_unitig_gfa's.  alns[nlinks] and ops as bella_hip_graph_get_link_alignments returned them;
+ * alns == NULL writes what bella_hip_write_unitig_gfa writes.  The sequences passed should be the ones the links were aligned on.  Plain
+ * host code, no context. */
+int bella_hip_write_unitig_gfa_links(const char* path, uint32_t nreads, const char* const* names, uint64_t nunitigs, const uint64_t* vertex_offsets, const uint32_t* vertices,
+                                     const uint64_t* pos, const uint32_t* nbases, const uint64_t* len, const uint8_t* circular, const uint64_t* base_offsets,
+                                     const uint8_t* bases, uint64_t nlinks, const bella_unitig_link* links, const bella_link_aln* alns, const uint32_t* ops);
 
 /* ---- read correction rounds: the partners' raw clips aligned against the corrected read, one more consensus (no
  * counterpart in the reference) ------------------------------------------------------------------------------------------------------

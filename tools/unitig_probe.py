@@ -13,7 +13,10 @@ launch each), the table bytes the decision read over its time, and the unitigs' 
 600 and 700 permille, tips and bubbles again after a cut that took an edge), unitigs -- and per set the edges cut, forks and weak edges per
 step, cut_ms per step next to clean_ms and pop_ms of the same run, and unitigs, largest and N50 with the schedule next to those without.
 --polish-rounds N: N - 1 realignment rounds after the polish, and per round the reads by status, place_ms, dp_ms,
-walk_ms, vote_ms and decide_ms next to the first trace's dp_ms of the same set, the DP cells, the batches and the length after the round."""
+walk_ms, vote_ms and decide_ms next to the first trace's dp_ms of the same set, the DP cells, the batches and the length after the round.
+--align-links: the links aligned on the newest sequences, written to profiles/links_probe.json: the links by status,
+the distribution of ovl_a - oa (found against expected overlap, in current coordinates) and of the identity over the ALIGNED links,
+pack_ms, dp_ms, walk_ms and the DP's cell updates per second next to the last realignment round's k_rea_dp of the same run."""
 import argparse
 import json
 import os
@@ -21,9 +24,10 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
 import torch  # noqa: F401,E402  (first: one HIP runtime per process)
 from bella_amd import BellaPars, Engine  # noqa: E402
-from bella_testkit import synth  # noqa: E402
+from bella_testkit import links_mirror, synth  # noqa: E402
 
 
 WEAK_RATIOS = (500, 600, 700)                                         # bella-hip --cut-weak's defaults: --weak-min 500 --weak-max 700 --weak-steps 2
@@ -63,7 +67,32 @@ def realign_rounds(eng, rounds):
     return out
 
 
-def probe(nreads, seed, repeats, fast, cut_weak=False, polish_rounds=1):
+def dist(values):
+    """min, 10 %, median, 90 %, max and mean of a list of numbers (None when it is empty)"""
+    if not len(values):
+        return None
+    v = np.sort(np.asarray(values, np.float64))
+    q = lambda f: float(v[min(len(v) - 1, int(f * len(v)))])
+    return dict(n=len(v), min=float(v[0]), p10=q(0.1), median=q(0.5), p90=q(0.9), max=float(v[-1]), mean=float(v.mean()))
+
+
+def align_links(eng, u, cur, rea):
+    """the links aligned on the sequences the context holds (cur: what the polish or the last round returned; None: raw) -> dict"""
+    eng.graph_align_links()
+    st = eng.link_stats()
+    alns, _ = eng.link_alignments()
+    al = np.flatnonzero(alns["status"] == links_mirror.ALIGNED)
+    shift = [int(alns[k]["ovl_a"]) - links_mirror.expected(u, cur, int(k))[0] for k in al]
+    cols = (alns["n_eq"] + alns["n_x"] + alns["n_ins"] + alns["n_del"]).astype(np.int64)
+    out = {k: (float(v) if k.endswith("_ms") else int(v)) for k, v in st.items() if k != "pad"}
+    out.update(found_minus_expected=dist(shift), identity_permille=dist((1000 * alns["n_eq"][al].astype(np.int64) // np.maximum(cols[al], 1)).tolist()),
+               cells_per_s=st["dp_cells"] / max(1e-9, st["dp_ms"] * 1e-3))
+    if rea:
+        out.update(realign_dp_ms=rea[-1]["dp_ms"], realign_dp_cells=rea[-1]["dp_cells"], realign_cells_per_s=rea[-1]["dp_cells"] / max(1e-9, rea[-1]["dp_ms"] * 1e-3))
+    return out
+
+
+def probe(nreads, seed, repeats, fast, cut_weak=False, polish_rounds=1, links=False):
     rs = (synth.make_reads_fast if fast else synth.make_reads)(nreads, read_len=10000, err=0.15, seed=seed)
     meta = [[int(x) for x in n.split("_")[1:]] for n in rs.names]     # (start, length, strand)
     span = max(m[0] + m[1] for m in meta) - min(m[0] for m in meta)
@@ -91,11 +120,12 @@ def probe(nreads, seed, repeats, fast, cut_weak=False, polish_rounds=1):
         eng.graph_clean()
         eng.graph_pop_bubbles()
         bs = eng.bubble_stats()
-        eng.graph_unitigs()
-        eng.graph_polish_unitigs()
+        u = eng.graph_unitigs()
+        cur = eng.graph_polish_unitigs()
         pst = eng.polish_stats()
         rea = realign_rounds(eng, polish_rounds)
-        runs.append((gs, us, bs, eng.unitig_stats(), pst, weak_pass(eng) if cut_weak else None, rea))
+        lnk = align_links(eng, u, eng.realigned() if rea else cur, rea) if links else None
+        runs.append((gs, us, bs, eng.unitig_stats(), pst, weak_pass(eng) if cut_weak else None, rea, lnk))
     gs, us = min(runs, key=lambda r: r[1]["rank_ms"] + r[1]["gather_ms"])[:2]
     bs, ps = min(runs, key=lambda r: r[2]["pop_ms"])[2:4]
     pol = min((r[4] for r in runs), key=lambda q: q["decide_ms"] + q["write_ms"])
@@ -122,6 +152,8 @@ def probe(nreads, seed, repeats, fast, cut_weak=False, polish_rounds=1):
         out["weak"] = dict(min((r[5] for r in runs), key=lambda w: w["cut_ms"]), unitigs_without=int(ps["unitigs"]), largest_without=int(ps["largest"]), n50_without=int(ps["n50"]))
     if polish_rounds > 1:                                             # (the run whose first round's DP was the fastest)
         out["realign"] = dict(rounds=min((r[6] for r in runs), key=lambda q: q[0]["dp_ms"]), trace_dp_ms=trace_dp_ms, genome_span=int(span))
+    if links:                                                         # (the run whose link DP was the fastest)
+        out["links"] = min((r[7] for r in runs), key=lambda q: q["dp_ms"])
     eng.close()
     return out
 
@@ -133,12 +165,14 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "unitig_probe.json"))
     ap.add_argument("--cut-weak", action="store_true", help="also run the weak-overlap schedule after the clean and the pop (DESIGN.md section 17)")
     ap.add_argument("--polish-rounds", type=int, default=1, help="consensus rounds: N - 1 realignment rounds after the polish (DESIGN.md section 18)")
+    ap.add_argument("--align-links", action="store_true", help="align the links on the newest sequences (DESIGN.md section 26); the result goes to --links-out")
+    ap.add_argument("--links-out", default=os.path.join(ROOT, "profiles", "links_probe.json"))
     a = ap.parse_args()
     res = []
     for s in a.sets:
         n, seed, gen = s.split(":")
-        res.append(probe(int(n), int(seed), a.repeats, gen == "fast", a.cut_weak, a.polish_rounds))
+        res.append(probe(int(n), int(seed), a.repeats, gen == "fast", a.cut_weak, a.polish_rounds, a.align_links))
         print(json.dumps(res[-1]), flush=True)
-    with open(a.out, "w") as f:
+    with open(a.links_out if a.align_links else a.out, "w") as f:
         json.dump(dict(sets=res), f, indent=1)
         f.write("\n")

@@ -3864,6 +3864,13 @@ int read_vote_counts(bella_ctx* c, bella_vote_stats& vs) {
     return 0;
 }
 
+// The band -> kernel mapping of the banded sweeps (band.hpp), once: f(C, cls) with C = 4, 8, 16 for the register kernels of 256, 512 and
+// 1,024 cells, C = 0 for the wide kernel above them; cls = 0 .. 3 numbers the classes.
+template <int C> using BandC = std::integral_constant<int, C>;
+template <class F> void for_band(uint32_t B, F&& f) {
+    B == 256 ? f(BandC<4>{}, 0u) : B == 512 ? f(BandC<8>{}, 1u) : B == 1024 ? f(BandC<16>{}, 2u) : f(BandC<0>{}, 3u);
+}
+
 // Traces jobs[0 .. n): out[n] records, ops appended to `ops` (op_off counts from the vector's start).  Pairs run in batches sized by
 // the free device memory (the direction bytes dominate); a pair whose path touched its band's edge on a side goes back into the queue
 // with that side's band doubled, until no side touches or the band holds the side's whole rectangle.
@@ -3969,8 +3976,7 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
                     TraceExt e{};
                     e.gH = s.gH; e.gV = s.gV; e.dir_off = dbytes; e.scr_off = sints; e.n = s.n; e.m = s.m; e.band = s.band; e.dH = s.dH; e.dV = s.dV;
                     e.comp = w.comp;
-                    const uint32_t cls = s.band == 256 ? 0u : s.band == 512 ? 1u : s.band == 1024 ? 2u : 3u;
-                    lists[cls].push_back((uint32_t)exts.size());
+                    for_band(s.band, [&](auto, uint32_t cls) { lists[cls].push_back((uint32_t)exts.size()); });
                     exts.push_back(e);
                     dbytes += side_dir_bytes(s);
                     sints += side_scr_ints(s);
@@ -4007,10 +4013,14 @@ int run_trace(bella_ctx* c, const bella_params* p, const std::vector<TraceJob>& 
             TraceExtRes* const dres = ptr<TraceExtRes>(c->tr_res);
             HIPCHK(c, hipEventRecord(ev.a, c->stream));
             const uint32_t wpb = kTraceBlock / 64;
-            if (lo[1] > lo[0]) { k_trace_dp<4><<<nblk(lo[1] - lo[0], wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[0], lo[1] - lo[0], packed, ddirs, dres); KCHK(c); }
-            if (lo[2] > lo[1]) { k_trace_dp<8><<<nblk(lo[2] - lo[1], wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[1], lo[2] - lo[1], packed, ddirs, dres); KCHK(c); }
-            if (lo[3] > lo[2]) { k_trace_dp<16><<<nblk(lo[3] - lo[2], wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[2], lo[3] - lo[2], packed, ddirs, dres); KCHK(c); }
-            if (lo[4] > lo[3]) { k_trace_dp_wide<<<lo[4] - lo[3], 64, 0, c->stream>>>(dex, dl + lo[3], lo[4] - lo[3], packed, ddirs, ptr<int>(c->tr_scr), dres); KCHK(c); }
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t nl = lo[q + 1] - lo[q];
+                if (nl) for_band(exts[lists[q][0]].band, [&](auto C, uint32_t) {
+                    if constexpr (decltype(C)::value != 0) k_trace_dp<decltype(C)::value><<<nblk(nl, wpb), kTraceBlock, 0, c->stream>>>(dex, dl + lo[q], nl, packed, ddirs, dres);
+                    else k_trace_dp_wide<<<nl, 64, 0, c->stream>>>(dex, dl + lo[q], nl, packed, ddirs, ptr<int>(c->tr_scr), dres);
+                });
+                KCHK(c);
+            }
             HIPCHK(c, hipEventRecord(ev.b, c->stream));
             k_trace_count<<<nblk(nb, 64), 64, 0, c->stream>>>(dex, dres, nb, packed, ddirs, (int)k, ptr<TracePairRes>(c->tr_pres));
             KCHK(c);
@@ -4380,8 +4390,11 @@ uint32_t round_max_jobs(uint32_t B, uint64_t budget) {
 }
 
 // A round's batches on the device.  The round cuts a batch -- `nj` jobs of band `B` in `jobs`, `dbytes` direction bytes -- and owns what
-// happens between the two steps: the read-backs, what becomes of every job, the jobs' op_off.
+// happens between the two steps: the read-backs, what becomes of every job, the jobs' op_off.  Family: ReaFamily (realign.hpp) or
+// LnkFamily (links.hpp) -- what the DP leaves per job, the DP kernels, whether the runs vote.
+template <class Family>
 struct RoundBatches {
+    using Res = typename Family::Res;
     bella_ctx* c;
     const char *who, *unit;                                           // for the messages: "realign" and its "reads", "recorrect" and its "jobs"
     EventSet& ev;
@@ -4392,34 +4405,22 @@ struct RoundBatches {
     std::vector<uint32_t>& kept;                                      // ... where the ops of every batch are appended
     double &dp_ms, &walk_ms, &vote_ms;
     TmpBuf jobs, res, cnt, dirs, scr, ops;
-    bool links = false;                                               // the batch's jobs are links (links.hpp; section 26): their DP and walks, and no votes
 
     // DP and the counting walk.  The caller launches what is its own behind them, records ev.d, reads back, waits, and calls counted().
     int dp_count(uint32_t nj, uint32_t B, uint64_t dbytes) {
-        ENSURE(c, res, sizeof(ReaRes) * (size_t)nj); ENSURE(c, cnt, sizeof(ReaCnt) * (size_t)nj);
+        ENSURE(c, res, sizeof(Res) * (size_t)nj); ENSURE(c, cnt, sizeof(ReaCnt) * (size_t)nj);
         if (ensure_bytes(c, dirs, (size_t)dbytes))
             return fail(c, BELLA_ERR_NOMEM, "%s: %llu direction bytes for a batch of %u %s do not fit", who, (unsigned long long)dbytes, nj, unit);
         if (B > kTrRegBand) ENSURE(c, scr, 8 * (size_t)nj * B);
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
-        const unsigned grid = nblk((uint64_t)nj * 64, kTraceBlock);
-        if (links) {
-            if (B == 256) k_lnk_dp<4><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<LnkRes>(res));
-            else if (B == 512) k_lnk_dp<8><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<LnkRes>(res));
-            else if (B == 1024) k_lnk_dp<16><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<LnkRes>(res));
-            else k_lnk_dp_wide<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<LnkRes>(res));
-            KCHK(c);
-            HIPCHK(c, hipEventRecord(ev.b, c->stream));
-            k_lnk_count<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<LnkRes>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
-            KCHK(c);
-            return 0;
-        }
-        if (B == 256) k_rea_dp<4><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
-        else if (B == 512) k_rea_dp<8><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
-        else if (B == 1024) k_rea_dp<16><<<grid, kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaRes>(res));
-        else k_rea_dp_wide<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<ReaRes>(res));
+        for_band(B, [&](auto C, uint32_t) {
+            if constexpr (decltype(C)::value != 0)
+                Family::template dp<decltype(C)::value>()<<<nblk((uint64_t)nj * 64, kTraceBlock), kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<Res>(res));
+            else Family::dp_wide()<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<Res>(res));
+        });
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.b, c->stream));
-        k_rea_count<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
+        k_rea_count<Res><<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<Res>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
         KCHK(c);
         return 0;
     }
@@ -4429,11 +4430,10 @@ struct RoundBatches {
     int write_vote(uint32_t nj, uint64_t nops) {
         ENSURE(c, ops, 4 * (size_t)nops);
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
-        if (links) k_lnk_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<LnkRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
-        else k_rea_write<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaRes>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
+        k_rea_write<Res><<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<Res>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.b, c->stream));
-        if (!links) {
+        if constexpr (Family::votes) {
             k_rea_vote<<<nblk((uint64_t)nj * 64, kPileBlock), kPileBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<ReaCnt>(cnt), nj, ptr<uint32_t>(ops), rpacked, table, votes);
             KCHK(c);
         }
@@ -5658,7 +5658,7 @@ static int realign_round(bella_ctx* c, const bella_realign_params* params, uint6
         // ---- DP, walks and votes: band by band, batch by batch
         uint64_t budget = 0;
         if ((rc = round_budget(c, &budget))) return rc;
-        RoundBatches rb{c, "realign", "reads", ev, rpacked, upacked, ptr<uint32_t>(table), ptr<unsigned long long>(votes), rp.keep_ops != 0, out.ops, st.dp_ms, st.walk_ms, st.vote_ms};
+        RoundBatches<ReaFamily> rb{c, "realign", "reads", ev, rpacked, upacked, ptr<uint32_t>(table), ptr<unsigned long long>(votes), rp.keep_ops != 0, out.ops, st.dp_ms, st.walk_ms, st.vote_ms};
         std::vector<ReaJob> hj;
         std::vector<ReaRes> hres;
         std::vector<ReaCnt> hcnt;
@@ -5936,8 +5936,7 @@ int bella_hip_graph_align_links(bella_ctx* c, const bella_link_params* params, u
         uint64_t budget = 0;
         if ((rc = round_budget(c, &budget))) return rc;
         double no_votes = 0;
-        RoundBatches rb{c, "align_links", "links", ev, ptr<uint32_t>(pack), ptr<uint32_t>(pack), nullptr, nullptr, true, out.ops, st.dp_ms, st.walk_ms, no_votes};
-        rb.links = true;
+        RoundBatches<LnkFamily> rb{c, "align_links", "links", ev, ptr<uint32_t>(pack), ptr<uint32_t>(pack), nullptr, nullptr, true, out.ops, st.dp_ms, st.walk_ms, no_votes};
         std::vector<ReaJob> hj;
         std::vector<LnkRes> hres;
         std::vector<ReaCnt> hcnt;
@@ -6143,7 +6142,7 @@ int bella_hip_recorrect(bella_ctx* c, const bella_recorrect_params* params, uint
         // ---- DP, walks and votes: band by band, batch by batch
         uint64_t budget = 0;
         if ((rc = round_budget(c, &budget))) return rc;
-        RoundBatches rb{c, "recorrect", "jobs", ev, rpacked, upacked, ptr<uint32_t>(table), ptr<unsigned long long>(votes), rp.keep_ops != 0, out.ops, st.dp_ms, st.walk_ms, st.vote_ms};
+        RoundBatches<ReaFamily> rb{c, "recorrect", "jobs", ev, rpacked, upacked, ptr<uint32_t>(table), ptr<unsigned long long>(votes), rp.keep_ops != 0, out.ops, st.dp_ms, st.walk_ms, st.vote_ms};
         TmpBuf vnops, opscan;
         for (uint32_t B = rp.band0; np; B *= 2) {
             k_rec_bytes<<<nblk((uint64_t)np + 1), 256, 0, c->stream>>>(ptr<uint32_t>(pend), np, ptr<ReaJob>(jbase), B, ptr<uint64_t>(bytes));

@@ -9,12 +9,11 @@
 // span << 32 | ~index, so the choice does not depend on the order the threads run in; k_rea_place (one thread per read) turns vertex or
 // record into the unitig, the orientation and the window [s, e) on the current sequence.
 //
-// DP.  trace.hpp's row sweep, called as it stands: one wavefront per read, the band of B = 64 C diagonals across the lanes, scores in
-// VGPRs, one prefix maximum per row.  What differs from k_trace_dp: row 0 is 0 in every cell of the band (the start is free along the
-// unitig), the band's diagonals are q - i - c for the read's centre diagonal c (the column origin moves, the row code does not know), the
-// rows are the read's clip in its orientation on the unitig (reversed and complemented for orientation 1) and the columns the 2-bit
-// pack of the unitig's bases, and the end is the best cell of row n alone: the running best is cleared before the last row, so the tie
-// rule of trace_best_take (smallest i + j) is the smallest q.  Per row that is one scalar compare more than k_trace_dp.
+// DP.  band.hpp's sweep with ReaProblem and ReaEnd: row 0 is 0 in every cell of the band (the start is free
+// along the unitig), the band's diagonals are q - i - c for the read's centre diagonal c, the rows are the read's clip in its orientation
+// on the unitig (reversed and complemented for orientation 1) and the columns the 2-bit pack of the unitig's bases, and the end is the
+// best cell of row n alone: the running best is cleared before the last row, so the tie rule of trace_best_take (smallest i + j) is
+// the smallest q.  Per row that is one scalar compare more than k_trace_dp.
 // The kernel is bound by VALU issue, as k_trace_dp is: ~30 C instructions per row against one C-byte store per lane.
 //
 // Walks.  One thread per read from (n, q_end) up to row 0: a counting walk (runs, op totals, whether the path touched the band's first
@@ -162,15 +161,14 @@ __global__ void k_rea_place(uint32_t nreads, const uint64_t* roff, const uint64_
     out[r] = P;
 }
 
+BELLA_HD uint32_t base_code(uint8_t ch) { return ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 0u; }      // ASCII -> the 2-bit code (anything else: A)
+
 // 16 ASCII bases -> one word of the 2-bit pack
 __global__ void k_rea_pack(const uint8_t* ascii, uint64_t total, uint32_t* packed) {
     const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w * 16 >= total) return;
     uint32_t v = 0;
-    for (uint32_t k = 0; k < 16 && w * 16 + k < total; ++k) {
-        const uint8_t ch = ascii[w * 16 + k];
-        v |= (ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 0u) << (2 * k);
-    }
+    for (uint32_t k = 0; k < 16 && w * 16 + k < total; ++k) v |= base_code(ascii[w * 16 + k]) << (2 * k);
     packed[w] = v;
 }
 
@@ -191,161 +189,109 @@ __global__ void k_rea_pack_unrolled(const uint8_t* ascii, const uint64_t* coffs,
         const uint64_t g = w * 16 + k;
         while (g >= pe) { ++u; pb = pe; pe = poffs[u + 1]; cb = coffs[u]; plen = coffs[u + 1] - cb; }       // (g < ptotal = poffs[nutg]: u stays below nutg)
         const uint64_t j = g - pb;
-        const uint8_t ch = ascii[cb + (j >= plen ? j - plen : j)];
-        v |= (ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 0u) << (2 * k);
+        v |= base_code(ascii[cb + (j >= plen ? j - plen : j)]) << (2 * k);
     }
     packed[w] = v;
 }
 
+struct ReaEnd {                  // the best cell of the last row: trace_best_take's smallest i + j is the smallest q there
+    TraceBest best{kTrNeg, 0, 0};
+    __device__ __forceinline__ void row0(int, int, int) {}
+    __device__ __forceinline__ void before_row(int i, int rows) { if (i == rows) best = TraceBest{kTrNeg, 0, 0}; }
+    template <int C> __device__ __forceinline__ void after_row(const int (&)[C], int, int) {}
+    __device__ __forceinline__ void reduce() { trace_best_reduce(best); }
+    __device__ __forceinline__ ReaRes res() const { return ReaRes{best.s, best.sum - best.i}; }
+};
+
+// a ReaJob as band.hpp's problem; kForward: V is known to run forwards and uncomplemented (links.hpp), so dV and comp are constants
+template <class EndRule, bool kForward>
+struct ReaProblemT {
+    using End = EndRule;
+    static constexpr bool anchored = false;
+    const ReaJob& e;
+    const uint32_t *rpacked, *upacked;
+    __device__ __forceinline__ int m() const { return e.m; }
+    __device__ __forceinline__ int rows(uint32_t) const { return (int)e.n; }
+    __device__ __forceinline__ int centre() const { return e.c; }
+    __device__ __forceinline__ int row0(int) const { return 0; }
+    __device__ __forceinline__ int h(int64_t t) const { return trace_base(upacked, e.gH, 1, 0u, t); }
+    __device__ __forceinline__ const uint32_t* vpack() const { return rpacked; }
+    __device__ __forceinline__ int64_t vidx(int64_t t) const { return e.gV + (int64_t)(kForward ? 1 : e.dV) * t; }
+    __device__ __forceinline__ uint32_t vcomp() const { return kForward ? 0u : e.comp; }
+    __device__ __forceinline__ uint64_t dir_off() const { return e.dir_off; }
+    __device__ __forceinline__ uint64_t scr_off() const { return e.scr_off; }
+    __device__ __forceinline__ uint32_t band() const { return e.band; }
+};
+using ReaProblem = ReaProblemT<ReaEnd, false>;
+
 // band of 64 * C diagonals in registers; wavefront w runs jobs[w]
 template <int C>
 __global__ __launch_bounds__(kTraceBlock) void k_rea_dp(const ReaJob* jobs, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, uint8_t* dirs, ReaRes* res) {
-    using Word = typename TraceDirWord<C>::type;
     const uint32_t w = (uint32_t)(((uint64_t)blockIdx.x * kTraceBlock + threadIdx.x) >> 6);
     if (w >= njobs) return;                                           // (whole wavefronts leave)
-    const int lane = (int)(threadIdx.x & 63);
     const ReaJob e = jobs[w];
-    constexpr int B = 64 * C, half = B / 2;
-    const int n = (int)e.n, m = e.m;
-    const int p0 = lane * C;
-    const int j0 = e.c + p0 - half;                                   // column of the lane's first cell in row 0
-    int prev[C];
-    uint32_t hwin = 0;                                                // the lane's bases of the unitig for row 1: cell c is column j0 + c + 1, its base u[j0 + c]
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int j = j0 + c;
-        prev[c] = (j >= 0 && j <= m) ? 0 : kTrNeg;
-        if (j >= 0 && j < m) hwin |= (uint32_t)trace_base(upacked, e.gH, 1, 0u, j) << (2 * c);
-    }
-    Word* const drow = (Word*)(dirs + e.dir_off) + lane;
-    TraceBest best{kTrNeg, 0, 0};
-    uint32_t vw = 0;
-    int64_t vwi = -1;
-    for (int i = 1; i <= n; ++i) {
-        const int64_t gv = e.gV + (int64_t)e.dV * (i - 1);
-        if ((gv >> 4) != vwi) { vwi = gv >> 4; vw = rpacked[vwi]; }
-        const int vb = (int)(((vw >> ((uint32_t)(gv & 15) * 2)) & 3u) ^ e.comp);
-        int upn = __shfl_down(prev[0], 1, 64);
-        if (lane == 63) upn = kTrNeg;
-        int carry = kTrNeg;
-        if (i == n) best = TraceBest{kTrNeg, 0, 0};                   // the end is a cell of the last row
-        const uint32_t bits = trace_row_tile<C>(prev, upn, hwin, vb, i + j0, m, p0, carry, i, best);
-        drow[(size_t)(i - 1) * 64] = (Word)bits;
-        const int t = i + j0 + C - 1;                                 // the column j - 1 of the lane's last cell in row i + 1
-        uint32_t nbase = 0;
-        if (t >= 0 && t < m) nbase = (uint32_t)trace_base(upacked, e.gH, 1, 0u, t);
-        hwin = (C == 16 ? (hwin >> 2) : ((hwin >> 2) & ((1u << (2 * (C - 1))) - 1u))) | (nbase << (2 * (C - 1)));
-    }
-    trace_best_reduce(best);
-    if (lane == 0) res[w] = ReaRes{best.s, best.sum - best.i};
+    const ReaEnd end = band_sweep<C>(ReaProblem{e, rpacked, upacked}, dirs);
+    if ((threadIdx.x & 63) == 0) res[w] = end.res();
 }
 
-// any band: tiles of 256 cells, the previous row in global scratch, one wavefront per block -- k_trace_dp_wide's shape, and its
-// invariant: a row computes the tiles that hold a column 0 .. m, and trace_row_tile masks every neighbour by its column.
+// any band; one wavefront per block
 __global__ __launch_bounds__(64) void k_rea_dp_wide(const ReaJob* jobs, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, uint8_t* dirs, int* scratch,
                                                     ReaRes* res) {
     const uint32_t w = blockIdx.x;
     if (w >= njobs) return;
-    const int lane = (int)threadIdx.x;
     const ReaJob e = jobs[w];
-    const int B = (int)e.band, half = B / 2;
-    const int n = (int)e.n, m = e.m;
-    int* bufP = scratch + e.scr_off;
-    int* bufC = bufP + B;
-    for (int p = lane; p < B; p += 64) {
-        const int j = e.c + p - half;
-        bufP[p] = (j >= 0 && j <= m) ? 0 : kTrNeg;
-    }
-    __syncthreads();
-    TraceBest best{kTrNeg, 0, 0};
-    uint8_t* const dbase = dirs + e.dir_off;
-    const size_t rowbytes = (size_t)B / 4;
-    for (int i = 1; i <= n; ++i) {
-        const int vb = trace_base(rpacked, e.gV, e.dV, e.comp, i - 1);
-        const int org = i + e.c - half;                               // column of position 0 in this row
-        const int plo = -org > 0 ? -org : 0;                          // positions of the columns 0 .. m
-        const int phi = m - org < B - 1 ? m - org : B - 1;
-        int carry = kTrNeg;
-        if (i == n) best = TraceBest{kTrNeg, 0, 0};
-        if (plo <= phi) {
-            for (int t = plo >> 8; t <= (phi >> 8); ++t) {
-                const int p0 = t * 256 + lane * 4;
-                int prev[4];
-                const int4 q = *(const int4*)(bufP + p0);
-                prev[0] = q.x; prev[1] = q.y; prev[2] = q.z; prev[3] = q.w;
-                const int upn = p0 + 4 < B ? bufP[p0 + 4] : kTrNeg;
-                const int jb = org + p0;
-                uint32_t hwin = 0;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int tt = jb + c - 1;
-                    if (tt >= 0 && tt < m) hwin |= (uint32_t)trace_base(upacked, e.gH, 1, 0u, tt) << (2 * c);
-                }
-                const uint32_t bits = trace_row_tile<4>(prev, upn, hwin, vb, jb, m, p0, carry, i, best);
-                *(int4*)(bufC + p0) = make_int4(prev[0], prev[1], prev[2], prev[3]);
-                dbase[(size_t)(i - 1) * rowbytes + (size_t)(p0 >> 2)] = (uint8_t)bits;
-            }
-        }
-        __syncthreads();                                              // the row is in memory before the next one reads it
-        int* tmp = bufP; bufP = bufC; bufC = tmp;
-    }
-    trace_best_reduce(best);
-    if (lane == 0) res[w] = ReaRes{best.s, best.sum - best.i};
+    const ReaEnd end = band_sweep_wide(ReaProblem{e, rpacked, upacked}, dirs, scratch);
+    if (threadIdx.x == 0) res[w] = end.res();
 }
 
-// Walks one read from (n, q_end) back to row 0 and hands every op to `put` (the read's last base first).  Returns whether the path
-// touched the first or the last diagonal of the band; qb = the junction where it reached row 0.
-template <class Put>
-__device__ __forceinline__ bool rea_walk(const ReaJob& e, const ReaRes& r, const uint32_t* rpacked, const uint32_t* upacked, const uint8_t* dirs, int& qb, Put&& put) {
-    int i = (int)e.n, q = r.q_end;
-    const int B = (int)e.band, half = B / 2;
-    const uint8_t* const d0 = dirs + e.dir_off;
-    const size_t rowbytes = (size_t)B / 4;
-    bool touch = false;
-    while (i > 0) {
-        int p = q - i - e.c + half;
-        if (p <= 0 || p >= B - 1) { touch = true; p = p < 0 ? 0 : (p > B - 1 ? B - 1 : p); }      // (the clamp keeps the read in bounds whatever the bytes say)
-        uint32_t d = q <= 0 ? 1u : (uint32_t)((d0[(size_t)(i - 1) * rowbytes + (size_t)(p >> 2)] >> (2 * (p & 3))) & 3u);
-        if (d == 3) d = 2;
-        if (d == 0) {
-            const int hb = trace_base(upacked, e.gH, 1, 0u, q - 1), vb = trace_base(rpacked, e.gV, e.dV, e.comp, i - 1);
-            put(hb == vb ? kOpEq : kOpX);
-            --i; --q;
-        } else if (d == 1) { put(kOpIns); --i; }
-        else { put(kOpDel); --q; }
-    }
-    qb = q;
-    return touch;
+struct ReaFamily {               // for the host: what the DP leaves per job, the DP kernels, whether the runs vote
+    using Res = ReaRes;
+    static constexpr bool votes = true;
+    template <int C> static constexpr auto dp() { return k_rea_dp<C>; }
+    static constexpr auto dp_wide() { return k_rea_dp_wide; }
+};
+
+constexpr int kReaNoEnd = kTrNeg / 2;      // a best score at or below this: the end rule found no cell that a path from row 0 reaches
+
+// where the walk of a job starts, and whether that is a cell of the rectangle (links.hpp has the LnkRes one)
+__device__ __forceinline__ bool rea_start(const ReaJob& e, const ReaRes& r, int& i, int& j) {
+    i = (int)e.n; j = r.q_end;
+    return r.q_end >= 0 && r.q_end <= e.m;
 }
 
-constexpr int kReaNoEnd = kTrNeg / 2;      // a best score at or below this: row n has no cell that a path from row 0 reaches
-
-__global__ void k_rea_count(const ReaJob* jobs, const ReaRes* res, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, const uint8_t* dirs, ReaCnt* out) {
+// The walks, one thread per job, from the DP's end (Res: a ReaRes or a LnkRes) back to row 0, the job's last op first.  The counting
+// walk: runs, op totals, whether the path touched the first or the last diagonal of the band (an end that nothing reaches counts as
+// touched), q_begin = the junction where it reached row 0.
+template <class Res>
+__global__ void k_rea_count(const ReaJob* jobs, const Res* res, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, const uint8_t* dirs, ReaCnt* out) {
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= njobs) return;
     ReaCnt o{};
-    const ReaRes r = res[x];
-    if (r.score <= kReaNoEnd || r.q_end < 0 || r.q_end > jobs[x].m) { o.touch = 1; out[x] = o; return; }
+    const ReaJob e = jobs[x];
+    const Res r = res[x];
+    int i, j;
+    if (!rea_start(e, r, i, j) || r.score <= kReaNoEnd) { o.touch = 1; out[x] = o; return; }
     TraceRuns runs;
-    int qb = 0;
-    const bool t = rea_walk(jobs[x], r, rpacked, upacked, dirs, qb, runs);
+    const bool t = band_walk(ReaProblem{e, rpacked, upacked}, dirs, i, j, runs);
     o.nops = runs.nruns;
     o.n_eq = runs.cnt[0]; o.n_x = runs.cnt[1]; o.n_ins = runs.cnt[2]; o.n_del = runs.cnt[3];
     o.touch = t ? 1u : 0u;
-    o.q_begin = qb;
+    o.q_begin = j;
     out[x] = o;
 }
 
-// one thread per read that votes: ops[op_off .. op_off + nops) in read order
-__global__ void k_rea_write(const ReaJob* jobs, const ReaRes* res, const ReaCnt* cnt, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, const uint8_t* dirs,
+// the writing walk, one thread per job with runs: ops[op_off .. op_off + nops) in the order of V
+template <class Res>
+__global__ void k_rea_write(const ReaJob* jobs, const Res* res, const ReaCnt* cnt, uint32_t njobs, const uint32_t* rpacked, const uint32_t* upacked, const uint8_t* dirs,
                             uint32_t* ops) {
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= njobs) return;
     const ReaJob e = jobs[x];
     if (e.op_off == ~0ull) return;
     TraceEmit bw{ops, (int64_t)(e.op_off + cnt[x].nops), -1};
-    int qb = 0;
-    rea_walk(e, res[x], rpacked, upacked, dirs, qb, bw);
+    int i, j;
+    rea_start(e, res[x], i, j);
+    band_walk(ReaProblem{e, rpacked, upacked}, dirs, i, j, bw);
     bw.flush();
 }
 

@@ -17,7 +17,7 @@ from bella_testkit.pipeline import raises, run_cli, with_round_budget
 
 pytestmark = pytest.mark.gpu
 
-SEEN = dict(plus_plus=False, plus_minus=False, minus_plus=False, minus_minus=False, m_is_the_unitig=False, n_is_the_unitig=False, doubled=False, capped=False, wide=False,
+SEEN = dict(plus_plus=False, plus_minus=False, minus_plus=False, minus_minus=False, m_is_the_unitig=False, n_is_the_unitig=False, doubled=False, capped=False, wide=False, dp16=False,
             aligned=False, empty=False, band_capped=False, low_identity=False, self_link=False, derived=False, polished=False, realigned=False)
 SIGNS = {0: "plus_plus", LM.B_MINUS: "plus_minus", LM.A_MINUS: "minus_plus", LM.A_MINUS | LM.B_MINUS: "minus_minus"}
 STATUS = {LM.ALIGNED: "aligned", LM.EMPTY: "empty", LM.BAND_CAPPED: "band_capped", LM.LOW_IDENTITY: "low_identity", LM.SELF: "self_link"}
@@ -166,6 +166,18 @@ def test_the_wide_kernel(eng):
     SEEN["wide"] = True
 
 
+def test_the_register_kernel_of_16_cells_a_lane(eng):
+    """band0 = 1,024 on the polished fork (rev="b", the wide kernel's case): every DP runs in k_lnk_dp<16>, which bands of 256, 512 and
+    2,048 never reach.  The mirror aligns all four links at this band (checked on the CPU before the test was written)"""
+    seqs, recs, trunk = LC.fork_case(rev="b")
+    u = _install(eng, seqs, recs)
+    p = _polish(eng, LC.fork_table(seqs, trunk))
+    got, m = _same(eng, u, p, band0=1024)
+    assert (got["alns"]["band"] == 1024).all() and (got["alns"]["status"] == LM.ALIGNED).all() and len(got["alns"]) == 4
+    assert m["counts"]["aligned"] == 4
+    SEEN["dp16"] = True
+
+
 # ---- 6. 7. links that are no overlaps -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("forged", [True, "A"])
 def test_a_forged_record_between_unrelated_reads(eng, forged):
@@ -210,7 +222,7 @@ def test_one_link_per_batch_gives_the_same_result(eng, params):
 
 def test_the_cases_cover_what_they_should():
     """over the cases above (pytest keeps file order): every sign combination among the links the device aligned, both window clamps, a
-    doubled band, a capped link, the wide kernel, every status, derived twins, a polished and a realigned sequence"""
+    doubled band, a capped link, the wide kernel, the widest register kernel, every status, derived twins, a polished and a realigned sequence"""
     assert all(SEEN.values()), SEEN
 
 

@@ -180,6 +180,39 @@ class LinkStats(C.Structure):
                 ("batches", C.c_uint32), ("pad", C.c_uint32), ("pack_ms", C.c_double), ("dp_ms", C.c_double), ("walk_ms", C.c_double)]
 
 
+ALIGN_GLOBAL, ALIGN_SEMIGLOBAL, ALIGN_DOVETAIL = range(3)
+ALIGN_MODES = {"global": ALIGN_GLOBAL, "semiglobal": ALIGN_SEMIGLOBAL, "dovetail": ALIGN_DOVETAIL}
+ALIGN_ALIGNED, ALIGN_BAND_CAPPED, ALIGN_TOO_LARGE = range(3)
+ALIGN_PAIR_RC = 1
+ALIGN_PAIR_DT = np.dtype([("q_off", "<u8"), ("t_off", "<u8"), ("q_len", "<u4"), ("t_len", "<u4"), ("flags", "<u4"), ("centre", "<i4")])
+ALIGN_RES_DT = np.dtype([("status", "<u4"), ("band", "<u4"), ("widened", "<u4"), ("score", "<i4"), ("q_begin", "<u4"), ("q_end", "<u4"), ("t_begin", "<u4"), ("t_end", "<u4"),
+                         ("n_eq", "<u4"), ("n_x", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("op_off", "<u8"), ("nops", "<u4"), ("pad", "<u4")])
+assert ALIGN_PAIR_DT.itemsize == 32 and ALIGN_RES_DT.itemsize == 64
+
+
+class AlignParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32), ("band0", C.c_uint32), ("band_max", C.c_uint32)]
+
+
+class AlignPair(C.Structure):
+    _fields_ = [("q_off", C.c_uint64), ("t_off", C.c_uint64), ("q_len", C.c_uint32), ("t_len", C.c_uint32), ("flags", C.c_uint32), ("centre", C.c_int32)]
+
+
+class AlignResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("band", C.c_uint32), ("widened", C.c_uint32), ("score", C.c_int32), ("q_begin", C.c_uint32), ("q_end", C.c_uint32),
+                ("t_begin", C.c_uint32), ("t_end", C.c_uint32), ("n_eq", C.c_uint32), ("n_x", C.c_uint32), ("n_ins", C.c_uint32), ("n_del", C.c_uint32),
+                ("op_off", C.c_uint64), ("nops", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class AlignStats(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("aligned", C.c_uint64), ("band_capped", C.c_uint64), ("too_large", C.c_uint64), ("repeated", C.c_uint64), ("dp_cells", C.c_uint64),
+                ("ops", C.c_uint64), ("batches", C.c_uint32), ("mode", C.c_uint32), ("pack_ms", C.c_double), ("dp_ms", C.c_double), ("walk_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
+assert C.sizeof(AlignPair) == ALIGN_PAIR_DT.itemsize and C.sizeof(AlignResult) == ALIGN_RES_DT.itemsize and C.sizeof(AlignStats) == 96
+
+
 class RecorrectParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("band0", C.c_uint32), ("band_max", C.c_uint32), ("min_identity", C.c_uint32), ("min_depth", C.c_uint32),
                 ("keep_ops", C.c_uint32)]
@@ -333,6 +366,9 @@ SIGNATURES = [
     ("bella_hip_graph_get_link_alignments", C.c_int, [vp, vp, C.POINTER(C.c_uint64), vp]),
     ("bella_hip_graph_get_link_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_write_unitig_gfa_links", C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]),
+    ("bella_hip_align_sequences", C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(AlignParams), vp, C.POINTER(C.c_uint64)]),
+    ("bella_hip_get_align_ops", C.c_int, [vp, vp, C.c_uint64]),
+    ("bella_hip_get_align_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_recorrect", C.c_int, [vp, C.POINTER(RecorrectParams), C.POINTER(C.c_uint64)]),
     ("bella_hip_get_recorrected", C.c_int, [vp, vp, vp, vp]),
     ("bella_hip_get_recorrect_jobs", C.c_int, [vp, C.POINTER(C.c_uint64), vp]),

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CLIP_DT, GraphTrimParams, TrimStats
+from ._lib import ALIGN_PAIR_DT, ALIGN_RES_DT, AlignParams, AlignStats
 from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_ALN_DT, LINK_DT, LinkParams, LinkStats, OVL_DT, PAIR_DT, PLACE_DT, POLISH_DT, PolishParams, PolishStats, RealignParams, RealignStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphWeakParams, WeakStats, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
@@ -766,6 +767,51 @@ class Engine:
         self._chk(self.lib.bella_hip_get_batch_ops(self.h, _p(ops), no.value))
         return tr, ops
 
+    # ---- pair alignment ----
+    def align_records(self, bases, records, mode="global", band0: int = 512, band_max: int = 4096):
+        """bella_hip_align_sequences as it is: bases uint8 (upper-case ACGT), records of ALIGN_PAIR_DT -> (results of ALIGN_RES_DT in the
+        records' order, the runs of all pairs as uint32 len << 4 | op)"""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        recs = np.ascontiguousarray(records, ALIGN_PAIR_DT)
+        ap = AlignParams(C.sizeof(AlignParams), _lib.ALIGN_MODES[mode] if isinstance(mode, str) else int(mode), int(band0), int(band_max))
+        out = np.zeros(len(recs), ALIGN_RES_DT)
+        no = C.c_uint64(0)
+        self._chk(self.lib.bella_hip_align_sequences(self.h, _p(bases), bases.size, _p(recs), len(recs), C.byref(ap), _p(out), C.byref(no)))
+        ops = np.zeros(no.value, np.uint32)
+        self._chk(self.lib.bella_hip_get_align_ops(self.h, _p(ops), no.value))
+        return out, ops
+
+    def align_sequences(self, seqs, pairs, mode="global", rc=None, centre=None, overlap=None, band0: int = 512, band_max: int = 4096):
+        """Aligns pairs of caller-supplied sequences on the device.  seqs: a list of bytes (upper-case ACGT); pairs: (query, target)
+        indices into it; rc (per pair, or one for all): the query is reverse-complemented first.  mode: "global" (both whole),
+        "semiglobal" (the query whole, a window of the target) or "dovetail" (a suffix of the target against a prefix of the query).
+        centre (per pair, or one for all): the diagonal target - query the band is centred on; the default is floor((m - n) / 2), and
+        m - overlap for a dovetail with an expected `overlap`.  Returns (results of ALIGN_RES_DT in the pairs' order, the runs)."""
+        lens = np.array([len(s) for s in seqs], np.uint64)
+        offs = np.concatenate([np.zeros(1, np.uint64), np.cumsum(lens, dtype=np.uint64)])
+        bases = np.frombuffer(b"".join(bytes(s) for s in seqs), np.uint8)
+        pr = np.asarray(pairs, np.int64).reshape(-1, 2)
+        recs = np.zeros(len(pr), ALIGN_PAIR_DT)
+        recs["q_off"], recs["t_off"] = offs[pr[:, 0]], offs[pr[:, 1]]
+        recs["q_len"], recs["t_len"] = lens[pr[:, 0]], lens[pr[:, 1]]
+        if rc is not None:
+            recs["flags"] = np.where(np.broadcast_to(np.asarray(rc, bool), len(pr)), _lib.ALIGN_PAIR_RC, 0)
+        n, m = recs["q_len"].astype(np.int64), recs["t_len"].astype(np.int64)
+        if centre is not None:
+            recs["centre"] = np.broadcast_to(np.asarray(centre, np.int64), len(pr))
+        elif overlap is not None:
+            if mode != "dovetail":
+                raise TypeError("overlap is the expected overlap of a dovetail")
+            recs["centre"] = m - np.broadcast_to(np.asarray(overlap, np.int64), len(pr))
+        elif mode == "dovetail":
+            raise TypeError("a dovetail needs the expected overlap (or a centre)")
+        else:
+            recs["centre"] = (m - n) // 2
+        return self.align_records(bases, recs, mode, band0, band_max)
+
+    def align_stats(self) -> dict:
+        return self._stats(self.lib.bella_hip_get_align_stats, AlignStats)
+
     def trace_stats(self) -> TraceStats:
         t = TraceStats()
         self._chk(self.lib.bella_hip_get_trace_stats(self.h, C.byref(t), C.sizeof(t)))
@@ -969,6 +1015,28 @@ def link_cigars(alns, ops) -> list:
         text, run, last = [], 0, None
         for w in np.asarray(ops[int(a["op_off"]):int(a["op_off"]) + int(a["nops"])], np.uint32).tolist():
             ch = b"MMID"[w & 15:(w & 15) + 1]
+            if ch != last and run:
+                text.append(b"%d%s" % (run, last))
+                run = 0
+            last, run = ch, run + (w >> 4)
+        if run:
+            text.append(b"%d%s" % (run, last))
+        out.append(b"".join(text))
+    return out
+
+
+def align_cigars(results, ops, eqx: bool = True) -> list:
+    """the CIGAR (bytes) of every ALIGNED pair of Engine.align_sequences, None for the others: '=' / 'X' / 'I' / 'D', or with eqx False
+    M / I / D ('=' and 'X' merged into M).  An ALIGNED pair without runs (a dovetail that ends in row 0) has the empty CIGAR."""
+    letters = b"=XID" if eqx else b"MMID"
+    out = []
+    for a in np.asarray(results):
+        if int(a["status"]) != _lib.ALIGN_ALIGNED:
+            out.append(None)
+            continue
+        text, run, last = [], 0, None
+        for w in np.asarray(ops[int(a["op_off"]):int(a["op_off"]) + int(a["nops"])], np.uint32).tolist():
+            ch = letters[w & 15:(w & 15) + 1]
             if ch != last and run:
                 text.append(b"%d%s" % (run, last))
                 run = 0

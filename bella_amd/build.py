@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbella_hip.so")
 SOURCES = ["bella_hip.hip"]
-HEADERS = ["core.hpp", "util.hpp", "assemble.hpp", "kcount.hpp", "fastq.hpp", "wide.hpp", "spgemm.hpp", "order.hpp", "slotorder.hpp", "writer.hpp", "band.hpp", "trace.hpp", "pileup.hpp", "clip.hpp", "graph.hpp", "trim.hpp", "unitig.hpp", "polish.hpp", "realign.hpp", "links.hpp", "recorrect.hpp", "bubble.hpp", "xdrop.hpp", "xdrop_packed.hpp", "logan.hpp", "comm.hpp", os.path.join("..", "..", "include", "bella_hip.h")]
+HEADERS = ["core.hpp", "util.hpp", "assemble.hpp", "kcount.hpp", "fastq.hpp", "wide.hpp", "spgemm.hpp", "order.hpp", "slotorder.hpp", "writer.hpp", "band.hpp", "trace.hpp", "pileup.hpp", "clip.hpp", "graph.hpp", "trim.hpp", "unitig.hpp", "polish.hpp", "realign.hpp", "links.hpp", "pairalign.hpp", "recorrect.hpp", "bubble.hpp", "xdrop.hpp", "xdrop_packed.hpp", "logan.hpp", "comm.hpp", os.path.join("..", "..", "include", "bella_hip.h")]
 
 
 CLI = os.path.join(HERE, "bin", "bella-hip")

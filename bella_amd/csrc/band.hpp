@@ -1,5 +1,6 @@
-// band.hpp -- the banded, direction-storing alignment sweep and its backtrace, written once for the three families that use it on
-// gfx950: trace.hpp, realign.hpp (sections 18 to 20) and links.hpp (section 26).  DESIGN.md section 27.
+// band.hpp -- the banded, direction-storing alignment sweep and its backtrace, written once for the families that use it on
+// gfx950: trace.hpp, realign.hpp (sections 18 to 20), links.hpp (section 26) and pairalign.hpp (section 28).
+// DESIGN.md section 27.
 //
 // The DP.  Rows i = 0 .. n are bases of V, columns j = 0 .. m bases of H; match +1, mismatch -1, gap -1 linear (the X-drop's
 // scoring).  A band of B diagonals around the centre diagonal c is computed: position p of row i is column j = i + c + p - B/2.
@@ -29,6 +30,7 @@
 //     vpack()  vidx(t)  vcomp()                  the pack that holds V, the index of V's base t in it, its complement mask
 //     dir_off()  scr_off()  band()               bytes into the direction buffer, ints into the scratch, B
 //     anchored                                   the path starts in (0, 0) (else anywhere in row 0)
+//     touch_row0                                 anchored only: a cell of row 0 on the band's first or last diagonal counts as touched
 //     End                                        its end rule
 // and an END RULE, which owns what the sweep reports: a TraceBest `best` that trace_row_tile keeps (the best cell so far, ties to the
 // smallest i + j, then the smallest i) and four hooks --
@@ -236,7 +238,8 @@ __device__ __forceinline__ typename Problem::End band_sweep_wide(const Problem& 
 }
 
 // Walks P back from (i, j) -- to (0, 0) if P is anchored, else to row 0 -- and hands every op to `put` (far end first).  Returns
-// whether the path touched the first or the last diagonal of the band; j = the column it stopped in.
+// whether the path touched the first or the last diagonal of the band (in row 0 only where P says touch_row0); j = the column it
+// stopped in.
 template <class Problem, class Put>
 __device__ __forceinline__ bool band_walk(const Problem& P, const uint8_t* dirs, int i, int& j, Put&& put) {
     const int B = (int)P.band(), half = B / 2, c = P.centre();
@@ -245,7 +248,7 @@ __device__ __forceinline__ bool band_walk(const Problem& P, const uint8_t* dirs,
     bool touch = false;
     while (i > 0 || (Problem::anchored && j > 0)) {
         int p = j - i - c + half;
-        if (p <= 0 || p >= B - 1) { touch = true; p = p < 0 ? 0 : (p > B - 1 ? B - 1 : p); }      // (a path never leaves the band; the clamp keeps a read in bounds whatever the bytes say)
+        if (p <= 0 || p >= B - 1) { touch = touch || i > 0 || Problem::touch_row0; p = p < 0 ? 0 : (p > B - 1 ? B - 1 : p); }      // (a path never leaves the band; the clamp keeps a read in bounds whatever the bytes say)
         uint32_t d = 2;
         if (i > 0) {
             d = j <= 0 ? 1u : (uint32_t)((d0[(size_t)(i - 1) * rowbytes + (size_t)(p >> 2)] >> (2 * (p & 3))) & 3u);

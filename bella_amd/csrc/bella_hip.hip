@@ -33,6 +33,7 @@
 #include "polish.hpp"
 #include "realign.hpp"
 #include "links.hpp"
+#include "pairalign.hpp"
 #include "recorrect.hpp"
 #include "spgemm.hpp"
 #include "trace.hpp"
@@ -259,6 +260,8 @@ struct bella_ctx {
     std::vector<uint32_t> trace_ops;
     std::vector<uint32_t> batch_ops;     // runs of the last bella_hip_trace_batch
     bella_trace_stats trace_stats{};
+    std::vector<uint32_t> pal_ops;       // runs of the last bella_hip_align_sequences (pairalign.hpp; section 28): no stage, the sequences were the caller's
+    bella_align_stats pal_stats{};
     Buf tr_exts, tr_lists, tr_res, tr_pres, tr_opoff, tr_dirs, tr_scr, tr_ops;
     bool trace_ops_kept = true;          // false: the last call piled its runs up on the device and did not stage them (keep_ops == 0)
     // read correction (pileup.hpp): the table of the loaded reads, and the last consensus
@@ -6050,6 +6053,228 @@ int bella_hip_graph_get_link_alignments(bella_ctx* c, bella_link_aln* alns, uint
 
 int bella_hip_graph_get_link_stats(bella_ctx* c, void* out, uint64_t struct_size) {
     return get_stats(c, LINKS, out, struct_size, [](const StageState& a) { return a.links.stats; });
+}
+
+}  // extern "C"
+
+// ---- pair alignment (pairalign.hpp) ---------------------------------------------------------------------------------
+// The caller's sequences are uploaded and packed once per (sequence, orientation); the DP and the walks run batched and band-doubled by
+// RoundBatches, as the links' do, one family per mode.  Nothing of the context's stages is read or written.
+namespace {
+struct PalPair { uint32_t n, m; int32_t c; uint32_t wq, wt; };       // a checked pair: rows, columns, centre, its two windows of the pack
+
+// whether a band of B can hold what the mode needs: global, the start (0, 0) and the end (n, m); else, any cell of the rectangle
+bool pal_feasible(uint32_t mode, const PalPair& p, uint32_t B) {
+    const int64_t half = B / 2, c = p.c;
+    auto in = [&](int64_t d) { return d - c >= -half && d - c < half; };      // the diagonal d = q - i
+    if (mode == BELLA_ALIGN_GLOBAL) return in(0) && in((int64_t)p.m - (int64_t)p.n);
+    return c + half > -(int64_t)p.n && c - half <= (int64_t)p.m;              // one of the diagonals -n .. m
+}
+
+// what a mode's DP result and the counting walk say about an ALIGNED pair
+void pal_fill(bella_align_result& R, const ReaJob& j, const GlbRes& r, const ReaCnt& q) {
+    R.score = r.score; R.q_begin = 0; R.q_end = j.n; R.t_begin = (uint32_t)q.q_begin; R.t_end = (uint32_t)j.m;
+}
+void pal_fill(bella_align_result& R, const ReaJob& j, const ReaRes& r, const ReaCnt& q) {
+    R.score = r.score; R.q_begin = 0; R.q_end = j.n; R.t_begin = (uint32_t)q.q_begin; R.t_end = (uint32_t)r.q_end;
+}
+void pal_fill(bella_align_result& R, const ReaJob& j, const LnkRes& r, const ReaCnt& q) {
+    R.score = r.score; R.q_begin = 0; R.q_end = (uint32_t)r.i_end; R.t_begin = (uint32_t)q.q_begin; R.t_end = (uint32_t)j.m;
+}
+
+template <class Family>
+int pal_run(bella_ctx* c, uint32_t mode, uint32_t band0, uint32_t band_max, const std::vector<PalPair>& pp, const std::vector<uint64_t>& woff, const uint32_t* pack, EventSet& ev,
+            std::vector<bella_align_result>& res, std::vector<uint32_t>& ops, bella_align_stats& st) {
+    using Res = typename Family::Res;
+    uint64_t budget = 0;
+    if (int rc = round_budget(c, &budget)) return rc;
+    // ---- the first band of every pair: doubled without a DP while it cannot hold what the mode needs
+    std::map<uint32_t, std::vector<uint32_t>> starters;              // band -> the pairs that begin with it, in index order
+    for (uint32_t k = 0; k < (uint32_t)pp.size(); ++k) {
+        bella_align_result& R = res[k];
+        R.band = band0;
+        if ((uint64_t)pp[k].n + pp[k].m >= kPalMaxCells) { R.status = BELLA_ALIGN_STATUS_TOO_LARGE; continue; }
+        while (!pal_feasible(mode, pp[k], R.band) && R.band < band_max) { R.band *= 2; ++R.widened; }
+        if (!pal_feasible(mode, pp[k], R.band)) { R.status = BELLA_ALIGN_STATUS_BAND_CAPPED; continue; }
+        starters[R.band].push_back(k);
+    }
+    double no_votes = 0;
+    RoundBatches<Family> rb{c, "align_sequences", "pairs", ev, pack, pack, nullptr, nullptr, true, ops, st.dp_ms, st.walk_ms, no_votes};
+    std::vector<ReaJob> hj;
+    std::vector<Res> hres;
+    std::vector<ReaCnt> hcnt;
+    std::vector<uint32_t> next, pending;
+    for (uint32_t B = band0;; B *= 2) {
+        pending.clear();
+        const std::vector<uint32_t>& fresh = starters[B];
+        std::merge(next.begin(), next.end(), fresh.begin(), fresh.end(), std::back_inserter(pending));
+        next.clear();
+        size_t keep = 0;                                              // a pair whose direction bytes exceed a batch at this band goes no further
+        for (uint32_t k : pending) {
+            if ((uint64_t)pp[k].n * (B / 4) > budget) { res[k].status = BELLA_ALIGN_STATUS_TOO_LARGE; res[k].band = B; }
+            else pending[keep++] = k;
+        }
+        pending.resize(keep);
+        const uint32_t maxjobs = round_max_jobs(B, budget);
+        for (size_t b0 = 0; b0 < pending.size();) {
+            hj.clear();
+            uint64_t dbytes = 0;
+            size_t b1 = b0;
+            for (; b1 < pending.size(); ++b1) {
+                const PalPair& p = pp[pending[b1]];
+                const uint64_t need_bytes = (uint64_t)p.n * (B / 4);
+                if (!hj.empty() && (dbytes + need_bytes > budget || hj.size() >= maxjobs)) break;
+                ReaJob j{};
+                j.gH = (int64_t)(16 * woff[p.wt]); j.gV = (int64_t)(16 * woff[p.wq]);
+                j.dir_off = dbytes; j.scr_off = 2ull * B * hj.size(); j.op_off = ~0ull;
+                j.n = p.n; j.m = (int32_t)p.m; j.mt = j.m; j.c = p.c;
+                j.band = B; j.dV = 1; j.comp = 0;
+                hj.push_back(j);
+                dbytes += need_bytes;
+                st.dp_cells += (uint64_t)p.n * B;
+            }
+            const uint32_t nj = (uint32_t)hj.size();
+            ENSURE(c, rb.jobs, sizeof(ReaJob) * (size_t)nj);
+            ++st.batches;
+            HIPCHK(c, c->stager.h2d(rb.jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
+            if (int rc = rb.dp_count(nj, B, dbytes)) return rc;
+            HIPCHK(c, hipEventRecord(ev.d, c->stream));
+            hres.resize(nj); hcnt.resize(nj);
+            HIPCHK(c, c->stager.d2h(hres.data(), rb.res.p, sizeof(Res) * (size_t)nj, c->stream));
+            HIPCHK(c, c->stager.d2h(hcnt.data(), rb.cnt.p, sizeof(ReaCnt) * (size_t)nj, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            rb.counted();
+            uint64_t nops = 0;
+            for (uint32_t x = 0; x < nj; ++x) {
+                const uint32_t k = pending[b0 + x];
+                bella_align_result& R = res[k];
+                const ReaCnt& q = hcnt[x];
+                R.band = B;
+                if (q.touch) {
+                    if (B < band_max) { next.push_back(k); ++R.widened; ++st.repeated; }
+                    else R.status = BELLA_ALIGN_STATUS_BAND_CAPPED;
+                    continue;
+                }
+                R.status = BELLA_ALIGN_STATUS_ALIGNED;
+                pal_fill(R, hj[x], hres[x], q);
+                R.n_eq = q.n_eq; R.n_x = q.n_x; R.n_ins = q.n_ins; R.n_del = q.n_del;
+                hj[x].op_off = nops;
+                R.nops = q.nops;
+                R.op_off = ops.size() + nops;
+                nops += q.nops;
+            }
+            if (nops) {
+                HIPCHK(c, c->stager.h2d(rb.jobs.p, hj.data(), sizeof(ReaJob) * (size_t)nj, c->stream));
+                if (int rc = rb.write_vote(nj, nops)) return rc;
+            }
+            b0 = b1;
+        }
+        if (B >= band_max) break;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int bella_hip_align_sequences(bella_ctx* c, const uint8_t* bases, uint64_t nbases, const bella_align_pair* pairs, uint64_t npairs, const bella_align_params* params,
+                              bella_align_result* out, uint64_t* nops) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    using clk = std::chrono::steady_clock;
+    const auto t_begin = clk::now();
+    // ---- everything is checked before anything is launched
+    bella_align_params ap{};
+    ap.mode = BELLA_ALIGN_GLOBAL;
+    if (int r = take_params(c, ap, params, "bella_align_params")) return r;
+    if (!ap.band0) ap.band0 = BELLA_ALIGN_DEFAULT_BAND;
+    if (!ap.band_max) ap.band_max = BELLA_ALIGN_DEFAULT_BAND_MAX;
+    auto pow2 = [](uint32_t x) { return x && !(x & (x - 1)); };
+    if (ap.mode > BELLA_ALIGN_DOVETAIL) return fail(c, BELLA_ERR_BAD_ARG, "align_sequences: mode %u is none of global, semi-global, dovetail", ap.mode);
+    if (!pow2(ap.band0) || !pow2(ap.band_max) || ap.band0 < kTrMinBand || ap.band_max > kPalMaxBand || ap.band0 > ap.band_max)
+        return fail(c, BELLA_ERR_BAD_ARG, "align_sequences: band0 and band_max must be powers of two with 256 <= band0 <= band_max <= 16384");
+    if (npairs && (!pairs || !out || !bases)) return fail(c, BELLA_ERR_BAD_ARG, "align_sequences: null argument");
+    if (npairs >= (1ull << 31)) return fail(c, BELLA_ERR_BAD_ARG, "align_sequences: at most 2^31 - 1 pairs a call");
+    std::vector<PalPair> pp((size_t)npairs);
+    std::vector<LnkWin> wins;                                         // one window per (sequence, orientation) in use
+    std::vector<uint64_t> woff(1, 0);
+    std::map<std::array<uint64_t, 3>, uint32_t> win_of;
+    uint64_t lo = nbases, hi = 0;                                     // the bases in use lie in [lo, hi)
+    bool is_base[256] = {};
+    is_base['A'] = is_base['C'] = is_base['G'] = is_base['T'] = true;
+    for (uint64_t k = 0; k < npairs; ++k) {
+        const bella_align_pair& a = pairs[k];
+        if (a.flags & ~BELLA_ALIGN_PAIR_RC) return fail(c, BELLA_ERR_BAD_ARG, "align_sequences: pair %llu: flags is 0 or BELLA_ALIGN_PAIR_RC", (unsigned long long)k);
+        auto window = [&](uint64_t off, uint32_t len, uint32_t rc, uint32_t* w) {
+            if (!len) return fail(c, BELLA_ERR_BAD_ARG, "align_sequences: pair %llu: a sequence of length 0", (unsigned long long)k);
+            if (len >= kPalMaxSeq) return fail(c, BELLA_ERR_BAD_ARG, "align_sequences: pair %llu: a sequence of 2^30 bases or more", (unsigned long long)k);
+            if (off > nbases || len > nbases - off) return fail(c, BELLA_ERR_BAD_ARG, "align_sequences: pair %llu: a sequence lies outside bases", (unsigned long long)k);
+            auto ins = win_of.emplace(std::array<uint64_t, 3>{off, len, rc}, (uint32_t)wins.size());
+            *w = ins.first->second;
+            if (!ins.second) return 0;
+            for (uint64_t t = off; t < off + len; ++t)
+                if (!is_base[bases[t]]) return fail(c, BELLA_ERR_BAD_ARG, "align_sequences: pair %llu: base %llu of bases is not one of ACGT", (unsigned long long)k, (unsigned long long)t);
+            wins.push_back(LnkWin{off, len, rc});
+            woff.push_back(woff.back() + ((uint64_t)len + 15) / 16);
+            lo = std::min(lo, off); hi = std::max(hi, off + len);
+            return 0;
+        };
+        PalPair& p = pp[(size_t)k];
+        p.n = a.q_len; p.m = a.t_len; p.c = a.centre;
+        if (int r = window(a.q_off, a.q_len, a.flags & BELLA_ALIGN_PAIR_RC, &p.wq)) return r;
+        if (int r = window(a.t_off, a.t_len, 0u, &p.wt)) return r;
+    }
+    std::vector<bella_align_result> res((size_t)npairs, bella_align_result{});
+    std::vector<uint32_t> ops;
+    bella_align_stats st{};
+    st.pairs = npairs; st.mode = ap.mode;
+    if (npairs) {
+        HIPCHK(c, hipSetDevice(c->device));
+        for (LnkWin& w : wins) w.src -= lo;
+        const uint64_t nwords = woff.back();
+        TmpBuf ascii, dwins, dwoff, pack;
+        ENSURE(c, ascii, (size_t)(hi - lo));
+        ENSURE(c, dwins, sizeof(LnkWin) * wins.size());
+        ENSURE(c, dwoff, 8 * woff.size());
+        ENSURE(c, pack, 4 * (size_t)(nwords + 1));
+        HIPCHK(c, c->stager.h2d(ascii.p, bases + lo, (size_t)(hi - lo), c->stream));
+        HIPCHK(c, c->stager.h2d(dwins.p, wins.data(), sizeof(LnkWin) * wins.size(), c->stream));
+        HIPCHK(c, c->stager.h2d(dwoff.p, woff.data(), 8 * woff.size(), c->stream));
+        EventSet ev;
+        int rc = ev.create(c, 3);
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        k_lnk_pack<<<nblk(nwords), 256, 0, c->stream>>>(ptr<uint8_t>(ascii), ptr<LnkWin>(dwins), ptr<uint64_t>(dwoff), (uint32_t)wins.size(), nwords, ptr<uint32_t>(pack));
+        KCHK(c);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        st.pack_ms = ev_ms(ev.a, ev.b);
+        ascii.reset();
+        rc = ap.mode == BELLA_ALIGN_GLOBAL       ? pal_run<PalGlobal>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st)
+             : ap.mode == BELLA_ALIGN_SEMIGLOBAL ? pal_run<PalSemi>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st)
+                                                 : pal_run<PalDovetail>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st);
+        if (rc) { (void)hipDeviceSynchronize(); return rc; }
+    }
+    for (const bella_align_result& R : res)
+        ++(R.status == BELLA_ALIGN_STATUS_ALIGNED ? st.aligned : R.status == BELLA_ALIGN_STATUS_BAND_CAPPED ? st.band_capped : st.too_large);
+    st.ops = ops.size();
+    st.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    copy_out(out, res);
+    c->pal_ops = std::move(ops);
+    c->pal_stats = st;
+    if (nops) *nops = st.ops;
+    return 0;
+}
+
+int bella_hip_get_align_ops(bella_ctx* c, uint32_t* ops, uint64_t cap) {
+    if (!c || (!ops && cap)) return BELLA_ERR_BAD_ARG;
+    if (c->pal_ops.size() > cap) return fail(c, BELLA_ERR_BAD_ARG, "get_align_ops: %zu ops, room for %llu", c->pal_ops.size(), (unsigned long long)cap);
+    copy_out(ops, c->pal_ops);
+    return 0;
+}
+
+int bella_hip_get_align_stats(bella_ctx* c, void* out, uint64_t struct_size) {
+    if (!c || !out) return BELLA_ERR_BAD_ARG;
+    return put_sized(out, struct_size, c->pal_stats);
 }
 
 // ---- read correction rounds (recorrect.hpp) -------------------------------------------------------------------------

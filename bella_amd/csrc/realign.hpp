@@ -203,17 +203,18 @@ struct ReaEnd {                  // the best cell of the last row: trace_best_ta
     __device__ __forceinline__ ReaRes res() const { return ReaRes{best.s, best.sum - best.i}; }
 };
 
-// a ReaJob as band.hpp's problem; kForward: V is known to run forwards and uncomplemented (links.hpp), so dV and comp are constants
-template <class EndRule, bool kForward>
+// a ReaJob as band.hpp's problem; kForward: V is known to run forwards and uncomplemented (links.hpp), so dV and comp are constants;
+// kAnchored: the path starts in (0, 0) and row 0 is -q (pairalign.hpp's global alignment), else anywhere in row 0, which is 0
+template <class EndRule, bool kForward, bool kAnchored = false>
 struct ReaProblemT {
     using End = EndRule;
-    static constexpr bool anchored = false;
+    static constexpr bool anchored = kAnchored, touch_row0 = false;
     const ReaJob& e;
     const uint32_t *rpacked, *upacked;
     __device__ __forceinline__ int m() const { return e.m; }
     __device__ __forceinline__ int rows(uint32_t) const { return (int)e.n; }
     __device__ __forceinline__ int centre() const { return e.c; }
-    __device__ __forceinline__ int row0(int) const { return 0; }
+    __device__ __forceinline__ int row0(int j) const { return kAnchored ? -j : 0; }
     __device__ __forceinline__ int h(int64_t t) const { return trace_base(upacked, e.gH, 1, 0u, t); }
     __device__ __forceinline__ const uint32_t* vpack() const { return rpacked; }
     __device__ __forceinline__ int64_t vidx(int64_t t) const { return e.gV + (int64_t)(kForward ? 1 : e.dV) * t; }
@@ -259,6 +260,9 @@ __device__ __forceinline__ bool rea_start(const ReaJob& e, const ReaRes& r, int&
     return r.q_end >= 0 && r.q_end <= e.m;
 }
 
+// the problem the walks of a result see: ReaProblem, unless the result says otherwise (pairalign.hpp's global one is anchored)
+template <class Res> struct ReaWalkOf { using type = ReaProblem; };
+
 // The walks, one thread per job, from the DP's end (Res: a ReaRes or a LnkRes) back to row 0, the job's last op first.  The counting
 // walk: runs, op totals, whether the path touched the first or the last diagonal of the band (an end that nothing reaches counts as
 // touched), q_begin = the junction where it reached row 0.
@@ -272,7 +276,7 @@ __global__ void k_rea_count(const ReaJob* jobs, const Res* res, uint32_t njobs, 
     int i, j;
     if (!rea_start(e, r, i, j) || r.score <= kReaNoEnd) { o.touch = 1; out[x] = o; return; }
     TraceRuns runs;
-    const bool t = band_walk(ReaProblem{e, rpacked, upacked}, dirs, i, j, runs);
+    const bool t = band_walk(typename ReaWalkOf<Res>::type{e, rpacked, upacked}, dirs, i, j, runs);
     o.nops = runs.nruns;
     o.n_eq = runs.cnt[0]; o.n_x = runs.cnt[1]; o.n_ins = runs.cnt[2]; o.n_del = runs.cnt[3];
     o.touch = t ? 1u : 0u;
@@ -291,7 +295,7 @@ __global__ void k_rea_write(const ReaJob* jobs, const Res* res, const ReaCnt* cn
     TraceEmit bw{ops, (int64_t)(e.op_off + cnt[x].nops), -1};
     int i, j;
     rea_start(e, res[x], i, j);
-    band_walk(ReaProblem{e, rpacked, upacked}, dirs, i, j, bw);
+    band_walk(typename ReaWalkOf<Res>::type{e, rpacked, upacked}, dirs, i, j, bw);
     bw.flush();
 }
 

@@ -68,7 +68,7 @@ struct TraceEnd {                // the best cell anywhere, row 0 included
 
 struct TraceProblem {
     using End = TraceEnd;
-    static constexpr bool anchored = true;
+    static constexpr bool anchored = true, touch_row0 = true;
     const TraceExt& e;
     const uint32_t* packed;
     __device__ __forceinline__ int m() const { return (int)e.m; }

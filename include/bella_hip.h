@@ -964,6 +964,83 @@ int bella_hip_write_unitig_gfa_links(const char* path, uint32_t nreads, const ch
                                      const uint64_t* pos, const uint32_t* nbases, const uint64_t* len, const uint8_t* circular, const uint64_t* base_offsets,
                                      const uint8_t* bases, uint64_t nlinks, const bella_unitig_link* links, const bella_link_aln* alns, const uint32_t* ops);
 
+/* ---- pair alignment: caller-supplied pairs of sequences aligned on the device, with their runs (no counterpart
+ * in the reference) -----------------------------------------------------------------------------------------------------------------
+ * bases[nbases] holds every sequence, upper-case ACGT.  Pair k names a query Q = bases[q_off, q_off + q_len) and a target T =
+ * bases[t_off, t_off + t_len), n = q_len >= 1 and m = t_len >= 1, and a centre diagonal c; with BELLA_ALIGN_PAIR_RC set, Q is
+ * reverse-complemented before anything else.  Rows i = 0 .. n are bases of Q, columns q = 0 .. m bases of T.
+ *   DP.  The realignment section's scoring (+1 / -1 / -1, linear), cell rule (cell (i, q) exists iff -B/2 <= q - i - c < B/2 and
+ * 0 <= q <= m), recurrence, direction preference (the first of diagonal, up, left that attains the maximum), clamp of the walk and
+ * TOUCHED rule (a visited cell with p = q - i - c + B/2 <= 0 or >= B - 1 in a row >= 1, or an end that no path reaches).  The mode
+ * sets row 0, the end and where the walk stops:
+ *   BELLA_ALIGN_GLOBAL      row 0 is -q; the end is the cell (n, m); the walk goes back to (0, 0), leftwards along row 0 as 'D'.  An end
+ *                           or a start outside the band counts as touched.
+ *   BELLA_ALIGN_SEMIGLOBAL  row 0 is 0; the end is the best cell of row n, ties to the smallest q; the walk stops in row 0: Q whole, a
+ *                           window of T (the realignment section's alignment).
+ *   BELLA_ALIGN_DOVETAIL    row 0 is 0; the end is the best cell of column m, ties to the smallest row; the walk stops in row 0: a
+ *                           suffix of T against a prefix of Q (the link section's alignment).
+ *   Bands.  B starts at band0 and doubles while the pair is touched, up to band_max.  A band that cannot hold what the mode needs is
+ * doubled without a DP: global, the start (0, 0) or the end (n, m) outside it; the other two, no cell of the rectangle inside it.
+ *   Status.  BELLA_ALIGN_STATUS_TOO_LARGE: n + m >= 2^27, or the pair's direction bytes n * B / 4 at the band it is to run with exceed
+ * one batch (BELLA_TUNE_ROUND_BUDGET, else by the free memory); band = that band.  BELLA_ALIGN_STATUS_BAND_CAPPED: touched at
+ * band_max.  Both leave every other field of the result but band and widened zero.  BELLA_ALIGN_STATUS_ALIGNED: everything else.
+ *   Result.  q_begin, q_end: the rows the alignment spans (0 and n, or 0 and the end row of a dovetail); t_begin, t_end: the columns (0
+ * and m for global, the window for semi-global, the start and m for a dovetail).  'I' is a base of Q only, 'D' a base of T only; the
+ * runs are in the order of Q, len << 4 | op with op 0 '=', 1 'X', 2 'I', 3 'D', adjacent runs differ, and only ALIGNED pairs have runs.  A
+ * dovetail whose best cell is (0, m) is ALIGNED with no runs.  The runs of all pairs lie by the pairs' last band, then by index. */
+#define BELLA_ALIGN_DEFAULT_BAND 512
+#define BELLA_ALIGN_DEFAULT_BAND_MAX 4096
+#define BELLA_ALIGN_MAX_BAND 16384
+#define BELLA_ALIGN_PAIR_RC 1u
+enum { BELLA_ALIGN_GLOBAL = 0, BELLA_ALIGN_SEMIGLOBAL = 1, BELLA_ALIGN_DOVETAIL = 2 };
+enum { BELLA_ALIGN_STATUS_ALIGNED = 0, BELLA_ALIGN_STATUS_BAND_CAPPED = 1, BELLA_ALIGN_STATUS_TOO_LARGE = 2 };
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_align_params) of the caller's header (the struct may grow)                */
+    uint32_t mode;                /* BELLA_ALIGN_GLOBAL / _SEMIGLOBAL / _DOVETAIL                                          */
+    uint32_t band0;               /* a power of two in [256, band_max]; 0: 512                                             */
+    uint32_t band_max;            /* a power of two <= 16384; 0: 4096                                                      */
+} bella_align_params;
+typedef struct {
+    uint64_t q_off, t_off;        /* first base of Q and of T in bases                                                     */
+    uint32_t q_len, t_len;        /* n and m: 1 .. 2^30 - 1                                                                */
+    uint32_t flags;               /* BELLA_ALIGN_PAIR_RC                                                                   */
+    int32_t centre;               /* c, taken as given                                                                     */
+} bella_align_pair;
+typedef struct {
+    uint32_t status;              /* BELLA_ALIGN_STATUS_*                                                                  */
+    uint32_t band;                /* the last band of the pair                                                             */
+    uint32_t widened;             /* doublings of the band                                                                 */
+    int32_t score;
+    uint32_t q_begin, q_end;      /* rows                                                                                  */
+    uint32_t t_begin, t_end;      /* columns                                                                               */
+    uint32_t n_eq, n_x, n_ins, n_del;
+    uint64_t op_off;              /* first run among the runs of the call                                                  */
+    uint32_t nops;                /* ALIGNED only                                                                          */
+    uint32_t pad;
+} bella_align_result;
+/* What the last bella_hip_align_sequences did.  A sized struct: bella_hip_get_align_stats writes at most struct_size bytes. */
+typedef struct {
+    uint64_t pairs;
+    uint64_t aligned, band_capped, too_large;     /* pairs by status                                                       */
+    uint64_t repeated;            /* DPs that ran again with the band doubled                                              */
+    uint64_t dp_cells;            /* rows x band summed over every DP that ran                                             */
+    uint64_t ops;                 /* runs of all pairs                                                                     */
+    uint32_t batches, mode;
+    double pack_ms, dp_ms, walk_ms;               /* device time between events                                            */
+    double total_ms;              /* the whole call on the host clock                                                      */
+} bella_align_stats;
+/* Aligns pairs[npairs] over bases[nbases]: out[npairs] in the order of the pairs, *nops (nullable) = the runs of all pairs, which stay
+ * with the context until the next successful call (bella_hip_get_align_ops).  params == NULL: global with the default bands.
+ * Everything is checked before anything is launched: BELLA_ERR_BAD_ARG, with `out` and the runs of the call before untouched, for a byte
+ * other than ACGT inside a window that a pair uses, a window outside bases, a length of zero, a sequence of 2^30 bases or more, mode > 2,
+ * a band that is no power of two or outside [256, 16384], band0 > band_max, a struct_size too small.  npairs == 0 launches nothing.
+ * The call needs a context but no loaded reads, and leaves every stage of the context as it found it. */
+int bella_hip_align_sequences(bella_ctx* ctx, const uint8_t* bases, uint64_t nbases, const bella_align_pair* pairs, uint64_t npairs, const bella_align_params* params,
+                              bella_align_result* out, uint64_t* nops);
+/* the runs of the last bella_hip_align_sequences into ops[cap]; BELLA_ERR_BAD_ARG when they do not fit */
+int bella_hip_get_align_ops(bella_ctx* ctx, uint32_t* ops, uint64_t cap);
+int bella_hip_get_align_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+
 /* ---- read correction rounds: the partners' raw clips aligned against the corrected read, one more consensus (no
  * counterpart in the reference) ------------------------------------------------------------------------------------------------------
  * One ROUND aligns, for every accumulated overlap record, each of the two reads' RAW clips against the CURRENT corrected sequence of the
@@ -1220,7 +1297,8 @@ int bella_hip_trim(bella_ctx* ctx);
  *   BELLA_TUNE_ROUND_BUDGET   values[0] = direction bytes of one batch of a realignment or correction round, taken as given (no 64 MB
  *                             floor; a batch always takes at least one job, so 1 means one job per batch -- tests run many batches on
  *                             small inputs).  Default (n = 0 or 0): half of the free device memory, 64 MB .. 8 GB.  Read at the start of
- *                             each round.  The trace's budget is not touched.
+ *                             each round.  The trace's budget is not touched.  bella_hip_graph_align_links and bella_hip_align_sequences
+ *                             batch by it too; in the latter a pair whose own direction bytes exceed it is TOO_LARGE.
  *   BELLA_TUNE_XDROP_BATCH    values[0] = extensions (two per pair) of one batch of the sliced X-drop kernels (variant 1, and variant 0's
  *                             fall-back), taken as given: neither the free-memory rule nor the floor of 65,536 extensions applies -- tests
  *                             run several batches, full and partial, on small inputs.  Default (n = 0 or 0): at most 16 M extensions, at

@@ -210,7 +210,11 @@ class AlignStats(C.Structure):
                 ("total_ms", C.c_double)]
 
 
-assert C.sizeof(AlignPair) == ALIGN_PAIR_DT.itemsize and C.sizeof(AlignResult) == ALIGN_RES_DT.itemsize and C.sizeof(AlignStats) == 96
+class AlignScoring(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("match", C.c_uint32), ("mismatch", C.c_uint32), ("gap_open", C.c_uint32), ("gap_extend", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(AlignPair) == ALIGN_PAIR_DT.itemsize and C.sizeof(AlignResult) == ALIGN_RES_DT.itemsize and C.sizeof(AlignStats) == 96 and C.sizeof(AlignScoring) == 24
 
 
 class RecorrectParams(C.Structure):
@@ -367,6 +371,7 @@ SIGNATURES = [
     ("bella_hip_graph_get_link_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_write_unitig_gfa_links", C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]),
     ("bella_hip_align_sequences", C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(AlignParams), vp, C.POINTER(C.c_uint64)]),
+    ("bella_hip_align_sequences_affine", C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(AlignParams), C.POINTER(AlignScoring), vp, C.POINTER(C.c_uint64)]),
     ("bella_hip_get_align_ops", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_get_align_stats", C.c_int, [vp, vp, C.c_uint64]),
     ("bella_hip_recorrect", C.c_int, [vp, C.POINTER(RecorrectParams), C.POINTER(C.c_uint64)]),

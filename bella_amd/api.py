@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CLIP_DT, GraphTrimParams, TrimStats
-from ._lib import ALIGN_PAIR_DT, ALIGN_RES_DT, AlignParams, AlignStats
+from ._lib import ALIGN_PAIR_DT, ALIGN_RES_DT, AlignParams, AlignScoring, AlignStats
 from ._lib import ALN_DT, CONS_DT, EDGE_DT, EXT_DT, LINK_ALN_DT, LINK_DT, LinkParams, LinkStats, OVL_DT, PAIR_DT, PLACE_DT, POLISH_DT, PolishParams, PolishStats, RealignParams, RealignStats, BubbleStats, GraphBubbleParams, GraphCleanParams, GraphWeakParams, WeakStats, GraphParams, GraphStats, UnitigStats, PILEUP_COUNTERS, SEED_DT, TRACE_DT, ConsensusParams, Memory, Params, Timings, TraceStats, WriteStats
 
 
@@ -768,25 +768,35 @@ class Engine:
         return tr, ops
 
     # ---- pair alignment ----
-    def align_records(self, bases, records, mode="global", band0: int = 512, band_max: int = 4096):
+    def align_records(self, bases, records, mode="global", band0: int = 512, band_max: int = 4096, scoring=None):
         """bella_hip_align_sequences as it is: bases uint8 (upper-case ACGT), records of ALIGN_PAIR_DT -> (results of ALIGN_RES_DT in the
-        records' order, the runs of all pairs as uint32 len << 4 | op)"""
+        records' order, the runs of all pairs as uint32 len << 4 | op).  scoring: None (+1 / -1 / -1, linear gaps), or (match, mismatch,
+        gap_open, gap_extend) for bella_hip_align_sequences_affine."""
         bases = np.ascontiguousarray(bases, np.uint8)
         recs = np.ascontiguousarray(records, ALIGN_PAIR_DT)
         ap = AlignParams(C.sizeof(AlignParams), _lib.ALIGN_MODES[mode] if isinstance(mode, str) else int(mode), int(band0), int(band_max))
         out = np.zeros(len(recs), ALIGN_RES_DT)
         no = C.c_uint64(0)
-        self._chk(self.lib.bella_hip_align_sequences(self.h, _p(bases), bases.size, _p(recs), len(recs), C.byref(ap), _p(out), C.byref(no)))
+        if scoring is None:
+            self._chk(self.lib.bella_hip_align_sequences(self.h, _p(bases), bases.size, _p(recs), len(recs), C.byref(ap), _p(out), C.byref(no)))
+        else:
+            a, b, o, e = (int(x) for x in scoring)
+            if min(a, b, o, e) < 0 or max(a, b, o, e) >= 1 << 32:
+                raise ValueError("scoring is four non-negative numbers (match, mismatch, gap_open, gap_extend)")
+            sc = AlignScoring(C.sizeof(AlignScoring), a, b, o, e, 0)
+            self._chk(self.lib.bella_hip_align_sequences_affine(self.h, _p(bases), bases.size, _p(recs), len(recs), C.byref(ap), C.byref(sc), _p(out), C.byref(no)))
         ops = np.zeros(no.value, np.uint32)
         self._chk(self.lib.bella_hip_get_align_ops(self.h, _p(ops), no.value))
         return out, ops
 
-    def align_sequences(self, seqs, pairs, mode="global", rc=None, centre=None, overlap=None, band0: int = 512, band_max: int = 4096):
+    def align_sequences(self, seqs, pairs, mode="global", rc=None, centre=None, overlap=None, band0: int = 512, band_max: int = 4096, scoring=None):
         """Aligns pairs of caller-supplied sequences on the device.  seqs: a list of bytes (upper-case ACGT); pairs: (query, target)
         indices into it; rc (per pair, or one for all): the query is reverse-complemented first.  mode: "global" (both whole),
         "semiglobal" (the query whole, a window of the target) or "dovetail" (a suffix of the target against a prefix of the query).
         centre (per pair, or one for all): the diagonal target - query the band is centred on; the default is floor((m - n) / 2), and
-        m - overlap for a dovetail with an expected `overlap`.  Returns (results of ALIGN_RES_DT in the pairs' order, the runs)."""
+        m - overlap for a dovetail with an expected `overlap`.  scoring: None for match +1, mismatch -1, gap -1 (linear), or a 4-tuple
+        (match, mismatch, gap_open, gap_extend): match +a, mismatch -b, a gap of L bases -(o + e L) (affine gaps; section 29).  Returns
+        (results of ALIGN_RES_DT in the pairs' order, the runs)."""
         lens = np.array([len(s) for s in seqs], np.uint64)
         offs = np.concatenate([np.zeros(1, np.uint64), np.cumsum(lens, dtype=np.uint64)])
         bases = np.frombuffer(b"".join(bytes(s) for s in seqs), np.uint8)
@@ -807,7 +817,7 @@ class Engine:
             raise TypeError("a dovetail needs the expected overlap (or a centre)")
         else:
             recs["centre"] = (m - n) // 2
-        return self.align_records(bases, recs, mode, band0, band_max)
+        return self.align_records(bases, recs, mode, band0, band_max, scoring)
 
     def align_stats(self) -> dict:
         return self._stats(self.lib.bella_hip_get_align_stats, AlignStats)

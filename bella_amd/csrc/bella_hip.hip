@@ -4387,17 +4387,37 @@ int round_budget(bella_ctx* c, uint64_t* budget) {
     return 0;
 }
 
-// jobs of a batch at most: the wide kernel keeps two rows of B ints per job in scratch, and a batch's scratch stays within the budget too
-uint32_t round_max_jobs(uint32_t B, uint64_t budget) {
-    return B > kTrRegBand ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kRecMaxBatch, budget / (8ull * B))) : kRecMaxBatch;
+// What a family's sweep stores and keeps: direction bits per cell, scratch ints of the wide kernel per job and band cell, the two walks.
+// The linear families (ReaFamily, LnkFamily, PalGlobal, PalSemi): 2 bits, two rows of B ints, k_rea_count / k_rea_write; an affine family
+// (pairalign.hpp; section 29) states its own, and its DP kernels take the scores.
+template <class Family, class = void>
+struct BandTraits {
+    static constexpr bool affine = false;
+    static constexpr uint32_t dir_bits = 2, scr_ints = 2;
+    static constexpr auto count() { return k_rea_count<typename Family::Res>; }
+    static constexpr auto write() { return k_rea_write<typename Family::Res>; }
+};
+template <class Family>
+struct BandTraits<Family, std::enable_if_t<Family::affine>> {
+    static constexpr bool affine = true;
+    static constexpr uint32_t dir_bits = Family::dir_bits, scr_ints = Family::scr_ints;
+    static constexpr auto count() { return Family::count(); }
+    static constexpr auto write() { return Family::write(); }
+};
+
+// jobs of a batch at most: the wide kernel keeps scr_ints rows of B ints per job in scratch (two: the linear sweep), and a batch's scratch
+// stays within the budget too
+uint32_t round_max_jobs(uint32_t B, uint64_t budget, uint32_t scr_ints = 2) {
+    return B > kTrRegBand ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kRecMaxBatch, budget / (4ull * scr_ints * B))) : kRecMaxBatch;
 }
 
 // A round's batches on the device.  The round cuts a batch -- `nj` jobs of band `B` in `jobs`, `dbytes` direction bytes -- and owns what
-// happens between the two steps: the read-backs, what becomes of every job, the jobs' op_off.  Family: ReaFamily (realign.hpp) or
-// LnkFamily (links.hpp) -- what the DP leaves per job, the DP kernels, whether the runs vote.
+// happens between the two steps: the read-backs, what becomes of every job, the jobs' op_off.  Family: ReaFamily (realign.hpp),
+// LnkFamily (links.hpp) or one of pairalign.hpp's -- what the DP leaves per job, the DP kernels, whether the runs vote.
 template <class Family>
 struct RoundBatches {
     using Res = typename Family::Res;
+    using Traits = BandTraits<Family>;
     bella_ctx* c;
     const char *who, *unit;                                           // for the messages: "realign" and its "reads", "recorrect" and its "jobs"
     EventSet& ev;
@@ -4408,22 +4428,27 @@ struct RoundBatches {
     std::vector<uint32_t>& kept;                                      // ... where the ops of every batch are appended
     double &dp_ms, &walk_ms, &vote_ms;
     TmpBuf jobs, res, cnt, dirs, scr, ops;
+    AfnScore score{1, 1, 0, 1};                                       // an affine family's scores (section 29); the linear kernels take none
 
     // DP and the counting walk.  The caller launches what is its own behind them, records ev.d, reads back, waits, and calls counted().
     int dp_count(uint32_t nj, uint32_t B, uint64_t dbytes) {
         ENSURE(c, res, sizeof(Res) * (size_t)nj); ENSURE(c, cnt, sizeof(ReaCnt) * (size_t)nj);
         if (ensure_bytes(c, dirs, (size_t)dbytes))
             return fail(c, BELLA_ERR_NOMEM, "%s: %llu direction bytes for a batch of %u %s do not fit", who, (unsigned long long)dbytes, nj, unit);
-        if (B > kTrRegBand) ENSURE(c, scr, 8 * (size_t)nj * B);
+        if (B > kTrRegBand) ENSURE(c, scr, 4 * (size_t)Traits::scr_ints * nj * B);
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        auto launch = [&](auto kernel, uint32_t grid, uint32_t block, auto... args) {      // an affine family's kernels take the scores last
+            if constexpr (Traits::affine) kernel<<<grid, block, 0, c->stream>>>(args..., score);
+            else kernel<<<grid, block, 0, c->stream>>>(args...);
+        };
         for_band(B, [&](auto C, uint32_t) {
             if constexpr (decltype(C)::value != 0)
-                Family::template dp<decltype(C)::value>()<<<nblk((uint64_t)nj * 64, kTraceBlock), kTraceBlock, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<Res>(res));
-            else Family::dp_wide()<<<nj, 64, 0, c->stream>>>(ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<Res>(res));
+                launch(Family::template dp<decltype(C)::value>(), nblk((uint64_t)nj * 64, kTraceBlock), kTraceBlock, ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<Res>(res));
+            else launch(Family::dp_wide(), nj, 64u, ptr<ReaJob>(jobs), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<int>(scr), ptr<Res>(res));
         });
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.b, c->stream));
-        k_rea_count<Res><<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<Res>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
+        Traits::count()<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<Res>(res), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<ReaCnt>(cnt));
         KCHK(c);
         return 0;
     }
@@ -4433,7 +4458,7 @@ struct RoundBatches {
     int write_vote(uint32_t nj, uint64_t nops) {
         ENSURE(c, ops, 4 * (size_t)nops);
         HIPCHK(c, hipEventRecord(ev.a, c->stream));
-        k_rea_write<Res><<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<Res>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
+        Traits::write()<<<nblk(nj), 256, 0, c->stream>>>(ptr<ReaJob>(jobs), ptr<Res>(res), ptr<ReaCnt>(cnt), nj, rpacked, upacked, ptr<uint8_t>(dirs), ptr<uint32_t>(ops));
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.b, c->stream));
         if constexpr (Family::votes) {
@@ -6084,8 +6109,12 @@ void pal_fill(bella_align_result& R, const ReaJob& j, const LnkRes& r, const Rea
 
 template <class Family>
 int pal_run(bella_ctx* c, uint32_t mode, uint32_t band0, uint32_t band_max, const std::vector<PalPair>& pp, const std::vector<uint64_t>& woff, const uint32_t* pack, EventSet& ev,
-            std::vector<bella_align_result>& res, std::vector<uint32_t>& ops, bella_align_stats& st) {
+            std::vector<bella_align_result>& res, std::vector<uint32_t>& ops, bella_align_stats& st, const AfnScore& score = AfnScore{1, 1, 0, 1}) {
     using Res = typename Family::Res;
+    using Traits = BandTraits<Family>;
+    constexpr uint32_t per_byte = 8 / Traits::dir_bits;               // cells of a direction byte: a row is B / per_byte bytes
+    // every reachable score stays above kTrNeg / 2: section 28's n + m >= 2^27 under +1 / -1 / -1
+    const uint64_t worst = Traits::affine ? (uint64_t)std::max(std::max(score.a, score.b), score.o + score.e) : 1;
     uint64_t budget = 0;
     if (int rc = round_budget(c, &budget)) return rc;
     // ---- the first band of every pair: doubled without a DP while it cannot hold what the mode needs
@@ -6093,13 +6122,14 @@ int pal_run(bella_ctx* c, uint32_t mode, uint32_t band0, uint32_t band_max, cons
     for (uint32_t k = 0; k < (uint32_t)pp.size(); ++k) {
         bella_align_result& R = res[k];
         R.band = band0;
-        if ((uint64_t)pp[k].n + pp[k].m >= kPalMaxCells) { R.status = BELLA_ALIGN_STATUS_TOO_LARGE; continue; }
+        if (((uint64_t)pp[k].n + pp[k].m) * worst >= kPalMaxCells) { R.status = BELLA_ALIGN_STATUS_TOO_LARGE; continue; }
         while (!pal_feasible(mode, pp[k], R.band) && R.band < band_max) { R.band *= 2; ++R.widened; }
         if (!pal_feasible(mode, pp[k], R.band)) { R.status = BELLA_ALIGN_STATUS_BAND_CAPPED; continue; }
         starters[R.band].push_back(k);
     }
     double no_votes = 0;
     RoundBatches<Family> rb{c, "align_sequences", "pairs", ev, pack, pack, nullptr, nullptr, true, ops, st.dp_ms, st.walk_ms, no_votes};
+    rb.score = score;
     std::vector<ReaJob> hj;
     std::vector<Res> hres;
     std::vector<ReaCnt> hcnt;
@@ -6111,22 +6141,22 @@ int pal_run(bella_ctx* c, uint32_t mode, uint32_t band0, uint32_t band_max, cons
         next.clear();
         size_t keep = 0;                                              // a pair whose direction bytes exceed a batch at this band goes no further
         for (uint32_t k : pending) {
-            if ((uint64_t)pp[k].n * (B / 4) > budget) { res[k].status = BELLA_ALIGN_STATUS_TOO_LARGE; res[k].band = B; }
+            if ((uint64_t)pp[k].n * (B / per_byte) > budget) { res[k].status = BELLA_ALIGN_STATUS_TOO_LARGE; res[k].band = B; }
             else pending[keep++] = k;
         }
         pending.resize(keep);
-        const uint32_t maxjobs = round_max_jobs(B, budget);
+        const uint32_t maxjobs = round_max_jobs(B, budget, Traits::scr_ints);
         for (size_t b0 = 0; b0 < pending.size();) {
             hj.clear();
             uint64_t dbytes = 0;
             size_t b1 = b0;
             for (; b1 < pending.size(); ++b1) {
                 const PalPair& p = pp[pending[b1]];
-                const uint64_t need_bytes = (uint64_t)p.n * (B / 4);
+                const uint64_t need_bytes = (uint64_t)p.n * (B / per_byte);
                 if (!hj.empty() && (dbytes + need_bytes > budget || hj.size() >= maxjobs)) break;
                 ReaJob j{};
                 j.gH = (int64_t)(16 * woff[p.wt]); j.gV = (int64_t)(16 * woff[p.wq]);
-                j.dir_off = dbytes; j.scr_off = 2ull * B * hj.size(); j.op_off = ~0ull;
+                j.dir_off = dbytes; j.scr_off = (uint64_t)Traits::scr_ints * B * hj.size(); j.op_off = ~0ull;
                 j.n = p.n; j.m = (int32_t)p.m; j.mt = j.m; j.c = p.c;
                 j.band = B; j.dV = 1; j.comp = 0;
                 hj.push_back(j);
@@ -6173,13 +6203,9 @@ int pal_run(bella_ctx* c, uint32_t mode, uint32_t band0, uint32_t band_max, cons
     }
     return 0;
 }
-}  // namespace
-
-extern "C" {
-
-int bella_hip_align_sequences(bella_ctx* c, const uint8_t* bases, uint64_t nbases, const bella_align_pair* pairs, uint64_t npairs, const bella_align_params* params,
-                              bella_align_result* out, uint64_t* nops) {
-    if (!c) return BELLA_ERR_BAD_ARG;
+// the two public calls: afn == nullptr runs the linear families (section 28), else the affine ones under *afn (section 29)
+int pal_align(bella_ctx* c, const uint8_t* bases, uint64_t nbases, const bella_align_pair* pairs, uint64_t npairs, const bella_align_params* params, const AfnScore* afn,
+              bella_align_result* out, uint64_t* nops) {
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     // ---- everything is checked before anything is launched
@@ -6249,9 +6275,14 @@ int bella_hip_align_sequences(bella_ctx* c, const uint8_t* bases, uint64_t nbase
         HIPCHK(c, hipStreamSynchronize(c->stream));
         st.pack_ms = ev_ms(ev.a, ev.b);
         ascii.reset();
-        rc = ap.mode == BELLA_ALIGN_GLOBAL       ? pal_run<PalGlobal>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st)
-             : ap.mode == BELLA_ALIGN_SEMIGLOBAL ? pal_run<PalSemi>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st)
-                                                 : pal_run<PalDovetail>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st);
+        if (afn)
+            rc = ap.mode == BELLA_ALIGN_GLOBAL       ? pal_run<PalAfnGlobal>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st, *afn)
+                 : ap.mode == BELLA_ALIGN_SEMIGLOBAL ? pal_run<PalAfnSemi>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st, *afn)
+                                                     : pal_run<PalAfnDovetail>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st, *afn);
+        else
+            rc = ap.mode == BELLA_ALIGN_GLOBAL       ? pal_run<PalGlobal>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st)
+                 : ap.mode == BELLA_ALIGN_SEMIGLOBAL ? pal_run<PalSemi>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st)
+                                                     : pal_run<PalDovetail>(c, ap.mode, ap.band0, ap.band_max, pp, woff, ptr<uint32_t>(pack), ev, res, ops, st);
         if (rc) { (void)hipDeviceSynchronize(); return rc; }
     }
     for (const bella_align_result& R : res)
@@ -6263,6 +6294,30 @@ int bella_hip_align_sequences(bella_ctx* c, const uint8_t* bases, uint64_t nbase
     c->pal_stats = st;
     if (nops) *nops = st.ops;
     return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int bella_hip_align_sequences(bella_ctx* c, const uint8_t* bases, uint64_t nbases, const bella_align_pair* pairs, uint64_t npairs, const bella_align_params* params,
+                              bella_align_result* out, uint64_t* nops) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    return pal_align(c, bases, nbases, pairs, npairs, params, nullptr, out, nops);
+}
+
+int bella_hip_align_sequences_affine(bella_ctx* c, const uint8_t* bases, uint64_t nbases, const bella_align_pair* pairs, uint64_t npairs, const bella_align_params* params,
+                                     const bella_align_scoring* scoring, bella_align_result* out, uint64_t* nops) {
+    if (!c) return BELLA_ERR_BAD_ARG;
+    AfnScore sc{1, 1, 0, 1};
+    if (scoring) {
+        if (scoring->struct_size < sizeof(bella_align_scoring))
+            return fail(c, BELLA_ERR_BAD_ARG, "bella_align_scoring: struct_size %u is smaller than the %zu bytes this library knows", scoring->struct_size, sizeof(bella_align_scoring));
+        if (scoring->reserved) return fail(c, BELLA_ERR_BAD_ARG, "bella_align_scoring: reserved must be 0");
+        if (scoring->match < 1 || scoring->match > 255 || scoring->mismatch > 255 || scoring->gap_open > 255 || scoring->gap_extend < 1 || scoring->gap_extend > 255)
+            return fail(c, BELLA_ERR_BAD_ARG, "bella_align_scoring: 1 <= match <= 255, mismatch <= 255, gap_open <= 255, 1 <= gap_extend <= 255");
+        sc = AfnScore{(int)scoring->match, (int)scoring->mismatch, (int)scoring->gap_open, (int)scoring->gap_extend};
+    }
+    return pal_align(c, bases, nbases, pairs, npairs, params, &sc, out, nops);
 }
 
 int bella_hip_get_align_ops(bella_ctx* c, uint32_t* ops, uint64_t cap) {

@@ -87,13 +87,16 @@ def evaluate(S, G, duplicate: bool = True):
     return {"recall": rc, "precision": pr, "f1": f1, "true_positives": len(T), "reported": len(S), "truth": len(G)}
 
 
-def sequence_identity(engine, queries, templates, mode: str = "global", **bands):
+def sequence_identity(engine, queries, templates, mode: str = "global", scoring=None, **bands):
     """Whole-sequence identity on the device (Engine.align_sequences): queries[k] is aligned against templates[k]
     over its full length.  Returns (identity float64[n], status uint32[n]): identity = n_eq / (n_eq + n_x + n_ins + n_del) of the
-    alignment's columns, NaN for a pair that is not ALIGNED or has no column; status as the results carry it.  bands: band0, band_max."""
+    alignment's columns, NaN for a pair that is not ALIGNED or has no column; status as the results carry it.  scoring: None, or
+    (match, mismatch, gap_open, gap_extend) for affine gaps (section 29).  bands: band0, band_max."""
     nq = len(queries)
     if nq != len(templates):
         raise ValueError("one template per query")
+    if scoring is not None:
+        bands = dict(bands, scoring=scoring)
     res, _ = engine.align_sequences(list(queries) + list(templates), [(k, nq + k) for k in range(nq)], mode=mode, **bands)
     cols = (res["n_eq"].astype(np.int64) + res["n_x"] + res["n_ins"] + res["n_del"]).astype(np.float64)
     ok = (res["status"] == 0) & (cols > 0)

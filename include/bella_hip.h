@@ -1037,9 +1037,46 @@ typedef struct {
  * The call needs a context but no loaded reads, and leaves every stage of the context as it found it. */
 int bella_hip_align_sequences(bella_ctx* ctx, const uint8_t* bases, uint64_t nbases, const bella_align_pair* pairs, uint64_t npairs, const bella_align_params* params,
                               bella_align_result* out, uint64_t* nops);
-/* the runs of the last bella_hip_align_sequences into ops[cap]; BELLA_ERR_BAD_ARG when they do not fit */
+/* the runs of the last bella_hip_align_sequences or bella_hip_align_sequences_affine, whichever succeeded last, into ops[cap];
+ * BELLA_ERR_BAD_ARG when they do not fit.  The stats are that call's too. */
 int bella_hip_get_align_ops(bella_ctx* ctx, uint32_t* ops, uint64_t cap);
 int bella_hip_get_align_stats(bella_ctx* ctx, void* out, uint64_t struct_size);
+
+/* ---- pair alignment with affine gaps and the caller's scores (no counterpart in the reference) -------------------
+ * The pair alignment above under Gotoh's three matrices.  Everything not said here is the section above's, word for word: the pairs, the
+ * rc flag, the centre diagonal, the cells that exist, the three modes' ends and tie rules, the doubling of the band, the statuses, the
+ * result fields, the run encoding and the order of the runs.
+ *   Scoring.  (a, b, o, e) = (match, mismatch, gap_open, gap_extend): a match +a, a mismatch -b, a gap of L bases -(o + e L);
+ * 1 <= a <= 255, 0 <= b <= 255, 0 <= o <= 255, 1 <= e <= 255.
+ *   Matrices.  Three per cell; a cell that does not exist is minus infinity in all three:
+ *       E[i][q] = max(H[i-1][q] - o - e, E[i-1][q] - e)      a gap that consumes Q ('I')
+ *       F[i][q] = max(H[i][q-1] - o - e, F[i][q-1] - e)      a gap that consumes T ('D')
+ *       H[i][q] = max(H[i-1][q-1] + s(i, q), E[i][q], F[i][q])
+ *   Row 0.  Global: H[0][0] = 0, H[0][q] = F[0][q] = -(o + e q) for q > 0; semi-global and dovetail: H[0][q] = 0.  E[0][.] is minus
+ * infinity in every mode, F[0][.] outside global.  Column 0 needs no special case: the E recurrence produces it.
+ *   Stored per cell, 4 bits.  hsrc (2 bits): the first of diagonal (0), E (1), F (2) that attains H.  closeE: H[i][q] - o >= E[i][q].
+ * closeF: H[i][q] - o >= F[i][q].  A set close bit says that a gap arriving at this cell from below (closeE) or from the right (closeF)
+ * is opened here, not extended; ties go to opening.
+ *   The walk has a state in {H, E, F} and starts in H at the mode's end cell.  In H at (i, q): hsrc 0 emits '=' or 'X' and moves
+ * diagonally; hsrc 1 switches to E without moving; hsrc 2 to F.  In E: emit 'I', i <- i - 1, then H if closeE of the new cell is set,
+ * else E.  In F: emit 'D', q <- q - 1, then H if closeF of the new cell is set, else F.  In row 0 (global only) it emits 'D' leftwards
+ * to (0, 0), in column 0 with i > 0 'I' upwards, whatever its state.  The clamp into the band and TOUCHED are the section above's: any
+ * visited cell with p <= 0 or p >= B - 1 in a row >= 1, in any state, or an end that no path reaches.
+ *   BELLA_ALIGN_STATUS_TOO_LARGE: (n + m) max(a, b, o + e) >= 2^27 (with (1, 1, 0, 1): n + m >= 2^27), or the pair's direction bytes
+ * n * B / 2 at the band it is to run with exceed one batch.
+ *   With (1, 1, 0, 1) the results and the runs are bella_hip_align_sequences', from other kernels. */
+typedef struct {
+    uint32_t struct_size;         /* sizeof(bella_align_scoring) of the caller's header (the struct may grow)               */
+    uint32_t match;               /* a: 1 .. 255                                                                           */
+    uint32_t mismatch;            /* b: 0 .. 255, subtracted                                                               */
+    uint32_t gap_open;            /* o: 0 .. 255, subtracted once per gap                                                  */
+    uint32_t gap_extend;          /* e: 1 .. 255, subtracted per base of a gap                                             */
+    uint32_t reserved;            /* 0                                                                                     */
+} bella_align_scoring;
+/* bella_hip_align_sequences under `scoring`; scoring == NULL: (1, 1, 0, 1), through the affine kernels.  Every check of that call applies;
+ * BELLA_ERR_BAD_ARG on top, with nothing written or launched, for a score outside its range, reserved != 0, a struct_size too small. */
+int bella_hip_align_sequences_affine(bella_ctx* ctx, const uint8_t* bases, uint64_t nbases, const bella_align_pair* pairs, uint64_t npairs, const bella_align_params* params,
+                                     const bella_align_scoring* scoring, bella_align_result* out, uint64_t* nops);
 
 /* ---- read correction rounds: the partners' raw clips aligned against the corrected read, one more consensus (no
  * counterpart in the reference) ------------------------------------------------------------------------------------------------------

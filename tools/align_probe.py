@@ -4,7 +4,11 @@ Two inputs: 2,000 pairs of 10 kb at 15 % error in each of the three modes (globa
 noisy copy of 10 kb against a template of 12 kb; dovetail: two reads of 10 kb that share 5 kb), and one global pair of 500 kb at 1 %.
 Reported per run: device time of the pack, the DP kernels and the walks, the whole call on the host clock, DP cells and cells per
 second of the DP kernels, pairs per second, batches, repeated DPs, pairs by status and the mean identity of the aligned pairs.
-tools/trace_probe.py reports the same cells per second for the traced alignments: the two share band.hpp's sweep."""
+tools/trace_probe.py reports the same cells per second for the traced alignments: the two share band.hpp's sweep.
+
+--scoring a,b,o,e: the three 2,000-pair inputs, each aligned with the linear call and then, in the same process,
+with the affine one under that scoring; both runs and the ratios affine / linear of dp_ms, walk_ms and cells per second go to
+profiles/align_probe_affine.json.  The 500 kb pair is not run."""
 import argparse
 import json
 import os
@@ -63,14 +67,15 @@ def inputs(mode, npairs, length, err, rng):
     return seqs, pairs, centre
 
 
-def probe(eng, name, mode, npairs, length, err, band0, band_max, seed):
+def probe(eng, name, mode, npairs, length, err, band0, band_max, seed, scoring=None):
     rng = np.random.default_rng(seed)
     seqs, pairs, centre = inputs(mode, npairs, length, err, rng)
-    res, ops = eng.align_sequences(seqs, pairs, mode, centre=centre, band0=band0, band_max=band_max)
+    kw = {} if scoring is None else dict(scoring=scoring)
+    res, ops = eng.align_sequences(seqs, pairs, mode, centre=centre, band0=band0, band_max=band_max, **kw)
     st = eng.align_stats()
     ok = res["status"] == 0
     cols = np.maximum(1, res["n_eq"].astype(np.int64) + res["n_x"] + res["n_ins"] + res["n_del"])
-    return dict(name=name, mode=mode, pairs=npairs, length=length, error=err, band0=band0, band_max=band_max, aligned=int(st["aligned"]), band_capped=int(st["band_capped"]),
+    return dict(name=name, mode=mode, **({} if scoring is None else dict(scoring=list(scoring))), pairs=npairs, length=length, error=err, band0=band0, band_max=band_max, aligned=int(st["aligned"]), band_capped=int(st["band_capped"]),
                 too_large=int(st["too_large"]), repeated=int(st["repeated"]), batches=int(st["batches"]), dp_cells=int(st["dp_cells"]), ops=int(st["ops"]),
                 pack_ms=st["pack_ms"], dp_ms=st["dp_ms"], walk_ms=st["walk_ms"], total_ms=st["total_ms"], dp_cells_per_s=st["dp_cells"] / max(1e-9, st["dp_ms"] / 1e3),
                 pairs_per_s_device=npairs / max(1e-9, (st["pack_ms"] + st["dp_ms"] + st["walk_ms"]) / 1e3), pairs_per_s_call=npairs / max(1e-9, st["total_ms"] / 1e3),
@@ -85,16 +90,38 @@ if __name__ == "__main__":
     ap.add_argument("--long", type=int, default=500000)
     ap.add_argument("--band0", type=int, default=512)
     ap.add_argument("--band-max", type=int, default=4096)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_probe.json"))
+    ap.add_argument("--scoring", default=None, help="match,mismatch,gap_open,gap_extend: compare the affine call with the linear one")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    scoring = tuple(int(x) for x in a.scoring.split(",")) if a.scoring else None
+    if scoring is not None and len(scoring) != 4:
+        ap.error("--scoring takes four numbers")
+    out = a.out or os.path.join(ROOT, "profiles", "align_probe_affine.json" if scoring else "align_probe.json")
     eng = Engine(0)
     probe(eng, "warm-up", "global", 8, 1000, 0.15, a.band0, a.band_max, 0)
+    if scoring is not None:
+        probe(eng, "warm-up", "global", 8, 1000, 0.15, a.band0, a.band_max, 0, scoring)
+        runs, ratios = [], []
+        for k, mode in enumerate(("global", "semiglobal", "dovetail")):
+            name = "%d pairs of %d bases at 15 %%" % (a.pairs, a.length)
+            lin = probe(eng, name, mode, a.pairs, a.length, 0.15, a.band0, a.band_max, 28 + k)
+            aff = probe(eng, name, mode, a.pairs, a.length, 0.15, a.band0, a.band_max, 28 + k, scoring)
+            runs += [lin, aff]
+            ratios.append(dict(mode=mode, dp_ms=aff["dp_ms"] / lin["dp_ms"], walk_ms=aff["walk_ms"] / lin["walk_ms"],
+                               dp_cells_per_s=aff["dp_cells_per_s"] / lin["dp_cells_per_s"], total_ms=aff["total_ms"] / lin["total_ms"]))
+        eng.close()
+        for r in runs + ratios:
+            print(json.dumps(r))
+        with open(out, "w") as f:
+            json.dump(dict(scoring=list(scoring), runs=runs, affine_over_linear=ratios), f, indent=1)
+            f.write("\n")
+        sys.exit(0)
     runs = [probe(eng, "%d pairs of %d bases at 15 %%" % (a.pairs, a.length), mode, a.pairs, a.length, 0.15, a.band0, a.band_max, 28 + k)
             for k, mode in enumerate(("global", "semiglobal", "dovetail"))]
     runs.append(probe(eng, "one pair of %d bases at 1 %%" % a.long, "global", 1, a.long, 0.01, a.band0, a.band_max, 31))
     eng.close()
     for r in runs:
         print(json.dumps(r))
-    with open(a.out, "w") as f:
+    with open(out, "w") as f:
         json.dump(dict(runs=runs), f, indent=1)
         f.write("\n")
